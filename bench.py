@@ -9,6 +9,9 @@ gather + classify + IoU histogram.  Inputs (point cloud, depth maps, poses, synt
 random-init student weights) are resident in HBM before the timed region.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+      [--full]               also the figures that take runs of their own (isolated pooling passes and ceilings, convolution
+                             ceilings, per-stage side passes, pool_iters=3 variant, training step, drop-in API rates, CPU baseline)
+      [--dump-outputs DIR]   what the timed path returned in its last step, as DIR/<name>.npy
 
 Scenes shard one per GPU with no data-path collective (weak scaling); the only collective is one
 int64 all-reduce of the [3,C] IoU counts after the local loop, as the reference's (dead) metric
@@ -55,7 +58,7 @@ def parse():
                     help="row order of the pooling operator: rcb (default: recursive coordinate bisection inside 1024-row Morton chunks into the "
                          "operator's 128-row blocks, smaller neighbour unions) or morton (the voxel order itself: rounds 1-5)")
     ap.add_argument("--api", default="both", choices=["device", "both"],
-                    help="both: after the headline run also time the DROP-IN call SonataXAffinityTrainer.evaluate_scene(20-tuple of "
+                    help="both (with --full): after the headline run also time the DROP-IN call SonataXAffinityTrainer.evaluate_scene(20-tuple of "
                          "CPU tensors) (run/validation.py:408), reported as the extra object `api_tuple` -- never as `value`")
     ap.add_argument("--scenes", type=int, default=2, help="distinct synthetic scenes rotated through the steps")
     ap.add_argument("--time-every", type=int, default=3, help="HIP-event pairs around the pooling launches and the convolution layers of every "
@@ -69,9 +72,18 @@ def parse():
                          "over --streams streams (3 %% more scenes/s, but the pooling launches then share the chip with the "
                          "other scene's kernels: 0.40 instead of 0.26 ms per launch)")
     ap.add_argument("--selftest-hang", default=None, help=argparse.SUPPRESS)      # rank id or "all": the launcher watchdog's test
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step rate (extra object `training_step`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (extra object `cpu_baseline`)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the training-step rate (extra object `training_step`)")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the bounded CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure what takes runs of its own: the isolated pooling passes and their gather + "
+                         "store ceiling, the convolution layer's ceilings, the per-stage side passes (stages_ms_per_scene, roofline_stages), "
+                         "the pool_iters=3 variant, the training step, the drop-in API rates and the CPU baseline (the last three as "
+                         "selected by --no-train / --api / --no-cpu-baseline).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path returned in its LAST step as DIR/<name>.npy (float32 / float64): "
+                         "a fixed seeded sample of the point features' rows and their row ids, the text features, every point's "
+                         "prediction and zero-row flag, and the IoU counts of the timed region")
     a = ap.parse_args()
     if a.steps is None:
         # 24 scenes = 0.6 s of timed region on S.  The schedule has edges: the first timed scene does its own loader + lift + prepare
@@ -568,6 +580,28 @@ def cpu_baseline(scene, vlm_np, sd, rigid, cfg, pool_iters, budget_s, mode="full
             "stages_s_sample": {k: round(v, 3) for k, v in timings.items()}}
 
 
+DUMP_FEATURE_ROWS = 16384                                 # --dump-outputs: sampled rows of the [N, D] point features (32 MiB at D = 512)
+
+
+def dump_outputs(path, out, counts):
+    """--dump-outputs: the arrays the caller of the timed path received in the last timed step (HotPath.refine's point features,
+    classify_and_count's predictions and zero-row flags, the text features of the scene) and the IoU counts of the timed region.
+    The [N, D] features are sampled: a fixed set of rows drawn by a seeded generator, their ids written beside them."""
+    os.makedirs(path, exist_ok=True)
+    feats = out["scene_features"]
+    n = int(feats.shape[0])
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_FEATURE_ROWS), replace=False))
+    arrays = {"scene_features_sample": feats[torch.from_numpy(rows).to(feats.device)].float().cpu().numpy(),
+              "scene_features_sample_rows": rows.astype(np.float64),
+              "text_features": out["text_features"].float().cpu().numpy(),
+              "predictions": out["pred"].double().cpu().numpy(),
+              "zero_rows": out["zero"].double().cpu().numpy(),
+              "iou_counts": counts.double().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in arrays.items()))
+
+
 def val_scene_sizes(per_gpu, world):
     """BASELINE configs[2]: a fixed subset of the 312 ScanNet-val scene sizes (labelled-point counts of
     dataset/scannet_val_metrics.tsv, committed as tests/golden/scannet_val_point_counts.txt): per_gpu * world sizes taken at
@@ -705,22 +739,44 @@ def main():
     else:
         todo = [(5557 + 1000 * rank + s, cfg.num_points) for s in range(args.scenes)]
     shared_vlm = None
+
+    def _dense_host(seed):
+        feat = syn.make_dense_feature_maps(cfg, cfg.num_views, seed)
+        text = np.random.default_rng(seed).normal(size=(cfg.num_classes, cfg.feat_dim)).astype(np.float32)
+        return feat, text
+    # the host side of every scene (geometry, depth maps, synthetic 2D outputs) is generated in a thread pool: each generator draws
+    # from its own seeded numpy Generator, so the inputs are the ones a serial loop makes; the uploads below keep the serial order
+    from concurrent.futures import ThreadPoolExecutor
+    gen_pool = ThreadPoolExecutor(max_workers=max(1, min(host_threads(), 2 * len(todo))))
+    scene_jobs, vlm_jobs = [], []
+    for s, (seed, npts) in enumerate(todo):
+        c = dataclasses.replace(cfg, num_points=npts) if npts != cfg.num_points else cfg
+        scene_jobs.append(gen_pool.submit(syn.make_scene, c, seed))
+        if cfg.dense_features:
+            vlm_jobs.append(gen_pool.submit(_dense_host, seed))
+        elif not val_mode or s == 0:
+            # config V: the shared 2D outputs are seeded independently of the rank and of the assignment, so that the reduced
+            # IoU counts of a scene set do not depend on the sharding policy (checked by the two-rank test)
+            vlm_jobs.append(gen_pool.submit(syn.make_vlm_outputs, cfg, cfg.num_views, 5557 if val_mode else seed))
+        else:
+            vlm_jobs.append(None)
+    gen_pool.shutdown(wait=False)
     for s, (seed, npts) in enumerate(todo):
         log(f"rank {rank}: generating synthetic scene {s + 1}/{len(todo)} ({cfg.name}, {npts} points)")
         c = dataclasses.replace(cfg, num_points=npts) if npts != cfg.num_points else cfg
-        sc = syn.make_scene(c, seed)
+        sc = scene_jobs[s].result()
+        scene_jobs[s] = None                              # (host copies go once uploaded)
         if cfg.dense_features:
-            feat = syn.make_dense_feature_maps(cfg, cfg.num_views, seed)
-            text = np.random.default_rng(seed).normal(size=(cfg.num_classes, cfg.feat_dim)).astype(np.float32)
+            feat, text = vlm_jobs[s].result()
+            vlm_jobs[s] = None
             vlm_np = {"text_embed": text, "logit_scale": np.float32(1 / 0.07), "dense": feat}
             vlms.append(pl.DenseFeatureVLM(feat, text, 1 / 0.07, dev))
         elif val_mode and shared_vlm is not None:
             vlms.append(shared_vlm)                       # config V: one set of synthetic 2D outputs serves every scene (the
             vlm_np = vlm_np0                              # geometry, hence every kernel's work, differs per scene)
         else:
-            # config V: the shared 2D outputs are seeded independently of the rank and of the assignment, so that the reduced
-            # IoU counts of a scene set do not depend on the sharding policy (checked by the two-rank test)
-            vlm_np = syn.make_vlm_outputs(cfg, cfg.num_views, 5557 if val_mode else seed)
+            vlm_np = vlm_jobs[s].result()
+            vlm_jobs[s] = None
             vlms.append(pl.SyntheticVLM(vlm_np, dev))
             shared_vlm = vlms[-1]
         if s == 0:
@@ -776,6 +832,7 @@ def main():
             return _step(i, stage)
 
     timeline = [] if os.environ.get("GP_BENCH_TIMELINE") == "1" else None
+    last_out = {"capture": False}                       # --dump-outputs: what the last timed step handed its caller
     student_end = {}
 
     def _lift_ahead(i, after=None):
@@ -832,8 +889,10 @@ def main():
                     streams[1].wait_event(pending[i + 1][4])
                 host_t["hook"] += time.perf_counter() - t_h
             feats = hp.refine(batch, F, after_student=hook, prepared=prep, classify_text=(text, scale))
-            hp.classify_and_count({"scene_features": feats, "text_features": text, "logit_scale": scale},
-                                  batch.scene_label, cfg.num_classes, cfg.ignore_ids, counts)
+            pred, zero = hp.classify_and_count({"scene_features": feats, "text_features": text, "logit_scale": scale},
+                                               batch.scene_label, cfg.num_classes, cfg.ignore_ids, counts)
+            if last_out["capture"]:
+                last_out.update(scene_features=feats, text_features=text, pred=pred, zero=zero)
         return batch
 
     def _step(i, stage=None):
@@ -854,8 +913,10 @@ def main():
         feats = hp.refine(batch, F, classify_text=(text, scale))
         if stage:
             stage.mark("refine: mean+student+knn+affinity+pool+gather")
-        hp.classify_and_count({"scene_features": feats, "text_features": text, "logit_scale": scale},
-                              batch.scene_label, cfg.num_classes, cfg.ignore_ids, counts)
+        pred, zero = hp.classify_and_count({"scene_features": feats, "text_features": text, "logit_scale": scale},
+                                           batch.scene_label, cfg.num_classes, cfg.ignore_ids, counts)
+        if last_out["capture"]:
+            last_out.update(scene_features=feats, text_features=text, pred=pred, zero=zero)
         if stage:
             stage.mark("classify+iou")
         hp.stage_mark = None
@@ -900,8 +961,10 @@ def main():
     for i in range(n_local):
         t_s = time.perf_counter()
         pool_timer.enabled = conv_timer.enabled = timers_on and i % max(args.time_every, 1) == 0
+        last_out["capture"] = args.dump_outputs is not None and i + 1 == n_local
         last = step(i, prefetch=i + 1 < n_local)
         host_t["step"] += time.perf_counter() - t_s
+    last_out["capture"] = False
     host_t["blocked"], host_t["readbacks"] = ops.READBACK["seconds"], ops.READBACK["calls"]
     join_streams()                                    # every scene's histogram atomics precede the collective
     hp.pool_chain_check()                             # (--pool-mode mfma_chain: the abort words of every timed scene's launch; else nothing pending)
@@ -946,6 +1009,8 @@ def main():
         busy_all = bt.cpu().tolist()
 
     if rank == 0:
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, last_out, counts)
         Nv = hp.stats["Nv"]
         D = cfg.feat_dim
         per_row = 2 * D * 4 + 96 * 8                      # algorithmic bytes per voxel row and application of A
@@ -955,72 +1020,76 @@ def main():
         pool_ms = tot_ms / n_launch                       # mean launch duration and mean algorithmic bytes per launch over the
         pool_bytes_mean = tot_rows / n_launch * per_row   # timed launches (scenes differ in size): achieved = their ratio
         p10, p50, p90 = pool_timer.percentiles()
-        # the same launches with nothing else on the GPU (with --streams 2 the timed region overlaps the pooling
-        # of one scene with the loader/lift kernels of the next, which share its L2 and HBM bandwidth): one warm pass
-        # (operator build, allocator, clocks), then three timed passes; the median pass is reported
-        hp._pool(*hp._last_pool_inputs, plan=hp._last_pool_plan)
-        hp.pool_chain_check()                    # (chained launches of these isolated passes: read and forget their operators)
-        torch.cuda.synchronize()
-        alone = []
-        for _ in range(3):
-            pool_timer.events, pool_timer.enabled = [], True
+        pool_bytes = Nv * per_row * (args.pool_iters if hp.stats["pool_kernel"] == "cs_chain_kernel" else 1)   # per LAUNCH
+        alone, pool_ms_alone, ceiling, conv_ceil = [], float("nan"), None, None
+        if args.full:                                     # (--full: the figures below take runs of their own)
+            # the same launches with nothing else on the GPU (with --streams 2 the timed region overlaps the pooling
+            # of one scene with the loader/lift kernels of the next, which share its L2 and HBM bandwidth): one warm pass
+            # (operator build, allocator, clocks), then three timed passes; the median pass is reported
             hp._pool(*hp._last_pool_inputs, plan=hp._last_pool_plan)
             hp.pool_chain_check()                    # (chained launches of these isolated passes: read and forget their operators)
             torch.cuda.synchronize()
-            pool_timer.enabled = False
-            alone.append(pool_timer.mean_ms())
-        pool_ms_alone = float(np.median(alone))
-        pool_bytes = Nv * per_row * (args.pool_iters if hp.stats["pool_kernel"] == "cs_chain_kernel" else 1)   # per LAUNCH
-        # the access pattern's own ceiling: the SAME launches with the LDS fragment reads, the MFMAs and the
-        # weight-fragment DMA switched off (tuning bits 0 and 3 of the kernel): every union row is still gathered into LDS through
-        # the same ring at the same occupancy and every output row is still stored.  Results of these passes are garbage; every
-        # later pass recomputes its scene from the inputs.
-        ceiling = None
-        if hp.stats["pool_kernel"] == "cs_pool_kernel":
-            from geopurify_amd import _lib
-            lib = _lib.load()
-            lib.gp_debug_set(4, 9)
-            try:
+            alone = []
+            for _ in range(3):
+                pool_timer.events, pool_timer.enabled = [], True
                 hp._pool(*hp._last_pool_inputs, plan=hp._last_pool_plan)
                 hp.pool_chain_check()                    # (chained launches of these isolated passes: read and forget their operators)
                 torch.cuda.synchronize()
-                cl = []
-                for _ in range(3):
-                    pool_timer.events, pool_timer.enabled = [], True
+                pool_timer.enabled = False
+                alone.append(pool_timer.mean_ms())
+            pool_ms_alone = float(np.median(alone))
+            # the access pattern's own ceiling: the SAME launches with the LDS fragment reads, the MFMAs and the
+            # weight-fragment DMA switched off (tuning bits 0 and 3 of the kernel): every union row is still gathered into LDS through
+            # the same ring at the same occupancy and every output row is still stored.  Results of these passes are garbage; every
+            # later pass recomputes its scene from the inputs.
+            ceiling = None
+            if hp.stats["pool_kernel"] == "cs_pool_kernel":
+                from geopurify_amd import _lib
+                lib = _lib.load()
+                lib.gp_debug_set(4, 9)
+                try:
                     hp._pool(*hp._last_pool_inputs, plan=hp._last_pool_plan)
                     hp.pool_chain_check()                    # (chained launches of these isolated passes: read and forget their operators)
                     torch.cuda.synchronize()
-                    pool_timer.enabled = False
-                    cl.append(pool_timer.mean_ms())
-            finally:
-                lib.gp_debug_set(4, 0)
-            c_ms = float(np.median(cl))
-            ceiling = {"avg_launch_ms": round(c_ms, 4), "passes_ms": [round(a, 4) for a in cl],
-                       "frac": round(pool_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                       "frac_isolated_over_ceiling": round(c_ms / pool_ms_alone, 4),
-                       "what": "the isolated launches repeated with the fragment reads, the MFMAs and the weight-fragment DMA switched "
-                               "off: union rows gathered into the LDS ring and output rows stored, nothing else (same grid, ring, occupancy)"}
-        try:
-            conv_ceil = conv_ceilings(hp, dev) if cfg.feat_dim == 512 else None
-        except Exception as e:                            # an extra: never lose the headline line over it
-            conv_ceil = {"error": repr(e)}
+                    cl = []
+                    for _ in range(3):
+                        pool_timer.events, pool_timer.enabled = [], True
+                        hp._pool(*hp._last_pool_inputs, plan=hp._last_pool_plan)
+                        hp.pool_chain_check()                    # (chained launches of these isolated passes: read and forget their operators)
+                        torch.cuda.synchronize()
+                        pool_timer.enabled = False
+                        cl.append(pool_timer.mean_ms())
+                finally:
+                    lib.gp_debug_set(4, 0)
+                c_ms = float(np.median(cl))
+                ceiling = {"avg_launch_ms": round(c_ms, 4), "passes_ms": [round(a, 4) for a in cl],
+                           "frac": round(pool_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                           "frac_isolated_over_ceiling": round(c_ms / pool_ms_alone, 4),
+                           "what": "the isolated launches repeated with the fragment reads, the MFMAs and the weight-fragment DMA switched "
+                                   "off: union rows gathered into the LDS ring and output rows stored, nothing else (same grid, ring, occupancy)"}
+            try:
+                conv_ceil = conv_ceilings(hp, dev) if cfg.feat_dim == 512 else None
+            except Exception as e:                            # an extra: never lose the headline line over it
+                conv_ceil = {"error": repr(e)}
         achieved = tot_rows * per_row / (tot_ms * 1e-3) / 1e9      # all timed launches, each priced by its own voxel count
-        # per-stage breakdown from a ONE-stream side pass (stage marks are meaningless while two scenes interleave)
-        stage = StageTimer()
-        side = min(2, max(args.scenes, 1))
-        for i in range(side):
-            step(i, stage, stream=streams[0])
-        torch.cuda.synchronize()
-        stages = stage.table()
-        # per-stage roofline: the same pass once more with marks inside the loader and refine
-        fine = StageTimer(fine=True)
-        fb = [step(i, fine, stream=streams[0]) for i in range(side)]
-        torch.cuda.synchronize()
-        fine_ms = {k: v / side for k, v in fine.table().items()}
-        n_pts = float(np.mean([int(b.scene_coords.shape[0]) for b in fb]))
-        n_vis = float(np.mean([sum(int(v.pt.shape[0]) for v in b.views) for b in fb]))
-        n_views = float(np.mean([len(b.views) for b in fb]))
-        stage_roof = stage_rooflines(fine_ms, n_pts, hp.stats["Nv"], n_views, n_vis, cfg, args.pool_iters, D)
+        stages, stage_roof, side = {}, None, 0
+        if args.full:
+            # per-stage breakdown from a ONE-stream side pass (stage marks are meaningless while two scenes interleave)
+            stage = StageTimer()
+            side = min(2, max(args.scenes, 1))
+            for i in range(side):
+                step(i, stage, stream=streams[0])
+            torch.cuda.synchronize()
+            stages = stage.table()
+            # per-stage roofline: the same pass once more with marks inside the loader and refine
+            fine = StageTimer(fine=True)
+            fb = [step(i, fine, stream=streams[0]) for i in range(side)]
+            torch.cuda.synchronize()
+            fine_ms = {k: v / side for k, v in fine.table().items()}
+            n_pts = float(np.mean([int(b.scene_coords.shape[0]) for b in fb]))
+            n_vis = float(np.mean([sum(int(v.pt.shape[0]) for v in b.views) for b in fb]))
+            n_views = float(np.mean([len(b.views) for b in fb]))
+            stage_roof = stage_rooflines(fine_ms, n_pts, hp.stats["Nv"], n_views, n_vis, cfg, args.pool_iters, D)
         pairs = int((hp.stats["nbr_map"] >= 0).sum().item())
         flops = student.flops(pairs, Nv)
         if val_mode:
@@ -1053,17 +1122,18 @@ def main():
                          "algorithmic_bytes_per_launch": int(round(pool_bytes_mean)), "avg_launch_ms": round(pool_ms, 5),
                          "launches": n_launch, "timed_every_nth_scene": args.time_every,
                          "launch_ms_p10": round(p10, 5), "launch_ms_p50": round(p50, 5), "launch_ms_p90": round(p90, 5),
-                         "avg_launch_ms_isolated": round(pool_ms_alone, 4),
-                         "isolated_passes_ms": [round(a, 4) for a in alone],
-                         "frac_isolated": round(pool_bytes / (pool_ms_alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "gather_store_ceiling": ceiling,
+                         **({"avg_launch_ms_isolated": round(pool_ms_alone, 4),
+                             "isolated_passes_ms": [round(a, 4) for a in alone],
+                             "frac_isolated": round(pool_bytes / (pool_ms_alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             "gather_store_ceiling": ceiling} if args.full else {}),
                          "note": "achieved = algorithmic_bytes_per_launch / avg_launch_ms, both means over the launches of the timed "
-                                 "region (HIP events around every launch); _isolated: the last scene's launches (Nv in config.workload) "
-                                 "repeated with nothing else on the GPU (one warm pass, then the median of three passes)"},
-            "roofline_conv": dict(conv_roofline(conv_timer) or {}, ceilings=conv_ceil) or None,
-            "roofline_stages": stage_roof,
-            "stages_ms_per_scene": {k: round(v / side, 3) for k, v in stages.items()},
-            "stages_note": f"one-stream side pass over {side} scene(s) after the timed region",
+                                 "region (HIP events around every launch)" + (
+                                     "; _isolated: the last scene's launches (Nv in config.workload) repeated with nothing else on the GPU "
+                                     "(one warm pass, then the median of three passes)" if args.full else "")},
+            "roofline_conv": (dict(conv_roofline(conv_timer) or {}, ceilings=conv_ceil) or None) if args.full else conv_roofline(conv_timer),
+            **({"roofline_stages": stage_roof,
+                "stages_ms_per_scene": {k: round(v / side, 3) for k, v in stages.items()},
+                "stages_note": f"one-stream side pass over {side} scene(s) after the timed region"} if args.full else {}),
             "student": {"pairs": pairs, "gflop_per_scene": round(flops / 1e9, 1)},
             "host_ms_per_scene": {"enqueue_total": round(host_t["step"] / max(n_local, 1) * 1e3, 3),
                                   "look_ahead_hook": round(host_t["hook"] / max(n_local, 1) * 1e3, 3),
@@ -1081,7 +1151,7 @@ def main():
             out["shard"] = dict(shard, busy_s_per_rank=[round(b, 4) for b in busy_all],
                                 imbalance_max_over_mean=round(max(busy_all) / (sum(busy_all) / len(busy_all)), 4))
         log(f"gpu: {out['value']} scenes/s, {out['ms_per_step']} ms/scene; pooling {pool_ms:.3f} ms/launch")
-        if world == 1 and args.pool_iters != 3 and not val_mode:
+        if args.full and world == 1 and args.pool_iters != 3 and not val_mode:
             # BASELINE.json words config 1 as "affinity pooling 3 iters"; the reference code applies A 19 times
             # (affinity_module.py:1584-1587), which is what `value` is measured on.  Same scenes with 3 applications:
             try:
@@ -1099,12 +1169,12 @@ def main():
                 out["variant_pool_iters_3"] = {"value": None, "error": repr(e)}
             finally:
                 hp.num_iters = args.pool_iters
-        if not args.no_train and world == 1 and cfg.feat_dim == 512 and not val_mode:
+        if args.full and not args.no_train and world == 1 and cfg.feat_dim == 512 and not val_mode:
             try:                                  # an extra; never lose the headline line over it
                 out["training_step"] = training_step_rate(last, dev, sd)
             except Exception as e:
                 out["training_step"] = {"value": None, "error": repr(e)}
-        if args.api == "both" and world == 1 and not val_mode and not cfg.dense_features and args.scenes:
+        if args.full and args.api == "both" and world == 1 and not val_mode and not cfg.dense_features and args.scenes:
             try:                                  # an extra; never lose the headline line over it
                 log("drop-in entry point: evaluate_scene(20-tuple of CPU tensors)")
                 with torch.cuda.stream(streams[0]):
@@ -1113,7 +1183,7 @@ def main():
                 out["api_tuple"] = api_tuple_rate(bts, vlms, sd, cfg, args.pool_iters, dev, side_stream=streams[0])
             except Exception as e:
                 out["api_tuple"] = {"value": None, "error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("cpu baseline (the oracle on the host cores)")
             try:
                 out["cpu_baseline"] = cpu_baseline(scenes[0], vlm_np0, sd, rigids[0], scene_cfgs[0], args.pool_iters, args.cpu_seconds,

@@ -11,7 +11,7 @@ for rep in 1 2; do
   for e in "$@"; do
     i=$((i+1))
     [ "$e" = "-" ] && e=""
-    env $e timeout -k 10 300 python bench.py --no-cpu-baseline --no-train --steps 8 > $O/api_${i}_$rep.json 2> $O/api_${i}_$rep.err || { tail -5 $O/api_${i}_$rep.err; exit 1; }
+    env $e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-train --steps 8 > $O/api_${i}_$rep.json 2> $O/api_${i}_$rep.err || { tail -5 $O/api_${i}_$rep.err; exit 1; }
     python - "$O/api_${i}_$rep.json" "$e" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

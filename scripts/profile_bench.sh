@@ -9,8 +9,8 @@ R=$GRAFT_REPO_ROOT
 T=${1:-r02}
 O=$R/gpurun_out/$T
 mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-train > $O/bench_under_rocprof.json 2> $O/stats.log
-B="python3 $R/bench.py --steps 2 --warmup 1 --scenes 1 --streams 1 --no-cpu-baseline --no-train"
+rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-train > $O/bench_under_rocprof.json 2> $O/stats.log
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --scenes 1 --streams 1 --no-cpu-baseline --no-train"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o c --output-format csv -- $B > $O/fetch.json 2> $O/fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o c --output-format csv -- $B > $O/write.json 2> $O/write.log
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum -d $O/tcc -o c --output-format csv -- $B > $O/tcc.json 2> $O/tcc.log

@@ -165,7 +165,7 @@ def test_bench_two_ranks_share_one_gpu_counts_are_the_sum(tmp_path):
     env = dict(os.environ, GP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1",
-           "--config", "T", "--scenes", str(nscn), "--streams", "2", "--no-cpu-baseline", "--no-train"]
+           "--config", "T", "--scenes", str(nscn), "--streams", "2", "--no-cpu-baseline", "--no-train", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
