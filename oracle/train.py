@@ -55,9 +55,19 @@ def sample_pairs(F_teacher, neighbor_indices, anchor_indices, num_negatives):
     return positive, torch.cat([macro, micro], dim=1), sim
 
 
-def student_train_forward(X, nbr_map, params, bn_state, num_blocks, momentum=0.1):
+def student_train_forward(X, nbr_map, params, bn_state, num_blocks, momentum=0.1, relu_masks=None, relu_inputs=None):
     """AffinityPredictor.forward with BatchNorm in training mode.  params: dict of leaf tensors (requires_grad);
-    bn_state: dict prefix -> (running_mean, running_var) updated in place like nn.BatchNorm1d."""
+    bn_state: dict prefix -> (running_mean, running_var) updated in place like nn.BatchNorm1d.
+    relu_masks: None, or one bool [Nv, C] tensor per ReLU in forward order (input layer, then norm1 and norm2 + identity of every
+    block): ReLU(x) becomes x * mask -- the decisions of another implementation, for comparing with one whose decisions inside its
+    own rounding noise went the other way.  relu_inputs: a list that receives every ReLU's input (detached), in the same order."""
+    masks = iter(relu_masks) if relu_masks is not None else None
+
+    def relu(x):
+        if relu_inputs is not None:
+            relu_inputs.append(x.detach())
+        return F.relu(x) if masks is None else x * next(masks).to(x.dtype)
+
     def bn(x, prefix):
         rm, rv = bn_state[prefix]
         return F.batch_norm(x, rm, rv, params[prefix + ".bn.weight"], params[prefix + ".bn.bias"], training=True,
@@ -73,12 +83,12 @@ def student_train_forward(X, nbr_map, params, bn_state, num_blocks, momentum=0.1
                 out = out.index_add(0, rows, x[m[rows]] @ W[k])
         return out
 
-    out = F.relu(bn(conv(X, "input_layer.0.kernel"), "input_layer.1"))
+    out = relu(bn(conv(X, "input_layer.0.kernel"), "input_layer.1"))
     for i in range(num_blocks):
         idt = out
-        o = F.relu(bn(conv(out, f"res_blocks.{i}.conv1.kernel"), f"res_blocks.{i}.norm1"))
+        o = relu(bn(conv(out, f"res_blocks.{i}.conv1.kernel"), f"res_blocks.{i}.norm1"))
         o = bn(conv(o, f"res_blocks.{i}.conv2.kernel"), f"res_blocks.{i}.norm2")
-        out = F.relu(o + idt)
+        out = relu(o + idt)
     return out @ params["output_layer.kernel"]
 
 
@@ -143,18 +153,23 @@ def lr_factor(step_index, warmup_iters, main_iters, eta_min_ratio=1e-3):
 
 
 def train_step_oracle(sd, X_vox, coords_vox, sample_to_voxel, point_to_batch, num_anchors, num_negatives, temperature,
-                      num_blocks, base_lr=1e-4, weight_decay=1e-5, step=1, opt_state=None, lr_factor_value=1.0):
+                      num_blocks, base_lr=1e-4, weight_decay=1e-5, step=1, opt_state=None, lr_factor_value=1.0, dtype=torch.float32,
+                      relu_masks=None):
     """One optimisation step on one scene.  sd: ME-layout state_dict (fp32); X_vox [Nv_s, Cin]; coords_vox int [Nv_s,3].
-    Returns dict(loss, grads, params (updated), bn (updated running stats), embeddings)."""
+    dtype: the precision of the whole step -- parameters, BatchNorm state, inputs, InfoNCE and the AdamW update
+    (torch.float64: the reference the fp32-class device step is measured against).  relu_masks: see student_train_forward.
+    Returns dict(loss, grads, params (updated), bn (updated running stats), embeddings, relu_inputs)."""
     names = [k for k in sd if k.endswith("kernel") or k.endswith(".bn.weight") or k.endswith(".bn.bias")]
-    params = {k: sd[k].clone().float().requires_grad_(True) for k in names}
-    bn_state = {k[:-len(".bn.running_mean")]: (sd[k].clone().float(), sd[k.replace("running_mean", "running_var")].clone().float())
+    params = {k: sd[k].clone().to(dtype).requires_grad_(True) for k in names}
+    bn_state = {k[:-len(".bn.running_mean")]: (sd[k].clone().to(dtype), sd[k.replace("running_mean", "running_var")].clone().to(dtype))
                 for k in sd if k.endswith(".bn.running_mean")}
     nbr_map = o_student.build_kernel_map(np.asarray(coords_vox))
-    E = student_train_forward(X_vox.float(), nbr_map, params, bn_state, num_blocks)
+    relu_inputs = []
+    E = student_train_forward(X_vox.to(dtype), nbr_map, params, bn_state, num_blocks, relu_masks=relu_masks, relu_inputs=relu_inputs)
     loss = info_nce(E[sample_to_voxel], point_to_batch, num_anchors, num_negatives, temperature)
     grads_list = torch.autograd.grad(loss, [params[k] for k in names])
     grads = dict(zip(names, grads_list))
     state = {} if opt_state is None else opt_state
     new = adamw_step({k: v.detach() for k, v in params.items()}, grads, state, step, base_lr, weight_decay, lr_factor_value)
-    return {"loss": float(loss.detach()), "grads": grads, "params": new, "bn": bn_state, "embeddings": E.detach(), "opt_state": state}
+    return {"loss": float(loss.detach()), "grads": grads, "params": new, "bn": bn_state, "embeddings": E.detach(), "opt_state": state,
+            "relu_inputs": relu_inputs}

@@ -505,3 +505,485 @@ def test_two_rank_sync_batchnorm_training_step(ops):
            "--master-port", str(port), os.path.join(root, "tests", "syncbn_worker.py")]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, (out.stdout[-3000:], out.stderr[-3000:])
+
+
+# ------------------------------------------------------------------------------------------ against fp64 at the product's width
+U32 = 2.0 ** -24                                                          # fp32 unit roundoff
+
+
+def _device_step(ops, sd, coords, X, s2v, p2b, A, Nn):
+    """one StudentTrainer step (forward, backward, AdamW) in the order of the reference's rows: ((loss, grads, embeddings, state_dict),
+    the fp32 output of every ReLU in forward order).  A layer whose fp32 output the step does not keep (want_f32=False: its split planes
+    are the same either way) is asked for it here, so that its ReLU decisions can be read."""
+    from geopurify_amd.training import StudentTrainer
+    tr = StudentTrainer(sd, "cuda", base_lr=1e-3, weight_decay=1e-2)
+    cs_ref = dev(coords.astype(np.int32))
+    perm, rank = ops.morton_order(cs_ref)
+    cs = cs_ref[perm.long()].contiguous()
+    Xd = torch.zeros((len(coords), tr.cin_pad), device="cuda")
+    Xd[:, :X.shape[1]] = dev(X)[perm.long()]
+    nbr_map = ops.kernel_map_build(ops.grid_build(cs), cs)
+    outs = []
+    apply = ops.bn_train_apply
+
+    def keeping_apply(*a, **k):
+        k["want_f32"] = True
+        out, sp = apply(*a, **k)
+        outs.append(out)
+        return out, sp
+    ops.bn_train_apply = keeping_apply
+    try:
+        loss, grads, E = tr.forward_backward(Xd, nbr_map, rank.long()[dev(s2v)].contiguous(), dev(p2b), A, Nn)
+    finally:
+        ops.bn_train_apply = apply
+    grads = {k: v.cpu() for k, v in grads.items()}
+    tr.optimizer_step({k: v.cuda() for k, v in grads.items()})
+    r = rank.long().cpu()
+    return (float(loss), grads, E.cpu()[r], {k: v.cpu() for k, v in tr.state_dict().items()}), [o.cpu()[r] for o in outs]
+
+
+def _fp64_step_with_device_relu(sd, coords, X, s2v, p2b, A, Nn, num_blocks, outs):
+    """the fp64 oracle step with the device's ReLU decisions (a decision inside the rounding noise of the pre-activation is not a
+    precision question, but it moves one dz by O(1) and a layer's gradients by percents).  The decisions may differ from fp64's only
+    where fp64's pre-activation is within 4x the device's own largest pre-activation error of that layer -- measured where the device
+    passed the value through, out = its pre-activation.  Returns (reference, number of differing decisions)."""
+    masks = [o > 0 for o in outs]
+    ref = o_train.train_step_oracle(sd, X, coords, s2v, p2b, A, Nn, 0.07, num_blocks, base_lr=1e-3, weight_decay=1e-2,
+                                    dtype=torch.float64, relu_masks=masks)
+    assert len(ref["relu_inputs"]) == len(masks) == 1 + 2 * num_blocks
+    flips = 0
+    for i, (m, pre, o) in enumerate(zip(masks, ref["relu_inputs"], outs)):
+        pre_err = float((o.double() - pre)[m].abs().max())
+        differ = m != (pre > 0)
+        assert (pre[differ].abs() <= 4 * pre_err).all(), (i, pre_err, pre[differ].abs().max())
+        flips += int(differ.sum())
+    return ref, flips
+
+
+def _step_errors(ref, loss, grads, E, new, cin):
+    """relative errors of one device step against the fp64 oracle: loss, embeddings and every gradient over the reference's maximum;
+    AdamW-updated weights (where |g| > 1e-5) and running statistics absolute"""
+    err = {"loss": abs(loss - ref["loss"]) / abs(ref["loss"]),
+           "embeddings": float((E.double() - ref["embeddings"]).abs().max() / ref["embeddings"].abs().max())}
+    for name, g_ref in ref["grads"].items():
+        g = grads[name]
+        if name == "input_layer.0.kernel":
+            assert float(g[:, cin:].abs().max()) == 0.0                   # padded input channels never receive gradient
+            g = g[:, :cin]
+        err["grad:" + name] = float((g.double() - g_ref).abs().max() / g_ref.abs().max())
+        d = (new[name].double() - ref["params"][name]).abs()
+        well = g_ref.abs() > 1e-5
+        err["param:" + name] = float(d[well].max())
+        err["param_any:" + name] = float(d.max() / o_train.PARAM_GROUP_LR[o_train.param_group(name)])
+    for prefix, (rm, rv) in ref["bn"].items():
+        err["running:" + prefix] = max(float((new[prefix + ".bn.running_mean"].double() - rm).abs().max()),
+                                       float((new[prefix + ".bn.running_var"].double() - rv).abs().max()))
+    return err
+
+
+# errors of the product-width step against fp64, measured on the MI355X (2430 voxels), the largest of eight runs -- the step is not
+# bitwise repeatable, its gradients' errors vary by ~20 % from run to run and the loss's by an ulp: relative to the reference's maximum
+# for the loss, the embeddings and the gradients; absolute for the AdamW-updated weights where |g| > 1e-5 and for the running statistics.
+# No ReLU decision of the step differed from fp64's.  The same step with f16-only weights, against fp64 with its own decisions (600 of
+# them differ from fp64's, all inside its pre-activation error): 3.5e-4 .. 6.6e-4 on the gradients, 3.1e-4 on the embeddings.
+PRODUCT_WIDTH_MEASURED = {
+    "loss": 2.227e-07,
+    "embeddings": 8.052e-07,
+    "grad:input_layer.0.kernel": 1.592e-06,
+    "param:input_layer.0.kernel": 4.378e-09,
+    "grad:input_layer.1.bn.weight": 1.249e-06,
+    "param:input_layer.1.bn.weight": 9.172e-08,
+    "grad:input_layer.1.bn.bias": 1.301e-06,
+    "param:input_layer.1.bn.bias": 2.885e-08,
+    "grad:res_blocks.0.conv1.kernel": 1.518e-06,
+    "param:res_blocks.0.conv1.kernel": 4.725e-09,
+    "grad:res_blocks.0.norm1.bn.weight": 1.266e-06,
+    "param:res_blocks.0.norm1.bn.weight": 1.340e-07,
+    "grad:res_blocks.0.norm1.bn.bias": 1.421e-06,
+    "param:res_blocks.0.norm1.bn.bias": 1.479e-08,
+    "grad:res_blocks.0.conv2.kernel": 1.317e-06,
+    "param:res_blocks.0.conv2.kernel": 4.386e-09,
+    "grad:res_blocks.0.norm2.bn.weight": 1.298e-06,
+    "param:res_blocks.0.norm2.bn.weight": 1.197e-07,
+    "grad:res_blocks.0.norm2.bn.bias": 1.091e-06,
+    "param:res_blocks.0.norm2.bn.bias": 2.702e-08,
+    "grad:res_blocks.1.conv1.kernel": 1.736e-06,
+    "param:res_blocks.1.conv1.kernel": 4.400e-09,
+    "grad:res_blocks.1.norm1.bn.weight": 1.399e-06,
+    "param:res_blocks.1.norm1.bn.weight": 1.297e-07,
+    "grad:res_blocks.1.norm1.bn.bias": 1.144e-06,
+    "param:res_blocks.1.norm1.bn.bias": 2.817e-08,
+    "grad:res_blocks.1.conv2.kernel": 1.479e-06,
+    "param:res_blocks.1.conv2.kernel": 4.395e-09,
+    "grad:res_blocks.1.norm2.bn.weight": 1.236e-06,
+    "param:res_blocks.1.norm2.bn.weight": 1.257e-07,
+    "grad:res_blocks.1.norm2.bn.bias": 7.498e-07,
+    "param:res_blocks.1.norm2.bn.bias": 1.552e-08,
+    "grad:output_layer.kernel": 1.236e-06,
+    "param:output_layer.kernel": 2.284e-08,
+    "running:input_layer.1": 1.394e-07,
+    "running:res_blocks.0.norm1": 1.288e-07,
+    "running:res_blocks.0.norm2": 1.325e-07,
+    "running:res_blocks.1.norm1": 1.280e-07,
+    "running:res_blocks.1.norm2": 1.363e-07,
+}
+# every bound is 3x its measured error: the gradients' all below 5.3e-6, a hundredth of the 5e-4 ceiling (the f16-only step misses each
+# gradient's bound by 104x or more)
+PRODUCT_WIDTH_BOUNDS = {k: 3 * v for k, v in PRODUCT_WIDTH_MEASURED.items()}
+
+
+def test_student_training_step_product_width_vs_fp64(ops, monkeypatch):
+    """BASELINE config 5's student width (518 -> 512 x 2 blocks -> 128) through one training step against the fp64 oracle: col_tiles = 2
+    pairs, the step-blocked transpose_flip weights of the data gradient, conv_wgrad_f16x3 with cout = 512, the 512 -> 128 output layer's
+    identity-plan weight gradient (operand zero-padded to 256 columns), several convolution chunks.  The bounds separate fp32-class from
+    fp16-class results: the same step with f16-only weights (the lo planes dropped) must miss every gradient's bound by 2x.
+    The fp64 reference takes the device's ReLU decisions (_fp64_step_with_device_relu): this step has pre-activations 2e-7 from zero,
+    and a decision inside fp32 rounding noise would move the gradients by percents whichever way is right -- seed 5 of the autograd test
+    above has one in its input layer at width 512."""
+    coords, sd, X, s2v, p2b, A, Nn = _setup_student(512, 2, seed=7, cin=518, nvox=3000)
+    chunks = []
+    build = ops.conv_pairs_build
+
+    def counting_build(nbr_map, *a, **k):
+        cp = build(nbr_map, *a, **k)
+        if nbr_map.shape[0] == 27:
+            chunks.append(cp.num_chunks)
+        return cp
+    monkeypatch.setattr(ops, "conv_pairs_build", counting_build)
+    old_target, ops.CONV_TARGET_TILES = ops.CONV_TARGET_TILES, 32
+    try:
+        got, outs = _device_step(ops, sd, coords, X, s2v, p2b, A, Nn)
+        split = ops.conv_weights_split
+
+        def f16_only(w, *a, **k):
+            hi, lo = split(w, *a, **k)
+            return hi, torch.zeros_like(lo)
+        monkeypatch.setattr(ops, "conv_weights_split", f16_only)
+        mutant, outs_m = _device_step(ops, sd, coords, X, s2v, p2b, A, Nn)
+        monkeypatch.setattr(ops, "conv_weights_split", split)
+    finally:
+        ops.CONV_TARGET_TILES = old_target
+    assert chunks and min(chunks) > 1, chunks
+    ref, flips = _fp64_step_with_device_relu(sd, coords, X, s2v, p2b, A, Nn, 2, outs)
+    assert flips <= 10, flips          # an fp32-class forward turns over a few decisions at most (none measured; the f16-only one 600)
+    err = _step_errors(ref, *got, X.shape[1])
+    for k, e in err.items():
+        if k.startswith("param_any:"):
+            # where |g| is near the 1e-8 epsilon the first AdamW step is ill-conditioned and only bounded by lr: opposite signs at most
+            assert e <= 2.02e-3, (k, e)
+        else:
+            assert e < PRODUCT_WIDTH_BOUNDS[k], (k, e, PRODUCT_WIDTH_BOUNDS[k])
+    # the bounds must separate fp32-class from fp16-class results: the step with f16-only weights, against fp64 with ITS ReLU decisions
+    # (its errors are then precision alone), misses every gradient bound by 2x or more
+    ref_m, _ = _fp64_step_with_device_relu(sd, coords, X, s2v, p2b, A, Nn, 2, outs_m)
+    err_m = _step_errors(ref_m, *mutant, X.shape[1])
+    for k, e in err_m.items():
+        if k.startswith("grad:"):
+            assert e >= 2 * PRODUCT_WIDTH_BOUNDS[k], (k, e, PRODUCT_WIDTH_BOUNDS[k])
+
+
+# ------------------------------------------------------------------------------------------ gather-GEMM direct store (plane_flags bit 4)
+@pytest.mark.parametrize("A,N,D", [(1, 256, 32), (255, 257, 160), (256, 257, 32), (256, 5000, 1088), (257, 5000, 160), (700, 5000, 1088)])
+def test_gather_gemm_direct_store_edges_vs_fp64(ops, A, N, D):
+    """the sampler's anchors x points similarity where the direct store's tiles are partly filled (A not a multiple of 256, A = 1),
+    the point columns padded to a multiple of 256 (N = 257, 5000) and the product's feature width (1088): every element within 2e-6 of
+    fp64, bit-identical to the two-phase form with fp32 partial rows, the padded columns exactly 0, and nothing written into the guard
+    rows behind the A output rows"""
+    torch.manual_seed(A * 7 + N)
+    Fn = F.normalize(torch.randn(N, D), dim=1)
+    anchors = torch.randperm(N)[:A]
+    Np = (N + 255) // 256 * 256
+    Fp = torch.zeros((Np, D))
+    Fp[:N] = Fn
+    hi, lo = ops.split_f16(dev(Fp))
+    pairs = ops.conv_pairs_build(dev(anchors.to(torch.int32)).view(1, -1).contiguous(), chunk_rows=None)
+    assert pairs.num_pairs == A and pairs.nv == A
+    w = (hi.view(1, Np, D), lo.view(1, Np, D))
+    G = 300                                                               # guard rows: more than one partly filled 256-row tile
+    buf = torch.full((A + G, Np), float("nan"), device="cuda")
+    direct = ops.sparse_conv_f16x3(None, pairs, w[0], w[1], x_split=(hi, lo), dense_single_offset=True, out=buf[:A])
+    two = ops.sparse_conv_f16x3(None, pairs, w[0], w[1], x_split=(hi, lo), fp32_partials=True)
+    torch.cuda.synchronize()
+    assert direct.data_ptr() == buf.data_ptr() and buf[A:].isnan().all(), "the direct store wrote behind its A rows"
+    assert torch.equal(direct, two)
+    assert not direct[:, N:].any()
+    ref = Fn[anchors].double() @ Fn.double().t()
+    err = float((direct[:, :N].double().cpu() - ref).abs().max())
+    assert err < 2e-6, err
+
+
+def test_anchor_similarities_padded_view_and_fallbacks_vs_fp64(ops):
+    """training._anchor_similarities on its three paths: N = 257 (gather-GEMM, point rows padded to 512, a [A, N] view of [A, 512]),
+    N < 256 and D % 32 != 0 (torch); all against fp64 of F.normalize"""
+    from geopurify_amd.training import _anchor_similarities
+    torch.manual_seed(13)
+    for N, D, A, padded in ((257, 160, 100, True), (200, 160, 50, False), (1000, 100, 255, False)):
+        Ft = torch.randn(N, D) * torch.rand(N, 1) * 4
+        anchors = torch.randperm(N)[:A]
+        sim = _anchor_similarities(dev(Ft), dev(anchors))
+        assert sim.shape == (A, N)
+        if padded:
+            assert sim.stride(0) == 512 and sim.stride(1) == 1
+        Fn = F.normalize(Ft.double(), dim=1)
+        err = float((sim.double().cpu() - Fn[anchors] @ Fn.t()).abs().max())
+        assert err < 2e-6, (N, D, err)
+
+
+def test_gather_gemm_direct_store_refuses_a_map_with_missing_rows(ops):
+    """plane_flags bit 4 needs a pair for every output row (num_pairs == nv): a one-offset map with a missing row is refused before
+    any launch -- the output buffer stays untouched"""
+    from geopurify_amd._lib import GeoPurifyHipError
+    torch.manual_seed(4)
+    n, d, A = 512, 64, 100
+    hi, lo = ops.split_f16(dev(F.normalize(torch.randn(n, d), dim=1)))
+    m = torch.randperm(n)[:A].to(torch.int32)
+    m[37] = -1
+    pairs = ops.conv_pairs_build(dev(m).view(1, -1).contiguous(), chunk_rows=None)
+    assert pairs.num_pairs == A - 1
+    buf = torch.full((A, n), float("nan"), device="cuda")
+    with pytest.raises(GeoPurifyHipError):
+        ops.sparse_conv_f16x3(None, pairs, hi.view(1, n, d), lo.view(1, n, d), x_split=(hi, lo), dense_single_offset=True, out=buf)
+    torch.cuda.synchronize()
+    assert buf.isnan().all()
+
+
+# ------------------------------------------------------------------------------------------ BatchNorm training kernels against fp64
+def _bn_case(nv, c, ld, seed):
+    g = torch.Generator().manual_seed(seed)
+    y = torch.randn(nv, c, generator=g) * 2 + 0.5
+    if c > 1:
+        y[:, 1] = 1e3 + torch.randn(nv, generator=g)                    # mean ~ 1e3 std: cancellation in E[x^2] - mean^2
+    res = torch.randn(nv, c, generator=g)
+    dout = torch.randn(nv, c, generator=g)
+    gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.1
+    rm, rv = torch.randn(c, generator=g) * 0.1, torch.rand(c, generator=g) + 0.5
+
+    def strided(t):                                                       # rows of ld >= c floats (the kernels read t.stride(0))
+        if ld == c:
+            return dev(t)
+        b = torch.zeros((nv, ld), device="cuda")
+        b[:, :c] = dev(t)
+        return b[:, :c]
+    return y, res, dout, gamma, beta, rm, rv, strided
+
+
+@pytest.mark.parametrize("nv,c,ld", [(1, 512, 512), (255, 128, 128), (257, 512, 512), (20001, 512, 512), (3001, 6, 6), (3001, 256, 260)])
+def test_batchnorm_training_kernels_vs_fp64(ops, nv, c, ld):
+    """col_stats, bn_train_apply (fp32 and split outputs, running statistics), bn_train_backward (plain, beta_mask, split planes),
+    bn_bwd_sums_f64 + bn_bwd_apply against fp64 F.batch_norm autograd -- at one row, ragged row counts, the product's widths, the
+    scalar (c % 4 != 0) path and strided rows.  Bounds are fp32 roundings (u = 2^-24) of each term: the kernels sum in fp64, so a sum of
+    nv terms carries a few u of the sum of its terms' magnitudes, and (y - mean) * invstd carries u of (|y| + |mean|) / sigma
+    (kappa below) -- the column with mean = 1e3 sigma is 1e3 times harder than the others, not a blanket tolerance."""
+    y, res, dout, gamma, beta, rm, rv, strided = _bn_case(nv, c, ld, seed=nv + c)
+    eps, mom = 1e-5, 0.1
+    yd, resd, doutd = strided(y), strided(res), strided(dout)
+    assert yd.stride(0) == ld
+    mean, var = ops.col_stats(yd)
+    y64 = y.double()
+    m64 = y64.mean(0)
+    v64 = ((y64 - m64) ** 2).mean(0)
+    mean_c, var_c = mean.cpu().double(), var.cpu().double()
+    assert ((mean_c - m64).abs() <= U32 * m64.abs() + 1e-12).all()
+    # var = E[y^2] - mean^2 from fp64 sums of 256-row blocks: its rounding (~(256 + nv/256) fp64 units of E[y^2]) is what the 1e3 sigma
+    # column tests -- an fp32 form of the same expression would be 2^-24 * 1e6 = 0.06 off there
+    assert ((var_c - v64).abs() <= 2 * U32 * v64 + (256 + nv / 256 + 4) * 2.0 ** -53 * (m64 ** 2 + v64)).all()
+    if nv == 1:
+        assert torch.equal(mean.cpu(), y[0]) and not var.any()
+    sigma = (v64 + eps).sqrt()
+    ymax = y64.abs().max(0).values
+    kappa = (ymax + m64.abs()) / sigma                                    # magnitude at which xhat is rounded
+    g64, b64 = gamma.double(), beta.double()
+    xhat = (y64 - m64) / sigma
+    pre1 = g64 * xhat + b64 + res.double()
+    pre2 = g64 * xhat + b64
+    tol_out = 8 * U32 * (g64.abs() * kappa + b64.abs() + res.double().abs().max(0).values)
+    # ---- forward: with a residual (the fp32 output and its split planes), without (split planes only, as a layer whose mask comes from y)
+    rmd, rvd = dev(rm), dev(rv)
+    out1, sp1 = ops.bn_train_apply(yd, mean, var, dev(gamma), dev(beta), eps, residual=resd, relu=True, want_split=True, momentum=mom,
+                                   running_mean=rmd, running_var=rvd)
+    out2, sp2 = ops.bn_train_apply(yd, mean, var, dev(gamma), dev(beta), eps, relu=True, want_split=True)
+    o1, o2 = out1.cpu().double(), out2.cpu().double()
+    e_out = max(float(((o1 - pre1.clamp(min=0)).abs() / tol_out).max()), float(((o2 - pre2.clamp(min=0)).abs() / tol_out).max()))
+    assert e_out <= 1.0, e_out
+    for o, sp in ((out1, sp1), (out2, sp2)):
+        assert torch.isfinite(o).all()
+        assert ((sp[0].float() + sp[1].float()) - o).abs().max() <= 2.0 ** -21 * max(float(o.abs().max()), 1e-30)
+    unb = v64 * nv / (nv - 1) if nv > 1 else v64                          # (one row: the biased 0 -- torch refuses a batch of one)
+    rm_ref = (1 - mom) * rm.double() + mom * m64
+    rv_ref = (1 - mom) * rv.double() + mom * unb
+    assert ((rmd.cpu().double() - rm_ref).abs() <= 8 * U32 * (rm.double().abs() + m64.abs())).all()
+    assert ((rvd.cpu().double() - rv_ref).abs() <= 8 * U32 * (rv.double().abs() + unb)).all()
+    # ---- backward.  The ReLU masks are the kernel's own (a mask bit flips where the pre-activation is inside the forward bound -- an
+    # O(1) change of dz that is not the BatchNorm backward's error); elsewhere they equal fp64's
+    M1, M2 = o1 > 0, o2 > 0
+    for M, pre in ((M1, pre1), (M2, pre2)):
+        assert ((M == (pre > 0)) | (pre.abs() <= tol_out)).all()
+
+    def reference(M):
+        dz = dout.double() * M
+        if nv == 1:                                                      # xhat = 0: dbeta = dz, dgamma = 0, dy = 0
+            return torch.zeros_like(dz), torch.zeros(c, dtype=torch.float64), dz[0].clone(), dz
+        yr, gr, br = y64.clone().requires_grad_(True), g64.clone().requires_grad_(True), b64.clone().requires_grad_(True)
+        bn = F.batch_norm(yr, None, None, gr, br, training=True, eps=eps)
+        dy, dg, db = torch.autograd.grad(bn, [yr, gr, br], dz)
+        return dy, dg, db, dz
+
+    f64_sum = (256 + nv / 256 + 4) * 2.0 ** -53                          # an fp64 sum of 256-row blocks, relative to the sum of |terms|
+
+    def tolerances(dz, db_r, dg_r):
+        """dbeta: a sum of exact fp32 terms (dz) in fp64, rounded once to fp32; dgamma: each term dz * xhat carries xhat's rounding
+        (2u kappa) and its own; dy: a few roundings of each of its three terms, whose sums enter divided by nv.  *_64: the fp64 vectors
+        of bn_bwd_sums_f64 (no final fp32 rounding)"""
+        a = dz.abs()
+        xa = xhat.abs()
+        tol_db64 = f64_sum * a.sum(0)
+        tol_dg64 = 2 * U32 * (a * (kappa + xa)).sum(0)
+        tol_db = U32 * db_r.abs() + tol_db64
+        tol_dg = U32 * dg_r.abs() + tol_dg64
+        s1, s2 = a.sum(0) / nv, (a * (kappa + xa)).sum(0) / nv
+        tol_dy = 8 * U32 * g64.abs() / sigma * (a.max(0).values + s1 + (kappa + xa.max(0).values) * s2)
+        return tol_dy, tol_dg, tol_db, tol_dg64, tol_db64
+
+    worst = {}
+    for tag, M, act, bmask in (("act", M1, out1, None), ("beta_mask", M2, None, dev(beta))):
+        dy_r, dg_r, db_r, dz_r = reference(M)
+        tol_dy, tol_dg, tol_db, tol_dg64, tol_db64 = tolerances(dz_r, db_r, dg_r)
+        dy, dg, db, dz = ops.bn_train_backward(doutd, act, yd, mean, var, eps, dev(gamma), want_dz=True, beta_mask=bmask)
+        assert torch.equal(dz.cpu(), dout * M.float())
+        worst[tag + ":dy"] = float(((dy.cpu().double() - dy_r).abs() / (tol_dy + 1e-300)).max())
+        worst[tag + ":dgamma"] = float(((dg.cpu().double() - dg_r).abs() / (tol_dg + 1e-300)).max())
+        worst[tag + ":dbeta"] = float(((db.cpu().double() - db_r).abs() / (tol_db + 1e-300)).max())
+        if nv == 1:
+            assert not dy.any() and not dg.any() and torch.equal(db.cpu(), dz_r[0].float())
+        if c % 4 == 0:                                                    # the split planes (the vector path only): dy * s, a zero row nv
+            sc = torch.empty(2, device="cuda")
+            (sh, sl), dg3, db3, dz3 = ops.bn_train_backward(doutd, act, yd, mean, var, eps, dev(gamma), want_dz=True, dy_scale2=sc,
+                                                            beta_mask=bmask, split=True)
+            assert float(sc[0] * sc[1]) == 1.0 and not sh[nv].any() and not sl[nv].any()
+            assert torch.equal(dg3, dg) and torch.equal(db3, db) and torch.equal(dz3, dz)
+            dys = ((sh[:nv].double() + sl[:nv].double()) * float(sc[1])).cpu()
+            # the planes hold dy to 2^-18 of the column block's bound of max |dy| (a bound up to 2^3 above the true maximum)
+            worst[tag + ":dy_split"] = float(((dys - dy_r).abs() / (tol_dy + 2.0 ** -18 * dy_r.abs().max() + 1e-300)).max())
+        # SyncBatchNorm's pair: fp64 reduction vectors, then the sweep with caller-supplied sums over n_total rows
+        sums = ops.bn_bwd_sums_f64(doutd, act, yd, mean, var, eps, mask_affine=(dev(gamma), bmask) if bmask is not None else None)
+        s = sums.cpu()
+        worst[tag + ":sums"] = max(float(((s[:c] - db_r).abs() / (tol_db64 + 1e-300)).max()),
+                                   float(((s[c:] - dg_r).abs() / (tol_dg64 + 1e-300)).max()))
+        dya = ops.bn_bwd_apply(doutd, act, yd, mean, var, eps, dev(gamma), sums.float(), nv, beta_mask=bmask)
+        worst[tag + ":apply"] = float(((dya.cpu().double() - dy_r).abs() / (tol_dy + 1e-300)).max())
+        assert torch.isfinite(dy).all() and torch.isfinite(dya).all()
+    for k, v in worst.items():
+        assert v <= 1.0, (k, v)
+
+
+# ------------------------------------------------------------------------------------------ weight and data gradients at 512 columns
+def _voxel_map(ops, seed, n):
+    rng = np.random.default_rng(seed)
+    coords = surface_voxels(rng, n)
+    cs_ref = dev(coords.astype(np.int32))
+    perm, _ = ops.morton_order(cs_ref)
+    cs = cs_ref[perm.long()].contiguous()
+    return ops.kernel_map_build(ops.grid_build(cs), cs)
+
+
+@pytest.mark.parametrize("cin_pad", [512, 544])
+def test_conv_weight_gradient_cout512_vs_fp64(ops, cin_pad):
+    """conv_wgrad_f16x3 at the hidden layers' shape (512 -> 512) and the input layer's (544 -> 512), with one kernel offset that has
+    no pairs (its dW is exactly 0), against fp64; the existing 2e-6 relative bound"""
+    nbr_map = _voxel_map(ops, 22, 3000)
+    nv, cout = nbr_map.shape[1], 512
+    torch.manual_seed(cin_pad)
+    X = torch.randn(nv, cin_pad, device="cuda")
+    dY = torch.randn(nv, cout, device="cuda") * 3e-5
+    pairs = []
+    for k in range(27):
+        m = nbr_map[k]
+        out_rows = torch.nonzero(m >= 0).squeeze(1)
+        pairs.append((out_rows, m[out_rows].long()))
+    empty = 4                                                             # (0, 0, -1): pairs on the y = 7 sheet, emptied -- no segments
+    assert pairs[empty][0].numel()
+    pairs[empty] = (pairs[empty][0][:0], pairs[empty][1][:0])
+    plan = ops.wgrad_plan_build(pairs, nv, steps_per_segment=8)
+    sc = ops.pow2_scale(dY)
+    dw = torch.full((27, cin_pad, cout), float("nan"), device="cuda")           # every element must be stored, the empty offset's too
+    ops.conv_wgrad_f16x3(ops.split_f16(X), ops.split_f16(dY, scale=sc[0:1], extra_zero_rows=1), plan, cin_pad, cin_pad, cout,
+                         inv_scale=sc[1:2], out=dw)
+    assert not dw[empty].isnan().any() and not dw[empty].any()
+    Xd, Yd = X.double(), dY.double()
+    worst = 0.0
+    for k, (o, i) in enumerate(pairs):
+        if o.numel():
+            ref = Xd[i].t() @ Yd[o]
+            worst = max(worst, float((dw[k].double() - ref).abs().max() / ref.abs().max()))
+    assert worst < 2e-6, worst
+
+
+def test_output_layer_identity_plan_weight_gradient_vs_fp64(ops):
+    """the 512 -> 128 output layer's weight gradient as StudentTrainer builds it: the identity plan over nv rows and the 128-column
+    gradient zero-padded to the kernel's 256 columns -- columns >= 128 of dW exactly 0, the rest within 2e-6 of fp64"""
+    nv, cin, embed = 2459, 512, 128                                       # nv % 32 != 0: padded pairs
+    torch.manual_seed(3)
+    h = torch.relu(torch.randn(nv, cin, device="cuda"))
+    dE = torch.randn(nv, embed, device="cuda") * 1e-4
+    ident = torch.arange(nv, device="cuda")
+    plan = ops.wgrad_plan_build([(ident, ident)], nv)
+    dEp = torch.zeros((nv, 256), device="cuda")
+    dEp[:, :embed] = dE
+    sc = ops.pow2_scale(dEp)
+    out = torch.full((1, cin, 256), float("nan"), device="cuda")                 # the zero columns must be stored, not left over
+    ops.conv_wgrad_f16x3(ops.split_f16(h), ops.split_f16(dEp, scale=sc[0:1], extra_zero_rows=1), plan, cin, cin, 256,
+                         inv_scale=sc[1:2], out=out)
+    dW = out[0]
+    assert not dW.isnan().any() and not dW[:, embed:].any()
+    ref = h.double().t() @ dE.double()
+    err = float((dW[:, :embed].double() - ref).abs().max() / ref.abs().max())
+    assert err < 2e-6, err
+
+
+# measured on the MI355X: 3.5e-7 of max |dx| (2430 voxels), the adjoint identity 2.3e-10 of |y| |g|
+DGRAD_BOUND, ADJOINT_BOUND = 1.2e-6, 8e-10
+
+
+def test_data_gradient_512_blocked_transpose_flip_vs_fp64(ops):
+    """the data gradient of a 512 -> 512 layer as StudentTrainer._dgrad runs it: V[k] = W[26-k]^T split straight from W into the
+    step-blocked layout, the gradient scaled by a power of two and split with a zero row (_grad_split), the identity branch's gradient
+    as residual=, a multi-chunk plan with two column tiles -- against the fp64 convolution with mirrored, transposed weights; and the
+    adjoint identity <conv_W(x), g> = <x, dgrad_W(g)> at C = 512"""
+    nbr_map = _voxel_map(ops, 23, 3000)
+    nv, C = nbr_map.shape[1], 512
+    torch.manual_seed(17)
+    W = torch.randn(27, C, C, device="cuda") * 0.02
+    dy = torch.randn(nv, C, device="cuda") * 3e-5
+    res = torch.randn(nv, C, device="cuda") * 1e-5
+    old_target, ops.CONV_TARGET_TILES = ops.CONV_TARGET_TILES, 32
+    try:
+        pairs = ops.conv_pairs_build(nbr_map, col_tiles=2)
+    finally:
+        ops.CONV_TARGET_TILES = old_target
+    assert pairs.num_chunks > 1
+    hi, lo = ops.conv_weights_split(W, 16.0, transpose_flip=True)
+    assert hi.dim() == 5 and hi.shape == (27, 2, 16, 256, 32)            # the blocked layout
+    sc = ops.pow2_scale(dy)                                               # as StudentTrainer._grad_split: dy * s, a zero row behind
+    hy, ly = ops.split_f16(dy, scale=sc[0:1], extra_zero_rows=1)
+    inv_s = sc[1:2]
+    scale = (torch.full((C,), 1 / 16.0, device="cuda") * inv_s).contiguous()
+    dx = ops.sparse_conv_f16x3(None, pairs, hi, lo, scale, None, residual=res, relu=False, x_split=(hy[:nv], ly[:nv]))
+    V = W.double().flip(0).transpose(1, 2)
+    ref = res.double().clone()
+    dyd = dy.double()
+    for k in range(27):
+        m = nbr_map[k]
+        rows = torch.nonzero(m >= 0).squeeze(1)
+        if rows.numel():
+            ref.index_add_(0, rows, dyd[m[rows].long()] @ V[k])
+    err = float((dx.double() - ref).abs().max() / ref.abs().max())
+    # adjoint identity: the forward operator on x against the same data-gradient operator without the residual
+    X = torch.randn(nv, C, device="cuda")
+    fhi, flo = ops.conv_weights_split(W, 16.0)
+    Y = ops.sparse_conv_f16x3(X, pairs, fhi, flo, torch.full((C,), 1 / 16.0, device="cuda"), None, x_split=ops.split_f16(X))
+    dx0 = ops.sparse_conv_f16x3(None, pairs, hi, lo, scale, None, relu=False, x_split=(hy[:nv], ly[:nv]))
+    a = float((Y.double() * dy.double()).sum())
+    b = float((X.double() * dx0.double()).sum())
+    adj = abs(a - b) / float(Y.double().norm() * dy.double().norm())
+    assert err < DGRAD_BOUND, err
+    assert adj < ADJOINT_BOUND, adj

@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import affinity, lift, student
+from oracle import train as o_train
 
 
 def _surface_voxels(rng, n=900):
@@ -134,3 +135,75 @@ def test_lift_masks_view_full_vs_explicit_resize():
     z = d1["zero_before_fill"]
     assert 0 < z.sum() < n                                           # both covered and uncovered pixels occur
     assert torch.allclose(f1.norm(dim=1), torch.ones(n), atol=1e-5)
+
+
+def _tiny_training_step_inputs(seed=4):
+    """hidden 32, one block, ~300 voxels: small enough for finite differences of the fp64 loss"""
+    rng = np.random.default_rng(seed)
+    torch.manual_seed(seed)
+    c = _surface_voxels(rng, 300)
+    sd = student.random_student_state_dict(10, hidden=32, embed=16, num_blocks=1, seed=seed)
+    X = torch.randn(len(c), 10) * 0.5
+    S, A, Nn = 150, 8, 63
+    s2v = torch.randint(0, len(c), (S,))
+    p2b = torch.randint(0, S, (A * (2 + Nn),))
+    return sd, X, c, s2v, p2b, A, Nn
+
+
+def test_train_step_oracle_fp64_agrees_with_fp32():
+    """dtype=torch.float64 runs the same step: loss, gradients, embeddings, AdamW weights and running statistics agree with the
+    fp32 step to fp32 rounding (sums of a few hundred terms, two layers deep; measured: loss 5e-9, embeddings 3e-7, gradients <= 5.7e-7
+    relative, weights 1.2e-7, running statistics 1.3e-7)"""
+    sd, X, c, s2v, p2b, A, Nn = _tiny_training_step_inputs()
+    kw = dict(base_lr=1e-3, weight_decay=1e-2)
+    r32 = o_train.train_step_oracle(sd, X, c, s2v, p2b, A, Nn, 0.07, 1, **kw)
+    r64 = o_train.train_step_oracle(sd, X, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64, **kw)
+    assert all(g.dtype == torch.float64 for g in r64["grads"].values()) and r64["embeddings"].dtype == torch.float64
+    assert all(p.dtype == torch.float64 for p in r64["params"].values())
+    assert all(rm.dtype == torch.float64 and rv.dtype == torch.float64 for rm, rv in r64["bn"].values())
+    assert abs(r32["loss"] - r64["loss"]) < 1e-7 * abs(r64["loss"])
+    assert (r32["embeddings"].double() - r64["embeddings"]).abs().max() < 4e-6 * r64["embeddings"].abs().max()
+    for name, g64 in r64["grads"].items():
+        err = float((r32["grads"][name].double() - g64).abs().max() / g64.abs().max())
+        assert err < 4e-6, (name, err)                               # measured <= 5.7e-7; an fp16-class step is ~5e-4
+        d = (r32["params"][name].double() - r64["params"][name]).abs()
+        well = g64.abs() > 1e-5                                       # (the first AdamW step: see test_gpu_training)
+        assert float(d[well].max()) < 1e-6, name
+    for prefix, (rm, rv) in r64["bn"].items():
+        assert (r32["bn"][prefix][0].double() - rm).abs().max() < 1e-6 and (r32["bn"][prefix][1].double() - rv).abs().max() < 1e-6
+
+
+def test_train_step_oracle_fp64_gradients_are_finite_differences_of_its_loss():
+    """two gradient entries of the fp64 step (a hidden conv kernel, a BatchNorm weight) against central differences of the fp64 loss
+    (h = 1e-6: truncation ~h^2, cancellation ~1e-16 / h; measured 1e-10 relative)"""
+    sd, X, c, s2v, p2b, A, Nn = _tiny_training_step_inputs()
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    X64 = X.double()
+    ref = o_train.train_step_oracle(sd64, X64, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64)
+    h = 1e-6
+    for name in ("res_blocks.0.conv2.kernel", "input_layer.1.bn.weight"):
+        g = ref["grads"][name]
+        idx = np.unravel_index(int(g.abs().argmax()), tuple(g.shape))      # an entry the loss depends on
+        losses = []
+        for sign in (1.0, -1.0):
+            sdp = dict(sd64)
+            w = sd64[name].clone()
+            w[idx] += sign * h
+            sdp[name] = w
+            losses.append(o_train.train_step_oracle(sdp, X64, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64)["loss"])
+        fd = (losses[0] - losses[1]) / (2 * h)
+        assert abs(fd - float(g[idx])) < 1e-7 * abs(float(g[idx])), (name, fd, float(g[idx]))
+
+
+def test_train_step_oracle_relu_masks_replace_the_decisions():
+    """relu_masks = the step's own decisions reproduce it bit for bit; one decision turned over changes the gradients"""
+    sd, X, c, s2v, p2b, A, Nn = _tiny_training_step_inputs()
+    ref = o_train.train_step_oracle(sd, X, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64)
+    masks = [pre > 0 for pre in ref["relu_inputs"]]
+    assert len(masks) == 3 and all(m.shape == (len(c), 32) for m in masks)
+    same = o_train.train_step_oracle(sd, X, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64, relu_masks=masks)
+    assert same["loss"] == ref["loss"] and all(torch.equal(same["grads"][k], g) for k, g in ref["grads"].items())
+    flipped = [m.clone() for m in masks]
+    flipped[0][0] = ~flipped[0][0]
+    other = o_train.train_step_oracle(sd, X, c, s2v, p2b, A, Nn, 0.07, 1, dtype=torch.float64, relu_masks=flipped)
+    assert not torch.equal(other["grads"]["input_layer.0.kernel"], ref["grads"]["input_layer.0.kernel"])
