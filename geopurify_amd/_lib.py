@@ -75,8 +75,6 @@ SIGNATURES = {
     "gp_pool_cs_structure_valid": (c_int32, [_P, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, _P, _P, _P]),
     "gp_affinity_cs_fragments": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "gp_pool_cs_apply": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P]),
-    "gp_pool_cs_apply_engine": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P]),
-    "gp_pool_cs_apply_half": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P]),
     "gp_pool_cs_deps": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     "gp_pool_cs_chain_flag_words": (c_size_t, [c_int64, c_int32]),
     "gp_pool_cs_apply_chain": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P,

@@ -24,8 +24,7 @@ extern "C" int gp_version(void) { return 100; }
 //      (written or read: the price of a centre-offset fold), 512 nothing (selects the twin)
 //   4  matrix-core pooling (mask): 1 no reads / MFMA, 2 hot piece instead of the row gather, 4 no epilogue, 8 hot piece instead of
 //      the weight fragments, 16 no output stores, 32 every wave issues its DMA first, 64 stamp the issue segment, 128 the bytes of an
-//      8-bit lo plane (a price: half of the lo rows from the hot piece, half of the lo output bytes),
-//      256 / 512 engine: no staged-row reads / no weight-fragment reads
+//      8-bit lo plane (a price: half of the lo rows from the hot piece, half of the lo output bytes)
 //   5  1-NN: 1 forces brute force          6  1-NN fine grid cells per axis (0 = 128, <= 256)
 //   7  1-NN: 2 brings back the fine-grid pass for near queries            9  64-row pooling: 1 forces one workgroup per CU
 //   8  matrix-core affinity (mask, tuning twin): 1 no fragment reads / MFMA, 2 no list stores, 4 no softmax, 8 no fragment pass, 16 no LDS-DMA
@@ -41,14 +40,14 @@ const KnobRule k_rules[16] = {
     {0, 4, 0},           // 1
     {0, 8, 0},           // 2
     {0, 0, 1u | 2u | 4u | 8u | 16u | 32u | 256u | 512u},               // 3
-    {0, 0, 1u | 2u | 4u | 8u | 16u | 32u | 64u | 128u | 256u | 512u},     // 4
+    {0, 0, 1u | 2u | 4u | 8u | 16u | 32u | 64u | 128u},                   // 4
     {0, 1, 0},           // 5
     {0, 256, 0},         // 6
     {0, 2, 0},           // 7
     {0, 0, 1u | 2u | 4u | 8u | 16u},                               // 8
     {0, 1, 0},           // 9
     {0, 64, 0},          // 10
-    {0, 4, 0},           // 11 (0 or 4; the engine is gp_pool_cs_apply_engine, not a knob)
+    {0, 4, 0},           // 11 (0 or 4)
     {0, 1, 0},           // 12
     {0, 64, 0},          // 13
     {0, 1, 0},           // 14

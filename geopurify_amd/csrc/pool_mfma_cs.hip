@@ -362,7 +362,8 @@ struct CsChain {
     const int32_t *dep;                // [nblocks][64]: word 0 = n, words 1 .. min(n, 63) = row blocks (n > 63: wait for every block)
     int32_t T;                         // applications (>= 2)
     uint32_t base;                     // flags epoch: a published application t reads base + t + 1
-    int32_t half_sel = -1;             // (not chained) 0 / 1: the grid covers this 256-column half only (cs_pool_half_kernel)
+    int32_t half_sel = -1;             // always -1 (0 / 1 selected one 256-column half: the half launch, retired);
+                                       // the field stays so that the kept kernels compile to the code that was measured
 };
 constexpr int CS_DEP_CAP = 64;
 constexpr int CS_FLAG_HDR = 32;
@@ -721,12 +722,6 @@ __global__ void __launch_bounds__(512, 2) cs_pool_kernel(CS_POOL_PARAMS) { cs_po
 // the same body with the tuning bits live, under its own name: launches with parts of the kernel switched off (bench.py's
 // gather + store ceiling, scripts/bench_pool.py ablations) do not mix into the product kernel's rows of a kernel trace
 __global__ void __launch_bounds__(512, 2) cs_pool_tuning_kernel(CS_POOL_PARAMS) { cs_pool_body<false, true>(CS_POOL_FWD, CsChain{}); }
-// one column half only (gp_pool_cs_apply_half: two independent chains of launches, one per half, on two streams)
-__global__ void __launch_bounds__(512, 2) cs_pool_half_kernel(CS_POOL_PARAMS, int half) {
-    CsChain ch{};
-    ch.half_sel = half;
-    cs_pool_body<false, false>(CS_POOL_FWD, ch);
-}
 #undef CS_POOL_PARAMS
 #undef CS_POOL_FWD
 // all T applications in one launch (see CsChain above)
@@ -1047,300 +1042,6 @@ cs_deps_sym_kernel(const int64_t *__restrict__ bu_off, const int32_t *__restrict
     }
 }
 
-// ------------------------------------------------------------------------------------------------ engine
-// Producer / consumer form of the same operator ("engine"): ONE persistent 512-thread workgroup per CU.
-//   waves 4-7 = loaders: nothing but LDS-DMA.  They fill a ring of four 32-KiB slots (32 union rows x 128 columns x
-//               {hi, lo} + the step's 8 x {hi, lo} weight fragments) as fast as slots come free -- up to three stages
-//               (96 KiB) in flight per CU, across tile boundaries -- and absorb the memory pipeline's back-pressure;
-//   waves 0-3 = consumers (one per SIMD): wave cw owns all 128 rows x 32 columns of the tile (16 accumulator tiles),
-//               copies a landed stage's operands into registers, releases the slot AT ONCE and only then multiplies.
-// A tile is (128-row block, 128-column quarter); tiles of an XCD label are handed out in order, so that the label's
-// 32 workgroups work on 8 neighbouring row blocks (a 1 024-row window: its union rows fit the XCD's 4-MiB L2, which the
-// 2 048-row window of cs_pool_kernel does not -- 41 % instead of 68 % L2 hits, 1.28 GB instead of 1.03 GB from memory).
-// There is no s_barrier: slot hand-over goes through two monotonic LDS counters per slot (full: +1 per loader once its
-// DMA has landed, s_waitcnt vmcnt; free: +1 per consumer once its operand reads have landed, s_waitcnt lgkmcnt), which the
-// other side polls.  Consumers issue no LDS-DMA, so their epilogue (wave-private LDS staging, stores) is plain code and
-// overlaps the loaders' work on the next tile.
-constexpr int EG_NC = 128;                          // columns per tile
-constexpr int EG_RB = EG_NC * 2;                    // bytes per staged row and plane
-constexpr int EG_PLANE = CS_KS * EG_RB;             // 8 KiB
-constexpr int EG_OFF_W = 2 * EG_PLANE;              // 16 KiB
-constexpr int EG_SLOT = EG_OFF_W + 2 * CS_WPL;      // 32 KiB
-constexpr int EG_NSLOT = 4;
-constexpr int EG_OFF_FLAG = EG_NSLOT * EG_SLOT;     // {full, fragment mask} x 4 | free[4] (uint32)
-constexpr int EG_OFF_STG = EG_OFF_FLAG + 256;       // epilogue staging: 4 waves x 32 rows x CS_EP floats
-constexpr int EG_STG_WAVE = 32 * CS_EP * 4;
-constexpr size_t EG_SMEM = (size_t)EG_OFF_STG + 4 * EG_STG_WAVE;
-constexpr int EG_DMA = 8;                           // LDS-DMA instructions per loader and stage: 4 x rows, 4 x weights
-
-__device__ __forceinline__ void eg_wait_ge(uint32_t flag_addr, uint32_t target) {
-    for (;;) {
-        uint32_t v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(flag_addr) : "memory");
-        if ((int32_t)(__builtin_amdgcn_readfirstlane(v) - target) >= 0) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-__device__ __forceinline__ void eg_signal(uint32_t flag_addr) {
-    if ((threadIdx.x & 63) == 0) {
-        const uint32_t one = 1;
-        asm volatile("ds_add_u32 %0, %1" ::"v"(flag_addr), "v"(one) : "memory");
-    }
-}
-
-// (TUNE: the tuning bits of `ablate_` are honoured; the product instantiation compiles them out.  The loaders wait vmcnt(0)
-// for their own stage, so a dropped instruction cannot mis-time a hand-over here.)
-template <bool STAMP, bool TUNE>
-__device__ __forceinline__ void
-cs_engine_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, int64_t ld_x,
-               const int64_t *__restrict__ bu_off, const int32_t *__restrict__ bu_row, const uint32_t *__restrict__ bu_mask,
-               const _Float16 *__restrict__ wa_hi, const _Float16 *__restrict__ wa_lo, int64_t nv, int64_t nblocks,
-               _Float16 *__restrict__ y_hi, _Float16 *__restrict__ y_lo, int64_t ld_y, float *__restrict__ y_f32, int64_t ld_yf,
-               int ablate_, const float *__restrict__ out_scale, uint64_t *__restrict__ stamp, int rpb) {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int ablate = TUNE ? ablate_ : 0;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem_raw;
-    if (tid < 12) reinterpret_cast<uint32_t *>(smem_raw + EG_OFF_FLAG)[tid] = 0u;
-    __syncthreads();
-    // ---- this workgroup's tiles: label q = blockIdx & 7 owns the contiguous tile range [lo, hi); workgroup wi of the label
-    //      takes tiles lo + wi, lo + wi + W, ...   (tile = 4 * row block + column quarter)
-    const int64_t T = nblocks * (CS_D / EG_NC);
-    const int label = blockIdx.x & 7, wi = blockIdx.x >> 3, W = (int)(gridDim.x >> 3);
-    const int64_t t_lo = label * T / 8, t_hi = (label + 1) * T / 8;
-    uint64_t st_t0 = 0, st_poll = 0, st_work = 0, st_epi = 0, st_steps = 0;
-    if constexpr (STAMP) st_t0 = cs_now();
-
-    if (wv >= 4) {
-        // ================================================================ loaders
-        // Loader l owns ring slot l and stages l, l + 4, l + 8, ... of the workgroup's stage sequence (all steps of all its tiles
-        // in order): it waits until the consumers have released the slot, issues the WHOLE stage (16 x 1 KiB of rows, the
-        // non-empty weight fragments), writes the stage's fragment mask next to the slot's counter, loads the scalars of its
-        // next stage while the DMA is in flight, waits for its own DMA (vmcnt(0): nothing else is in its queue) and signals.
-        // Four loaders = up to four stages between issue and release, and the per-stage latency chain (scalar loads, poll,
-        // issue, landing) runs four stages wide instead of once per stage.
-        const int l = wv - 4;
-        const int du = lane >> 4, dc = lane & 15;
-        const int dsw0 = (dc ^ (2 * du)) * 8, dsw1 = (dc ^ (2 * (du | 4))) * 8;  // source column of this lane's chunk: rows 0-7 / 8-15 (mod 16)
-        int64_t t = t_lo + wi;
-        if (t >= t_hi) return;
-        int64_t ub0 = bu_off[t >> 2];
-        int n = (int)((bu_off[(t >> 2) + 1] - ub0) / CS_KS);
-        int k = l;                                                            // this loader's next stage = step k of tile t (k may run past n)
-        uint32_t j = 0;                                                       // uses of the slot so far
-        for (;;) {
-            while (k >= n) {                                                  // on to the tile that holds the stage
-                k -= n;
-                t += W;
-                if (t >= t_hi) break;
-                ub0 = bu_off[t >> 2];
-                n = (int)((bu_off[(t >> 2) + 1] - ub0) / CS_KS);
-            }
-            if (t >= t_hi) break;
-            const int col0 = (int)(t & 3) * EG_NC;
-            const int32_t *idg = bu_row + ub0 + (int64_t)k * CS_KS;
-            i32x4 id[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) id[i] = *reinterpret_cast<const i32x4 *>(idg + 4 * i);
-            const unsigned mk = bu_mask[ub0 / CS_KS + k];
-            eg_wait_ge(lds0 + EG_OFF_FLAG + 32 + l * 4, 4u * j);                // free[l]: the slot's previous stage is consumed
-            unsigned char *dst = smem_raw + l * EG_SLOT;
-            if (!(ablate & 2)) {                                              // tuning aid: bit 1 skips the row gather
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {                                 // rows 4 i .. 4 i + 3
-                    const int idr = du == 0 ? id[i].x : du == 1 ? id[i].y : du == 2 ? id[i].z : id[i].w;
-                    const int64_t so = (int64_t)idr * ld_x + col0 + (((i >> 1) & 1) ? dsw1 : dsw0);
-                    cs_glds16(x_hi + so, dst + (4 * i) * EG_RB);
-                    cs_glds16(x_lo + so, dst + EG_PLANE + (4 * i) * EG_RB);
-                }
-            }
-            const int64_t wk = (ub0 / CS_KS + k) * (CS_NG * 512) + lane * 8;
-#pragma unroll
-            for (int gq = 0; gq < CS_NG; ++gq)
-                if ((mk >> gq) & 1u) {                                        // empty fragments are neither fetched nor read
-                    cs_glds16(wa_hi + wk + gq * 512, dst + EG_OFF_W + gq * 1024);
-                    cs_glds16(wa_lo + wk + gq * 512, dst + EG_OFF_W + CS_WPL + gq * 1024);
-                }
-            if (lane == 0) {
-                const uint32_t ma = lds0 + EG_OFF_FLAG + l * 8 + 4;
-                asm volatile("ds_write_b32 %0, %1" ::"v"(ma), "v"(mk) : "memory");
-            }
-            k += 4;
-            ++j;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            eg_signal(lds0 + EG_OFF_FLAG + l * 8);                              // full[l]
-        }
-        return;
-    }
-    // ==================================================================== consumers
-    const int cw = wv;
-    const int gq = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    uint32_t addr[2];
-    {
-        const uint32_t rowb = (uint32_t)(8 * gq + q) * EG_RB + (uint32_t)(cw * CS_WC * 2) + (uint32_t)(p * 8);
-        const uint32_t t5 = (uint32_t)(q | ((gq & 1) << 2)) << 5;
-        addr[0] = lds0 + (rowb ^ t5);
-        addr[1] = lds0 + ((rowb + 32u) ^ t5);
-    }
-    const uint32_t addr_w = lds0 + EG_OFF_W + lane * 16;
-    const float inv = 1.f / CS_WSCALE;
-    const float so = (y_f32 && out_scale) ? out_scale[0] : 1.f;
-    float *stg = reinterpret_cast<float *>(smem_raw + EG_OFF_STG + cw * EG_STG_WAVE);
-    const int fl = lane & 15, fq = lane >> 4;
-    const int er = lane >> 2, ec = (lane & 3) * 8;
-    const bool do_mma = !(ablate & 1);
-    uint32_t g = 0;
-    s16x4 fb[2][2][2];
-    f16x8 ah[8], al[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ah[i] = al[i] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t ub0_n = 0;
-    int n_n = 0;
-    {
-        const int64_t t = t_lo + wi;
-        if (t < t_hi) {
-            ub0_n = bu_off[t >> 2];
-            n_n = (int)((bu_off[(t >> 2) + 1] - ub0_n) / CS_KS);
-        }
-    }
-    for (int64_t t = t_lo + wi; t < t_hi; t += W) {
-        const int64_t b = t >> 2;
-        const int col0 = (int)(t & 3) * EG_NC;
-        const int64_t ub0 = ub0_n;
-        const int n = n_n;
-        f32x4 acc[CS_NG * 2];
-#pragma unroll
-        for (int i = 0; i < CS_NG * 2; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (t + W < t_hi) {                                  // next tile's descriptor and first mask (scalar loads, used a tile later)
-            const int64_t bn = (t + W) >> 2;
-            ub0_n = bu_off[bn];
-            n_n = (int)((bu_off[bn + 1] - ub0_n) / CS_KS);
-        }
-        for (int k = 0; k < n; ++k, ++g) {
-            const uint32_t slot = g & 3u;
-            uint64_t st_a = 0, st_b = 0;
-            if constexpr (STAMP) st_a = cs_now();
-            unsigned m;                                                                    // the stage's fragment mask rides next to the counter
-            for (;;) {                                                                     // full[slot]: the slot's loader has signalled this stage
-                int2 fm;
-                asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(fm) : "v"(lds0 + EG_OFF_FLAG + slot * 8) : "memory");
-                m = (unsigned)__builtin_amdgcn_readfirstlane(fm.y);
-                if ((int32_t)((uint32_t)__builtin_amdgcn_readfirstlane(fm.x) - ((g >> 2) + 1u)) >= 0) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if constexpr (STAMP) { st_b = cs_now(); st_poll += st_b - st_a; }
-            const uint32_t so_ = slot * EG_SLOT;
-            const uint32_t a0 = addr[0] + so_, a1 = addr[1] + so_, aw = addr_w + so_;
-            if (!(ablate & 256)) {                           // tuning aid: bit 8 skips the staged-row reads
-            cs_tr<0>(fb[0][0][0], a0);
-            cs_tr<4 * EG_RB>(fb[0][0][1], a0);
-            cs_tr<EG_PLANE>(fb[0][1][0], a0);
-            cs_tr<EG_PLANE + 4 * EG_RB>(fb[0][1][1], a0);
-            cs_tr<0>(fb[1][0][0], a1);
-            cs_tr<4 * EG_RB>(fb[1][0][1], a1);
-            cs_tr<EG_PLANE>(fb[1][1][0], a1);
-            cs_tr<EG_PLANE + 4 * EG_RB>(fb[1][1][1], a1);
-            }
-            if (ablate & 512) m = 0;                         // tuning aid: bit 9 skips the weight-fragment reads (and their MFMAs)
-            if (m & 1u) { cs_rd128<0 * 1024>(ah[0], aw); cs_rd128<CS_WPL + 0 * 1024>(al[0], aw); }
-            if (m & 2u) { cs_rd128<1 * 1024>(ah[1], aw); cs_rd128<CS_WPL + 1 * 1024>(al[1], aw); }
-            if (m & 4u) { cs_rd128<2 * 1024>(ah[2], aw); cs_rd128<CS_WPL + 2 * 1024>(al[2], aw); }
-            if (m & 8u) { cs_rd128<3 * 1024>(ah[3], aw); cs_rd128<CS_WPL + 3 * 1024>(al[3], aw); }
-            if (m & 16u) { cs_rd128<4 * 1024>(ah[4], aw); cs_rd128<CS_WPL + 4 * 1024>(al[4], aw); }
-            if (m & 32u) { cs_rd128<5 * 1024>(ah[5], aw); cs_rd128<CS_WPL + 5 * 1024>(al[5], aw); }
-            if (m & 64u) { cs_rd128<6 * 1024>(ah[6], aw); cs_rd128<CS_WPL + 6 * 1024>(al[6], aw); }
-            if (m & 128u) { cs_rd128<7 * 1024>(ah[7], aw); cs_rd128<CS_WPL + 7 * 1024>(al[7], aw); }
-            cs_wait_b(fb);
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(ah[0]), "+v"(ah[1]), "+v"(ah[2]), "+v"(ah[3]), "+v"(ah[4]), "+v"(ah[5]), "+v"(ah[6]), "+v"(ah[7]),
-                           "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(al[4]), "+v"(al[5]), "+v"(al[6]), "+v"(al[7]));
-            eg_signal(lds0 + EG_OFF_FLAG + 32 + slot * 4);                                  // free[slot]: the operands are in registers
-            if (do_mma) {
-                f16x8 bh[2], bl[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) { bh[u] = cs_cat(fb[u][0][0], fb[u][0][1]); bl[u] = cs_cat(fb[u][1][0], fb[u][1][1]); }
-#pragma unroll
-                for (int mt = 0; mt < CS_NG; ++mt)
-                    if (__builtin_expect((m >> mt) & 1u, 1)) {
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) acc[mt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh[u], acc[mt * 2 + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) acc[mt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bl[u], acc[mt * 2 + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) acc[mt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[mt], bh[u], acc[mt * 2 + u], 0, 0, 0);
-                    }
-            }
-            if constexpr (STAMP) { st_work += cs_now() - st_b; ++st_steps; }
-        }
-        if (ablate & 4) continue;                            // tuning aid: bit 2 skips the epilogue
-        // ---- epilogue: 32 rows at a time through the wave's private staging area; every store instruction writes 16 rows x 64 bytes
-        uint64_t st_e = 0;
-        if constexpr (STAMP) st_e = cs_now();
-        const int64_t row0 = b * rpb;
-        const int colw = col0 + cw * CS_WC;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) stg[(mt * 16 + fq * 4 + r) * CS_EP + cb * 16 + fl] = acc[(ch * 2 + mt) * 2 + cb][r] * inv;
-            gp_wave_sync();
-            float4 v[2][2];
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const float *sp = stg + (it * 16 + er) * CS_EP + ec;
-                v[it][0] = *reinterpret_cast<const float4 *>(sp);
-                v[it][1] = *reinterpret_cast<const float4 *>(sp + 4);
-            }
-            gp_wave_sync();
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int lrow = ch * 32 + it * 16 + er;
-                const int64_t grow = row0 + lrow;
-                if (lrow < rpb && grow < nv && !(ablate & 16)) {
-                    const float xv[8] = {v[it][0].x, v[it][0].y, v[it][0].z, v[it][0].w, v[it][1].x, v[it][1].y, v[it][1].z, v[it][1].w};
-                    if (y_hi) {
-                        f16x8 h, lo8;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) { h[i] = (_Float16)xv[i]; lo8[i] = (_Float16)(xv[i] - (float)h[i]); }
-                        *reinterpret_cast<f16x8 *>(y_hi + grow * ld_y + colw + ec) = h;
-                        *reinterpret_cast<f16x8 *>(y_lo + grow * ld_y + colw + ec) = lo8;
-                    }
-                    if (y_f32) {
-                        float *yp = y_f32 + grow * ld_yf + colw + ec;
-                        *reinterpret_cast<float4 *>(yp) = make_float4(xv[0] * so, xv[1] * so, xv[2] * so, xv[3] * so);
-                        *reinterpret_cast<float4 *>(yp + 4) = make_float4(xv[4] * so, xv[5] * so, xv[6] * so, xv[7] * so);
-                    }
-                }
-            }
-        }
-        if constexpr (STAMP) st_epi += cs_now() - st_e;
-    }
-    if constexpr (STAMP) {
-        const uint64_t t3 = cs_now();
-        if (lane == 0 && stamp) {
-            uint64_t *o = stamp + ((int64_t)blockIdx.x * 4 + cw) * 10;
-            o[0] = 0; o[1] = 0; o[2] = 0; o[3] = st_work; o[4] = st_poll; o[5] = 0; o[6] = st_epi; o[7] = t3 - st_t0; o[8] = st_steps; o[9] = 0;
-        }
-    }
-}
-
-#define EG_PARAMS const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, int64_t ld_x, const int64_t *__restrict__ bu_off,            \
-                  const int32_t *__restrict__ bu_row, const uint32_t *__restrict__ bu_mask, const _Float16 *__restrict__ wa_hi,                      \
-                  const _Float16 *__restrict__ wa_lo, int64_t nv, int64_t nblocks, _Float16 *__restrict__ y_hi, _Float16 *__restrict__ y_lo,         \
-                  int64_t ld_y, float *__restrict__ y_f32, int64_t ld_yf, int ablate, const float *__restrict__ out_scale, uint64_t *__restrict__ stamp, \
-                  int rpb
-#define EG_FWD x_hi, x_lo, ld_x, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, nblocks, y_hi, y_lo, ld_y, y_f32, ld_yf, ablate, out_scale, stamp, rpb
-// the product engine (no tuning bits, no stamps) and the same body with both live, under its own name in a kernel trace
-__global__ void __launch_bounds__(512, 2) cs_engine_kernel(EG_PARAMS) { cs_engine_body<false, false>(EG_FWD); }
-template <bool STAMP>
-__global__ void __launch_bounds__(512, 2) cs_engine_tuning_kernel(EG_PARAMS) { cs_engine_body<STAMP, true>(EG_FWD); }
-#undef EG_PARAMS
-#undef EG_FWD
-
 size_t cs_scan_tmp(int64_t n) {
     size_t t = 0;
     (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
@@ -1448,62 +1149,31 @@ extern "C" int gp_pool_cs_structure(const int32_t *nbr, int64_t nv, int32_t k, i
 }
 
 // One application y = A x on pre-split operands (see gp_pool_mfma_apply for the operand conventions).  d must be 512.
-// engine = false: cs_pool_kernel (one tile per workgroup, the default); engine = true: cs_engine_kernel (persistent producer /
-// consumer form, one workgroup per CU).  The choice is an ARGUMENT of the call (round 3 selected the engine through the
-// process-global debug knob 11: a raised error left every later launch on the engine, and two host threads raced on it).
 // rows_per_block: the builder's (gp_pool_cs_count / _fill).
-static int cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                    const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d, int32_t rpb,
-                    void *y_hi, void *y_lo, int64_t ld_y, float *y_f32, int64_t ld_yf,
-                    const float *out_scale, bool engine, void *stream_, int half = -1) {
+extern "C" int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
+                                const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
+                                int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32,
+                                int64_t ld_yf, const float *out_scale, void *stream_) {
     GP_CHECK_ARG(x_hi && x_lo && bu_off && bu_row && bu_mask && wa_hi && wa_lo && nv > 0, "gp_pool_cs_apply: null/empty argument");
-    GP_CHECK_ARG(half >= -1 && half <= 1 && !(engine && half >= 0), "gp_pool_cs_apply_half: half=%d (0 or 1)", half);
     GP_CHECK_ARG(d == CS_D, "gp_pool_cs_apply: d=%d (kernel specialised for %d columns)", d, CS_D);
-    GP_CHECK_ARG(cs_rpb_ok(rpb), "gp_pool_cs_apply: rows_per_block=%d (16..%d)", rpb, CS_BR);
+    GP_CHECK_ARG(cs_rpb_ok(rows_per_block), "gp_pool_cs_apply: rows_per_block=%d (16..%d)", rows_per_block, CS_BR);
     GP_CHECK_ARG((y_hi && y_lo) || y_f32, "gp_pool_cs_apply: no output requested");
     GP_CHECK_ARG(ld_x % 8 == 0 && (uintptr_t)x_hi % 16 == 0 && (uintptr_t)x_lo % 16 == 0, "gp_pool_cs_apply: x rows must be 16-byte aligned");
     GP_CHECK_ARG(!y_hi || (ld_y % 8 == 0 && (uintptr_t)y_hi % 16 == 0 && (uintptr_t)y_lo % 16 == 0 && y_hi != x_hi && y_lo != x_lo),
                  "gp_pool_cs_apply: y rows must be 16-byte aligned and must not alias x");
     GP_CHECK_ARG(!y_f32 || (ld_yf % 4 == 0 && (uintptr_t)y_f32 % 16 == 0), "gp_pool_cs_apply: fp32 output rows must be 16-byte aligned");
     hipStream_t s = gp_stream(stream_);
-    const int64_t nb = (nv + rpb - 1) / rpb;
-    const int64_t per_xcd = half >= 0 ? (nb + 7) / 8 : (nb * (CS_D / CS_NC) + 7) / 8;
+    const int64_t nb = (nv + rows_per_block - 1) / rows_per_block;
+    const int64_t per_xcd = (nb * (CS_D / CS_NC) + 7) / 8;
     uint64_t *stamp = static_cast<uint64_t *>(g_gp_debug_ptr[0]);
-    const int tune = g_gp_knobs[4];                       // tuning bits: only ever handed to the *_tuning_kernel twins
-    if (engine) {
-        const int n_cu = gp_cu_count();
-        GP_CHECK_ARG(n_cu > 0, "gp_pool_cs_apply_engine: cannot read the device's compute-unit count");
-        const unsigned grid = (unsigned)((n_cu >= 8 ? n_cu / 8 : 1) * 8);
-        GP_CHECK_ARG(!stamp || g_gp_debug_bytes[0] >= (size_t)grid * 4 * 10 * sizeof(uint64_t),
-                     "gp_pool_cs_apply_engine: the stamp buffer of gp_debug_ptr(0) holds %zu bytes, this launch writes %zu",
-                     g_gp_debug_bytes[0], (size_t)grid * 4 * 10 * sizeof(uint64_t));
-#define EG_ARGS static_cast<const _Float16 *>(x_hi), static_cast<const _Float16 *>(x_lo), ld_x, bu_off, bu_row, bu_mask,              \
-                static_cast<const _Float16 *>(wa_hi), static_cast<const _Float16 *>(wa_lo), nv, nb, static_cast<_Float16 *>(y_hi),     \
-                static_cast<_Float16 *>(y_lo), ld_y, y_f32, ld_yf, tune, out_scale, stamp, rpb
-        if (stamp) {
-            GP_SMEM_ATTR(cs_engine_tuning_kernel<true>, EG_SMEM);
-            cs_engine_tuning_kernel<true><<<grid, 512, EG_SMEM, s>>>(EG_ARGS);
-        } else if (tune != 0) {
-            GP_SMEM_ATTR(cs_engine_tuning_kernel<false>, EG_SMEM);
-            cs_engine_tuning_kernel<false><<<grid, 512, EG_SMEM, s>>>(EG_ARGS);
-        } else {
-            GP_SMEM_ATTR(cs_engine_kernel, EG_SMEM);
-            cs_engine_kernel<<<grid, 512, EG_SMEM, s>>>(EG_ARGS);
-        }
-#undef EG_ARGS
-        GP_CHECK_LAUNCH();
-        return GP_OK;
-    }
+    const int tune = g_gp_knobs[4];                       // tuning bits: only ever handed to cs_pool_tuning_kernel
     GP_CHECK_ARG(!stamp || g_gp_debug_bytes[0] >= (size_t)(per_xcd * 8) * CS_NW * 10 * sizeof(uint64_t),
                  "gp_pool_cs_apply: the stamp buffer of gp_debug_ptr(0) holds %zu bytes, this launch writes %zu",
                  g_gp_debug_bytes[0], (size_t)(per_xcd * 8) * CS_NW * 10 * sizeof(uint64_t));
 #define CS_ARGS static_cast<const _Float16 *>(x_hi), static_cast<const _Float16 *>(x_lo), ld_x, bu_off, bu_row, bu_mask,              \
                 static_cast<const _Float16 *>(wa_hi), static_cast<const _Float16 *>(wa_lo), nv, nb, static_cast<_Float16 *>(y_hi),     \
-                static_cast<_Float16 *>(y_lo), ld_y, y_f32, ld_yf, per_xcd, tune, out_scale, stamp, rpb
-    if (half >= 0) {
-        GP_SMEM_ATTR(cs_pool_half_kernel, CS_SMEM);
-        cs_pool_half_kernel<<<(unsigned)(per_xcd * 8), 512, CS_SMEM, s>>>(CS_ARGS, half);
-    } else if (stamp) {
+                static_cast<_Float16 *>(y_lo), ld_y, y_f32, ld_yf, per_xcd, tune, out_scale, stamp, rows_per_block
+    if (stamp) {
         GP_SMEM_ATTR(cs_pool_kernel<true>, CS_SMEM);
         cs_pool_kernel<true><<<(unsigned)(per_xcd * 8), 512, CS_SMEM, s>>>(CS_ARGS);
     } else if (tune != 0) {
@@ -1516,34 +1186,6 @@ static int cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int6
 #undef CS_ARGS
     GP_CHECK_LAUNCH();
     return GP_OK;
-}
-
-extern "C" int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                                const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
-                                int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32,
-                                int64_t ld_yf, const float *out_scale, void *stream_) {
-    return cs_apply(x_hi, x_lo, ld_x, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, d, rows_per_block, y_hi, y_lo, ld_y, y_f32,
-                    ld_yf, out_scale, false, stream_);
-}
-
-// One 256-column half (0 or 1) of the same application: columns 256 half .. 256 half + 255 of every row.  The halves are
-// independent, so two streams can each carry one half's chain of applications (measured in round 5).
-extern "C" int gp_pool_cs_apply_half(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                                     const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
-                                     int32_t rows_per_block, int32_t half, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32,
-                                     int64_t ld_yf, const float *out_scale, void *stream_) {
-    GP_CHECK_ARG(half == 0 || half == 1, "gp_pool_cs_apply_half: half=%d (0 or 1)", half);
-    return cs_apply(x_hi, x_lo, ld_x, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, d, rows_per_block, y_hi, y_lo, ld_y, y_f32,
-                    ld_yf, out_scale, false, stream_, half);
-}
-
-// The same application through the persistent producer / consumer engine (cs_engine_kernel); bit-identical results.
-extern "C" int gp_pool_cs_apply_engine(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                                       const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
-                                       int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32, int64_t ld_yf,
-                                       const float *out_scale, void *stream_) {
-    return cs_apply(x_hi, x_lo, ld_x, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, d, rows_per_block, y_hi, y_lo, ld_y, y_f32, ld_yf,
-                    out_scale, true, stream_);
 }
 
 // gp_pool_cs_structure for gp_affinity_cs_fragments: union rows, fragment masks and valid u32 [total_rows / 32 * 128 + 64] (bit p of

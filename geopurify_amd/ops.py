@@ -737,30 +737,18 @@ def pool_cs_build(nbr, w, rows_per_block=128):
     return pool_cs_fill(pool_cs_plan(nbr, rows_per_block), nbr, w)
 
 
-def pool_cs_apply(x_split, op, d, out_split=None, out_f32=None, out_scale=None, engine=False):
+def pool_cs_apply(x_split, op, d, out_split=None, out_f32=None, out_scale=None):
     """x_split / out_split: (hi, lo) f16 [Nv, >=d] pairs; out_f32 fp32 [Nv, >=d]; at least one output.
-    out_scale: device scalar multiplied into out_f32 (1/s of a pow2_scale()-scaled x_split).
-    engine: the producer / consumer form of the kernel (gp_pool_cs_apply_engine; same results)."""
+    out_scale: device scalar multiplied into out_f32 (1/s of a pow2_scale()-scaled x_split)."""
     lib = _lib.load()
     xh, xl = x_split
     assert xh.stride(0) == xl.stride(0)
     yh, yl = out_split if out_split is not None else (None, None)
-    fn, name = (lib.gp_pool_cs_apply_engine, "gp_pool_cs_apply_engine") if engine else (lib.gp_pool_cs_apply, "gp_pool_cs_apply")
-    check(fn(_ptr(xh), _ptr(xl), xh.stride(0), _ptr(op.bu_off), _ptr(op.bu_row), _ptr(op.bu_mask), _ptr(op.wa_hi), _ptr(op.wa_lo),
-             op.nv, int(d), int(op.block_rows), _ptr(yh), _ptr(yl), yh.stride(0) if yh is not None else 0,
-             _ptr(out_f32), out_f32.stride(0) if out_f32 is not None else 0, _ptr(out_scale), _stream()), name)
+    check(lib.gp_pool_cs_apply(_ptr(xh), _ptr(xl), xh.stride(0), _ptr(op.bu_off), _ptr(op.bu_row), _ptr(op.bu_mask), _ptr(op.wa_hi),
+                               _ptr(op.wa_lo), op.nv, int(d), int(op.block_rows), _ptr(yh), _ptr(yl), yh.stride(0) if yh is not None else 0,
+                               _ptr(out_f32), out_f32.stride(0) if out_f32 is not None else 0, _ptr(out_scale), _stream()),
+          "gp_pool_cs_apply")
     return out_f32 if out_f32 is not None else out_split
-
-
-def pool_cs_apply_half(x_split, op, d, half, out_split=None, out_f32=None, out_scale=None):
-    """One 256-column half (0 / 1) of pool_cs_apply: the halves are independent chains."""
-    lib = _lib.load()
-    xh, xl = x_split
-    yh, yl = out_split if out_split is not None else (None, None)
-    check(lib.gp_pool_cs_apply_half(_ptr(xh), _ptr(xl), xh.stride(0), _ptr(op.bu_off), _ptr(op.bu_row), _ptr(op.bu_mask), _ptr(op.wa_hi),
-                                    _ptr(op.wa_lo), op.nv, int(d), int(op.block_rows), int(half), _ptr(yh), _ptr(yl),
-                                    yh.stride(0) if yh is not None else 0, _ptr(out_f32), out_f32.stride(0) if out_f32 is not None else 0,
-                                    _ptr(out_scale), _stream()), "gp_pool_cs_apply_half")
 
 
 def pool_cs_deps(op):

@@ -363,6 +363,44 @@ class LSegFeatureVLM:
 
 
 # --------------------------------------------------------------------------------------------------
+# Row 12's pooling modes and the kernel family each asks for ("auto": chosen by shape in resolve_pool_mode).  "mfma_cs" is the
+# column-sliced matrix-core kernel (pool_mfma_cs.hip), "mfma_chain" all of its applications in one launch, "mfma" / "mfma_persist"
+# the 64-row matrix-core kernels (pool_mfma.hip), "tiles" / "ell" the fp32 kernels (pool_tiles.hip, pool.hip).
+POOL_MODES = {"auto": None, "mfma_cs": "cs", "mfma_chain": "chain", "mfma": "mfma", "mfma_persist": "mfma_persist", "tiles": "tiles",
+              "ell": "ell"}
+
+
+def _known_pool_mode(mode):
+    if mode not in POOL_MODES:
+        raise ValueError(f"pool_mode={mode!r}: one of {', '.join(POOL_MODES)}")
+    return mode
+
+
+def resolve_pool_mode(mode, D, K, num_iters, tile_rows, block_rows):
+    """The kernel family that row 12 runs for `mode` at width D: "cs", "chain", "mfma", "mfma_persist", "tiles" or "ell".
+    An unknown mode raises ValueError, and so does a matrix-core mode the shape does not admit; "tiles" falls back to "ell",
+    "chain" to "cs" for a single application.  ("mfma_persist" still falls back to "mfma" when the built operator has too few
+    steps per row block, or blocks other than 64 rows: HotPath._pool.)"""
+    family = POOL_MODES[_known_pool_mode(mode)]
+    mfma_ok = D == 512 and block_rows * K <= 16384 and num_iters >= 1
+    cs_ok = D == 512 and 128 * K <= 12288 and num_iters >= 1
+    # what gp_pool_tiles_apply accepts: multiples of 512 columns, or config P's D = 64 in 4- or 8-row tiles (pool_tiles64_kernel)
+    tiles_ok = num_iters > 1 and tile_rows * K <= 1536 and (D % 512 == 0 or (D == 64 and tile_rows in (4, 8)))
+    if family is None:
+        if (cs_ok or mfma_ok) and num_iters >= 3:
+            return "cs" if cs_ok else "mfma"
+        return "tiles" if tiles_ok else "ell"
+    if family in ("cs", "chain"):
+        if not cs_ok:
+            raise ValueError(f"pool_mode='{mode}' needs D == 512 and K <= 96 (D={D}, K={K})")
+        return "chain" if family == "chain" and num_iters >= 2 else "cs"
+    if family in ("mfma", "mfma_persist") and not mfma_ok:
+        raise ValueError(f"pool_mode='mfma' needs D == 512 and block_rows*K <= 16384 (D={D}, K={K})")
+    if family == "tiles" and not tiles_ok:
+        return "ell"
+    return family
+
+
 class HotPath:
     """evaluate_scene on the device.  K, sharpen and num_iters are the reference's hard-coded
     constants (affinity_module.py:1492-1493,1584-1587) exposed as options."""
@@ -377,7 +415,7 @@ class HotPath:
         # (80 views of 30-60k visible points) is 4e10 pair tests and takes the lift from 23.6 to 14.4 ms against the view-by-view
         # grid search; beyond 2e11 (a scene with views of several hundred thousand visible points) the view-by-view path is taken.
         self.all_views_max_pairs = float(all_views_max_pairs)
-        self.pool_mode, self.pool_tile_rows, self.pool_block_rows = pool_mode, pool_tile_rows, pool_block_rows
+        self.pool_mode, self.pool_tile_rows, self.pool_block_rows = _known_pool_mode(pool_mode), pool_tile_rows, pool_block_rows
         # `prepare` also builds the pooling operator's structure (gp_pool_cs_structure) so that the affinity kernel writes the
         # weights in fragment order and no fill pass sits between the student and the pooling (pool_structure_ahead=False: the
         # two-pass form of rounds 3-4; last A/B 25.61 = 25.61 ms per scene: the pass left the critical path, the work stayed)
@@ -569,8 +607,8 @@ class HotPath:
         mark("kNN")
         state = {"X": X, "rank": rank, "nbr_map": nbr_map, "pairs": pairs, "nbr": nbr, "Nv": Nv, "D": D, "pool": None,
                  "xs": st.split_input(X)}                   # the first layer's pre-split operand (per-row scales)
-        mode = self._pool_mode(D)
-        if mode in ("mfma_cs", "mfma_engine", "mfma_chain"):
+        family = self._pool_family(D)
+        if family in ("cs", "chain"):
             sc = ops.pow2_scale(X, D)
             # "valid": the structure for the matrix-core affinity kernel (gp_affinity_cs_fragments: needs 128-wide embeddings and
             # K <= 96); True: the dst table of rounds 3-4 (affinity_block_kernel scatters its weights); False: the two-pass build
@@ -589,7 +627,7 @@ class HotPath:
             state["pool"] = {"op": ops.pool_cs_plan(nbr_op, structure=how), "sc": sc, "rho": rho, "nbr": nbr_op,
                              "x_split": ops.split_f16(X, D, scale=sc[0:1], dst_row=rho),
                              "pong": tuple(torch.empty((Nv, D), dtype=torch.float16, device=dev) for _ in range(2))}
-            if mode == "mfma_chain" and (state["pool"]["op"].dst is not None or state["pool"]["op"].valid is not None):   # (the lists need bu_row only)
+            if family == "chain" and (state["pool"]["op"].dst is not None or state["pool"]["op"].valid is not None):   # (the lists need bu_row only)
                 ops.pool_cs_deps(state["pool"]["op"])
             mark("pool plan+split")
         return state
@@ -640,27 +678,14 @@ class HotPath:
                       "pool_kernel": self._pool_kernel}
         return out
 
-    def _pool_mode(self, D):
-        mode = self.pool_mode
-        mfma_ok = D == 512 and self.pool_block_rows * self.K <= 16384 and self.num_iters >= 1
-        cs_ok = D == 512 and 128 * self.K <= 12288 and self.num_iters >= 1
-        tiles_ok = self.num_iters > 1 and self.pool_tile_rows * self.K <= 1536 and (D % 512 == 0 or D == 64)     # (D = 64: pool_tiles64_kernel, config P)
-        if mode == "auto":
-            mode = ("mfma_cs" if cs_ok else "mfma") if ((cs_ok or mfma_ok) and self.num_iters >= 3) else ("tiles" if tiles_ok else "ell")
-        if mode in ("mfma", "mfma_persist") and not mfma_ok:
-            raise ValueError(f"pool_mode='mfma' needs D == 512 and block_rows*K <= 16384 (D={D}, K={self.K})")
-        if mode in ("mfma_cs", "mfma_engine", "mfma_chain") and not cs_ok:
-            raise ValueError(f"pool_mode='{mode}' needs D == 512 and K <= 96 (D={D}, K={self.K})")
-        return mode
+    def _pool_family(self, D):
+        return resolve_pool_mode(self.pool_mode, D, self.K, self.num_iters, self.pool_tile_rows, self.pool_block_rows)
 
     def _pool(self, X, nbr, w, Nv, D, plan=None):
         """Row 12: num_iters applications of the row-stochastic affinity operator (affinity_module.py:1575-1587).
-        pool_mode: "auto" (matrix cores when the shape allows, else tiles, else ELL), "mfma_cs", "mfma_engine", "mfma",
-        "mfma_persist", "tiles", "ell".  plan: what `prepare` built ahead for the default path (operator plan, split planes)."""
+        The kernel family is resolve_pool_mode's.  plan: what `prepare` built ahead for the default path (operator plan, split planes)."""
         dev = X.device
-        mode = self._pool_mode(D)
-        R = self.pool_tile_rows
-        tiles_ok = self.num_iters > 1 and R * self.K <= 1536 and (D % 512 == 0 or D == 64)
+        family = self._pool_family(D)
         if w is None and (plan is None or not plan["op"].filled):
             # (isolated calls after a scene whose weights went straight into fragments: the [Nv, K] weights from the embedding planes)
             E = self._last_E
@@ -674,10 +699,9 @@ class HotPath:
             out.copy_(X[:, :D])
             self._pool_kernel = "none"
             return out
-        if mode in ("mfma_cs", "mfma_engine", "mfma_chain"):
+        if family in ("cs", "chain"):
             # column-sliced matrix-core pooling (default): 128-row blocks x 256-column halves, union rows grouped by the 16-row
-            # groups that use them, empty weight fragments skipped (pool_mfma_cs.hip).  "mfma_engine": the producer / consumer
-            # form of the same operator (persistent, 128-column tiles) -- same bits, same speed on MI355X.
+            # groups that use them, empty weight fragments skipped (pool_mfma_cs.hip)
             if plan is None:                            # (isolated calls: bench.py's pooling-only passes, tests)
                 sc = ops.pow2_scale(X, D)
                 plan = {"op": ops.pool_cs_plan(nbr), "sc": sc, "x_split": ops.split_f16(X, D, scale=sc[0:1]),
@@ -688,7 +712,7 @@ class HotPath:
             sp = [plan["x_split"], plan["pong"]]
             if self.stage_mark is not None:
                 self.stage_mark("pool operator fill")
-            if mode == "mfma_chain" and self.num_iters >= 2:
+            if family == "chain":
                 # all applications in ONE launch (gp_pool_cs_apply_chain: per-block flags instead of kernel boundaries; same planes,
                 # same bits).  The abort word of its contract is read at the next host synchronisation (pool_chain_check).
                 if op.dep is None:
@@ -702,19 +726,18 @@ class HotPath:
             for t in range(self.num_iters):
                 last = t == self.num_iters - 1
                 dst = None if last else sp[(t + 1) % 2]
-                ops.pool_cs_apply(src, op, D, out_split=dst, out_f32=out if last else None, out_scale=sc[1:2] if last else None,
-                                  engine=mode == "mfma_engine")
+                ops.pool_cs_apply(src, op, D, out_split=dst, out_f32=out if last else None, out_scale=sc[1:2] if last else None)
                 src = dst
-            self._pool_kernel = "cs_engine_kernel" if mode == "mfma_engine" else "cs_pool_kernel"
+            self._pool_kernel = "cs_pool_kernel"
             return out
-        if mode in ("mfma", "mfma_persist"):
+        if family in ("mfma", "mfma_persist"):
             # matrix-core pooling: operands stay split (hi, lo) f16 between applications, fp32 only at the end.
             # "mfma" (default): one (64 rows x 128 columns) tile per workgroup, two workgroups per CU.
             # "mfma_persist": the persistent kernel (one workgroup per CU, 256 columns per workgroup, weight fragments shared
             # by both column groups, rings kept full across row blocks) -- same speed within run-to-run noise on MI355X
             # (DESIGN.md section 6); needs >= 4 steps per row block and 64-row blocks, else falls back to "mfma"
-            op = ops.pool_mfma_build(nbr, w, self.pool_block_rows, min_steps=9 if mode == "mfma_persist" else 0)
-            persistent = mode == "mfma_persist" and op.min_steps >= 9 and self.pool_block_rows == 64
+            op = ops.pool_mfma_build(nbr, w, self.pool_block_rows, min_steps=9 if family == "mfma_persist" else 0)
+            persistent = family == "mfma_persist" and op.min_steps >= 9 and self.pool_block_rows == 64
             rows = op.rows_padded if persistent else Nv
             out = torch.empty((rows, D), dtype=torch.float32, device=dev)
             # one power of two for the whole operand (pooling is a convex combination: magnitudes never grow), so that the lo
@@ -732,8 +755,8 @@ class HotPath:
                 src = dst
             self._pool_kernel = "pool_mfma_persist_kernel" if persistent else "pool_mfma_kernel"
             return out[:Nv]
-        use_tiles = mode == "tiles" and tiles_ok
-        tiles = ops.pool_tiles_build(nbr, w, R) if use_tiles else None
+        use_tiles = family == "tiles"
+        tiles = ops.pool_tiles_build(nbr, w, self.pool_tile_rows) if use_tiles else None
         bufs = [torch.empty((Nv, D), dtype=torch.float32, device=dev) for _ in range(2)]
         cur = X
         for t in range(self.num_iters):

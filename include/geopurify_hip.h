@@ -345,17 +345,6 @@ int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int
                      const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
                      int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32, int64_t ld_yf,
                      const float *out_scale, void *stream);
-/* The same application through the persistent producer / consumer form of the kernel (cs_engine_kernel, one workgroup per */
-/* CU); bit-identical results.  Its own entry point: the choice of kernel is an argument of the call, not process state.   */
-int gp_pool_cs_apply_engine(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                            const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
-                            int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32, int64_t ld_yf,
-                            const float *out_scale, void *stream);
-/* One 256-column half (0 or 1) of the same application; the halves are independent (two streams can each carry one).     */
-int gp_pool_cs_apply_half(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
-                          const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
-                          int32_t rows_per_block, int32_t half, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32,
-                          int64_t ld_yf, const float *out_scale, void *stream);
 /* ALL `applications` (2..65535) of the operator in ONE launch (the T = 19 torch.sparse.mm calls of                          */
 /* models/affinity_module.py:1575-1587 as one kernel): application t reads plane set (t even ? x : p) and writes the other   */
 /* one, the last one writes y_f32 (x out_scale[0]) only -- the sequence, planes and bits of `applications` calls of           */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Round 5: all T applications of the pooling operator in ONE launch (gp_pool_cs_apply_chain) and the cheaper alternative (the two
-column halves as two chains of launches on two streams) against the T launches of cs_pool_kernel -- bits, time, in-kernel stamps.
+"""Round 5: all T applications of the pooling operator in ONE launch (gp_pool_cs_apply_chain) against the T launches of
+cs_pool_kernel -- bits, time, in-kernel stamps.
 usage: bench_pool_chain.py [num_points] [T] [stamps]"""
 import dataclasses
 import os
@@ -63,25 +63,6 @@ def run_launches(xs, pong, out):
         src = dst
 
 
-side = torch.cuda.Stream()
-
-
-def run_halves(xs, pong, out):
-    """the two 256-column halves as two chains: half 0 on the current stream, half 1 on `side`, started half an application apart"""
-    main = torch.cuda.current_stream()
-    side.wait_stream(main)
-    for half, st in ((0, main), (1, side)):
-        with torch.cuda.stream(st):
-            sp = [xs, pong]
-            src = sp[0]
-            for t in range(T):
-                last = t == T - 1
-                dst = None if last else sp[(t + 1) % 2]
-                ops.pool_cs_apply_half(src, op, D, half, out_split=dst, out_f32=out if last else None, out_scale=scl[1:2] if last else None)
-                src = dst
-    main.wait_stream(side)
-
-
 def run_chain(xs, pong, out):
     ops.pool_cs_apply_chain(xs, pong, op, D, T, out, out_scale=scl[1:2])
 
@@ -102,8 +83,7 @@ def timed(fn, reps=5):
 
 
 ref_t, ref = timed(run_launches)
-for name, fn in (("T launches of cs_pool_kernel", run_launches), ("two column-half chains on two streams", run_halves),
-                 ("ONE chained launch", run_chain)):
+for name, fn in (("T launches of cs_pool_kernel", run_launches), ("ONE chained launch", run_chain)):
     for rnd in range(2):
         ts, got = timed(fn)
         same = all(torch.equal(a, b) for a, b in zip([got[0], *got[1], *got[2]], [ref[0], *ref[1], *ref[2]]))
@@ -116,6 +96,7 @@ print("abort word:", int(op.flags[0].item()), " epoch:", op.epoch, flush=True)
 # ---- the hand-off under uneven load: a second stream streams 1 GiB copies beside the chained launch; every word is compared
 big = torch.empty(256 << 20, dtype=torch.float32, device="cuda")
 big2 = torch.empty_like(big)
+side = torch.cuda.Stream()
 bad = 0
 for it in range(8):
     xs, pong = planes()

@@ -41,12 +41,12 @@ def test_size_queries_without_gpu():
 
 def test_debug_knobs_reject_what_is_not_in_the_table():
     """gp_debug_set is a declared export; a key or value outside the table of csrc/error.hip is GP_EINVAL
-    (host-side check, no GPU needed).  The engine is no longer a knob (11 = 8): it is gp_pool_cs_apply_engine."""
+    (host-side check, no GPU needed).  Pooling bits 256 / 512 belonged to the retired producer / consumer kernel."""
     lib = _lib.load()
     EINVAL = -22
     for key, value in ((0, 0), (16, 0), (-1, 0),                 # no such knob
                        (8, 32), (8, -1),                         # matrix-core affinity mask (round 5): bits 0-4 only
-                       (4, 1024), (4, 2048), (4, -1),            # pooling mask: bits >= 10 are undefined
+                       (4, 256), (4, 512), (4, 1024), (4, 2048), (4, -1),   # pooling mask: bits >= 8 are undefined
                        (3, 64), (11, 8), (11, 1), (7, 1), (5, 2), (15, 3), (1, 5), (10, 65)):
         assert lib.gp_debug_set(key, value) == EINVAL, (key, value)
         assert b"gp_debug_set" in lib.gp_last_error()

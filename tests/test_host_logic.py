@@ -355,3 +355,48 @@ def test_conv_partial_row_format_restatement():
     Eb = cp.exponents(bad)
     assert Eb[2, 1] == 255 and Eb[4, 0] == 255 and (Eb[2, 0] < 255) and (Eb[4, 1] < 255)
     assert cp.exponent_offset(P, cout) == ((P * cout * 3 + 15) // 16) * 16
+
+
+def test_pool_mode_resolver_table():
+    """pipeline.resolve_pool_mode is the one place that turns a pool_mode name and a shape into row 12's kernel family.  Shape
+    fallbacks stay quiet (tiles -> ELL, a single chained application -> cs); an explicit matrix-core mode the shape does not admit and
+    a name that is not a mode raise (the retired producer / consumer mode no longer times another kernel under its name)."""
+    from geopurify_amd import pipeline as pl
+    S = dict(D=512, K=96, num_iters=19, tile_rows=8, block_rows=64)            # bench.py's default run
+    table = [
+        ("auto", S, "cs"),
+        ("auto", dict(S, K=128), "mfma"),                                       # K > 96: the 64-row matrix-core kernel
+        ("auto", dict(S, D=64), "tiles"),                                       # config P: D = 64 in 8-row tiles (pool_tiles64_kernel)
+        ("auto", dict(S, D=64, tile_rows=16), "ell"),                           # gp_pool_tiles_apply takes D = 64 in 4- or 8-row tiles only
+        ("tiles", dict(S, D=64, tile_rows=4), "tiles"),
+        ("tiles", dict(S, D=64, tile_rows=16), "ell"),
+        ("tiles", dict(S, K=200), "ell"),                                       # R K > 1536
+        ("auto", dict(S, num_iters=0), "ell"),
+        ("auto", dict(S, num_iters=1), "ell"),
+        ("auto", dict(S, num_iters=2), "tiles"),
+        ("tiles", dict(S, num_iters=1), "ell"),
+        ("mfma_cs", dict(S, num_iters=1), "cs"),
+        ("mfma_chain", dict(S, num_iters=1), "cs"),
+        ("mfma_chain", dict(S, num_iters=2), "chain"),
+        ("mfma", dict(S, num_iters=1), "mfma"),
+        ("mfma_cs", S, "cs"),
+        ("mfma_chain", S, "chain"),
+        ("mfma", S, "mfma"),
+        ("mfma", dict(S, block_rows=128), "mfma"),
+        ("mfma_persist", S, "mfma_persist"),
+        ("tiles", S, "tiles"),
+        ("ell", S, "ell"),
+        ("ell", dict(S, D=64), "ell"),
+    ]
+    for mode, shape, family in table:
+        assert pl.resolve_pool_mode(mode, **shape) == family, (mode, shape)
+    for mode, shape, match in [("mfma_cs", dict(S, K=128), "K <= 96"), ("mfma_chain", dict(S, D=64), "K <= 96"),
+                               ("mfma_cs", dict(S, num_iters=0), "K <= 96"), ("mfma", dict(S, D=64), "block_rows"),
+                               ("mfma_persist", dict(S, block_rows=256), "block_rows")]:
+        with pytest.raises(ValueError, match=match):
+            pl.resolve_pool_mode(mode, **shape)
+    for mode in ("mfma_engine", "mfma-cs", "MFMA_CS", ""):                    # the retired producer / consumer mode, misspellings
+        with pytest.raises(ValueError, match="pool_mode="):
+            pl.resolve_pool_mode(mode, **S)
+        with pytest.raises(ValueError, match="pool_mode="):
+            pl.HotPath(None, (8, 8), device="cpu", pool_mode=mode)
