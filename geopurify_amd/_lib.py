@@ -77,6 +77,7 @@ SIGNATURES = {
     "gp_pool_cs_apply": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P]),
     "gp_pool_cs_deps": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     "gp_pool_cs_chain_flag_words": (c_size_t, [c_int64, c_int32]),
+    "gp_pool_cs_chain_flag_words_d": (c_size_t, [c_int64, c_int32, c_int32]),
     "gp_pool_cs_apply_chain": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P,
                                          c_uint32, _P]),
     "gp_lift_dense_accum": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, c_int64, _P, _P]),

@@ -489,6 +489,77 @@ classify16_lds_kernel(const float *__restrict__ feat, int64_t ld, int d, int64_t
     }
 }
 
+// gp_gather_rows_classify for rows wider than the 16-lane form holds (512 < d <= 1024): gp_classify_argmax classifies those rows with
+// classify_kernel below, so this is ITS arithmetic -- one wave per point, lane l owns columns l, l + 64, ... (up to CL_WJ of them, in
+// registers), the same per-lane order, the same wave sums and divisions: the same labels and zero flags, bit for bit.  The text matrix
+// is staged once per workgroup in LDS and each wave classifies CL_Q points per class sweep, as in classify16_lds_kernel.
+constexpr int CL_WJ = 16;                     // floats per lane -> d <= 1024
+__global__ void __launch_bounds__(256)
+classify_wave_gather_kernel(const float *__restrict__ feat, int64_t ld, int d, int64_t n, const float *__restrict__ text, int C,
+                            float scale, int64_t *__restrict__ pred, uint8_t *__restrict__ zero_row, const int64_t *__restrict__ index,
+                            const int32_t *__restrict__ row_map, float *__restrict__ out, int64_t ld_out) {
+    extern __shared__ __align__(16) float cl_text[];        // [C][d]
+    for (int i = threadIdx.x * 4; i < C * d; i += 256 * 4) *reinterpret_cast<float4 *>(cl_text + i) = *reinterpret_cast<const float4 *>(text + i);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nj = d / 64;
+    for (int64_t base = blockIdx.x * (int64_t)(4 * CL_Q); base < n; base += (int64_t)gridDim.x * (4 * CL_Q)) {
+        float u[CL_Q][CL_WJ];
+        float sa[CL_Q], bestv[CL_Q];
+        int bestc[CL_Q];
+        bool live[CL_Q];
+#pragma unroll
+        for (int q = 0; q < CL_Q; ++q) {
+            const int64_t p = base + w * CL_Q + q;
+            live[q] = p < n;
+            int64_t src_row = 0;
+            if (live[q]) { src_row = index[p]; if (row_map) src_row = row_map[src_row]; }
+            float ss = 0.f;                                  // (the columns past d add exact zeros)
+#pragma unroll
+            for (int j = 0; j < CL_WJ; ++j) {
+                u[q][j] = (live[q] && j < nj) ? feat[src_row * ld + j * 64 + lane] : 0.f;
+                if (live[q] && j < nj) out[p * ld_out + j * 64 + lane] = u[q][j];
+                ss += u[q][j] * u[q][j];
+            }
+            ss = gp_wave_sum(ss);
+            const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+            float a = 0.f;
+#pragma unroll
+            for (int j = 0; j < CL_WJ; ++j) {
+                u[q][j] = u[q][j] / nrm;
+                a += fabsf(u[q][j]);
+            }
+            sa[q] = gp_wave_sum(a);
+            bestv[q] = -INFINITY;
+            bestc[q] = 0;
+        }
+        for (int k = 0; k < C; ++k) {
+            float dot[CL_Q];
+#pragma unroll
+            for (int q = 0; q < CL_Q; ++q) dot[q] = 0.f;
+#pragma unroll
+            for (int j = 0; j < CL_WJ; ++j)
+                if (j < nj) {
+                    const float t = cl_text[k * d + j * 64 + lane];
+#pragma unroll
+                    for (int q = 0; q < CL_Q; ++q) dot[q] += u[q][j] * t;
+                }
+#pragma unroll
+            for (int q = 0; q < CL_Q; ++q) {
+                const float dv = gp_wave_sum(dot[q]) * scale;
+                if (dv > bestv[q]) { bestv[q] = dv; bestc[q] = k; }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < CL_Q; ++q)
+            if (live[q] && lane == 0) {
+                const int64_t p = base + w * CL_Q + q;
+                pred[p] = bestc[q];
+                if (zero_row) zero_row[p] = (sa[q] == 0.f) ? 1 : 0;
+            }
+    }
+}
+
 // generic shape: one wave per point
 __global__ void classify_kernel(const float *__restrict__ feat, int64_t ld, int d, int64_t n,
                                 const float *__restrict__ text, int C, float scale, int64_t *__restrict__ pred,
@@ -729,15 +800,22 @@ extern "C" int gp_gather_rows_classify(const float *src, int64_t ld_src, int32_t
                                        float *out, int64_t ld_out, const float *text_norm, int32_t c, float logit_scale, int64_t *pred,
                                        uint8_t *zero_row, void *stream_) {
     GP_CHECK_ARG(src && index && out && text_norm && pred && n > 0 && d > 0 && c > 0, "gp_gather_rows_classify: null/empty argument");
-    GP_CHECK_ARG(d % 64 == 0 && d <= 64 * CL_MAXJ && ld_src % 4 == 0 && ld_out % 4 == 0 && ld_out >= d && (uintptr_t)src % 16 == 0 &&
+    GP_CHECK_ARG(d % 64 == 0 && d <= 64 * CL_WJ && ld_src % 4 == 0 && ld_out % 4 == 0 && ld_out >= d && (uintptr_t)src % 16 == 0 &&
                      (uintptr_t)out % 16 == 0 && (uintptr_t)text_norm % 16 == 0 && (size_t)c * d * sizeof(float) <= 64 * 1024,
                  "gp_gather_rows_classify: d=%d must be a multiple of 64 up to %d, rows 16-byte aligned, c * d * 4 <= 64 KiB (use gp_gather_rows + "
-                 "gp_classify_argmax otherwise)", d, 64 * CL_MAXJ);
+                 "gp_classify_argmax otherwise)", d, 64 * CL_WJ);
     GP_CHECK_ARG(out != src, "gp_gather_rows_classify: out must not alias src");
-    GP_SMEM_ATTR(classify16_lds_kernel<true>, 64 * 1024);
-    const int64_t groups = (n + 16 * CL_Q - 1) / (16 * CL_Q);
-    classify16_lds_kernel<true><<<(int)(groups < 2048 ? groups : 2048), 256, (size_t)c * d * sizeof(float), gp_stream(stream_)>>>(
-        src, ld_src, d, n, text_norm, c, logit_scale, pred, zero_row, index, row_map, out, ld_out);
+    if (d <= 64 * CL_MAXJ) {                               // the 16-lane form of gp_classify_argmax at these widths
+        GP_SMEM_ATTR(classify16_lds_kernel<true>, 64 * 1024);
+        const int64_t groups = (n + 16 * CL_Q - 1) / (16 * CL_Q);
+        classify16_lds_kernel<true><<<(int)(groups < 2048 ? groups : 2048), 256, (size_t)c * d * sizeof(float), gp_stream(stream_)>>>(
+            src, ld_src, d, n, text_norm, c, logit_scale, pred, zero_row, index, row_map, out, ld_out);
+    } else {                                               // wider rows: gp_classify_argmax's one-wave-per-point arithmetic
+        GP_SMEM_ATTR(classify_wave_gather_kernel, 64 * 1024);
+        const int64_t groups = (n + 4 * CL_Q - 1) / (4 * CL_Q);
+        classify_wave_gather_kernel<<<(int)(groups < 2048 ? groups : 2048), 256, (size_t)c * d * sizeof(float), gp_stream(stream_)>>>(
+            src, ld_src, d, n, text_norm, c, logit_scale, pred, zero_row, index, row_map, out, ld_out);
+    }
     GP_CHECK_LAUNCH();
     return GP_OK;
 }

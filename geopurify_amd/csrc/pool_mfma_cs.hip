@@ -34,7 +34,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CS_KS = 32;              // union rows per step (MFMA K)
-constexpr int CS_D = 512;              // feature columns
+constexpr int CS_D = 512;              // feature columns of the product kernels (cs_pool_kernel, cs_chain_kernel)
+constexpr int CS_DMAX = 1024;          // widest d of the other slice counts (cs_pool_ns_kernel, cs_chain_ns_kernel): 256, 768, 1024
 constexpr int CS_BR = 128;             // rows per block
 constexpr int CS_NG = CS_BR / 16;      // 16-row groups per block = weight fragments per step
 constexpr int CS_NC = 256;             // columns per workgroup
@@ -330,7 +331,9 @@ cs_fill_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, int
 
 // ------------------------------------------------------------------------------------------------ apply
 // One 512-thread workgroup = 128 rows x 256 columns (grid = row blocks x 2 column halves, the halves of a row block
-// adjacent on one XCD); wave wv owns columns 32 wv .. 32 wv + 31 of the half for all 128 rows (16 accumulator tiles).
+// adjacent on one XCD; NS: 256-column slices per row, d = 256 NS -- NS = 2 is the product width, the other counts tile their
+// slices the same way: tile lb = NS b + slice, a row block's slices back to back); wave wv owns columns 32 wv .. 32 wv + 31 of
+// the slice for all 128 rows (16 accumulator tiles).
 // A 3-deep ring of 48-KiB stages is filled by LDS-DMA two steps ahead (96 KiB in flight per CU); wave wv stages union
 // rows 4 wv .. 4 wv + 3 of a step (two 1-KiB instructions per plane, two rows each) and the weight fragment of group wv.
 // The image is XOR-swizzled through the DMA source addresses exactly as in pool_mfma.hip (physical 16-byte chunk c of
@@ -358,7 +361,7 @@ struct CsChain {
     const _Float16 *a_hi, *a_lo;       // plane set A (application 0's input; rewritten by applications 1, 3, ...)
     _Float16 *b_hi, *b_lo;             // plane set B
     int64_t ld;                        // row pitch of both sets (elements)
-    uint32_t *flags;                   // [32 header words: word 0 = abort] [2 halves][nblocks]
+    uint32_t *flags;                   // [32 header words: word 0 = abort] [NS slices (2 halves at d = 512)][nblocks]
     const int32_t *dep;                // [nblocks][64]: word 0 = n, words 1 .. min(n, 63) = row blocks (n > 63: wait for every block)
     int32_t T;                         // applications (>= 2)
     uint32_t base;                     // flags epoch: a published application t reads base + t + 1
@@ -368,7 +371,7 @@ struct CsChain {
 constexpr int CS_DEP_CAP = 64;
 constexpr int CS_FLAG_HDR = 32;
 
-template <bool STAMP, bool TUNE, bool CHAIN = false>
+template <bool STAMP, bool TUNE, bool CHAIN = false, int NS = 2>
 __device__ __forceinline__ void
 cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_lo_, int64_t ld_x_,
                const int64_t *__restrict__ bu_off, const int32_t *__restrict__ bu_row, const uint32_t *__restrict__ bu_mask,
@@ -413,12 +416,14 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
         lb = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
         if (ch.half_sel >= 0) lb = 2 * lb + ch.half_sel;         // (per_xcd then counts row blocks, not tiles)
     }
-    const int64_t b = lb >> 1;
-    const int col0 = (int)(lb & 1) * CS_NC;
+    // (NS = 2 keeps the shift and mask of the measured kernel)
+    const int64_t b = NS == 2 ? lb >> 1 : (int64_t)((uint64_t)lb / NS);
+    const int64_t slice = NS == 2 ? lb & 1 : lb - b * NS;
+    const int col0 = (int)slice * CS_NC;
     if (b >= nblocks) return;
     uint32_t *my_flag = nullptr;
     if constexpr (CHAIN) {
-        uint32_t *fl = ch.flags + CS_FLAG_HDR + (lb & 1) * nblocks;
+        uint32_t *fl = ch.flags + CS_FLAG_HDR + slice * nblocks;
         my_flag = fl + b;
         if (app > 0) {
             // every wave polls for itself (no barrier in front of the first DMA): lane 0 watches abort, lanes 1 .. n the row blocks
@@ -722,17 +727,25 @@ __global__ void __launch_bounds__(512, 2) cs_pool_kernel(CS_POOL_PARAMS) { cs_po
 // the same body with the tuning bits live, under its own name: launches with parts of the kernel switched off (bench.py's
 // gather + store ceiling, scripts/bench_pool.py ablations) do not mix into the product kernel's rows of a kernel trace
 __global__ void __launch_bounds__(512, 2) cs_pool_tuning_kernel(CS_POOL_PARAMS) { cs_pool_body<false, true>(CS_POOL_FWD, CsChain{}); }
+// the other widths (d = 256 NS, NS = 1, 3, 4): the same body over NS slices per row block, under their own names, so that the d = 512
+// kernels above stay the code that was measured
+template <bool STAMP, int NS>
+__global__ void __launch_bounds__(512, 2) cs_pool_ns_kernel(CS_POOL_PARAMS) { cs_pool_body<STAMP, false, false, NS>(CS_POOL_FWD, CsChain{}); }
 #undef CS_POOL_PARAMS
 #undef CS_POOL_FWD
 // all T applications in one launch (see CsChain above)
+#define CS_CHAIN_PARAMS CsChain ch, const int64_t *__restrict__ bu_off, const int32_t *__restrict__ bu_row, const uint32_t *__restrict__ bu_mask, \
+                        const _Float16 *__restrict__ wa_hi, const _Float16 *__restrict__ wa_lo, int64_t nv, int64_t nblocks,                      \
+                        float *__restrict__ y_f32, int64_t ld_yf, int64_t per_xcd, const float *__restrict__ out_scale,                          \
+                        uint64_t *__restrict__ stamp, int rpb
+#define CS_CHAIN_FWD nullptr, nullptr, 0, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, nblocks, nullptr, nullptr, 0, y_f32, ld_yf, per_xcd, 0, \
+                     out_scale, stamp, rpb, ch
 template <bool STAMP>
-__global__ void __launch_bounds__(512, 2)
-cs_chain_kernel(CsChain ch, const int64_t *__restrict__ bu_off, const int32_t *__restrict__ bu_row, const uint32_t *__restrict__ bu_mask,
-                const _Float16 *__restrict__ wa_hi, const _Float16 *__restrict__ wa_lo, int64_t nv, int64_t nblocks, float *__restrict__ y_f32,
-                int64_t ld_yf, int64_t per_xcd, const float *__restrict__ out_scale, uint64_t *__restrict__ stamp, int rpb) {
-    cs_pool_body<STAMP, false, true>(nullptr, nullptr, 0, bu_off, bu_row, bu_mask, wa_hi, wa_lo, nv, nblocks, nullptr, nullptr, 0, y_f32, ld_yf,
-                                     per_xcd, 0, out_scale, stamp, rpb, ch);
-}
+__global__ void __launch_bounds__(512, 2) cs_chain_kernel(CS_CHAIN_PARAMS) { cs_pool_body<STAMP, false, true>(CS_CHAIN_FWD); }
+template <bool STAMP, int NS>
+__global__ void __launch_bounds__(512, 2) cs_chain_ns_kernel(CS_CHAIN_PARAMS) { cs_pool_body<STAMP, false, true, NS>(CS_CHAIN_FWD); }
+#undef CS_CHAIN_PARAMS
+#undef CS_CHAIN_FWD
 
 // ------------------------------------------------------------------------------------------------ affinity -> fragments
 // Row 11 on the matrix cores, fused with the operator fill (models/affinity_module.py:1559-1572: cosine similarity of the unit
@@ -1148,14 +1161,32 @@ extern "C" int gp_pool_cs_structure(const int32_t *nbr, int64_t nv, int32_t k, i
     return GP_OK;
 }
 
-// One application y = A x on pre-split operands (see gp_pool_mfma_apply for the operand conventions).  d must be 512.
+// widths of the column-sliced kernels: whole 256-column slices, 1 to 4 of them (d = 512: the product kernels)
+static bool cs_d_ok(int32_t d) { return d % CS_NC == 0 && d >= CS_NC && d <= CS_DMAX; }
+#define CS_D_MSG "d=%d (the column-sliced kernels take d = 256, 512, 768 or 1024)"
+
+// a kernel of the other widths (d = 256 NS, NS != 2): one instantiation per slice count (GP_SMEM_ATTR's state is per instantiation)
+template <bool STAMP, int NS, typename... A>
+static int cs_launch_pool_ns(unsigned grid, hipStream_t s, A... args) {
+    GP_SMEM_ATTR((cs_pool_ns_kernel<STAMP, NS>), CS_SMEM);
+    cs_pool_ns_kernel<STAMP, NS><<<grid, 512, CS_SMEM, s>>>(args...);
+    return GP_OK;
+}
+template <bool STAMP, int NS, typename... A>
+static int cs_launch_chain_ns(unsigned grid, hipStream_t s, A... args) {
+    GP_SMEM_ATTR((cs_chain_ns_kernel<STAMP, NS>), CS_SMEM);
+    cs_chain_ns_kernel<STAMP, NS><<<grid, 512, CS_SMEM, s>>>(args...);
+    return GP_OK;
+}
+// One application y = A x on pre-split operands (see gp_pool_mfma_apply for the operand conventions).  d = 256, 512, 768 or 1024
+// (d / 256 column slices per row block; 512 runs cs_pool_kernel, the others cs_pool_ns_kernel).
 // rows_per_block: the builder's (gp_pool_cs_count / _fill).
 extern "C" int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
                                 const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
                                 int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32,
                                 int64_t ld_yf, const float *out_scale, void *stream_) {
     GP_CHECK_ARG(x_hi && x_lo && bu_off && bu_row && bu_mask && wa_hi && wa_lo && nv > 0, "gp_pool_cs_apply: null/empty argument");
-    GP_CHECK_ARG(d == CS_D, "gp_pool_cs_apply: d=%d (kernel specialised for %d columns)", d, CS_D);
+    GP_CHECK_ARG(cs_d_ok(d), "gp_pool_cs_apply: " CS_D_MSG, d);
     GP_CHECK_ARG(cs_rpb_ok(rows_per_block), "gp_pool_cs_apply: rows_per_block=%d (16..%d)", rows_per_block, CS_BR);
     GP_CHECK_ARG((y_hi && y_lo) || y_f32, "gp_pool_cs_apply: no output requested");
     GP_CHECK_ARG(ld_x % 8 == 0 && (uintptr_t)x_hi % 16 == 0 && (uintptr_t)x_lo % 16 == 0, "gp_pool_cs_apply: x rows must be 16-byte aligned");
@@ -1163,8 +1194,9 @@ extern "C" int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x
                  "gp_pool_cs_apply: y rows must be 16-byte aligned and must not alias x");
     GP_CHECK_ARG(!y_f32 || (ld_yf % 4 == 0 && (uintptr_t)y_f32 % 16 == 0), "gp_pool_cs_apply: fp32 output rows must be 16-byte aligned");
     hipStream_t s = gp_stream(stream_);
+    const int ns = d / CS_NC;                             // 256-column slices per row block (tiles of a row block)
     const int64_t nb = (nv + rows_per_block - 1) / rows_per_block;
-    const int64_t per_xcd = (nb * (CS_D / CS_NC) + 7) / 8;
+    const int64_t per_xcd = (nb * ns + 7) / 8;
     uint64_t *stamp = static_cast<uint64_t *>(g_gp_debug_ptr[0]);
     const int tune = g_gp_knobs[4];                       // tuning bits: only ever handed to cs_pool_tuning_kernel
     GP_CHECK_ARG(!stamp || g_gp_debug_bytes[0] >= (size_t)(per_xcd * 8) * CS_NW * 10 * sizeof(uint64_t),
@@ -1173,7 +1205,15 @@ extern "C" int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x
 #define CS_ARGS static_cast<const _Float16 *>(x_hi), static_cast<const _Float16 *>(x_lo), ld_x, bu_off, bu_row, bu_mask,              \
                 static_cast<const _Float16 *>(wa_hi), static_cast<const _Float16 *>(wa_lo), nv, nb, static_cast<_Float16 *>(y_hi),     \
                 static_cast<_Float16 *>(y_lo), ld_y, y_f32, ld_yf, per_xcd, tune, out_scale, stamp, rows_per_block
-    if (stamp) {
+    GP_CHECK_ARG(ns == 2 || tune == 0, "gp_pool_cs_apply: the tuning bits of knob 4 apply to d = 512 only (d=%d)", d);
+    if (ns != 2) {
+        const unsigned grid = (unsigned)(per_xcd * 8);
+        int rc;
+        if (ns == 1) rc = stamp ? cs_launch_pool_ns<true, 1>(grid, s, CS_ARGS) : cs_launch_pool_ns<false, 1>(grid, s, CS_ARGS);
+        else if (ns == 3) rc = stamp ? cs_launch_pool_ns<true, 3>(grid, s, CS_ARGS) : cs_launch_pool_ns<false, 3>(grid, s, CS_ARGS);
+        else rc = stamp ? cs_launch_pool_ns<true, 4>(grid, s, CS_ARGS) : cs_launch_pool_ns<false, 4>(grid, s, CS_ARGS);
+        if (rc != GP_OK) return rc;
+    } else if (stamp) {
         GP_SMEM_ATTR(cs_pool_kernel<true>, CS_SMEM);
         cs_pool_kernel<true><<<(unsigned)(per_xcd * 8), 512, CS_SMEM, s>>>(CS_ARGS);
     } else if (tune != 0) {
@@ -1261,17 +1301,20 @@ extern "C" int gp_pool_cs_deps(const int64_t *bu_off, const int32_t *bu_row, int
     return GP_OK;
 }
 
-// words of the flags array of gp_pool_cs_apply_chain: 32 header words (word 0 = abort) + 2 column halves x nblocks
-extern "C" size_t gp_pool_cs_chain_flag_words(int64_t nv, int32_t rows_per_block) {
-    if (nv <= 0 || !cs_rpb_ok(rows_per_block)) return 0;
-    return (size_t)CS_FLAG_HDR + 2 * (size_t)((nv + rows_per_block - 1) / rows_per_block);
+// words of the flags array of gp_pool_cs_apply_chain: 32 header words (word 0 = abort) + d / 256 column slices x nblocks
+// (gp_pool_cs_chain_flag_words: d = 512, 2 column halves)
+extern "C" size_t gp_pool_cs_chain_flag_words_d(int64_t nv, int32_t rows_per_block, int32_t d) {
+    if (nv <= 0 || !cs_rpb_ok(rows_per_block) || !cs_d_ok(d)) return 0;
+    return (size_t)CS_FLAG_HDR + (size_t)(d / CS_NC) * (size_t)((nv + rows_per_block - 1) / rows_per_block);
 }
+extern "C" size_t gp_pool_cs_chain_flag_words(int64_t nv, int32_t rows_per_block) { return gp_pool_cs_chain_flag_words_d(nv, rows_per_block, CS_D); }
 
 // ALL `applications` (>= 2) of y = A x in ONE launch: application t reads plane set (t even ? x : p) and writes the other one, the
 // last one writes y_f32 (x out_scale[0]) only -- the same sequence, planes and bits as `applications` calls of gp_pool_cs_apply
 // that ping-pong between x and p.  x_hi / x_lo are REWRITTEN (from application 1 on), as in that sequence.
 //   dep    gp_pool_cs_deps' lists.
-//   flags  u32 [gp_pool_cs_chain_flag_words]: zeroed ONCE by the caller when allocated, never again; word 0 is the abort word: the
+//   flags  u32 [gp_pool_cs_chain_flag_words_d(nv, rows_per_block, d)]: zeroed ONCE by the caller when allocated, never again; word 0
+//          is the abort word: the
 //          kernel sets it to 1 if a workgroup waited 2 s for a dependency (the launch then drains without computing; the outputs
 //          are invalid) -- the caller reads it at its next synchronisation point and must treat non-zero as an error.
 //   epoch  a counter the caller keeps per flags array: every call passes a value at least `applications` above the previous call's
@@ -1285,7 +1328,7 @@ extern "C" int gp_pool_cs_apply_chain(void *x_hi, void *x_lo, void *p_hi, void *
                                       const float *out_scale, const int32_t *dep, uint32_t *flags, uint32_t epoch, void *stream_) {
     GP_CHECK_ARG(x_hi && x_lo && p_hi && p_lo && bu_off && bu_row && bu_mask && wa_hi && wa_lo && y_f32 && dep && flags && nv > 0,
                  "gp_pool_cs_apply_chain: null/empty argument");
-    GP_CHECK_ARG(d == CS_D, "gp_pool_cs_apply_chain: d=%d (kernel specialised for %d columns)", d, CS_D);
+    GP_CHECK_ARG(cs_d_ok(d), "gp_pool_cs_apply_chain: " CS_D_MSG, d);
     GP_CHECK_ARG(cs_rpb_ok(rows_per_block), "gp_pool_cs_apply_chain: rows_per_block=%d (16..%d)", rows_per_block, CS_BR);
     GP_CHECK_ARG(applications >= 2 && applications < 65536, "gp_pool_cs_apply_chain: applications=%d (2..65535; one: gp_pool_cs_apply)", applications);
     GP_CHECK_ARG(ld % 8 == 0 && (uintptr_t)x_hi % 16 == 0 && (uintptr_t)x_lo % 16 == 0 && (uintptr_t)p_hi % 16 == 0 && (uintptr_t)p_lo % 16 == 0,
@@ -1293,8 +1336,9 @@ extern "C" int gp_pool_cs_apply_chain(void *x_hi, void *x_lo, void *p_hi, void *
     GP_CHECK_ARG(x_hi != p_hi && x_lo != p_lo && x_hi != x_lo && p_hi != p_lo, "gp_pool_cs_apply_chain: the four planes must not alias");
     GP_CHECK_ARG(ld_yf % 4 == 0 && (uintptr_t)y_f32 % 16 == 0, "gp_pool_cs_apply_chain: fp32 output rows must be 16-byte aligned");
     hipStream_t s = gp_stream(stream_);
+    const int ns = d / CS_NC;                             // 256-column slices per row block (tiles of a row block)
     const int64_t nb = (nv + rows_per_block - 1) / rows_per_block;
-    const int64_t per_xcd = (nb * (CS_D / CS_NC) + 7) / 8;
+    const int64_t per_xcd = (nb * ns + 7) / 8;
     const int64_t grid = per_xcd * 8 * applications;
     GP_CHECK_ARG(grid < (int64_t)INT32_MAX, "gp_pool_cs_apply_chain: %lld workgroups", (long long)grid);
     CsChain ch;
@@ -1311,7 +1355,16 @@ extern "C" int gp_pool_cs_apply_chain(void *x_hi, void *x_lo, void *p_hi, void *
     GP_CHECK_ARG(!stamp || g_gp_debug_bytes[0] >= (size_t)grid * CS_NW * 10 * sizeof(uint64_t),
                  "gp_pool_cs_apply_chain: the stamp buffer of gp_debug_ptr(0) holds %zu bytes, this launch writes %zu",
                  g_gp_debug_bytes[0], (size_t)grid * CS_NW * 10 * sizeof(uint64_t));
-    if (stamp) {
+    if (ns != 2) {
+#define CS_CHAIN_ARGS ch, bu_off, bu_row, bu_mask, static_cast<const _Float16 *>(wa_hi), static_cast<const _Float16 *>(wa_lo), nv, nb, y_f32, ld_yf, \
+                      per_xcd, out_scale, stamp, rows_per_block
+        int rc;
+        if (ns == 1) rc = stamp ? cs_launch_chain_ns<true, 1>((unsigned)grid, s, CS_CHAIN_ARGS) : cs_launch_chain_ns<false, 1>((unsigned)grid, s, CS_CHAIN_ARGS);
+        else if (ns == 3) rc = stamp ? cs_launch_chain_ns<true, 3>((unsigned)grid, s, CS_CHAIN_ARGS) : cs_launch_chain_ns<false, 3>((unsigned)grid, s, CS_CHAIN_ARGS);
+        else rc = stamp ? cs_launch_chain_ns<true, 4>((unsigned)grid, s, CS_CHAIN_ARGS) : cs_launch_chain_ns<false, 4>((unsigned)grid, s, CS_CHAIN_ARGS);
+#undef CS_CHAIN_ARGS
+        if (rc != GP_OK) return rc;
+    } else if (stamp) {
         GP_SMEM_ATTR(cs_chain_kernel<true>, CS_SMEM);
         cs_chain_kernel<true><<<(unsigned)grid, 512, CS_SMEM, s>>>(ch, bu_off, bu_row, bu_mask, static_cast<const _Float16 *>(wa_hi),
                                                                     static_cast<const _Float16 *>(wa_lo), nv, nb, y_f32, ld_yf, per_xcd,

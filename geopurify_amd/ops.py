@@ -190,7 +190,7 @@ def gather_rows(src, d, index, out=None, row_map=None):
 
 def gather_rows_classify(src, d, index, text_norm, logit_scale, row_map=None):
     """gather_rows + classify_argmax in one pass (gp_gather_rows_classify): returns (out [n, d], pred i64 [n], zero u8 [n]).
-    d a multiple of 64 up to 512 and C * d * 4 <= 64 KiB (can_gather_rows_classify)."""
+    d a multiple of 64 up to 1024 and C * d * 4 <= 64 KiB (can_gather_rows_classify)."""
     lib = _lib.load()
     n = index.shape[0]
     out = torch.empty((n, d), dtype=torch.float32, device=src.device)
@@ -203,7 +203,13 @@ def gather_rows_classify(src, d, index, text_norm, logit_scale, row_map=None):
 
 
 def can_gather_rows_classify(d, num_classes):
-    return d % 64 == 0 and d <= 512 and num_classes * d * 4 <= 64 * 1024
+    # up to 512 columns the 16-lane form of classify_argmax, wider rows (<= 1024) its one-wave-per-point form; the text matrix in LDS
+    return d % 64 == 0 and d <= 1024 and num_classes * d * 4 <= 64 * 1024
+
+
+def pool_cs_width_ok(d):
+    """Widths the column-sliced pooling kernels take (gp_pool_cs_apply / _apply_chain): whole 256-column slices, 1 to 4 of them."""
+    return d % 256 == 0 and 256 <= d <= 1024
 
 
 def sparse_conv(x, nbr_map, w, scale=None, shift=None, residual=None, relu=False, out=None):
@@ -738,8 +744,8 @@ def pool_cs_build(nbr, w, rows_per_block=128):
 
 
 def pool_cs_apply(x_split, op, d, out_split=None, out_f32=None, out_scale=None):
-    """x_split / out_split: (hi, lo) f16 [Nv, >=d] pairs; out_f32 fp32 [Nv, >=d]; at least one output.
-    out_scale: device scalar multiplied into out_f32 (1/s of a pow2_scale()-scaled x_split)."""
+    """x_split / out_split: (hi, lo) f16 [Nv, >=d] pairs; out_f32 fp32 [Nv, >=d]; at least one output.  d: pool_cs_width_ok
+    (256, 512, 768 or 1024).  out_scale: device scalar multiplied into out_f32 (1/s of a pow2_scale()-scaled x_split)."""
     lib = _lib.load()
     xh, xl = x_split
     assert xh.stride(0) == xl.stride(0)
@@ -751,18 +757,27 @@ def pool_cs_apply(x_split, op, d, out_split=None, out_f32=None, out_scale=None):
     return out_f32 if out_f32 is not None else out_split
 
 
-def pool_cs_deps(op):
-    """Dependency lists + flags of the chained launch (pool_cs_apply_chain); needs the operator's structure (bu_row) only."""
+def pool_cs_deps(op, d=512):
+    """Dependency lists + flags of the chained launch (pool_cs_apply_chain) at width d; needs the operator's structure (bu_row) only."""
     lib = _lib.load()
+    words = _pool_cs_flag_words(op, d)                     # (an unsupported width raises before anything is built)
     dev = op.bu_row.device
     nb = op.bu_off.numel() - 1
     op.dep = torch.empty(nb * 64, dtype=torch.int32, device=dev)
     scratch = torch.empty(nb, dtype=torch.int32, device=dev)
     check(lib.gp_pool_cs_deps(_ptr(op.bu_off), _ptr(op.bu_row), op.nv, int(op.block_rows), _ptr(op.dep), _ptr(scratch), _stream()),
           "gp_pool_cs_deps")
-    op.flags = torch.zeros(lib.gp_pool_cs_chain_flag_words(op.nv, int(op.block_rows)), dtype=torch.int32, device=dev)
+    op.flags = torch.zeros(words, dtype=torch.int32, device=dev)          # (a fresh array: the abort word cleared)
     op.epoch = 0
     return op
+
+
+def _pool_cs_flag_words(op, d):
+    """Words of the chained launch's flags array at width d: [32 header][d / 256 slices][nblocks]."""
+    words = _lib.load().gp_pool_cs_chain_flag_words_d(op.nv, int(op.block_rows), int(d))
+    if words == 0:
+        raise ValueError(f"pool_cs: d={d} (the column-sliced kernels take d = 256, 512, 768 or 1024)")
+    return words
 
 
 def pool_cs_apply_chain(x_split, pong, op, d, applications, out_f32, out_scale=None):
@@ -771,7 +786,10 @@ def pool_cs_apply_chain(x_split, pong, op, d, applications, out_f32, out_scale=N
     caller's next synchronisation point: pool_cs_chain_check) means the launch gave up and the outputs are invalid."""
     lib = _lib.load()
     if getattr(op, "dep", None) is None:
-        pool_cs_deps(op)
+        pool_cs_deps(op, d)
+    elif op.flags is None or op.flags.numel() < _pool_cs_flag_words(op, d):      # flags sized for a narrower width: a fresh array
+        op.flags = torch.zeros(_pool_cs_flag_words(op, d), dtype=torch.int32, device=op.bu_row.device)
+        op.epoch = 0
     xh, xl = x_split
     ph, pl_ = pong
     assert xh.stride(0) == xl.stride(0) == ph.stride(0) == pl_.stride(0)

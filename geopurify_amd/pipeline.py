@@ -383,16 +383,19 @@ def resolve_pool_mode(mode, D, K, num_iters, tile_rows, block_rows):
     steps per row block, or blocks other than 64 rows: HotPath._pool.)"""
     family = POOL_MODES[_known_pool_mode(mode)]
     mfma_ok = D == 512 and block_rows * K <= 16384 and num_iters >= 1
-    cs_ok = D == 512 and 128 * K <= 12288 and num_iters >= 1
+    # the column-sliced kernels take whole 256-column slices: D = 256, 512, 768 or 1024
+    cs_ok = D % 256 == 0 and 256 <= D <= 1024 and 128 * K <= 12288 and num_iters >= 1
     # what gp_pool_tiles_apply accepts: multiples of 512 columns, or config P's D = 64 in 4- or 8-row tiles (pool_tiles64_kernel)
     tiles_ok = num_iters > 1 and tile_rows * K <= 1536 and (D % 512 == 0 or (D == 64 and tile_rows in (4, 8)))
     if family is None:
-        if (cs_ok or mfma_ok) and num_iters >= 3:
+        # the matrix cores where the choice was made at D = 512, and at D = 256 / 768, which had only the ELL kernel before;
+        # D = 1024 keeps its fp32 tiles (the cs kernels run there when asked for by name)
+        if (cs_ok or mfma_ok) and num_iters >= 3 and D in (256, 512, 768):
             return "cs" if cs_ok else "mfma"
         return "tiles" if tiles_ok else "ell"
     if family in ("cs", "chain"):
         if not cs_ok:
-            raise ValueError(f"pool_mode='{mode}' needs D == 512 and K <= 96 (D={D}, K={K})")
+            raise ValueError(f"pool_mode='{mode}' needs D in (256, 512, 768, 1024) and K <= 96 (D={D}, K={K})")
         return "chain" if family == "chain" and num_iters >= 2 else "cs"
     if family in ("mfma", "mfma_persist") and not mfma_ok:
         raise ValueError(f"pool_mode='mfma' needs D == 512 and block_rows*K <= 16384 (D={D}, K={K})")
@@ -628,7 +631,7 @@ class HotPath:
                              "x_split": ops.split_f16(X, D, scale=sc[0:1], dst_row=rho),
                              "pong": tuple(torch.empty((Nv, D), dtype=torch.float16, device=dev) for _ in range(2))}
             if family == "chain" and (state["pool"]["op"].dst is not None or state["pool"]["op"].valid is not None):   # (the lists need bu_row only)
-                ops.pool_cs_deps(state["pool"]["op"])
+                ops.pool_cs_deps(state["pool"]["op"], D)
             mark("pool plan+split")
         return state
 
@@ -700,7 +703,7 @@ class HotPath:
             self._pool_kernel = "none"
             return out
         if family in ("cs", "chain"):
-            # column-sliced matrix-core pooling (default): 128-row blocks x 256-column halves, union rows grouped by the 16-row
+            # column-sliced matrix-core pooling (default): 128-row blocks x 256-column slices, union rows grouped by the 16-row
             # groups that use them, empty weight fragments skipped (pool_mfma_cs.hip)
             if plan is None:                            # (isolated calls: bench.py's pooling-only passes, tests)
                 sc = ops.pow2_scale(X, D)
@@ -716,11 +719,11 @@ class HotPath:
                 # all applications in ONE launch (gp_pool_cs_apply_chain: per-block flags instead of kernel boundaries; same planes,
                 # same bits).  The abort word of its contract is read at the next host synchronisation (pool_chain_check).
                 if op.dep is None:
-                    ops.pool_cs_deps(op)
+                    ops.pool_cs_deps(op, D)
                 ops.pool_cs_apply_chain(sp[0], sp[1], op, D, self.num_iters, out, out_scale=sc[1:2])
                 if op not in self._chain_ops:            # (an operator re-applied by isolated timing passes is pending once)
                     self._chain_ops.append(op)
-                self._pool_kernel = "cs_chain_kernel"
+                self._pool_kernel = "cs_chain_kernel" if D == 512 else "cs_chain_ns_kernel"     # (the kernel a trace shows)
                 return out
             src = sp[0]
             for t in range(self.num_iters):
@@ -728,7 +731,7 @@ class HotPath:
                 dst = None if last else sp[(t + 1) % 2]
                 ops.pool_cs_apply(src, op, D, out_split=dst, out_f32=out if last else None, out_scale=sc[1:2] if last else None)
                 src = dst
-            self._pool_kernel = "cs_pool_kernel"
+            self._pool_kernel = "cs_pool_kernel" if D == 512 else "cs_pool_ns_kernel"
             return out
         if family in ("mfma", "mfma_persist"):
             # matrix-core pooling: operands stay split (hi, lo) f16 between applications, fp32 only at the end.

@@ -303,7 +303,8 @@ int gp_pool_mfma_apply_persistent(const void *x_hi, const void *x_lo, int64_t ld
                                   int64_t ld_y, float *y_f32, int64_t ld_yf, int64_t y_rows,
                                   const float *out_scale, uint32_t *queue, void *stream);
 
-/* Column-sliced matrix-core variant (d = 512; the default from round 3 on): blocks of rows x 256-column halves, every     */
+/* Column-sliced matrix-core variant (d = 256, 512, 768 or 1024; the default from round 3 on): blocks of rows x 256-column */
+/* slices (d / 256 per row block: the two halves at d = 512), every                                                        */
 /* wave owns all rows x 32 columns; the builder orders a block's union rows by the 16-row groups that use them and         */
 /* stores one bit per (32-row step, group): all-zero 16 x 32 weight fragments are neither fetched nor multiplied.        */
 /* rows_per_block (16..128, the same value for count, fill and apply; 128 unless there is a reason): the block height.    */
@@ -341,6 +342,8 @@ int gp_pool_cs_structure_valid(const int32_t *nbr, int64_t nv, int32_t k, int32_
 int gp_affinity_cs_fragments(const void *e_hi, const void *e_lo, int64_t nv, int32_t d, int32_t k, float sharpen,
                              const int64_t *bu_off, const int32_t *bu_row, const uint32_t *bu_mask, const uint32_t *bu_valid,
                              int32_t rows_per_block, void *wa_hi, void *wa_lo, void *stream);
+/* One application y = A x.  d = 256, 512, 768 or 1024 (whole 256-column slices; any other d: GP_EINVAL).  The tuning bits of    */
+/* knob 4 apply to d = 512 only.                                                                                                 */
 int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int64_t *bu_off, const int32_t *bu_row,
                      const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv, int32_t d,
                      int32_t rows_per_block, void *y_hi, void *y_lo, int64_t ld_y, float *y_f32, int64_t ld_yf,
@@ -352,14 +355,18 @@ int gp_pool_cs_apply(const void *x_hi, const void *x_lo, int64_t ld_x, const int
 /* application t starts when the row blocks of its dependency list have published application t - 1 (per-block flags,         */
 /* written-through stores, L1-bypassing gathers); workgroups wait only for workgroups with a smaller index.                   */
 /*   gp_pool_cs_deps: dep i32 [nblocks * 64] from the operator's structure (bu_off, bu_row), scratch i32 [nblocks].           */
-/*   flags u32 [gp_pool_cs_chain_flag_words()]: zeroed ONCE at allocation.  Word 0 is the ABORT word: set to 1 by the kernel   */
-/*     if a workgroup waited 2 s for a dependency (the launch drains without computing, outputs invalid); the caller reads it   */
+/*   d: as gp_pool_cs_apply (256, 512, 768 or 1024).                                                                         */
+/*   flags u32 [gp_pool_cs_chain_flag_words_d(nv, rows_per_block, d)]: zeroed ONCE at allocation.  Word 0 is the ABORT      */
+/*     word: set to 1 by the kernel if a workgroup waited 2 s for a dependency (the launch drains without computing, outputs invalid); the caller reads it   */
 /*     at its next synchronisation point and treats non-zero as an error.                                                     */
 /*   epoch: kept by the caller per flags array, each call at least `applications` above the previous call's.                  */
 /* One flags array serves one launch at a time (do not share it between streams).                                             */
 int gp_pool_cs_deps(const int64_t *bu_off, const int32_t *bu_row, int64_t nv, int32_t rows_per_block, int32_t *dep,
                     int32_t *scratch, void *stream);
+/* words of the flags array: 32 header words + d / 256 column slices x nblocks (0 for a d or rows_per_block the kernels reject); */
+/* gp_pool_cs_chain_flag_words is the d = 512 size.                                                                           */
 size_t gp_pool_cs_chain_flag_words(int64_t nv, int32_t rows_per_block);
+size_t gp_pool_cs_chain_flag_words_d(int64_t nv, int32_t rows_per_block, int32_t d);
 int gp_pool_cs_apply_chain(void *x_hi, void *x_lo, void *p_hi, void *p_lo, int64_t ld, const int64_t *bu_off,
                            const int32_t *bu_row, const uint32_t *bu_mask, const void *wa_hi, const void *wa_lo, int64_t nv,
                            int32_t d, int32_t rows_per_block, int32_t applications, float *y_f32, int64_t ld_yf,
@@ -473,7 +480,7 @@ int gp_classify_argmax(const float *feat, int64_t ld, int32_t d, int64_t n, cons
                        int32_t c, float logit_scale, int64_t *pred, uint8_t *zero_row, void *stream);
 /* gp_gather_rows (the final voxel -> point gather, affinity_module.py:1589) and gp_classify_argmax (run/validation.py:413-416) in   */
 /* ONE pass: out[p, 0:d] = src[row_map[index[p]], 0:d] and pred / zero_row of those rows -- the per-point matrix is written once    */
-/* and not read back.  Same bits and labels as the two calls.  d a multiple of 64 up to 512, c * d * 4 <= 64 KiB.                  */
+/* and not read back.  Same bits and labels as the two calls.  d a multiple of 64 up to 1024, c * d * 4 <= 64 KiB.                 */
 int gp_gather_rows_classify(const float *src, int64_t ld_src, int32_t d, const int64_t *index, int64_t n, const int32_t *row_map,
                             float *out, int64_t ld_out, const float *text_norm, int32_t c, float logit_scale, int64_t *pred,
                             uint8_t *zero_row, void *stream);

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Interleaved timing of the pooling kernel variants on one S-shaped voxel set (tuning aid)."""
+"""Interleaved timing of the pooling kernel variants on one S-shaped voxel set (tuning aid).
+usage: bench_pool.py [--d D] [variant word] [num_points] [ablation bits] [knob 9]
+--d: feature width (512 default; 256, 768 or 1024 time the column-sliced kernel against ELL only -- the other matrix-core and
+tiled kernels are 512-only)."""
 import os
 import sys
 import time
@@ -9,6 +12,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geopurify_amd import _lib, ops, pipeline as pl, synthetic as syn  # noqa: E402
+
+D_ARG = 512
+if "--d" in sys.argv:
+    _i = sys.argv.index("--d")
+    D_ARG = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
+    assert ops.pool_cs_width_ok(D_ARG), f"--d {D_ARG}: the column-sliced kernels take 256, 512, 768 or 1024"
+WIDE = D_ARG != 512
 
 cfg = syn.CONFIGS["S"]
 import dataclasses
@@ -20,7 +31,7 @@ coords = vox["coords_aug"].to(torch.int32).contiguous()
 perm, rank = ops.morton_order(coords)
 cs = coords[perm.long()].contiguous()
 grid = ops.grid_build(cs)
-K, D = 96, 512
+K, D = 96, D_ARG
 nbr = ops.knn_lattice(grid, cs, perm, K)
 Nv = cs.shape[0]
 E = torch.nn.functional.normalize(torch.randn(Nv, 128, device="cuda"), dim=1)
@@ -55,7 +66,7 @@ if ORDER:
     nbr = torch.from_numpy(rk).cuda()[nbr.long()[sg]].to(torch.int32).contiguous()
     w = w[sg].contiguous()
     print(f"rows re-numbered: {ORDER}", flush=True)
-X = torch.randn(Nv, 544, device="cuda")
+X = torch.randn(Nv, D + 32, device="cuda")
 Y = torch.empty(Nv, D, device="cuda")
 lib = _lib.load()
 bytes_alg = Nv * (2 * D * 4 + K * 8)
@@ -73,7 +84,7 @@ def timeit(fn, n=20):
 
 variants = [("ell", None)]
 tiles = {}
-for R in (4, 8, 16):
+for R in (() if WIDE else (4, 8, 16)):
     tiles[R] = ops.pool_tiles_build(nbr, w, R)
     print(f"R={R}: union entries/row = {tiles[R].total / Nv:.2f}", flush=True)
     for nf4 in (1, 2):
@@ -83,11 +94,11 @@ for R in (4, 8, 16):
             variants.append((f"tiles R={R} nf4={nf4} unroll={un}", (R, nf4, un)))
 variants = [v for v in variants if v[1] is None or v[1][0] == 8 and v[1][2] == 4]
 mf = {}
-for BR in (64, 128):
+for BR in (() if WIDE else (64, 128)):
     mf[BR] = ops.pool_mfma_build(nbr, w, BR, min_steps=9); torch.cuda.synchronize()
     t0 = time.time(); mf[BR] = ops.pool_mfma_build(nbr, w, BR, min_steps=9); torch.cuda.synchronize()
     print(f"mfma BR={BR}: union rows/row (padded) {mf[BR].total / Nv:.2f}  build (2nd call) {1e3 * (time.time() - t0):.2f} ms", flush=True)
-for R in (8,):
+for R in (() if WIDE else (8,)):
     t0 = time.time(); ops.pool_tiles_build(nbr, w, R); torch.cuda.synchronize()
     print(f"tiles R={R}: build (2nd call) {1e3 * (time.time() - t0):.2f} ms", flush=True)
 xs = ops.split_f16(X, D)
@@ -103,9 +114,12 @@ variants += [("cs128 column-sliced (split out)", ("cs", 0)), ("cs128 column-slic
              ("mfma128 8w x (32r x 128c) (split out)", ("mfma", 128, 0, 0)),
              ("persist64 (split out)", ("persist", 64, 0, 0)), ("persist64 (fp32 out)", ("persist32", 64, 0, 0)),
              ("persist64 static tile lists (split out)", ("persist", 64, 0, 0, 1))]
-ysp = {br: tuple(torch.empty((mf[br].rows_padded, D), dtype=torch.float16, device="cuda") for _ in range(2)) for br in (64,)}
-Yp = {br: torch.empty((mf[br].rows_padded, D), device="cuda") for br in (64,)}
-print("min steps per row block:", {br: mf[br].min_steps for br in (64, 128)}, flush=True)
+if WIDE:
+    variants = [v for v in variants if v[1] is None or v[1][0] in ("cs", "cs32")]
+ysp = {} if WIDE else {br: tuple(torch.empty((mf[br].rows_padded, D), dtype=torch.float16, device="cuda") for _ in range(2)) for br in (64,)}
+Yp = {} if WIDE else {br: torch.empty((mf[br].rows_padded, D), device="cuda") for br in (64,)}
+if not WIDE:
+    print("min steps per row block:", {br: mf[br].min_steps for br in (64, 128)}, flush=True)
 ABL = int(sys.argv[3]) if len(sys.argv) > 3 else 0      # pool_mfma ablation bits (timing only, results invalid)
 lib.gp_debug_set(4, ABL)
 lib.gp_debug_set(9, int(sys.argv[4]) if len(sys.argv) > 4 else 0)
@@ -141,12 +155,14 @@ for rnd in range(3):
         res.setdefault(name, []).append(t)
 for name, ts in res.items():
     t = min(ts)
-    print(f"{name:32s} min {t:7.3f} ms  med {np.median(ts):7.3f} ms  -> {bytes_alg / t / 1e6:7.1f} GB/s algorithmic ({bytes_alg / t / 1e6 / 80:.1f}% of 8 TB/s)", flush=True)
+    print(f"D={D} {name:32s} min {t:7.3f} ms  med {np.median(ts):7.3f} ms  -> {bytes_alg / t / 1e6:7.1f} GB/s algorithmic ({bytes_alg / t / 1e6 / 80:.1f}% of 8 TB/s)", flush=True)
 lib.gp_debug_set(4, 0)                                   # the comparisons below run the product kernels
 yc = torch.empty((Nv, D), device="cuda"); ye = torch.empty((Nv, D), device="cuda")
 ops.pool_cs_apply(xs, cs, D, out_f32=yc)
 ops.pool_ell(X, nbr, w, D, ye)
 print("cs128 vs ELL max |diff|:", float((yc - ye).abs().max()), flush=True)
+if WIDE:
+    sys.exit(0)
 # the column-sliced wave mapping computes the same sums in the same order per element: identical outputs
 ya = tuple(torch.empty((Nv, D), dtype=torch.float16, device="cuda") for _ in range(2))
 yb = tuple(torch.empty((Nv, D), dtype=torch.float16, device="cuda") for _ in range(2))

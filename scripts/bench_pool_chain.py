@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Round 5: all T applications of the pooling operator in ONE launch (gp_pool_cs_apply_chain) against the T launches of
 cs_pool_kernel -- bits, time, in-kernel stamps.
-usage: bench_pool_chain.py [num_points] [T] [stamps]"""
+usage: bench_pool_chain.py [--d D] [num_points] [T] [stamps]   (--d: feature width, 256, 512 (default), 768 or 1024)"""
 import dataclasses
 import os
 import sys
@@ -11,6 +11,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geopurify_amd import _lib, ops, pipeline as pl, synthetic as syn  # noqa: E402
+
+D_ARG = 512
+if "--d" in sys.argv:
+    _i = sys.argv.index("--d")
+    D_ARG = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
+    assert ops.pool_cs_width_ok(D_ARG), f"--d {D_ARG}: the column-sliced kernels take 256, 512, 768 or 1024"
 
 NPTS = int(sys.argv[1]) if len(sys.argv) > 1 else 150000
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 19
@@ -23,16 +30,16 @@ coords = vox["coords_aug"].to(torch.int32).contiguous()
 perm, rank = ops.morton_order(coords)
 cs = coords[perm.long()].contiguous()
 grid = ops.grid_build(cs)
-K, D = 96, 512
+K, D = 96, D_ARG
 nbr = ops.knn_lattice(grid, cs, perm, K)
 Nv = cs.shape[0]
 E = torch.nn.functional.normalize(torch.randn(Nv, 128, device="cuda"), dim=1)
 w = ops.affinity_softmax(E, nbr, 20.0)
-X = torch.randn(Nv, 544, device="cuda")
+X = torch.randn(Nv, D + 32, device="cuda")
 lib = _lib.load()
 bytes_alg = Nv * (2 * D * 4 + K * 8)
 op = ops.pool_cs_build(nbr, w)
-ops.pool_cs_deps(op)
+ops.pool_cs_deps(op, D)
 torch.cuda.synchronize()
 dep = op.dep.view(-1, 64)[:, 0].cpu().numpy()
 print(f"Nv {Nv}  row blocks {dep.size}  dependency lists: mean {dep.mean():.1f} p50 {np.median(dep):.0f} p99 {np.percentile(dep, 99):.0f} max {dep.max()}"
@@ -88,7 +95,7 @@ for name, fn in (("T launches of cs_pool_kernel", run_launches), ("ONE chained l
         ts, got = timed(fn)
         same = all(torch.equal(a, b) for a, b in zip([got[0], *got[1], *got[2]], [ref[0], *ref[1], *ref[2]]))
         t = float(np.median(ts))
-        print(f"{name:40s} {t:7.3f} ms for {T} applications = {t / T:7.4f} ms each  (min {min(ts) / T:.4f})  "
+        print(f"D={D} {name:40s} {t:7.3f} ms for {T} applications = {t / T:7.4f} ms each  (min {min(ts) / T:.4f})  "
               f"{bytes_alg * T / t / 1e6 / 80:5.1f} % of 8 TB/s   bits == the {T} launches: {same}", flush=True)
 ops.pool_cs_chain_check(op)
 print("abort word:", int(op.flags[0].item()), " epoch:", op.epoch, flush=True)
@@ -113,7 +120,7 @@ print(f"chained launch beside 3 GiB of copies on a second stream, 8 runs: {8 - b
 
 if STAMPS:
     nb = dep.size
-    per_xcd = (2 * nb + 7) // 8
+    per_xcd = ((D // 256) * nb + 7) // 8
     grid_wg = per_xcd * 8 * T
     buf = torch.zeros(grid_wg * 8 * 10, dtype=torch.int64, device="cuda")
     lib.gp_debug_ptr(0, buf.data_ptr(), buf.numel() * 8)
