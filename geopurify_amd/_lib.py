@@ -34,6 +34,9 @@ SIGNATURES = {
     "gp_scatter_mean_csr": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int64, _P, _P, c_int64, c_int32, _P]),
     "gp_gather_rows": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int64, _P]),
     "gp_kernel_map_build": (c_int32, [_P, _P, c_int64, _P, _P]),
+    "gp_coords_order_batched_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_coords_order_batched": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_kernel_map_sorted": (c_int32, [_P, c_int64, _P, _P]),
     "gp_sparse_conv": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P,
                                  c_int64, c_int32, _P, c_int64, _P]),
     "gp_conv_pairs_workspace_bytes": (c_size_t, [c_int64, c_int32]),

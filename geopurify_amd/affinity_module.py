@@ -9,7 +9,7 @@ five X-Decoder outputs the lift consumes; `SyntheticVLM` is the offline stand-in
 import torch
 import torch.nn as nn
 
-from . import pipeline
+from . import ops, pipeline, sharding
 from .pipeline import GEO_DIM, HotPath, SceneBatch, StudentWeights, ViewLists
 
 
@@ -80,16 +80,194 @@ class AffinityPredictor(nn.Module):
         return (str(device),) + tuple((id(t), t._version, t.device.type) for t in list(self.parameters()) + list(self.buffers()))
 
     def device_weights(self, device):
-        key = self._weights_key(device)
+        eps = self.input_layer[1].bn.eps                 # (the BatchNorm fold uses the module's eps; 1e-5 unless it was changed)
+        key = self._weights_key(device) + (eps,)
         if self._dev_weights is None or self.training or self._dev_key != key:
-            self._dev_weights = StudentWeights(self.state_dict(), device)
+            self._dev_weights = StudentWeights(self.state_dict(), device, eps=eps)
             self._dev_key = key
         return self._dev_weights
 
-    def forward(self, features, nbr_map):
-        """features fp32 [Nv, cin_pad] in Morton order + its 27-offset kernel map -> unnormalised is
-        not exposed: returns the L2-normalised embeddings the caller applies next (:1546-1547)."""
+    def _bn_settings(self, need_momentum):
+        """(momentum, eps) shared by every BatchNorm layer: the HIP paths take one value of each for all nine layers"""
+        bns = [m.bn for m in self.modules() if isinstance(m, _SparseBatchNorm)]
+        eps = {b.eps for b in bns}
+        if len(eps) != 1:
+            raise ValueError(f"AffinityPredictor: the BatchNorm layers have different eps {sorted(eps)}; the HIP path takes one for all")
+        if not need_momentum:
+            return None, eps.pop()
+        mom = {b.momentum for b in bns}
+        if None in mom:
+            raise ValueError("AffinityPredictor: BatchNorm momentum=None (cumulative moving average) is not supported in train mode; "
+                             "set a momentum")
+        if len(mom) != 1:
+            raise ValueError(f"AffinityPredictor: the BatchNorm layers have different momenta {sorted(mom)}; the HIP path takes one for all")
+        return mom.pop(), eps.pop()
+
+    def forward(self, features, nbr_map=None):
+        """Two call forms.
+        forward(x) with x an ME-style SparseTensor (`.F` [N, input_dim] features, `.C` int32 [N, 4] = batch, x, y, z in any row order,
+        e.g. ME.utils.batched_coordinates): returns type(x)(features=E, coordinates=x.C), E fp32 [N, embed] the raw output-layer rows in
+        x's row order (models/affinity_module.py:68-72), under autograd; see _forward_sparse.
+        forward(features, nbr_map): features fp32 [Nv, cin_pad] in Morton order + its 27-offset kernel map -> the L2-normalised
+        embeddings the caller applies next (:1546-1547), the inference path of HotPath."""
+        if nbr_map is None:
+            if hasattr(features, "F") and hasattr(features, "C"):
+                return self._forward_sparse(features)
+            raise TypeError("AffinityPredictor.forward takes a SparseTensor (an object with .F and .C) or (features, nbr_map)")
         return self.device_weights(features.device).forward(features, nbr_map)
+
+    def _forward_sparse(self, x):
+        """Voxel order and kernel map of the batched coordinates on the device (ops.coords_order_batched / kernel_map_sorted: one
+        status read-back), then
+          * eval mode without autograd (torch.no_grad(), or nothing requires grad): the folded inference path, StudentWeights(raw=True);
+          * otherwise the training kernels of StudentTrainer (forward_half / backward_half) as an autograd Function: train mode takes
+            BatchNorm batch statistics over all rows of all batch entries and updates running_mean / running_var / num_batches_tracked
+            in place; eval mode normalises with the running statistics and updates nothing.  Gradients reach every parameter and x.F."""
+        Fe, C = x.F, x.C
+        cin = self.input_layer[0].kernel.shape[-2]
+        if not torch.is_tensor(C) or C.dim() != 2 or C.shape[1] != 4:
+            raise ValueError(f"AffinityPredictor: coordinates must be [N, 4] (batch, x, y, z), got "
+                             f"{list(C.shape) if torch.is_tensor(C) else type(C).__name__}")
+        if C.dtype.is_floating_point or C.dtype == torch.bool:
+            raise ValueError(f"AffinityPredictor: coordinates must be integers, got {C.dtype}")
+        if not torch.is_tensor(Fe) or Fe.dim() != 2 or Fe.shape[0] != C.shape[0]:
+            raise ValueError(f"AffinityPredictor: features must be [N, {cin}] with N = {C.shape[0]} coordinate rows, got "
+                             f"{list(Fe.shape) if torch.is_tensor(Fe) else type(Fe).__name__}")
+        if Fe.shape[1] != cin:
+            raise ValueError(f"AffinityPredictor: features have {Fe.shape[1]} channels, the input layer takes input_dim={cin}")
+        if not (Fe.is_cuda and C.is_cuda):
+            raise ValueError(f"AffinityPredictor: features and coordinates must be CUDA tensors (got {Fe.device} / {C.device}); "
+                             "the student has no CPU path")
+        if not Fe.dtype.is_floating_point:
+            raise ValueError(f"AffinityPredictor: features must be floating point, got {Fe.dtype}")
+        if C.shape[0] == 0:
+            raise ValueError("AffinityPredictor: empty SparseTensor")
+        dev = Fe.device
+        params = list(self.named_parameters())
+        grad = torch.is_grad_enabled() and (Fe.requires_grad or any(p.requires_grad for _, p in params))
+        momentum, eps = self._bn_settings(need_momentum=self.training)
+        with torch.cuda.device(dev):
+            if C.dtype != torch.int32:
+                # (range-checked before the cast: an int64 coordinate beyond int32 must not wrap into a valid one)
+                lo, hi = ops.readback(torch.stack(torch.aminmax(C)).to(torch.int64))
+                if lo < -2 ** 31 or hi >= 2 ** 31:
+                    raise ValueError(f"AffinityPredictor: coordinates outside the int32 range ({lo} .. {hi})")
+            perm, rank, keys, status = ops.coords_order_batched(C.to(device=dev, dtype=torch.int32).contiguous())
+            dups, bad_batch, bad_axes = ops.readback(status)
+            # (range first: a row whose batch index is out of range has a meaningless key, which may equal another row's)
+            if bad_batch:
+                raise ValueError(f"AffinityPredictor: {bad_batch} rows have a batch index outside 0..65535")
+            if bad_axes:
+                axes = [n for a, n in enumerate("xyz") if bad_axes >> a & 1]
+                raise ValueError(f"AffinityPredictor: coordinate extent of 65536 or more along {', '.join(axes)} (16 bits per axis)")
+            if dups:
+                raise ValueError(f"AffinityPredictor: {dups} duplicate coordinate rows (MinkowskiEngine would merge them; quantise first)")
+            nbr_map = ops.kernel_map_sorted(keys)
+            if not grad and not self.training:
+                st = self.device_weights(dev)
+                X = torch.zeros((Fe.shape[0], st.cin_pad), dtype=torch.float32, device=dev)
+                X[:, :cin] = Fe.detach().float().index_select(0, perm.long())
+                E = st.forward(X, nbr_map, raw=True).index_select(0, rank.long())
+            else:
+                if self.training and sharding._world() > 1:
+                    raise NotImplementedError("AffinityPredictor on a SparseTensor in train mode does not synchronise BatchNorm over ranks: "
+                                              "train through SonataXAffinityTrainer.forward, whose step does")
+                if any(p.device != dev for _, p in params):
+                    raise ValueError(f"AffinityPredictor: the parameters must live on the features' device {dev} to take gradients")
+                run = _SparseStudentRun(self, perm, rank, nbr_map, [n for n, _ in params], cin, momentum if self.training else 0.1, eps)
+                E = _SparseStudentFunction.apply(run, Fe, *[p for _, p in params])
+        return type(x)(features=E, coordinates=C)
+
+
+class _SparseStudentRun:
+    """One call of AffinityPredictor on a SparseTensor through the training kernels: the forward half keeps its activations for the
+    backward half (training.StudentTrainer.forward_half / backward_half); rows are in the voxel order of `perm` inside."""
+
+    def __init__(self, module, perm, rank, nbr_map, names, cin, momentum, eps):
+        self.module, self.perm, self.rank, self.nbr_map, self.names, self.cin = module, perm.long(), rank.long(), nbr_map, names, cin
+        self.momentum, self.eps = momentum, eps
+
+    def forward(self, feats):
+        """-> (E [N, embed] in the input's row order, the forward half's state)"""
+        from .training import StudentTrainer
+        m = self.module
+        dev = feats.device
+        # (a device-side clone of the parameters and buffers: the trainer's working copy, updated in place by train mode)
+        self.tr = tr = StudentTrainer(m.state_dict(), dev, bn_momentum=self.momentum, bn_eps=self.eps)
+        X = torch.zeros((feats.shape[0], tr.cin_pad), dtype=torch.float32, device=dev)
+        X[:, :self.cin] = feats.detach().float().index_select(0, self.perm)
+        fw = tr.forward_half(X, self.nbr_map, update_running=m.training, bn_eval=not m.training)
+        if m.training:
+            with torch.no_grad():
+                for k, b in m.named_buffers():
+                    if k in tr.buffers:
+                        b.copy_(tr.buffers[k])
+                    elif k.endswith("num_batches_tracked"):
+                        b += 1
+        return fw["E"].index_select(0, self.rank), fw
+
+    def backward(self, fw, dE, want_dx):
+        g, dX = self.tr.backward_half(fw, dE.float().index_select(0, self.perm).contiguous(), want_dx=want_dx)
+        grads = []
+        for n, p in zip(self.names, self.module.parameters()):
+            t = g[n]
+            if n == "input_layer.0.kernel":
+                t = t[:, :self.cin]
+            grads.append(t.reshape(p.shape).to(p.dtype))
+        dF = dX[:, :self.cin].index_select(0, self.rank) if want_dx else None
+        return dF, grads
+
+
+def _flatten_tensors(obj, out):
+    """obj with every tensor inside dicts / lists / tuples replaced by its index in `out` (_TensorSlot)"""
+    if torch.is_tensor(obj):
+        out.append(obj)
+        return _TensorSlot(len(out) - 1)
+    if isinstance(obj, dict):
+        return {k: _flatten_tensors(v, out) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        vals = [_flatten_tensors(v, out) for v in obj]
+        return type(obj)(*vals) if hasattr(obj, "_fields") else type(obj)(vals)
+    return obj
+
+
+def _unflatten_tensors(obj, tensors):
+    if isinstance(obj, _TensorSlot):
+        return tensors[obj.i]
+    if isinstance(obj, dict):
+        return {k: _unflatten_tensors(v, tensors) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        vals = [_unflatten_tensors(v, tensors) for v in obj]
+        return type(obj)(*vals) if hasattr(obj, "_fields") else type(obj)(vals)
+    return obj
+
+
+class _TensorSlot:
+    __slots__ = ("i",)
+
+    def __init__(self, i):
+        self.i = i
+
+
+class _SparseStudentFunction(torch.autograd.Function):
+    """The activations of the forward half are saved tensors of this node: autograd frees them after a backward pass (and raises its
+    own error on a second one) unless retain_graph=True keeps them for another."""
+
+    @staticmethod
+    def forward(ctx, run, feats, *params):
+        E, fw = run.forward(feats)
+        tensors = []
+        ctx.fw = _flatten_tensors(fw, tensors)
+        ctx.save_for_backward(*tensors)
+        ctx.run = run
+        ctx.feats_dtype = feats.dtype
+        return E
+
+    @staticmethod
+    def backward(ctx, dE):
+        fw = _unflatten_tensors(ctx.fw, ctx.saved_tensors)
+        dF, grads = ctx.run.backward(fw, dE, want_dx=ctx.needs_input_grad[1])
+        return (None, dF.to(ctx.feats_dtype) if dF is not None else None) + tuple(grads)
 
 
 _VLM_FACTORY = None

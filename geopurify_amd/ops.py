@@ -168,6 +168,36 @@ def kernel_map_build(grid, coords_sorted):
     return nm
 
 
+def coords_order_batched(coords_b):
+    """Batched coordinates i32 [nv,4] (batch, x, y, z; any row order) -> perm, rank (i32 [nv], as morton_order), the sorted keys
+    (u64 held in an i64 [nv]) and status i32 [3] = (duplicate rows, rows with a batch index outside 0..65535, mask of the axes
+    whose extent is 65536 or more), all on the device, no sync (gp_coords_order_batched)."""
+    lib = _lib.load()
+    _chk(coords_b, torch.int32, "coords")
+    if coords_b.dim() != 2 or coords_b.shape[1] != 4:
+        raise ValueError(f"coords_order_batched: expected [nv, 4], got {list(coords_b.shape)}")
+    nv = coords_b.shape[0]
+    dev = coords_b.device
+    ws = _ws(lib.gp_coords_order_batched_workspace_bytes(nv), dev)
+    perm = torch.empty(nv, dtype=torch.int32, device=dev)
+    rank = torch.empty(nv, dtype=torch.int32, device=dev)
+    keys = torch.empty(nv, dtype=torch.int64, device=dev)
+    status = torch.empty(3, dtype=torch.int32, device=dev)
+    check(lib.gp_coords_order_batched(_ptr(coords_b), nv, _ptr(perm), _ptr(rank), _ptr(keys), _ptr(status), _ptr(ws), ws.numel(),
+                                      _stream()), "gp_coords_order_batched")
+    return perm, rank, keys, status
+
+
+def kernel_map_sorted(keys_sorted):
+    """27-offset kernel map i32 [27, nv] over the sorted keys of coords_order_batched (rows in that order; gp_kernel_map_sorted)."""
+    lib = _lib.load()
+    _chk(keys_sorted, torch.int64, "keys")
+    nv = keys_sorted.shape[0]
+    nm = torch.empty((27, nv), dtype=torch.int32, device=keys_sorted.device)
+    check(lib.gp_kernel_map_sorted(_ptr(keys_sorted), nv, _ptr(nm), _stream()), "gp_kernel_map_sorted")
+    return nm
+
+
 # ------------------------------------------------------------------------------------------ rows 8-12
 def scatter_mean_csr(src, d, order, seg_start, nv, out, col0=0, row_map=None):
     lib = _lib.load()

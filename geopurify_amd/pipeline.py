@@ -129,13 +129,16 @@ class StudentWeights:
             return None
         return ops.split_f16(x, self.cin_pad, per_row=True, interleaved=self.residual_from_planes and self.interleaved_rows)
 
-    def forward(self, x, nbr_map, pairs=None, x_split=None, mark=None, planes=False, plane_rows=None):
-        """x fp32 [Nv, >=cin_pad] (internal order).  Returns L2-normalised embeddings [Nv, embed].
+    def forward(self, x, nbr_map, pairs=None, x_split=None, mark=None, planes=False, plane_rows=None, raw=False):
+        """x fp32 [Nv, >=cin_pad] (internal order).  Returns L2-normalised embeddings [Nv, embed] (raw=True: the output layer's rows
+        before F.normalize -- what AffinityPredictor.forward returns on a SparseTensor).
         On the f16x3 path every layer also emits its output pre-split (hi/lo f16) so that the next
         layer stages both operands by LDS-DMA.  x_split: split_input(x) when it was made ahead.
         planes=True (only with the fused output layer): returns the embeddings x 2^10 as f16 (hi, lo) planes INSTEAD -- the operand
         of the matrix-core affinity kernel, written by the output layer's epilogue (no fp32 rows, no split pass); plane_rows (i32 [Nv]):
         the plane row of voxel row r (the pooling operator's own row order, ops.rcb_order)."""
+        if raw and planes:
+            raise ValueError("StudentWeights.forward: raw=True returns fp32 rows, not planes")
         ctx = {"nbr_map": nbr_map, "pairs": pairs}
         fast = self.fast
         if pairs is None and any(l[0] == "f16x3" for l in self.layers):
@@ -157,11 +160,16 @@ class StudentWeights:
         if mark is not None:
             mark("student convolutions")                  # (stage marks of bench.py's per-stage pass)
         if fast and self.head is not None and hs is not None:
+            if raw:
+                return ops.embed_head_f16x3(hs[:2], self.head[0], self.head[1], self.head[2], x_row_inv=hs[2], normalize=False)
             if planes:
                 return ops.embed_head_f16x3(hs[:2], self.head[0], self.head[1], self.head[2], x_row_inv=hs[2], normalize=True,
                                             planes=True, want_f32=False, plane_rows=plane_rows)[1]
             return ops.embed_head_f16x3(hs[:2], self.head[0], self.head[1], self.head[2], x_row_inv=hs[2], normalize=True)
-        e = ops.l2norm_rows_(ops.sparse_conv(h, None, self.w_out))
+        e = ops.sparse_conv(h, None, self.w_out)
+        if raw:
+            return e
+        e = ops.l2norm_rows_(e)
         if planes:
             return ops.split_f16(e, self.embed, scale=torch.tensor([ops.AFFINITY_PLANE_SCALE], dtype=torch.float32, device=e.device),
                                  dst_row=plane_rows)

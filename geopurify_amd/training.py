@@ -100,7 +100,7 @@ class StudentTrainer:
         w0 = sd["input_layer.0.kernel"].float()
         self.cin, self.hidden = w0.shape[1], w0.shape[2]
         self.cin_pad = _pad_to(self.cin, CONV_PAD)
-        w0p = torch.zeros((27, self.cin_pad, self.hidden), dtype=torch.float32)
+        w0p = torch.zeros((27, self.cin_pad, self.hidden), dtype=torch.float32, device=w0.device)     # (no host round trip)
         w0p[:, :self.cin] = w0
         sd["input_layer.0.kernel"] = w0p
         self.num_blocks = 0
@@ -192,6 +192,15 @@ class StudentTrainer:
         grad_sink (sharding.GradientBuckets over gradient_order()): the weight gradients are written into its slices and every gradient is
         announced the moment its kernels are enqueued, so that the buckets' all-reduces run beside the rest of the backward pass; the
         returned dict then holds the slices -- LOCAL sums until grad_sink.finish() has averaged them."""
+        fw = self.forward_half(X, nbr_map, update_running=update_running)
+        loss, dE = ops.infonce_fwd_bwd(fw["E"], sample_to_voxel, point_to_batch, num_anchors, num_negatives, self.temperature)
+        g, _ = self.backward_half(fw, dE, grad_sink=grad_sink)
+        return loss, g, fw["E"]
+
+    def forward_half(self, X, nbr_map, update_running=True, bn_eval=False):
+        """The forward pass of forward_backward: raw embeddings fw["E"] [Nv, embed] and the activations backward_half needs.
+        bn_eval=True: every BatchNorm normalises with the running statistics (an nn.Module in eval mode under autograd) and
+        nothing is updated; the backward pass then takes the eval-mode gradient formula."""
         P, B = self.params, self.buffers
         dev = X.device
         Nv = X.shape[0]
@@ -212,14 +221,20 @@ class StudentTrainer:
                 ctx["offset_pairs"].append((out_rows, m[out_rows].long()))
             ctx["wgrad_plan"] = None
         mom = self.bn_momentum
-        n_all = sharding.sync_row_count(Nv, dev, self.group) if self.sync_bn else Nv       # one count per step, not one per layer
+        sync_bn = self.sync_bn and not bn_eval
+        n_all = sharding.sync_row_count(Nv, dev, self.group) if sync_bn else Nv       # one count per step, not one per layer
 
         def bn_fwd(y, prefix, residual=None, want_split=True, want_f32=True):
             """(out fp32 | None, planes, statistics).  want_f32=False: a layer without a residual whose fp32 output nothing reads -- the next
             convolution and the weight gradient take the planes, the backward pass recomputes the ReLU mask from y (bn_bwd(beta=))"""
             want_f32 = want_f32 or not (want_split and self.fast)
+            if bn_eval:
+                mean, var = B[prefix + ".bn.running_mean"], B[prefix + ".bn.running_var"]
+                out, sp = ops.bn_train_apply(y, mean, var, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], self.bn_eps, residual=residual,
+                                             relu=True, want_split=want_split and self.fast, momentum=mom, want_f32=want_f32)
+                return out, sp, (mean, var)
             rm, rv = (B[prefix + ".bn.running_mean"], B[prefix + ".bn.running_var"]) if update_running else (None, None)
-            if self.sync_bn:
+            if sync_bn:
                 c = y.shape[1]
                 mean, var, n_tot = sharding.sync_batch_stats(lambda m: ops.col_sums_f64(y, c, m), y.shape[0], c, dev, self.group,
                                                              n_total=n_all)
@@ -234,26 +249,7 @@ class StudentTrainer:
                                          want_f32=want_f32)
             return out, sp, (mean, var)
 
-        def bn_bwd(dout, act, y, st, gamma, want_dz=False, beta=None, allow_split=True):
-            """(dy, dgamma, dbeta, dz | None, scale2 of dy | None); with SyncBatchNorm the dy formula uses the reductions over all ranks.
-            beta (a layer without a residual): the ReLU mask comes from y, act is not read"""
-            if beta is not None:
-                act = None
-            sc2 = torch.empty(2, dtype=torch.float32, device=dev) if self.fast else None
-            if self.sync_bn:
-                c = st[0].shape[0]
-                g_sums, l_sums = sharding.sync_bwd_sums(ops.bn_bwd_sums_f64(dout, act, y, st[0], st[1], self.bn_eps,
-                                                                            mask_affine=(gamma, beta) if beta is not None else None), self.group)
-                r = ops.bn_bwd_apply(dout, act, y, st[0], st[1], self.bn_eps, gamma, g_sums, st[2], want_dz=want_dz, dy_scale2=sc2, beta_mask=beta)
-                dy, dz = r if want_dz else (r, None)
-                return dy, l_sums[c:].clone(), l_sums[:c].clone(), dz, sc2
-            # one process: the sweep writes the gradient's split planes itself (scale from a bound taken in the reduction pass)
-            r = ops.bn_train_backward(dout, act, y, st[0], st[1], self.bn_eps, gamma, want_dz=want_dz, dy_scale2=sc2, beta_mask=beta,
-                                      split=allow_split and self.fast and y.shape[1] % 256 == 0)
-            return r[0], r[1], r[2], (r[3] if want_dz else None), sc2
-
         # ---------------- forward (activations kept for the backward pass)
-        saved = []
         xs = ops.split_f16(X, self.cin_pad) if self.fast else None
         y0 = self._conv(X, xs, P["input_layer.0.kernel"], ctx)
         h, hs, st0 = bn_fwd(y0, "input_layer.1")
@@ -268,7 +264,44 @@ class StudentTrainer:
         Wo = P["output_layer.kernel"]
         dense_hip = self.fast and hs is not None and Wo.shape[0] % 32 == 0 and Wo.shape[0] >= 256 and Wo.shape[1] % 128 == 0 and Wo.shape[1] <= 256
         E = ops.sparse_conv(h, None, Wo.unsqueeze(0).contiguous()) if dense_hip else h @ Wo
-        loss, dE = ops.infonce_fwd_bwd(E, sample_to_voxel, point_to_batch, num_anchors, num_negatives, self.temperature)
+        return {"X": X, "xs": xs, "ctx": ctx, "y0": y0, "st0": st0, "blocks": blocks, "h": h, "hs": hs, "dense_hip": dense_hip, "E": E,
+                "Nv": Nv, "sync_bn": sync_bn, "bn_eval": bn_eval}
+
+    def backward_half(self, fw, dE, grad_sink=None, want_dx=False):
+        """The backward pass of forward_backward from dE = d loss / d fw["E"] [Nv, embed].  Returns (grads dict, dX): dX fp32 [Nv, cin_pad]
+        (the input layer's data gradient) when want_dx, else None."""
+        P = self.params
+        dev = dE.device
+        ctx, Nv, h, hs, dense_hip = fw["ctx"], fw["Nv"], fw["h"], fw["hs"], fw["dense_hip"]
+        X, xs, y0, st0, blocks = fw["X"], fw["xs"], fw["y0"], fw["st0"], fw["blocks"]
+        sync_bn, bn_eval = fw["sync_bn"], fw["bn_eval"]
+        Wo = P["output_layer.kernel"]
+
+        def bn_bwd(dout, act, y, st, gamma, want_dz=False, beta=None, allow_split=True):
+            """(dy, dgamma, dbeta, dz | None, scale2 of dy | None); with SyncBatchNorm the dy formula uses the reductions over all ranks.
+            beta (a layer without a residual): the ReLU mask comes from y, act is not read"""
+            if beta is not None:
+                act = None
+            sc2 = torch.empty(2, dtype=torch.float32, device=dev) if self.fast else None
+            if bn_eval:
+                # running statistics are constants: dy = gamma * invstd * dz, i.e. the training formula with zero reductions
+                c = st[0].shape[0]
+                sums = ops.bn_bwd_sums_f64(dout, act, y, st[0], st[1], self.bn_eps, mask_affine=(gamma, beta) if beta is not None else None)
+                r = ops.bn_bwd_apply(dout, act, y, st[0], st[1], self.bn_eps, gamma, torch.zeros(2 * c, dtype=torch.float32, device=dev), Nv,
+                                     want_dz=want_dz, dy_scale2=sc2, beta_mask=beta)
+                dy, dz = r if want_dz else (r, None)
+                return dy, sums[c:].float(), sums[:c].float(), dz, sc2
+            if sync_bn:
+                c = st[0].shape[0]
+                g_sums, l_sums = sharding.sync_bwd_sums(ops.bn_bwd_sums_f64(dout, act, y, st[0], st[1], self.bn_eps,
+                                                                            mask_affine=(gamma, beta) if beta is not None else None), self.group)
+                r = ops.bn_bwd_apply(dout, act, y, st[0], st[1], self.bn_eps, gamma, g_sums, st[2], want_dz=want_dz, dy_scale2=sc2, beta_mask=beta)
+                dy, dz = r if want_dz else (r, None)
+                return dy, l_sums[c:].clone(), l_sums[:c].clone(), dz, sc2
+            # one process: the sweep writes the gradient's split planes itself (scale from a bound taken in the reduction pass)
+            r = ops.bn_train_backward(dout, act, y, st[0], st[1], self.bn_eps, gamma, want_dz=want_dz, dy_scale2=sc2, beta_mask=beta,
+                                      split=allow_split and self.fast and y.shape[1] % 256 == 0)
+            return r[0], r[1], r[2], (r[3] if want_dz else None), sc2
 
         # ---------------- backward
         class _Grads(dict):                               # g[name] = tensor: into the sink's slice (copied unless it was written there)
@@ -313,12 +346,20 @@ class StudentTrainer:
             g[f"res_blocks.{i}.conv1.kernel"] = self._wgrad(h_in, h_in_s, dy1, ctx, self.hidden, gs1, out=buf(f"res_blocks.{i}.conv1.kernel"))
             dh = self._dgrad(dy1, P[f"res_blocks.{i}.conv1.kernel"], ctx, gs1, residual=dz)
         h0 = blocks[0][0] if self.num_blocks else h
+        # (the data gradient of the input layer takes fp32 rows of dy0: no split planes in its place then)
         dy0, dg0, db0, _, sc0 = bn_bwd(dh, h0, y0, st0, P["input_layer.1.bn.weight"], beta=P["input_layer.1.bn.bias"],
-                                       allow_split=self.cin_pad >= 256)          # (a narrow input layer's weight gradient takes fp32 rows)
+                                       allow_split=self.cin_pad >= 256 and not want_dx)   # (a narrow input layer's weight gradient takes fp32 rows)
         g["input_layer.1.bn.weight"], g["input_layer.1.bn.bias"] = dg0, db0
-        g["input_layer.0.kernel"] = self._wgrad(X, xs, dy0, ctx, self.cin_pad, self._grad_split(dy0, sc0) if self.fast else None,
-                                                out=buf("input_layer.0.kernel"))
-        return loss, dict(g), E
+        gs0 = self._grad_split(dy0, sc0) if self.fast else None
+        g["input_layer.0.kernel"] = self._wgrad(X, xs, dy0, ctx, self.cin_pad, gs0, out=buf("input_layer.0.kernel"))
+        dX = None
+        if want_dx:
+            # dx = sum_k dy[nbr_k] @ W0[26-k]^T on the exact-fp32 kernel at every width (its output width is a multiple of 128: zero
+            # columns); the input layer is the only one whose data gradient the training step itself never needs
+            wt = torch.zeros((27, self.hidden, _pad_to(self.cin_pad, 128)), dtype=torch.float32, device=dev)
+            wt[:, :, :self.cin_pad] = P["input_layer.0.kernel"].flip(0).transpose(1, 2)
+            dX = ops.sparse_conv(dy0, ctx["nbr_map"], wt)[:, :self.cin_pad]
+        return dict(g), dX
 
     # ---- optimizer ---------------------------------------------------------------------------------------
     def optimizer_step(self, grads):

@@ -110,6 +110,17 @@ int gp_gather_rows(const float *src, int64_t ld_src, int32_t d, const int64_t *i
 /* k = (dx+1)+3(dy+1)+9(dz+1).  Needs the grid built from the same Morton-ordered coords.         */
 int gp_kernel_map_build(const void *grid, const int32_t *coords, int64_t nv, int32_t *nbr_map,
                         void *stream);
+/* Batched coordinates (ME's batched_coordinates: int32 [nv,4] = batch, x, y, z, any row order).  key = batch << 48 |           */
+/* morton(xyz - min) with 16 bits per axis (gp_morton3's interleave, x lowest; min per axis over all rows), radix-sorted:        */
+/* perm / rank as gp_morton_order, keys_sorted u64 [nv].  status i32 [3] (device, written by the call): [0] rows equal to the     */
+/* sorted row before them (duplicates), [1] rows whose batch index is outside 0..65535, [2] mask of the axes whose extent       */
+/* (max - min + 1) is 65536 or more.  Any nonzero status: the order and keys are undefined.  No host sync.                     */
+size_t gp_coords_order_batched_workspace_bytes(int64_t nv);
+int gp_coords_order_batched(const int32_t *coords, int64_t nv, int32_t *perm, int32_t *rank, uint64_t *keys_sorted,
+                            int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+/* 27-offset map over the sorted keys of gp_coords_order_batched (same layout and offset order as gp_kernel_map_build):        */
+/* nbr_map[k][u] = row of the key of voxel u + o_k in the same batch entry, or -1.  Binary search of the keys.                 */
+int gp_kernel_map_sorted(const uint64_t *keys_sorted, int64_t nv, int32_t *nbr_map, void *stream);
 /* Y[u, :] = epilogue( sum_k X[nbr_map[k][u], :] @ W[k] ),  W fp32 [kv, cin, cout] row-major,      */
 /* kv = 27 (nbr_map [27,nv]) or 1 (nbr_map NULL: identity).  epilogue: y = acc*scale + shift      */
 /* (scale/shift fp32 [cout] or NULL), optional residual add (fp32 [nv, ld_res] or NULL), optional  */
