@@ -14,10 +14,9 @@
 // 64 channels x two planes = 32 KB) is shared by the four waves through a double-buffered LDS image with a 144-byte row pitch
 // (16 lanes x 16-byte reads fall on 64 distinct banks).  Chunk c + 1's loads are issued before chunk c's 96 MFMAs.
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
 namespace {
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int EH_ROWS = 128, EH_COLS = 128, EH_KC = 64, EH_PITCH = EH_KC + 8, EH_NT = 256;
 constexpr int EH_EP = EH_COLS + 8;                  // halfs per row of the epilogue's plane image (272 bytes)
@@ -148,9 +147,10 @@ embed_head_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict_
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float sv = v[j] * plane_scale;
-                    const _Float16 h = (_Float16)sv;
+                    _Float16 h, l;
+                    gp_split_f16(sv, h, l);
                     st[lrow * EH_EP + j * 16 + fl] = h;
-                    st[32 * EH_EP + lrow * EH_EP + j * 16 + fl] = (_Float16)(sv - (float)h);
+                    st[32 * EH_EP + lrow * EH_EP + j * 16 + fl] = l;
                 }
             }
         }

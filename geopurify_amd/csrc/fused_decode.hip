@@ -13,6 +13,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
 namespace {
 
@@ -52,7 +53,7 @@ fd_copy_kernel(const unsigned char *__restrict__ feat, int64_t row_bytes, const 
     } else {
         dst = v;
     }
-    typedef unsigned char piece __attribute__((ext_vector_type(VEC)));
+    typedef gp_vec<unsigned char, VEC> piece;
     const piece *s = reinterpret_cast<const piece *>(feat + (int64_t)(r < 0 ? 0 : r) * row_bytes);
     piece *d = reinterpret_cast<piece *>(out + dst * row_bytes);
     const int64_t np = row_bytes / VEC;

@@ -18,6 +18,11 @@
 // (internal to the library: hidden, not part of the C-ABI of include/geopurify_hip.h -- the message is read with gp_last_error)
 extern "C" __attribute__((visibility("hidden"))) void gp_set_error(const char *fmt, ...);
 
+// tuning knobs (gp_debug_knob) and debug buffers (gp_debug_ptr), defined in error.hip; not part of the C-ABI
+extern int g_gp_knobs[16];
+extern void *g_gp_debug_ptr[4];
+extern size_t g_gp_debug_bytes[4];
+
 #define GP_CHECK_ARG(cond, ...)                \
     do {                                       \
         if (!(cond)) {                         \

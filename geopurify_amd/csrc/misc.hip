@@ -4,8 +4,6 @@
 
 #include "gp_common.h"
 
-extern int g_gp_knobs[16];
-
 namespace {
 
 constexpr int NN_TILE = 1024;

@@ -2,8 +2,7 @@
 // affinity pooling in ELL form.  All HBM/L2-bandwidth-bound gathers: one wave per destination row,
 // 16 B per lane coalesced row segments, wave-uniform neighbour indices and weights in SGPRs.
 #include "gp_common.h"
-
-extern int g_gp_knobs[16];
+#include "gp_gfx950.h"
 
 namespace {
 
@@ -88,9 +87,7 @@ __global__ void l2norm_rows_kernel(float *__restrict__ x, int64_t ld, int d, int
 // fragment arrays (gp_pool_cs_structure) -- the same value gp_pool_cs_fill would read back from w, so the operator keeps its bits.
 __device__ __forceinline__ void affinity_emit_fragment(float wgt, int32_t idx, _Float16 *__restrict__ wa_hi, _Float16 *__restrict__ wa_lo) {
     const float v = wgt * GP_POOL_CS_WSCALE;
-    const _Float16 h = (_Float16)v;
-    wa_hi[idx] = h;
-    wa_lo[idx] = (_Float16)(v - (float)h);
+    gp_split_f16(v, wa_hi, wa_lo, idx);
 }
 template <int D, bool SCATTER>
 __global__ void affinity_softmax_kernel(const float *__restrict__ e, int64_t ld_e, const int32_t *__restrict__ nbr,

@@ -8,7 +8,7 @@
 //     (x = hi + lo, two f16 planes written by the previous application's epilogue);
 //   * each wave multiplies its dense 16 x 32 weight block (pre-split f16, stored in MFMA A-fragment
 //     order) with the staged rows on v_mfma_f32_16x16x32_f16, the B fragments read column-major from the
-//     row-major image by ds_read_b64_tr_b16 (hardware transpose; the image is XOR-swizzled through the
+//     row-major image by gp_lds_tr16 (the transposed LDS read; the image is XOR-swizzled through the
 //     DMA source addresses so that the reads are conflict-free: SQ_LDS_BANK_CONFLICT = 0);
 //   * hi*hi + hi*lo + lo*hi with fp32 accumulation = fp32-class accuracy (same scheme as the sparse
 //     convolution; the dropped lo*lo term is 2^-22 relative).
@@ -17,29 +17,9 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
-
-extern int g_gp_knobs[16];
-extern void *g_gp_debug_ptr[4];
-extern size_t g_gp_debug_bytes[4];
+#include "gp_gfx950.h"
 
 namespace {
-
-// in-kernel time stamps (tuning aid, STAMP instantiations only: gp_debug_ptr(0, buffer) selects them)
-__device__ __forceinline__ uint64_t pq_now() {
-    uint64_t t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-__device__ __forceinline__ uint64_t pq_real() {
-    uint64_t t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((vector_size(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PM_KS = 32;             // union rows per step (MFMA K)
 constexpr int PM_MIN_STEPS = 9;       // every row block is padded to at least this many steps
@@ -47,27 +27,7 @@ constexpr int PM_D = 512;             // columns
 constexpr int PM_MAXID = 16384;       // ids sorted per block in the builder (block_rows x K <= 16384)
 constexpr float PM_WSCALE = 1024.f;   // weights (<= 1) are stored x 2^10 so that their f16 lo parts stay normal
 
-__device__ __forceinline__ void glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)l, 16, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------------ builder
-__device__ __forceinline__ void bitonic_sort_lds(int *a, int n_pow2, int tid, int nthreads) {
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n_pow2; i += nthreads) {
-                int ixj = i ^ j;
-                if (ixj > i) {
-                    int x = a[i], y = a[ixj];
-                    bool up = (i & k) == 0;
-                    if ((x > y) == up) { a[i] = y; a[ixj] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // sorted unique union of the neighbour ids of rows [b*br, b*br+br): de-duplicated through an LDS hash table
 // (the union is ~7 % of the br*k ids), then a bitonic sort of the unique ids only.
 // count pass: bu_n / padded count; fill pass: bu_row (padding repeats the first id; its weights stay zero).
@@ -136,7 +96,7 @@ pm_union_kernel(const int32_t *__restrict__ nbr, int64_t nv, int k, int br, int 
     while (np2 < U) np2 <<= 1;
     for (int i = U + tid; i < np2; i += 1024) dense[i] = INT32_MAX;
     __syncthreads();
-    bitonic_sort_lds(dense, np2, tid, 1024);
+    gp_bitonic_sort_lds(dense, np2, tid, 1024);
     const int64_t o = bu_off[b];
     for (int i = tid; i < Up; i += 1024) bu_row[o + i] = i < U ? dense[i] : dense[0];
 }
@@ -178,9 +138,7 @@ pm_weights_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, 
         const int kk = lo % PM_KS;
         const int64_t idx = ((ks * nw + wv) * 64 + (kk >> 3) * 16 + m) * 8 + (kk & 7);
         const float v = w[e] * PM_WSCALE;
-        const _Float16 h = (_Float16)v;
-        wa_hi[idx] = h;
-        wa_lo[idx] = (_Float16)(v - (float)h);
+        gp_split_f16(v, wa_hi, wa_lo, idx);
     }
 }
 
@@ -228,23 +186,8 @@ struct PqGeo {
     static_assert(OFF_W + 2 * NW * 1024 < 65536, "intra-stage LDS offsets are 16-bit immediates");
 };
 
-template <int OFF>
-__device__ __forceinline__ void pq_tr(s16x4 &d, uint32_t addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-template <int OFF>
-__device__ __forceinline__ void pq_rd128(f16x8 &d, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
 __device__ __forceinline__ void pq_rd64(int2 &d, uint32_t addr) {
     asm volatile("ds_read_b64 %0, %1" : "=v"(d) : "v"(addr));
-}
-template <int N>
-__device__ __forceinline__ void pq_wait_lgkm(s16x4 (&f)[2][2][2]) {
-    asm volatile("s_waitcnt lgkmcnt(%[n])"
-                 : "+v"(f[0][0][0]), "+v"(f[0][0][1]), "+v"(f[0][1][0]), "+v"(f[0][1][1]), "+v"(f[1][0][0]), "+v"(f[1][0][1]),
-                   "+v"(f[1][1][0]), "+v"(f[1][1][1])
-                 : [n] "n"(N));
 }
 template <int N>
 __device__ __forceinline__ void pq_wait_lgkm3(int2 &id, f16x8 (&a)[1], f16x8 (&b)[1]) {
@@ -260,15 +203,6 @@ __device__ __forceinline__ void pq_wait_lgkm3(int2 &id, f16x8 (&a)[4], f16x8 (&b
                  : "+v"(id), "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3])
                  : [n] "n"(N));
 }
-template <int N>
-__device__ __forceinline__ void pq_handover() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ f16x8 pq_cat(s16x4 a, s16x4 b) {
-    typedef short s16x8 __attribute__((vector_size(16)));
-    s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
 // transposed reads of 2 column blocks (CB0, CB0+1) from the stage based at the address registers:
 // f[u][plane][half]   (lgkmcnt is a 4-bit counter: groups of 8 reads, at most 11 LDS operations outstanding)
 template <typename G, int CB0>
@@ -276,17 +210,17 @@ __device__ __forceinline__ void pq_read_group(s16x4 (&f)[2][2][2], const uint32_
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         constexpr int HI = ((CB0 + 0) >> 3) * 256;       // CB0 even: both blocks share the 128-column half
-        pq_tr<HI>(f[u][0][0], addr[(CB0 + u) & 7]);
-        pq_tr<HI + G::ROWB>(f[u][0][1], addr[(CB0 + u) & 7]);
-        pq_tr<HI + G::PLANE>(f[u][1][0], addr[(CB0 + u) & 7]);
-        pq_tr<HI + G::PLANE + G::ROWB>(f[u][1][1], addr[(CB0 + u) & 7]);
+        gp_lds_tr16<HI>(f[u][0][0], addr[(CB0 + u) & 7]);
+        gp_lds_tr16<HI + G::ROWB>(f[u][0][1], addr[(CB0 + u) & 7]);
+        gp_lds_tr16<HI + G::PLANE>(f[u][1][0], addr[(CB0 + u) & 7]);
+        gp_lds_tr16<HI + G::PLANE + G::ROWB>(f[u][1][1], addr[(CB0 + u) & 7]);
     }
 }
 template <typename G, int MT>
 __device__ __forceinline__ void pq_mma_group(f32x4 *acc, const s16x4 (&f)[2][2][2], const f16x8 (&ah)[MT], const f16x8 (&al)[MT]) {
     f16x8 bh[2], bl[2];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) { bh[u] = pq_cat(f[u][0][0], f[u][0][1]); bl[u] = pq_cat(f[u][1][0], f[u][1][1]); }
+    for (int u = 0; u < 2; ++u) { bh[u] = gp_cat(f[u][0][0], f[u][0][1]); bl[u] = gp_cat(f[u][1][0], f[u][1][1]); }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -310,11 +244,11 @@ __device__ __forceinline__ void pq_sweep(f32x4 *acc, s16x4 (&fa)[2][2][2], s16x4
     // entry: group CB is in flight in fa
     if constexpr (CB + 2 < G::NCB) {
         pq_read_group<G, CB + 2>(fb, addr);
-        pq_wait_lgkm<8>(fa);
+        gp_wait_frags<8>(fa);
         pq_mma_group<G, MT>(acc + CB, fa, ah, al);
         pq_sweep<G, MT, CB + 2>(acc, fb, fa, addr, ah, al);
     } else {
-        pq_wait_lgkm<0>(fa);
+        gp_wait_frags<0>(fa);
         pq_mma_group<G, MT>(acc + CB, fa, ah, al);
     }
 }
@@ -326,7 +260,7 @@ template <typename G, int MT>
 __device__ __forceinline__ void pg_mma_group(f32x4 *acc, const s16x4 (&f)[2][2][2], const f16x8 (&ah)[MT], const f16x8 (&al)[MT]) {
     f16x8 bh[2], bl[2];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) { bh[u] = pq_cat(f[u][0][0], f[u][0][1]); bl[u] = pq_cat(f[u][1][0], f[u][1][1]); }
+    for (int u = 0; u < 2; ++u) { bh[u] = gp_cat(f[u][0][0], f[u][0][1]); bl[u] = gp_cat(f[u][1][0], f[u][1][1]); }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -348,11 +282,11 @@ __device__ __forceinline__ void pg_sweep(f32x4 *acc, s16x4 (&fa)[2][2][2], s16x4
                                          const f16x8 (&ah)[MT], const f16x8 (&al)[MT]) {
     if constexpr (CB + 2 < G::NCB) {
         pq_read_group<G, CB + 2>(fb, addr);
-        pq_wait_lgkm<8>(fa);
+        gp_wait_frags<8>(fa);
         pg_mma_group<G, MT>(acc + CB, fa, ah, al);
         pg_sweep<G, MT, CB + 2>(acc, fb, fa, addr, ah, al);
     } else {
-        pq_wait_lgkm<0>(fa);
+        gp_wait_frags<0>(fa);
         pg_mma_group<G, MT>(acc + CB, fa, ah, al);
     }
 }
@@ -406,7 +340,6 @@ struct PgGeo {
 };
 
 struct PgTile { int64_t b; int col0; int64_t ub0; int n; };
-typedef int pg_i32x4 __attribute__((ext_vector_type(4)));
 
 template <int OFF>
 __device__ __forceinline__ void pg_wr64(uint32_t addr, f16x4 v) {
@@ -415,10 +348,6 @@ __device__ __forceinline__ void pg_wr64(uint32_t addr, f16x4 v) {
 template <int OFF>
 __device__ __forceinline__ void pg_wr128(uint32_t addr, f32x4 v) {
     asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void pg_rd128(f32x4 &d, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
 }
 __device__ __forceinline__ void pg_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void pg_lgkm0(f32x4 (&r)[4]) {
@@ -486,10 +415,10 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
     auto issue_x = [&](const PgTile &TT, int2 id, int xslot) {
         unsigned char *dst = smem_raw + xslot * P::XSTAGE;
         const int64_t s0 = (int64_t)id.x * ld_x + TT.col0 + dcol0, s1 = (int64_t)id.y * ld_x + TT.col0 + dcol1;
-        glds16(x_hi + s0, dst + (G::RPW * wv) * G::RB);
-        glds16(x_lo + s0, dst + G::PLANE + (G::RPW * wv) * G::RB);
-        glds16(x_hi + s1, dst + (G::RPW * wv) * G::RB + 1024);
-        glds16(x_lo + s1, dst + G::PLANE + (G::RPW * wv) * G::RB + 1024);
+        gp_glds16(x_hi + s0, dst + (G::RPW * wv) * G::RB);
+        gp_glds16(x_lo + s0, dst + G::PLANE + (G::RPW * wv) * G::RB);
+        gp_glds16(x_hi + s1, dst + (G::RPW * wv) * G::RB + 1024);
+        gp_glds16(x_lo + s1, dst + G::PLANE + (G::RPW * wv) * G::RB + 1024);
     };
     // W stage (TT, k) -> W-ring slot, with the row ids of (IT, kid)
     auto issue_w = [&](const PgTile &TT, int k, const PgTile &IT, int kid, int wslot) {
@@ -500,10 +429,9 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
         for (int i = 0; i < MT; ++i) {
             const int L = wv + 8 * i, plane = L / NWF, frag = L % NWF;
             const _Float16 *src = (plane ? wa_lo : wa_hi) + ((ks * NWF + frag) * 64 + lane) * 8;
-            glds16(src, dst + L * 1024);
+            gp_glds16(src, dst + L * 1024);
         }
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)ids,
-                                         (__attribute__((address_space(3))) void *)(dst + P::OFF_ID + wv * 256), 4, 0, 0);
+        gp_glds4(ids, dst + P::OFF_ID + wv * 256);
     };
 
     // ---- read roles
@@ -542,7 +470,7 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
         issue_w(cur, 1, cur, AHX + 1, 1);
         issue_x(cur, ip[1], 1);
         if constexpr (AHX == 3) issue_x(cur, ip[2], 2);
-        pq_handover<P::BASE_WAIT>();
+        gp_handover<P::BASE_WAIT>();
     }
     // split outputs stay in the pre-scaled domain of the planes (pooling is linear); only the fp32 output is scaled back
     const float inv = (1.f / PM_WSCALE) * ((F32OUT && out_scale) ? out_scale[0] : 1.f);
@@ -581,7 +509,7 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
                                          "v_readlane_b32 %2, v202, 1\n\tv_readlane_b32 %3, v203, 1"
                                          : "=s"(d0l), "=s"(d0h), "=s"(d1l), "=s"(d1h)::"memory");
                             const int64_t u0 = (int64_t)(((uint64_t)d0h << 32) | d0l), u1 = (int64_t)(((uint64_t)d1h << 32) | d1l);
-                            pg_i32x4 sv;                   // (an int vector: bit casts of float-vector elements are miscompiled)
+                            i32x4 sv;                   // (an int vector: bit casts of float-vector elements are miscompiled)
                             sv[0] = claimed < hi ? (int32_t)(claimed - lo) : (int32_t)-1;
                             sv[1] = (int32_t)((u1 - u0) / PM_KS);
                             sv[2] = (int32_t)d0l;
@@ -590,8 +518,8 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
                         }
                     }
                     if (s == 5) {
-                        pg_i32x4 sv;
-                        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(sv) : "v"(slot) : "memory");
+                        i32x4 sv;
+                        gp_lds_rd128_now(sv, slot);
                         const int32_t rel = __builtin_amdgcn_readfirstlane(sv[0]);
                         has1 = rel >= 0;
                         if (has1) {
@@ -612,11 +540,11 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
 #pragma unroll
             for (int k = 0; k < 8; ++k) a[k] = addr[k] + xoff;
             pq_rd64(idn, addr_id + woff);
-            pq_rd128<0>(ah[0], addr_w + woff);
-            pq_rd128<NWF * 1024>(al[0], addr_w + woff);
+            gp_lds_rd128<0>(ah[0], addr_w + woff);
+            gp_lds_rd128<NWF * 1024>(al[0], addr_w + woff);
             if constexpr (MT == 2) {
-                pq_rd128<1024>(ah[1], addr_w + woff);
-                pq_rd128<NWF * 1024 + 1024>(al[1], addr_w + woff);
+                gp_lds_rd128<1024>(ah[1], addr_w + woff);
+                gp_lds_rd128<NWF * 1024 + 1024>(al[1], addr_w + woff);
             }
             pq_read_group<G, 0>(f0, a);
             pq_wait_lgkm3<8>(idn, ah, al);
@@ -658,10 +586,10 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
                         pg_wr128<128>(wr, acc[half * 4 + 2] * inv);
                         pg_wr128<192>(wr, acc[half * 4 + 3] * inv);
                         pg_lgkm0();
-                        pg_rd128<0>(r[0], rd);
-                        pg_rd128<4 * P::STG_PITCH>(r[1], rd);
-                        pg_rd128<8 * P::STG_PITCH>(r[2], rd);
-                        pg_rd128<12 * P::STG_PITCH>(r[3], rd);
+                        gp_lds_rd128_mem<0>(r[0], rd);
+                        gp_lds_rd128_mem<4 * P::STG_PITCH>(r[1], rd);
+                        gp_lds_rd128_mem<8 * P::STG_PITCH>(r[2], rd);
+                        gp_lds_rd128_mem<12 * P::STG_PITCH>(r[3], rd);
                         pg_lgkm0(r);
 #pragma unroll
                         for (int ps = 0; ps < 4; ++ps)
@@ -674,7 +602,7 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
                     for (int cb = 0; cb < G::NCB; ++cb) {
                         const f32x4 v = acc[cb] * inv;
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) { h[cb][i] = (_Float16)v[i]; l[cb][i] = (_Float16)(v[i] - (float)h[cb][i]); }
+                        for (int i = 0; i < 4; ++i) gp_split_f16(v[i], h[cb], l[cb], i);
                     }
 #pragma unroll
                     for (int plane = 0; plane < 2; ++plane) {
@@ -682,10 +610,10 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
                         pg_wr64<0>(wr, src[0]);   pg_wr64<32>(wr, src[1]);  pg_wr64<64>(wr, src[2]);  pg_wr64<96>(wr, src[3]);
                         pg_wr64<128>(wr, src[4]); pg_wr64<160>(wr, src[5]); pg_wr64<192>(wr, src[6]); pg_wr64<224>(wr, src[7]);
                         pg_lgkm0();
-                        pg_rd128<0>(r[0], rd);
-                        pg_rd128<4 * P::STG_PITCH>(r[1], rd);
-                        pg_rd128<8 * P::STG_PITCH>(r[2], rd);
-                        pg_rd128<12 * P::STG_PITCH>(r[3], rd);
+                        gp_lds_rd128_mem<0>(r[0], rd);
+                        gp_lds_rd128_mem<4 * P::STG_PITCH>(r[1], rd);
+                        gp_lds_rd128_mem<8 * P::STG_PITCH>(r[2], rd);
+                        gp_lds_rd128_mem<12 * P::STG_PITCH>(r[3], rd);
                         pg_lgkm0(r);
                         _Float16 *yp = plane ? y_lo : y_hi;
 #pragma unroll
@@ -700,9 +628,9 @@ pool_mfma_persist_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__re
             // the previous step (AHX = 3) and the stores of an epilogue issued since the stage being waited for.
             if (x_any && w_any) {
                 const bool stores_since = last || (s == 0 && !first_tile);
-                if (stores_since) pq_handover<P::BASE_WAIT + NSTORE>(); else pq_handover<P::BASE_WAIT>();
+                if (stores_since) gp_handover<P::BASE_WAIT + NSTORE>(); else gp_handover<P::BASE_WAIT>();
             } else {
-                pq_handover<0>();                  // the last steps of the workgroup's last tile: nothing left to overlap
+                gp_handover<0>();                  // the last steps of the workgroup's last tile: nothing left to overlap
             }
             xs = xs + 1 >= XD ? 0 : xs + 1;
             ws = ws + 1 >= P::WD ? 0 : ws + 1;
@@ -735,7 +663,7 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
     const int ablate = TUNE ? ablate_ : 0;
     static_assert(G::BR / 16 == NW, "one weight fragment group per wave to stage");
     uint64_t st_t0 = 0, st_r0 = 0, st_pro = 0, st_work = 0, st_wait = 0, st_issue = 0;
-    if constexpr (STAMP) { st_t0 = pq_now(); st_r0 = pq_real(); }
+    if constexpr (STAMP) { st_t0 = gp_clock(); st_r0 = gp_clock_real(); }
     constexpr int NQ = PM_D / NC;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -764,17 +692,15 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
         // fragments -- the same 7 instructions per stage either way (see the note above the kernel)
         const bool hot_x = (ablate & 2) != 0, hot_w = (ablate & 8) != 0;
         const int64_t s0 = hot_x ? 0 : (int64_t)id.x * ld_x + dsrc0, s1 = hot_x ? 0 : (int64_t)id.y * ld_x + dsrc1;
-        glds16(x_hi + s0, dst + (G::RPW * wv) * G::RB);
-        glds16(x_lo + s0, dst + G::PLANE + (G::RPW * wv) * G::RB);
-        glds16(x_hi + s1, dst + (G::RPW * wv) * G::RB + 1024);
-        glds16(x_lo + s1, dst + G::PLANE + (G::RPW * wv) * G::RB + 1024);
-        glds16(hot_w ? wa_hi : wah + (int64_t)k * WSTEP, dst + G::OFF_W + wv * 1024);
-        glds16(hot_w ? wa_lo : wal + (int64_t)k * WSTEP, dst + G::OFF_W + NW * 1024 + wv * 1024);
+        gp_glds16(x_hi + s0, dst + (G::RPW * wv) * G::RB);
+        gp_glds16(x_lo + s0, dst + G::PLANE + (G::RPW * wv) * G::RB);
+        gp_glds16(x_hi + s1, dst + (G::RPW * wv) * G::RB + 1024);
+        gp_glds16(x_lo + s1, dst + G::PLANE + (G::RPW * wv) * G::RB + 1024);
+        gp_glds16(hot_w ? wa_hi : wah + (int64_t)k * WSTEP, dst + G::OFF_W + wv * 1024);
+        gp_glds16(hot_w ? wa_lo : wal + (int64_t)k * WSTEP, dst + G::OFF_W + NW * 1024 + wv * 1024);
         const int kid = k + 2 < n ? k + 2 : n - 1;
         // 64 lanes x 4 B: the wave's RPW ids, repeated (lane & (RPW-1)): always inside the block's padded union
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void *)(idg + (int64_t)kid * PM_KS + (lane & (G::RPW - 1))),
-            (__attribute__((address_space(3))) void *)(dst + G::OFF_ID + wv * 256), 4, 0, 0);
+        gp_glds4(idg + (int64_t)kid * PM_KS + (lane & (G::RPW - 1)), dst + G::OFF_ID + wv * 256);
     };
 
     // ---- read roles
@@ -806,9 +732,9 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
         asm volatile("" ::"v"(i0.x), "v"(i0.y), "v"(i1.x), "v"(i1.y));    // both id loads land before the first DMA
         issue(i0, 0, 0);
         issue(i1, k1, 1);
-        pq_handover<G::DMA_PER_STAGE>();
+        gp_handover<G::DMA_PER_STAGE>();
     }
-    if constexpr (STAMP) st_pro = pq_now();
+    if constexpr (STAMP) st_pro = gp_clock();
     s16x4 f0[2][2][2], f1[2][2][2];
     f16x8 ah[MT], al[MT];
     int2 idn;
@@ -819,21 +745,21 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
             if (s < n) {
                 uint32_t a[8];
                 uint64_t st_a = 0, st_b = 0;
-                if constexpr (STAMP) st_a = pq_now();
+                if constexpr (STAMP) st_a = gp_clock();
 #pragma unroll
                 for (int k = 0; k < 8; ++k) a[k] = addr[k] + J * G::STAGE;
                 pq_rd64(idn, addr_id + J * G::STAGE);
-                pq_rd128<0>(ah[0], addr_w + J * G::STAGE);
-                pq_rd128<NW * 1024>(al[0], addr_w + J * G::STAGE);
+                gp_lds_rd128<0>(ah[0], addr_w + J * G::STAGE);
+                gp_lds_rd128<NW * 1024>(al[0], addr_w + J * G::STAGE);
                 if constexpr (MT >= 2) {
-                    pq_rd128<1024>(ah[1], addr_w + J * G::STAGE);
-                    pq_rd128<NW * 1024 + 1024>(al[1], addr_w + J * G::STAGE);
+                    gp_lds_rd128<1024>(ah[1], addr_w + J * G::STAGE);
+                    gp_lds_rd128<NW * 1024 + 1024>(al[1], addr_w + J * G::STAGE);
                 }
                 if constexpr (MT == 4) {                   // a wave that owns all 64 rows reads all four weight fragments
-                    pq_rd128<2048>(ah[2], addr_w + J * G::STAGE);
-                    pq_rd128<NW * 1024 + 2048>(al[2], addr_w + J * G::STAGE);
-                    pq_rd128<3072>(ah[3], addr_w + J * G::STAGE);
-                    pq_rd128<NW * 1024 + 3072>(al[3], addr_w + J * G::STAGE);
+                    gp_lds_rd128<2048>(ah[2], addr_w + J * G::STAGE);
+                    gp_lds_rd128<NW * 1024 + 2048>(al[2], addr_w + J * G::STAGE);
+                    gp_lds_rd128<3072>(ah[3], addr_w + J * G::STAGE);
+                    gp_lds_rd128<NW * 1024 + 3072>(al[3], addr_w + J * G::STAGE);
                     pq_wait_lgkm3<0>(idn, ah, al);         // 9 + 8 reads would overflow the 4-bit LDS counter
                     pq_read_group<G, 0>(f0, a);
                 } else {
@@ -841,18 +767,18 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
                     pq_wait_lgkm3<8>(idn, ah, al);
                 }
                 if (s + 2 < n) issue(idn, s + 2, (J + 2) % G::NST);
-                if constexpr (STAMP) if (ablate & 64) { pq_wait_lgkm<0>(f0); st_issue += pq_now() - st_a; }
+                if constexpr (STAMP) if (ablate & 64) { gp_wait_frags<0>(f0); st_issue += gp_clock() - st_a; }
                 if (!(ablate & 1)) pq_sweep<G, MT, 0>(acc, f0, f1, a, ah, al);   // tuning aid: bit 0 skips reads + MFMAs
-                else pq_wait_lgkm<0>(f0);
-                if constexpr (STAMP) { st_b = pq_now(); st_work += st_b - st_a; }
-                if (s + 2 < n) pq_handover<G::DMA_PER_STAGE>(); else pq_handover<0>();
-                if constexpr (STAMP) st_wait += pq_now() - st_b;
+                else gp_wait_frags<0>(f0);
+                if constexpr (STAMP) { st_b = gp_clock(); st_work += st_b - st_a; }
+                if (s + 2 < n) gp_handover<G::DMA_PER_STAGE>(); else gp_handover<0>();
+                if constexpr (STAMP) st_wait += gp_clock() - st_b;
             }
         }
     }
     if (ablate & 4) return;                                // tuning aid: bit 2 skips the epilogue
     uint64_t st_e0 = 0;
-    if constexpr (STAMP) st_e0 = pq_now();
+    if constexpr (STAMP) st_e0 = gp_clock();
     // ---- epilogue through LDS (the ring is drained: the last hand-over waited for vmcnt(0))
     // the split planes carry x * s (s = the power of two of gp_pow2_scale, so that the lo halves stay normal f16 numbers);
     // pooling is linear, so the planes written for the next application stay in that domain and only the fp32 output is
@@ -888,8 +814,7 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
         if (grow < nv && !(ablate & 16)) {      // tuning aid: bit 4 skips the output stores
             float xv[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
             f16x4 h, l;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { h[i] = (_Float16)xv[i]; l[i] = (_Float16)(xv[i] - (float)h[i]); }
+            gp_split_f16<4>(xv, h, l);
             if (y_hi) {
                 *reinterpret_cast<f16x4 *>(y_hi + grow * ld_y + colw + c4 * 4) = h;
                 *reinterpret_cast<f16x4 *>(y_lo + grow * ld_y + colw + c4 * 4) = l;
@@ -902,7 +827,7 @@ pq_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_lo, in
     }
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint64_t t3 = pq_now(), r3 = pq_real();
+        const uint64_t t3 = gp_clock(), r3 = gp_clock_real();
         if (lane == 0 && stamp) {
             uint64_t *o = stamp + ((int64_t)blockIdx.x * NW + wv) * 10;
             unsigned xcc;

@@ -21,17 +21,10 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
-extern int g_gp_knobs[16];
-extern void *g_gp_debug_ptr[4];
-extern size_t g_gp_debug_bytes[4];
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((vector_size(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CS_KS = 32;              // union rows per step (MFMA K)
 constexpr int CS_D = 512;              // feature columns of the product kernels (cs_pool_kernel, cs_chain_kernel)
@@ -58,22 +51,6 @@ constexpr int CS_EP = CS_WC + 4;                   // epilogue staging pitch (fl
 constexpr size_t CS_SMEM = (size_t)CS_NST * CS_STAGE;
 static_assert((size_t)CS_NW * CS_BR * CS_EP * sizeof(float) <= CS_SMEM, "epilogue staging must fit in the ring");
 
-__device__ __forceinline__ uint64_t cs_now() {
-    uint64_t t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-__device__ __forceinline__ uint64_t cs_real() {
-    uint64_t t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-// AUX: the cache-policy bits of the instruction (0 = default; 16 = sc1: served by L2, never by this CU's L1)
-template <int AUX = 0>
-__device__ __forceinline__ void cs_glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)l, 16, 0, AUX);
-}
 // agent-visible accesses of the chained launch (cs_chain_kernel): sc1 stores are written through to memory, sc1 loads are never
 // served by a CU's L1 (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility")
 __device__ __forceinline__ uint32_t cs_ld_sc1(const uint32_t *p) {           // global_load_dword ... sc1 (the compiler counts it in vmcnt)
@@ -93,50 +70,12 @@ __device__ __forceinline__ void cs_st16_sc1(void *p, V v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
-template <int OFF>
-__device__ __forceinline__ void cs_tr(s16x4 &d, uint32_t addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-template <int OFF>
-__device__ __forceinline__ void cs_rd128(f16x8 &d, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-// every LDS read issued so far has landed; ties the fragment registers to the wait so that no use moves above it
-__device__ __forceinline__ void cs_wait_b(s16x4 (&f)[2][2][2]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(f[0][0][0]), "+v"(f[0][0][1]), "+v"(f[0][1][0]), "+v"(f[0][1][1]), "+v"(f[1][0][0]), "+v"(f[1][0][1]),
-                   "+v"(f[1][1][0]), "+v"(f[1][1][1]));
-}
 __device__ __forceinline__ void cs_wait_a(f16x8 (&h)[4], f16x8 (&l)[4]) {
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]));
 }
-template <int N>
-__device__ __forceinline__ void cs_handover() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ f16x8 cs_cat(s16x4 a, s16x4 b) {
-    typedef short s16x8 __attribute__((vector_size(16)));
-    s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
 
 // ------------------------------------------------------------------------------------------------ builder
-__device__ __forceinline__ void cs_bitonic(int *a, int n_pow2, int tid, int nthreads) {
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n_pow2; i += nthreads) {
-                int ixj = i ^ j;
-                if (ixj > i) {
-                    int x = a[i], y = a[ixj];
-                    bool up = (i & k) == 0;
-                    if ((x > y) == up) { a[i] = y; a[ixj] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // distinct neighbour ids of the rows of block b -> dense[0 .. U) (unsorted), through an LDS hash table of `cap` slots (a power of two
 // >= 2048; `dense` holds cap entries too): a 2048-slot table first (unions of lattice neighbourhoods are a few hundred ids), all
 // `cap` slots if that overflows.  Returns -1 if the union does not fit cap / 2 ids (the caller sized cap from the largest union, or
@@ -233,7 +172,7 @@ cs_fill_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, int
     while (np2 < U) np2 <<= 1;
     for (int i = U + tid; i < np2; i += 1024) B[i] = INT32_MAX;
     __syncthreads();
-    cs_bitonic(B, np2, tid, 1024);                            // B[0 .. U): the ids, ascending
+    gp_bitonic_sort_lds(B, np2, tid, 1024);                            // B[0 .. U): the ids, ascending
     // group set of every union row
     for (int i = tid; i < U; i += 1024) A[i] = 0;
     __syncthreads();
@@ -255,7 +194,7 @@ cs_fill_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, int
         A[i] = key;
     }
     __syncthreads();
-    cs_bitonic(A, np2, tid, 1024);
+    gp_bitonic_sort_lds(A, np2, tid, 1024);
     const int64_t o = bu_off[b];
     const int Up = (int)(bu_off[b + 1] - o);
     for (int p = tid; p < Up; p += 1024) {
@@ -320,9 +259,7 @@ cs_fill_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, int
         const int64_t idx = ((ks * CS_NG + (rl >> 4)) * 64 + (kk >> 3) * 16 + (rl & 15)) * 8 + (kk & 7);
         if constexpr (WEIGHTS) {
             const float v = w[r0 * k + t] * GP_POOL_CS_WSCALE;
-            const _Float16 h = (_Float16)v;
-            wa_hi[idx] = h;
-            wa_lo[idx] = (_Float16)(v - (float)h);
+            gp_split_f16(v, wa_hi, wa_lo, idx);
         } else {
             dst[r0 * k + t] = (int32_t)idx;                              // (the host checks total_rows * 128 < 2^31)
         }
@@ -338,7 +275,7 @@ cs_fill_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w, int
 // rows 4 wv .. 4 wv + 3 of a step (two 1-KiB instructions per plane, two rows each) and the weight fragment of group wv.
 // The image is XOR-swizzled through the DMA source addresses exactly as in pool_mfma.hip (physical 16-byte chunk c of
 // row r holds logical chunk c ^ 2 t(r), t(r) = (r & 3) | ((r >> 3) & 1) << 2), which makes the transposed fragment
-// reads (ds_read_b64_tr_b16) conflict-free.  Synchronisation is hand-counted: LDS reads are inline asm with their own
+// reads (gp_lds_tr16) conflict-free.  Synchronisation is hand-counted: LDS reads are inline asm with their own
 // lgkmcnt waits (a compiler-visible LDS read would wait for every outstanding LDS-DMA), the hand-over is
 // `s_waitcnt vmcnt(6); s_barrier` (6 = the DMA instructions of the younger stage; vector memory operations complete in
 // issue order and the loop issues no other).  Row ids and fragment masks are scalar loads issued one step ahead.
@@ -383,7 +320,7 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
     constexpr int AUX = CHAIN ? 16 : 0;
     const int ablate = TUNE ? ablate_ : 0;
     uint64_t st_t0 = 0, st_r0 = 0, st_pro = 0, st_work = 0, st_wait = 0, st_issue = 0;
-    if constexpr (STAMP) { st_t0 = cs_now(); st_r0 = cs_real(); }
+    if constexpr (STAMP) { st_t0 = gp_clock(); st_r0 = gp_clock_real(); }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-contiguous order: blocks b, b + 8, ... share an XCD (observed round-robin placement); each XCD walks a contiguous range of
@@ -430,7 +367,7 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
             const uint32_t want = ch.base + (uint32_t)app;
             const int32_t dv = ch.dep[b * CS_DEP_CAP + lane];
             const int n = __builtin_amdgcn_readfirstlane(dv);
-            const uint64_t w0 = cs_real();
+            const uint64_t w0 = gp_clock_real();
             for (int64_t i0 = 0;;) {
                 uint32_t v = want, ab = 0;
                 if (n < CS_DEP_CAP) {
@@ -444,14 +381,14 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
                     if (n < CS_DEP_CAP || (i0 += 64) >= nblocks) break;
                     continue;
                 }
-                if (cs_real() - w0 > 200000000ull) {                                       // 2 s: a dependency that never comes
+                if (gp_clock_real() - w0 > 200000000ull) {                                       // 2 s: a dependency that never comes
                     if (lane == 0) cs_st_sc1(ch.flags, 1u);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     return;
                 }
                 __builtin_amdgcn_s_sleep(8);
             }
-            if constexpr (STAMP) st_issue = cs_now() - st_t0;                              // (slot 5 of the stamps: the dependency wait)
+            if constexpr (STAMP) st_issue = gp_clock() - st_t0;                              // (slot 5 of the stamps: the dependency wait)
         }
     }
     const int64_t ub0 = bu_off[b];
@@ -478,25 +415,25 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
         // 64-row kernel of pool_mfma.hip, whose row ids ride in the ring, read stale ids and faulted).
         const bool hot_x = (ablate & 2) != 0, hot_w = (ablate & 8) != 0;
         const int64_t s0 = hot_x ? 0 : (int64_t)ida * ld_x + dsrc0, s1 = hot_x ? 0 : (int64_t)idb * ld_x + dsrc1;
-        cs_glds16<AUX>(x_hi + s0, dst + (4 * wv) * CS_RB);
-        cs_glds16<AUX>(x_lo + s0, dst + CS_PLANE + (4 * wv) * CS_RB);
-        cs_glds16<AUX>(x_hi + s1, dst + (4 * wv) * CS_RB + 1024);
+        gp_glds16<AUX>(x_hi + s0, dst + (4 * wv) * CS_RB);
+        gp_glds16<AUX>(x_lo + s0, dst + CS_PLANE + (4 * wv) * CS_RB);
+        gp_glds16<AUX>(x_hi + s1, dst + (4 * wv) * CS_RB + 1024);
         // tuning bit 7: what would an 8-BIT lo plane buy?  Half of the lo rows come from the hot piece (the bytes of the gather as they
         // would be; one instruction more than the real thing would issue), and the epilogue stores half of its lo bytes -- a price, not
         // a result
-        cs_glds16<AUX>(x_lo + ((ablate & 128) ? 0 : s1), dst + CS_PLANE + (4 * wv) * CS_RB + 1024);
+        gp_glds16<AUX>(x_lo + ((ablate & 128) ? 0 : s1), dst + CS_PLANE + (4 * wv) * CS_RB + 1024);
         // an empty fragment (half of them on the S scene) is never read and -- round 5 -- never fetched: the wave issues 4 instead of 6
         // instructions for that stage, and the hand-over that lets this stage stay in flight counts accordingly (cs_stage_dma below).
         // (Rounds 3-5a fetched one hot piece instead, to keep the count fixed: a third of the loop's LDS-DMA instructions were dummies.)
         if ((mk >> wv) & 1u) {
             const int lo = hot_w ? 0 : lane * 8;
-            cs_glds16(wah + (int64_t)k * (CS_NG * 512) + lo, dst + CS_OFF_W + wv * 1024);
-            cs_glds16(wal + (int64_t)k * (CS_NG * 512) + lo, dst + CS_OFF_W + CS_WPL + wv * 1024);
+            gp_glds16(wah + (int64_t)k * (CS_NG * 512) + lo, dst + CS_OFF_W + wv * 1024);
+            gp_glds16(wal + (int64_t)k * (CS_NG * 512) + lo, dst + CS_OFF_W + CS_WPL + wv * 1024);
         }
     };
     // hand-over with the stage of mask `mk` (the youngest, issued by THIS wave) allowed to stay in flight: 4 row pieces + its fragment's 2
     auto handover_behind = [&](unsigned mk) {
-        if ((mk >> wv) & 1u) cs_handover<CS_DMA>(); else cs_handover<CS_DMA - 2>();
+        if ((mk >> wv) & 1u) gp_handover<CS_DMA>(); else gp_handover<CS_DMA - 2>();
     };
     auto load_ids = [&](int k) { return *reinterpret_cast<const i32x4 *>(idg + (int64_t)k * CS_KS); };
 
@@ -531,7 +468,7 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
         asm volatile("" ::"s"(idv.x), "s"(idv.y), "s"(idv.z), "s"(idv.w), "s"(mC));   // (waited for here, not inside the loop)
         handover_behind(mB);                                   // stage 0 has landed; stage 1 may be in flight
     }
-    if constexpr (STAMP) st_pro = cs_now();
+    if constexpr (STAMP) st_pro = gp_clock();
     // Software pipeline (the fragment reads of all eight waves leave the barrier together and take ~500 cycles to come back;
     // an MFMA batch in front of each wait hides part of that):
     //   step s:  reads {staged rows, weight fragments of groups 0-3} of stage s      | waves 0-3: DMA of stage s + 2
@@ -571,29 +508,29 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
             const int s = s0 + J;
             if (s < n) {
                 uint64_t st_a = 0, st_b = 0;
-                if constexpr (STAMP) st_a = cs_now();
+                if constexpr (STAMP) st_a = gp_clock();
                 const uint32_t a0 = addr[0] + J * CS_STAGE, a1 = addr[1] + J * CS_STAGE, aw = addr_w + J * CS_STAGE;
                 const unsigned m = mA;
                 if (do_reads) {
                     // staged rows: fb[col block][plane][rows 8g+q | 8g+q+4]; weight fragments of groups 0-3
-                    cs_tr<0>(fb[0][0][0], a0);
-                    cs_tr<4 * CS_RB>(fb[0][0][1], a0);
-                    cs_tr<CS_PLANE>(fb[0][1][0], a0);
-                    cs_tr<CS_PLANE + 4 * CS_RB>(fb[0][1][1], a0);
-                    cs_tr<0>(fb[1][0][0], a1);
-                    cs_tr<4 * CS_RB>(fb[1][0][1], a1);
-                    cs_tr<CS_PLANE>(fb[1][1][0], a1);
-                    cs_tr<CS_PLANE + 4 * CS_RB>(fb[1][1][1], a1);
-                    if (m & 1u) { cs_rd128<0 * 1024>(ah0[0], aw); cs_rd128<CS_WPL + 0 * 1024>(al0[0], aw); }
-                    if (m & 2u) { cs_rd128<1 * 1024>(ah0[1], aw); cs_rd128<CS_WPL + 1 * 1024>(al0[1], aw); }
-                    if (m & 4u) { cs_rd128<2 * 1024>(ah0[2], aw); cs_rd128<CS_WPL + 2 * 1024>(al0[2], aw); }
-                    if (m & 8u) { cs_rd128<3 * 1024>(ah0[3], aw); cs_rd128<CS_WPL + 3 * 1024>(al0[3], aw); }
+                    gp_lds_tr16<0>(fb[0][0][0], a0);
+                    gp_lds_tr16<4 * CS_RB>(fb[0][0][1], a0);
+                    gp_lds_tr16<CS_PLANE>(fb[0][1][0], a0);
+                    gp_lds_tr16<CS_PLANE + 4 * CS_RB>(fb[0][1][1], a0);
+                    gp_lds_tr16<0>(fb[1][0][0], a1);
+                    gp_lds_tr16<4 * CS_RB>(fb[1][0][1], a1);
+                    gp_lds_tr16<CS_PLANE>(fb[1][1][0], a1);
+                    gp_lds_tr16<CS_PLANE + 4 * CS_RB>(fb[1][1][1], a1);
+                    if (m & 1u) { gp_lds_rd128<0 * 1024>(ah0[0], aw); gp_lds_rd128<CS_WPL + 0 * 1024>(al0[0], aw); }
+                    if (m & 2u) { gp_lds_rd128<1 * 1024>(ah0[1], aw); gp_lds_rd128<CS_WPL + 1 * 1024>(al0[1], aw); }
+                    if (m & 4u) { gp_lds_rd128<2 * 1024>(ah0[2], aw); gp_lds_rd128<CS_WPL + 2 * 1024>(al0[2], aw); }
+                    if (m & 8u) { gp_lds_rd128<3 * 1024>(ah0[3], aw); gp_lds_rd128<CS_WPL + 3 * 1024>(al0[3], aw); }
                 }
                 if (!late && s + 2 < n) issue(idv, mC, s + 2, (J + 2) % CS_NST);
-                if constexpr (STAMP) if (ablate & 64) st_issue += cs_now() - st_a;
+                if constexpr (STAMP) if (ablate & 64) st_issue += gp_clock() - st_a;
                 if (do_reads) {
                     mfma_hi(mP);                            // groups 4-7 of the previous step
-                    cs_wait_b(fb);
+                    gp_wait_frags(fb);
                     cs_wait_a(ah0, al0);
                 }
                 // scalars of the stage issued in the next step (clamped: never past the block's padded union); they are
@@ -602,12 +539,12 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
                 const i32x4 idn = load_ids(kn);
                 const unsigned mN = mkg[kn];
                 if (do_reads) {
-                    if (m & 16u) { cs_rd128<4 * 1024>(ah1[0], aw); cs_rd128<CS_WPL + 4 * 1024>(al1[0], aw); }
-                    if (m & 32u) { cs_rd128<5 * 1024>(ah1[1], aw); cs_rd128<CS_WPL + 5 * 1024>(al1[1], aw); }
-                    if (m & 64u) { cs_rd128<6 * 1024>(ah1[2], aw); cs_rd128<CS_WPL + 6 * 1024>(al1[2], aw); }
-                    if (m & 128u) { cs_rd128<7 * 1024>(ah1[3], aw); cs_rd128<CS_WPL + 7 * 1024>(al1[3], aw); }
+                    if (m & 16u) { gp_lds_rd128<4 * 1024>(ah1[0], aw); gp_lds_rd128<CS_WPL + 4 * 1024>(al1[0], aw); }
+                    if (m & 32u) { gp_lds_rd128<5 * 1024>(ah1[1], aw); gp_lds_rd128<CS_WPL + 5 * 1024>(al1[1], aw); }
+                    if (m & 64u) { gp_lds_rd128<6 * 1024>(ah1[2], aw); gp_lds_rd128<CS_WPL + 6 * 1024>(al1[2], aw); }
+                    if (m & 128u) { gp_lds_rd128<7 * 1024>(ah1[3], aw); gp_lds_rd128<CS_WPL + 7 * 1024>(al1[3], aw); }
 #pragma unroll
-                    for (int u = 0; u < 2; ++u) { bhp[u] = cs_cat(fb[u][0][0], fb[u][0][1]); blp[u] = cs_cat(fb[u][1][0], fb[u][1][1]); }
+                    for (int u = 0; u < 2; ++u) { bhp[u] = gp_cat(fb[u][0][0], fb[u][0][1]); blp[u] = gp_cat(fb[u][1][0], fb[u][1][1]); }
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt)
                         if (__builtin_expect((m >> mt) & 1u, 1)) {
@@ -624,9 +561,9 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
                 // loads are waited for HERE, so that no compiler-placed lgkmcnt(0) sits inside the next step
                 cs_wait_a(ah1, al1);
                 asm volatile("" ::"s"(idn.x), "s"(idn.y), "s"(idn.z), "s"(idn.w), "s"(mN));
-                if constexpr (STAMP) { st_b = cs_now(); st_work += st_b - st_a; }
-                if (s + 2 < n) handover_behind(mC); else cs_handover<0>();      // (mC: the stage issued in this step)
-                if constexpr (STAMP) st_wait += cs_now() - st_b;
+                if constexpr (STAMP) { st_b = gp_clock(); st_work += st_b - st_a; }
+                if (s + 2 < n) handover_behind(mC); else gp_handover<0>();      // (mC: the stage issued in this step)
+                if constexpr (STAMP) st_wait += gp_clock() - st_b;
                 mP = m; mA = mB; mB = mC; mC = mN; idv = idn;
             }
         }
@@ -634,7 +571,7 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
     if (do_reads) mfma_hi(mP);                               // groups 4-7 of the last step
     if (ablate & 4) return;                                // tuning aid: bit 2 skips the epilogue
     uint64_t st_e0 = 0;
-    if constexpr (STAMP) st_e0 = cs_now();
+    if constexpr (STAMP) st_e0 = gp_clock();
     // ---- epilogue through LDS (the ring is drained: the last hand-over waited for vmcnt(0)).  The split planes carry
     // x * s (s = the power of two of gp_pow2_scale); pooling is linear, so the planes written for the next application stay
     // in that domain and only the fp32 output is multiplied by out_scale = 1/s.
@@ -672,15 +609,14 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
                 if (y_hi) {
                     f16x8 h, l;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { h[i] = (_Float16)xv[i]; l[i] = (_Float16)(xv[i] - (float)h[i]); }
+                    for (int i = 0; i < 8; ++i) gp_split_f16(xv[i], h, l, i);
                     if constexpr (CHAIN) {                  // written through: another XCD gathers these rows in the same launch
                         cs_st16_sc1(y_hi + grow * ld_y + colw + ec, h);
                         cs_st16_sc1(y_lo + grow * ld_y + colw + ec, l);
                     } else {
                         *reinterpret_cast<f16x8 *>(y_hi + grow * ld_y + colw + ec) = h;
                         if (ablate & 128) {
-                            typedef _Float16 f16x4_ __attribute__((ext_vector_type(4)));
-                            *reinterpret_cast<f16x4_ *>(y_lo + grow * ld_y + colw + (ec >> 1)) = f16x4_{l[0], l[1], l[2], l[3]};   // 8 of the 16 bytes, packed
+                            *reinterpret_cast<f16x4 *>(y_lo + grow * ld_y + colw + (ec >> 1)) = f16x4{l[0], l[1], l[2], l[3]};   // 8 of the 16 bytes, packed
                         } else {
                             *reinterpret_cast<f16x8 *>(y_lo + grow * ld_y + colw + ec) = l;
                         }
@@ -704,7 +640,7 @@ cs_pool_body(const _Float16 *__restrict__ x_hi_, const _Float16 *__restrict__ x_
     }
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint64_t t3 = cs_now(), r3 = cs_real();
+        const uint64_t t3 = gp_clock(), r3 = gp_clock_real();
         if (lane == 0 && stamp) {
             uint64_t *o = stamp + ((int64_t)blockIdx.x * CS_NW + wv) * 10;
             unsigned xcc;
@@ -826,10 +762,9 @@ affinity_cs_kernel(const _Float16 *__restrict__ e_hi, const _Float16 *__restrict
         if (tune & 16) return;
         const int64_t id = srow_l == 0 ? id4.x : srow_l == 1 ? id4.y : srow_l == 2 ? id4.z : id4.w;
         unsigned char *dst = smem_raw + slot * AF_STAGE + (4 * g) * AF_RB;
-        cs_glds16<0>(e_hi + id * AF_D + spiece * 8, dst);
-        cs_glds16<0>(e_lo + id * AF_D + spiece * 8, dst + AF_PLANE);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(vgl + (int64_t)k * CS_BR),
-                                         (__attribute__((address_space(3))) void *)(smem_raw + AF_OFF_V + (slot * CS_NW + g) * 256), 4, 0, 0);
+        gp_glds16(e_hi + id * AF_D + spiece * 8, dst);
+        gp_glds16(e_lo + id * AF_D + spiece * 8, dst + AF_PLANE);
+        gp_glds4(vgl + (int64_t)k * CS_BR, smem_raw + AF_OFF_V + (slot * CS_NW + g) * 256);
     };
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem_raw;
     // fragment read of tile t, K step ks: staged row 8 (m / 4) + 4 t + m % 4 (key m), logical piece 4 ks + q
@@ -861,9 +796,9 @@ affinity_cs_kernel(const _Float16 *__restrict__ e_hi, const _Float16 *__restrict
         {
             const int younger = (tune & 16) ? 0 : n - 1 - s < AF_NST - 2 ? n - 1 - s : AF_NST - 2;
             static_assert(AF_NST == 4, "the hand-over below lists the waits of a four-stage ring");
-            if (younger == 2) cs_handover<2 * AF_DMA>();
-            else if (younger == 1) cs_handover<1 * AF_DMA>();
-            else cs_handover<0>();
+            if (younger == 2) gp_handover<2 * AF_DMA>();
+            else if (younger == 1) gp_handover<1 * AF_DMA>();
+            else gp_handover<0>();
         }
         if (s + AF_NST - 1 < n) issue(idn, s + AF_NST - 1, (s + AF_NST - 1) % AF_NST);
         const int kn = s + AF_NST < n ? s + AF_NST : n - 1;
@@ -878,10 +813,10 @@ affinity_cs_kernel(const _Float16 *__restrict__ e_hi, const _Float16 *__restrict
                 f16x8 ah0[4], al0[4], ah1[4], al1[4];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
-                    cs_rd128<0>(ah0[ks], rd[0][ks] + so);
-                    cs_rd128<AF_PLANE>(al0[ks], rd[0][ks] + so);
-                    cs_rd128<0>(ah1[ks], rd[1][ks] + so);
-                    cs_rd128<AF_PLANE>(al1[ks], rd[1][ks] + so);
+                    gp_lds_rd128<0>(ah0[ks], rd[0][ks] + so);
+                    gp_lds_rd128<AF_PLANE>(al0[ks], rd[0][ks] + so);
+                    gp_lds_rd128<0>(ah1[ks], rd[1][ks] + so);
+                    gp_lds_rd128<AF_PLANE>(al1[ks], rd[1][ks] + so);
                 }
                 cs_wait_a(ah0, al0);
                 cs_wait_a(ah1, al1);
@@ -961,8 +896,7 @@ affinity_cs_kernel(const _Float16 *__restrict__ e_hi, const _Float16 *__restrict
                 const int sl = base + __popc(v & ((1u << kb) - 1u));
                 if (sl < AF_KMAX) wv_ = plist[sl] * rs;
             }
-            h[e] = (_Float16)wv_;
-            l[e] = (_Float16)(wv_ - (float)h[e]);
+            gp_split_f16(wv_, h, l, e);
         }
         *reinterpret_cast<f16x8 *>(fh + lane * 8) = h;
         *reinterpret_cast<f16x8 *>(fl + lane * 8) = l;

@@ -144,7 +144,7 @@ pool_tiles_kernel(const float *__restrict__ x, int64_t ld_x, const int64_t *__re
         for (int i = 0; i < WF4; ++i) reinterpret_cast<float4 *>(s_w[wv][buf])[i * 64 + lane] = pw[i];
     };
     const float *xbase = x + c0;
-    // group of 4 union rows: row ids by one broadcast ds_read_b128, then 4*NF4 independent 16-byte loads
+    // group of 4 union rows: row ids by one broadcast 16-byte LDS read, then 4*NF4 independent 16-byte loads
     auto load_group = [&](float4 (&xv)[4][NF4], const int *rbuf, int e) {
         const int4 rr = *reinterpret_cast<const int4 *>(rbuf + e);
         const int rows[4] = {__builtin_amdgcn_readfirstlane(rr.x), __builtin_amdgcn_readfirstlane(rr.y),
@@ -298,7 +298,6 @@ size_t scan64_tmp(int64_t n) {
 
 }  // namespace
 
-extern int g_gp_knobs[16];
 #define g_pool_nf4 g_gp_knobs[1]
 #define g_pool_unroll g_gp_knobs[2]
 

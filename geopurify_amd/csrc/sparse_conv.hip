@@ -11,6 +11,7 @@
 // are added into the fp32 tile accumulator in LDS at their output rows (waves own disjoint
 // columns: no atomics, no barrier).  Epilogue fuses BatchNorm(eval) scale/shift, residual and ReLU.
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
 namespace {
 
@@ -19,8 +20,6 @@ constexpr int NTHREADS = 512, NWAVES = 8;
 constexpr int MAXG = BM / 16;          // pair groups per offset
 constexpr int PITCH = BM + 16;         // LDS row pitch (floats) for A (k-major) and B: == 16 mod 32 banks
 constexpr int KV_MAX = 27;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvSmem {
     float acc[BM][BN];                 // 64 KiB tile accumulator

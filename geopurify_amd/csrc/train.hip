@@ -9,6 +9,7 @@
 // All of them are HBM-bound row/column sweeps; the convolutions (forward, dgrad = the same kernel with mirrored,
 // transposed weights) stay in sparse_conv_v2.hip.
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
 namespace {
 
@@ -163,7 +164,6 @@ bn_apply_kernel(const float *__restrict__ y, int64_t ld, int64_t nv, int c, cons
                 const float *__restrict__ var, const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
                 const float *__restrict__ residual, int64_t ld_res, int relu, float *__restrict__ out, int64_t ld_out,
                 _Float16 *__restrict__ out_hi, _Float16 *__restrict__ out_lo, int64_t ld_sp) {
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     const int cw = c / W;
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
     const int col = (int)(t % cw) * W;
@@ -193,14 +193,11 @@ bn_apply_kernel(const float *__restrict__ y, int64_t ld, int64_t nv, int c, cons
         if (out_hi) {
             if (W == 4) {
                 f16x4 h, l;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { h[k] = (_Float16)v[k]; l[k] = (_Float16)(v[k] - (float)h[k]); }
+                gp_split_f16<4>(v, h, l);
                 *reinterpret_cast<f16x4 *>(out_hi + r * ld_sp + col) = h;
                 *reinterpret_cast<f16x4 *>(out_lo + r * ld_sp + col) = l;
             } else {
-                const _Float16 h = (_Float16)v[0];
-                out_hi[r * ld_sp + col] = h;
-                out_lo[r * ld_sp + col] = (_Float16)(v[0] - (float)h);
+                gp_split_f16(v[0], out_hi, out_lo, r * ld_sp + col);
             }
         }
     }
@@ -368,7 +365,6 @@ bn_bwd_apply_split_kernel(const float *__restrict__ dout, int64_t ld_d, const fl
                           float eps, const float *__restrict__ gamma, const float *__restrict__ beta_m, const float *__restrict__ sums, int64_t n_total,
                           int64_t nv, int c, const float *__restrict__ scale2, _Float16 *__restrict__ dy_hi, _Float16 *__restrict__ dy_lo, int64_t ld_h,
                           float *__restrict__ dz_out, int64_t ld_dz) {
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     constexpr int W = 4;
     const int cw = c / W;
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
@@ -398,8 +394,7 @@ bn_bwd_apply_split_kernel(const float *__restrict__ dout, int64_t ld_d, const fl
             else if (beta_m) { if (!((yv[k] - mu[k]) * is[k] * ga[k] + be[k] > 0.f)) dz[k] = 0.f; }
             const float xhat = (yv[k] - mu[k]) * is[k];
             const float o = ga[k] * is[k] * (dz[k] - s1[k] - xhat * s2[k]) * sc;
-            h[k] = (_Float16)o;
-            l[k] = (_Float16)(o - (float)h[k]);
+            gp_split_f16(o, h, l, k);
         }
         *reinterpret_cast<f16x4 *>(dy_hi + r * ld_h + col) = h;
         *reinterpret_cast<f16x4 *>(dy_lo + r * ld_h + col) = l;
@@ -934,7 +929,6 @@ sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n, const in
 __global__ void __launch_bounds__(256)
 normalize_split_kernel(const float *__restrict__ x, int64_t ld_x, int d, int64_t n, int64_t n_pad, float eps, _Float16 *__restrict__ hi,
                        _Float16 *__restrict__ lo, int64_t ld_h) {
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     const int lane = gp_lane();
     for (int64_t r = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; r < n_pad; r += ((int64_t)gridDim.x * blockDim.x) >> 6) {
         float inv = 0.f;
@@ -953,12 +947,17 @@ normalize_split_kernel(const float *__restrict__ x, int64_t ld_x, int d, int64_t
                 v[0] = a.x / inv; v[1] = a.y / inv; v[2] = a.z / inv; v[3] = a.w / inv;
             }
             f16x4 h, l;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { h[q] = (_Float16)v[q]; l[q] = (_Float16)(v[q] - (float)h[q]); }
+            gp_split_f16<4>(v, h, l);
             *reinterpret_cast<f16x4 *>(hi + r * ld_h + c) = h;
             *reinterpret_cast<f16x4 *>(lo + r * ld_h + c) = l;
         }
     }
+}
+
+// (gp_col_sums_f64: the partial sums reduced in fp64, unscaled)
+__global__ void __launch_bounds__(CF_WAVES * 64) cs_final_f64_kernel(const double *__restrict__ partial, int64_t nchunks, int nq, int c,
+                                                                     double *__restrict__ out) {
+    cs_final_body(partial, nchunks, nq, c, 1.0, out);
 }
 
 }  // namespace
@@ -986,10 +985,6 @@ extern "C" int gp_col_stats(const float *y, int64_t ld, int64_t nv, int32_t c, f
 
 // fp64 column sums for SyncBatchNorm (run/train.py:212-213 converts the student to MinkowskiSyncBatchNorm): the caller
 // all-reduces them over the ranks.  mean == NULL: out[col] = sum_r y[r][col]; else out[col] = sum_r (y[r][col] - mean[col])^2.
-__global__ void __launch_bounds__(CF_WAVES * 64) cs_final_f64_kernel(const double *__restrict__ partial, int64_t nchunks, int nq, int c,
-                                                                     double *__restrict__ out) {
-    cs_final_body(partial, nchunks, nq, c, 1.0, out);
-}
 extern "C" int gp_col_sums_f64(const float *y, int64_t ld, int64_t nv, int32_t c, const float *mean, double *out, void *workspace,
                                size_t workspace_bytes, void *stream_) {
     GP_CHECK_ARG(y && out && workspace && nv > 0 && c > 0, "gp_col_sums_f64: null/empty argument");

@@ -1,7 +1,7 @@
 // weight gradient of the submanifold 3x3x3 convolution on the matrix cores.
 //   dW[k][ci][co] = sum over the pairs p of offset k of  X[in_p][ci] * dY[out_p][co]
 // A GEMM whose reduction dimension is the pair list: both operands are GATHERED ROWS (ci / co contiguous), i.e. both
-// are K-major for the MFMA, so both fragments come out of row-major LDS images through ds_read_b64_tr_b16.
+// are K-major for the MFMA, so both fragments come out of row-major LDS images through gp_lds_tr16.
 // One 512-thread workgroup owns a 256 x 256 tile of dW[k] and a segment of the pair list of offset k; per step it
 // stages 32 pairs (32 rows x 256 columns x {hi, lo} of X and of dY = 64 KiB) by LDS-DMA into a two-stage ring while
 // the 8 waves (4 x 2, 64 x 128 outputs each) run hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 (96 MFMAs per
@@ -11,12 +11,9 @@
 // transposed reads), inline-asm LDS reads with explicit lgkmcnt waits (compiler-visible reads would wait for the
 // DMA in flight), `s_waitcnt vmcnt(0); s_barrier` hand-over.
 #include "gp_common.h"
+#include "gp_gfx950.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((vector_size(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WG_T = 256;                      // tile edge (rows of dW = ci, columns = co)
 constexpr int WG_KS = 32;                      // pairs per step
@@ -25,20 +22,12 @@ constexpr int WG_PLANE = WG_KS * WG_RB;        // 16 KiB
 constexpr int WG_STAGE = 4 * WG_PLANE;         // X_hi | X_lo | Y_hi | Y_lo
 constexpr size_t WG_SMEM = 2 * (size_t)WG_STAGE;
 
-__device__ __forceinline__ void wg_glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)l, 16, 0, 0);
-}
-template <int OFF>
-__device__ __forceinline__ void wg_tr(s16x4 &d, uint32_t addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
 // fragment = 2 transposed reads (k rows 8g+q and 8g+q+4 -> 2048 bytes apart)
 struct WgFrag { s16x4 a, b; };
 template <int OFF>
 __device__ __forceinline__ void wg_read(WgFrag &f, uint32_t addr) {
-    wg_tr<OFF>(f.a, addr);
-    wg_tr<OFF + 4 * WG_RB>(f.b, addr);
+    gp_lds_tr16<OFF>(f.a, addr);
+    gp_lds_tr16<OFF + 4 * WG_RB>(f.b, addr);
 }
 template <int N>
 __device__ __forceinline__ void wg_wait4(WgFrag &f0, WgFrag &f1, WgFrag &f2, WgFrag &f3) {
@@ -46,12 +35,7 @@ __device__ __forceinline__ void wg_wait4(WgFrag &f0, WgFrag &f1, WgFrag &f2, WgF
                  : "+v"(f0.a), "+v"(f0.b), "+v"(f1.a), "+v"(f1.b), "+v"(f2.a), "+v"(f2.b), "+v"(f3.a), "+v"(f3.b)
                  : [n] "n"(N));
 }
-__device__ __forceinline__ void wg_handover() { asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ f16x8 wg_cat(const WgFrag &f) {
-    typedef short s16x8 __attribute__((vector_size(16)));
-    s16x8 v = __builtin_shufflevector(f.a, f.b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
+__device__ __forceinline__ f16x8 wg_cat(const WgFrag &f) { return gp_cat(f.a, f.b); }
 
 // segs[s] = {offset k, first step (units of 32 pairs in the padded pair arrays), number of steps, 0}
 __global__ void __launch_bounds__(512, 1)
@@ -90,10 +74,10 @@ wgrad_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_l
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int64_t sx = (int64_t)ix[i] * ld_x + xoff[i], sy = (int64_t)iy[i] * ld_y + yoff[i];
-            wg_glds16(x_hi + sx, dst + i * 2 * WG_RB);
-            wg_glds16(x_lo + sx, dst + WG_PLANE + i * 2 * WG_RB);
-            wg_glds16(y_hi + sy, dst + 2 * WG_PLANE + i * 2 * WG_RB);
-            wg_glds16(y_lo + sy, dst + 3 * WG_PLANE + i * 2 * WG_RB);
+            gp_glds16(x_hi + sx, dst + i * 2 * WG_RB);
+            gp_glds16(x_lo + sx, dst + WG_PLANE + i * 2 * WG_RB);
+            gp_glds16(y_hi + sy, dst + 2 * WG_PLANE + i * 2 * WG_RB);
+            gp_glds16(y_lo + sy, dst + 3 * WG_PLANE + i * 2 * WG_RB);
         }
     };
 
@@ -124,7 +108,7 @@ wgrad_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_l
     load_ids(0, ix, iy);
     issue(ix, iy, 0);
     if (n > 1) load_ids(1, ixn, iyn);
-    wg_handover();
+    gp_handover();
     for (int s0 = 0; s0 < n; s0 += 2) {
 #pragma unroll
         for (int J = 0; J < 2; ++J) {
@@ -174,7 +158,7 @@ wgrad_kernel(const _Float16 *__restrict__ x_hi, const _Float16 *__restrict__ x_l
                 WG_MMA(b1h, b1l, 6)
 #undef WG_READ_B
 #undef WG_MMA
-                wg_handover();
+                gp_handover();
             }
         }
     }

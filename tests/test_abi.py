@@ -1,7 +1,8 @@
-"""The C-ABI library loads on a CPU-only host and exports every symbol include/*.h declares."""
+"""The C-ABI library loads on a CPU-only host and exports every symbol include/*.h declares, and no function besides."""
 import ctypes
 import os
 import re
+import subprocess
 
 from geopurify_amd import _lib
 
@@ -20,6 +21,14 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
+    # ... and nothing else: every strong text symbol of the dynamic table is a declared gp_* name.  A kernel defined outside the
+    # anonymous namespace shows up here as its host stub (_Z..__device_stub__..).  (Weak symbols -- type W / V: rocPRIM's templates and
+    # the stubs of template kernels, vague linkage -- and the data symbols of the HIP runtime's registration are not functions of ours.)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    text = sorted(f[2] for f in (ln.split() for ln in out.splitlines()) if len(f) == 3 and f[1] == "T")
+    assert len(text) >= 30
+    undeclared = [n for n in text if n not in names]
+    assert not undeclared, undeclared
 
 
 def test_binding_table_matches_header():
