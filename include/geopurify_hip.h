@@ -270,7 +270,8 @@ int gp_pool_ell(const float *x, int64_t ld_x, const int32_t *nbr, const float *w
 /* Morton-adjacent rows (r in {4,8,16}); per tile the union of its rows' neighbours and a dense        */
 /* [union, r] weight block.  count: tile_off i64 [ntiles+1] (exclusive scan; last = total entries,     */
 /* read it back to size u_row i32 [total] and u_w f32 [total, r]); fill; apply = one application.       */
-/* apply: d a multiple of 256 (r = 4, 8, 16), or d = 64 with r = 4 or 8 (a tile per wave).               */
+/* apply: d a multiple of 256 (r = 8, 16) or of 512 (r = 4: a wave keeps 512 columns; d = 256 is       */
+/* GP_EINVAL), or d = 64 with r = 4 or 8 (a tile per wave).                                            */
 size_t gp_pool_tiles_workspace_bytes(int64_t nv, int32_t r);
 int gp_pool_tiles_count(const int32_t *nbr, int64_t nv, int32_t k, int32_t r, int64_t *tile_off,
                         void *workspace, size_t workspace_bytes, void *stream);
