@@ -37,6 +37,9 @@ SIGNATURES = {
     "gp_coords_order_batched_workspace_bytes": (c_size_t, [c_int64]),
     "gp_coords_order_batched": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gp_kernel_map_sorted": (c_int32, [_P, c_int64, _P, _P]),
+    "gp_quantize_batched_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_quantize_batched": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_segment_labels": (c_int32, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P]),
     "gp_sparse_conv": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P,
                                  c_int64, c_int32, _P, c_int64, _P]),
     "gp_conv_pairs_workspace_bytes": (c_size_t, [c_int64, c_int32]),

@@ -198,6 +198,75 @@ def kernel_map_sorted(keys_sorted):
     return nm
 
 
+class QuantizedIndex:
+    """Result of quantize_batched, every tensor sliced to the nv voxels found: coordinates i32 [nv,4] in ascending key order,
+    unique_index i64 [nv] (lowest input row of each voxel), inverse i64 [n], the CSR order i64 [n] + seg_start i64 [nv+1] and
+    counts i64 [nv]; bad_batch / bad_axes are the status fields of coords_order_batched (nonzero: the rest is meaningless)."""
+
+    def __init__(self, n, nv, coordinates, unique_index, inverse, order, seg_start, bad_batch, bad_axes):
+        self.n, self.nv, self.coordinates, self.unique_index, self.inverse = n, nv, coordinates, unique_index, inverse
+        self.order, self.seg_start, self.bad_batch, self.bad_axes = order, seg_start, bad_batch, bad_axes
+        self.counts = seg_start[1:] - seg_start[:-1]
+
+
+QUANTIZE_OUTPUTS = {"vox_coords": (torch.int32, lambda n: (n, 4)), "unique_index": (torch.int64, lambda n: (n,)),
+                    "inverse": (torch.int64, lambda n: (n,)), "order": (torch.int64, lambda n: (n,)),
+                    "seg_start": (torch.int64, lambda n: (n + 1,)), "status": (torch.int32, lambda n: (3,))}
+
+
+def quantize_batched(coords_b, buffers=None):
+    """Batched coordinates i32 [n,4] (batch, x, y, z; any row order, duplicate rows allowed) -> QuantizedIndex (gp_quantize_batched).
+    One read-back, of status (the voxel count sizes the slices).  buffers: optional dict of caller-owned contiguous outputs at
+    capacity, by the names and shapes of QUANTIZE_OUTPUTS."""
+    lib = _lib.load()
+    _chk(coords_b, torch.int32, "coords")
+    if coords_b.dim() != 2 or coords_b.shape[1] != 4:
+        raise ValueError(f"quantize_batched: expected [n, 4], got {list(coords_b.shape)}")
+    n = coords_b.shape[0]
+    if not 0 < n < 2 ** 31:
+        raise ValueError(f"quantize_batched: n={n} out of range (1 .. 2^31 - 1)")
+    dev = coords_b.device
+    b = {}
+    for name, (dtype, shape) in QUANTIZE_OUTPUTS.items():
+        t = (buffers or {}).get(name)
+        if t is None:
+            t = torch.empty(shape(n), dtype=dtype, device=dev)
+        elif _chk(t, dtype, name).shape != shape(n) or t.device != dev:
+            raise ValueError(f"quantize_batched: buffer {name} must be {list(shape(n))} on {dev}, got {list(t.shape)} on {t.device}")
+        b[name] = t
+    ws = _ws(lib.gp_quantize_batched_workspace_bytes(n), dev)
+    check(lib.gp_quantize_batched(_ptr(coords_b), n, _ptr(b["vox_coords"]), _ptr(b["unique_index"]), _ptr(b["inverse"]),
+                                  _ptr(b["order"]), _ptr(b["seg_start"]), _ptr(b["status"]), _ptr(ws), ws.numel(), _stream()),
+          "gp_quantize_batched")
+    nv, bad_batch, bad_axes = readback(b["status"])
+    return QuantizedIndex(n, nv, b["vox_coords"][:nv], b["unique_index"][:nv], b["inverse"], b["order"], b["seg_start"][:nv + 1],
+                     bad_batch, bad_axes)
+
+
+SEGMENT_LABEL_RULES = {"first": 0, "differ": 1, "count": 2}
+
+
+def segment_labels(labels, q, ignore_label, rule, out=None):
+    """Per-voxel label i64 [nv] of the points' labels i64 [n] over the CSR of q = quantize_batched(...) (gp_segment_labels).
+    rule "first": the label of the voxel's lowest row; "differ": ignore_label where two labels of the voxel differ; "count":
+    ignore_label where the voxel holds more than one point."""
+    lib = _lib.load()
+    if rule not in SEGMENT_LABEL_RULES:
+        raise ValueError(f"segment_labels: rule={rule!r}, expected one of {sorted(SEGMENT_LABEL_RULES)}")
+    _chk(labels, torch.int64, "labels")
+    if labels.dim() != 1 or labels.shape[0] != q.n:
+        raise ValueError(f"segment_labels: expected labels [{q.n}], got {list(labels.shape)}")
+    if labels.device != q.order.device:
+        raise ValueError(f"segment_labels: labels on {labels.device}, the quantisation on {q.order.device}")
+    if out is None:
+        out = torch.empty(q.nv, dtype=torch.int64, device=labels.device)
+    elif _chk(out, torch.int64, "out").shape != (q.nv,) or out.device != labels.device:
+        raise ValueError(f"segment_labels: expected out [{q.nv}], got {list(out.shape)}")
+    check(lib.gp_segment_labels(_ptr(labels), q.n, _ptr(q.order), _ptr(q.seg_start), _ptr(q.unique_index), q.nv, int(ignore_label),
+                                SEGMENT_LABEL_RULES[rule], _ptr(out), _stream()), "gp_segment_labels")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ rows 8-12
 def scatter_mean_csr(src, d, order, seg_start, nv, out, col0=0, row_map=None):
     lib = _lib.load()

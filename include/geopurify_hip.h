@@ -118,6 +118,24 @@ int gp_kernel_map_build(const void *grid, const int32_t *coords, int64_t nv, int
 size_t gp_coords_order_batched_workspace_bytes(int64_t nv);
 int gp_coords_order_batched(const int32_t *coords, int64_t nv, int32_t *perm, int32_t *rank, uint64_t *keys_sorted,
                             int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+/* Quantisation of a batched point cloud, the step the reference does by hand in front of the student                           */
+/* (models/affinity_module.py:1192-1212: torch.unique(return_inverse) + scatter_mean + ME.SparseTensor; this entry replaces the   */
+/* unique / inverse part and hands the reductions their CSR).  coords int32 [n,4] = batch, x, y, z, any row order, duplicate      */
+/* rows allowed, 16-byte aligned.  Same key and sort as gp_coords_order_batched.  Outputs, all sized at capacity (nv is only      */
+/* known on the device): vox_coords i32 [n,4] the unique rows in ascending key order; unique_index i64 [n] the lowest input row   */
+/* of each voxel; inverse i64 [n] input row -> voxel row; order i64 [n] + seg_start i64 [n+1] the CSR gp_scatter_mean_csr takes   */
+/* (order ascends in input row inside every voxel); status i32 [3] = (nv, rows whose batch index is outside 0..65535, mask of     */
+/* the axes whose extent is 65536 or more).  Rows nv.. of the per-voxel outputs are not written.  A nonzero status[1] or [2]:     */
+/* the outputs are defined and in range but meaningless.  1 <= n < 2^31.  No host sync, no float atomics.                         */
+size_t gp_quantize_batched_workspace_bytes(int64_t n);
+int gp_quantize_batched(const int32_t *coords, int64_t n, int32_t *vox_coords, int64_t *unique_index, int64_t *inverse,
+                        int64_t *order, int64_t *seg_start, int32_t *status, void *workspace, size_t workspace_bytes,
+                        void *stream);
+/* Per-voxel label over the CSR of gp_quantize_batched: labels i64 [n], out i64 [nv].  rule 0 (first): labels[unique_index[v]];   */
+/* 1 (differ): ignore_label when any two labels of the voxel differ, else that label (ME's sparse_quantize(labels=,               */
+/* ignore_label=)); 2 (count): ignore_label when the voxel holds more than one row (dataset/voxelization_utils.py:86-89).         */
+int gp_segment_labels(const int64_t *labels, int64_t n, const int64_t *order, const int64_t *seg_start,
+                      const int64_t *unique_index, int64_t nv, int64_t ignore_label, int32_t rule, int64_t *out, void *stream);
 /* 27-offset map over the sorted keys of gp_coords_order_batched (same layout and offset order as gp_kernel_map_build):        */
 /* nbr_map[k][u] = row of the key of voxel u + o_k in the same batch entry, or -1.  Binary search of the keys.                 */
 int gp_kernel_map_sorted(const uint64_t *keys_sorted, int64_t nv, int32_t *nbr_map, void *stream);
