@@ -441,8 +441,12 @@ __global__ void nce_normalize_kernel(const float *__restrict__ e, int64_t ld, co
 }
 // one wave per anchor: logits over (positive, negatives), cross entropy with target 0, gradient w.r.t. the
 // normalised rows (atomics: a sampled point serves many anchors).  nl = 1 + negatives <= 64.
+// The gradient rows are summed in FP64: a sample that is one anchor's positive and many anchors' negative receives -(1 - p) a / T once
+// and +p a / T many times, terms that cancel (all samples equal: to zero), and fp32 atomics left the rounding of the LARGEST partial
+// sum behind -- 1.07e-6 where the gradient is 0 and the bound 1e-6 (tests/test_gpu_train_edges.py, all_equal_map).  The products
+// g_j * a of two floats are exact in fp64, so what remains is the rounding of g and of the final sum.
 __global__ void nce_anchor_kernel(const float *__restrict__ en, int d, const int64_t *__restrict__ p2b, int64_t na, int nneg,
-                                  float inv_t, float *__restrict__ loss, float *__restrict__ den) {
+                                  float inv_t, float *__restrict__ loss, double *__restrict__ den) {
     int64_t a = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     if (a >= na) return;
     int lane = gp_lane();
@@ -468,16 +472,16 @@ __global__ void nce_anchor_kernel(const float *__restrict__ en, int d, const int
     float l0 = __shfl(logit, 0, 64);
     if (lane == 0) atomicAdd(loss, (mx + logf(den_s) - l0) / (float)na);
     float g = lane < nl ? (p - (lane == 0 ? 1.f : 0.f)) * inv_t / (float)na : 0.f;       // d loss / d (a . e_j)
-    float ga[4] = {0.f, 0.f, 0.f, 0.f};
+    double ga[4] = {0.0, 0.0, 0.0, 0.0};
     for (int j = 0; j < nl; ++j) {
         int64_t ij = __shfl(mine, j, 64);
-        float gj = __shfl(g, j, 64);
+        const double gj = (double)__shfl(g, j, 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             int k = lane + 64 * t;
             if (k < d) {
-                ga[t] += gj * en[ij * d + k];
-                atomicAdd(&den[ij * d + k], gj * av[t]);
+                ga[t] += gj * (double)en[ij * d + k];
+                atomicAdd(&den[ij * d + k], gj * (double)av[t]);
             }
         }
     }
@@ -485,7 +489,7 @@ __global__ void nce_anchor_kernel(const float *__restrict__ en, int d, const int
     for (int t = 0; t < 4; ++t) { int k = lane + 64 * t; if (k < d) atomicAdd(&den[ia * d + k], ga[t]); }
 }
 // normalize backward, then add into the voxel row: dE[s2v[s]] += (dEn - En (En . dEn)) / norm
-__global__ void nce_scatter_kernel(const float *__restrict__ en, const float *__restrict__ den, const float *__restrict__ norm,
+__global__ void nce_scatter_kernel(const float *__restrict__ en, const double *__restrict__ den, const float *__restrict__ norm,
                                    const int64_t *__restrict__ s2v, int64_t ns, int d, float *__restrict__ de, int64_t ld) {
     int64_t s = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     if (s >= ns) return;
@@ -495,7 +499,7 @@ __global__ void nce_scatter_kernel(const float *__restrict__ en, const float *__
     for (int t = 0; t < 4; ++t) {
         int k = lane + 64 * t;
         e[t] = k < d ? en[s * d + k] : 0.f;
-        g[t] = k < d ? den[s * d + k] : 0.f;
+        g[t] = k < d ? (float)den[s * d + k] : 0.f;
         dot += e[t] * g[t];
     }
     dot = gp_wave_sum(dot);
@@ -1103,7 +1107,8 @@ extern "C" int gp_bn_train_backward(const float *dout, int64_t ld_dout, const fl
 }
 
 extern "C" size_t gp_infonce_workspace_bytes(int64_t num_samples, int32_t d) {
-    return gp_align_up((size_t)num_samples * d * sizeof(float), 256) * 2 + gp_align_up((size_t)num_samples * sizeof(float), 256);
+    return gp_align_up((size_t)num_samples * d * sizeof(float), 256) + gp_align_up((size_t)num_samples * d * sizeof(double), 256) +
+           gp_align_up((size_t)num_samples * sizeof(float), 256);
 }
 
 // loss (device scalar, overwritten) and dE [nv, d] (overwritten) of the InfoNCE of affinity_module.py:1219-1233
@@ -1118,9 +1123,9 @@ extern "C" int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int3
     hipStream_t s = gp_stream(stream_);
     GpCarver cv(workspace, workspace_bytes);
     float *en = cv.take<float>(num_samples * d);
-    float *den = cv.take<float>(num_samples * d);
+    double *den = cv.take<double>(num_samples * d);
     float *norm = cv.take<float>(num_samples);
-    GP_CHECK_HIP(hipMemsetAsync(den, 0, (size_t)num_samples * d * sizeof(float), s));
+    GP_CHECK_HIP(hipMemsetAsync(den, 0, (size_t)num_samples * d * sizeof(double), s));
     GP_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), s));
     GP_CHECK_HIP(hipMemset2DAsync(de, (size_t)ld_de * sizeof(float), 0, (size_t)d * sizeof(float), (size_t)nv, s));
     nce_normalize_kernel<<<(unsigned)((num_samples * 64 + 255) / 256), 256, 0, s>>>(e, ld_e, sample_to_voxel, num_samples, d, en, norm);
@@ -1143,8 +1148,9 @@ extern "C" int gp_adamw_step(float *param, const float *grad, float *exp_avg, fl
 }
 
 // out i64 [num_queries, k]: the k nearest OTHER rows of xyz for each query row (faiss IndexFlatL2.search(k+1)[:, 1:]),
-// ordered by (squared distance in fp64 of the fp32 coordinates, row id).  *flag_dev != 0: a query had more than 2048
-// candidates inside its (k+1)-th distance bin (massively duplicated points): result invalid.
+// ordered by (squared distance in fp64 of the fp32 coordinates, row id); column 0 of that order is what is dropped (the query itself
+// unless a coincident point has a lower id).  *flag_dev != 0: a query had more than 2048 candidates inside its (k+1)-th distance bin
+// (massively duplicated points): out is unspecified.  1 <= k <= KP_CAP / 2 - 1 = 1023, k + 1 <= n.
 extern "C" int gp_knn_points_f32(const float *xyz, int64_t n, const int64_t *queries, int64_t num_queries, int32_t k, int64_t *out,
                                  int32_t *flag_dev, void *stream_) {
     GP_CHECK_ARG(xyz && queries && out && flag_dev && n > 0 && num_queries > 0, "gp_knn_points_f32: null/empty argument");

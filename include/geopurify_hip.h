@@ -582,7 +582,9 @@ int gp_bn_bwd_apply(const float *dout, int64_t ld_dout, const float *act, int64_
                     void *stream);
 /* InfoNCE (affinity_module.py:1219-1233) forward + backward: samples s -> voxel rows sample_to_voxel[s]; */
 /* point_to_batch i64 [A*(2+Nn)] = sample ids of (anchors | positives | negatives row-major).           */
-/* loss f32 device scalar; de f32 [nv, d] = d loss / d e (overwritten).                                  */
+/* loss f32 device scalar (overwritten, not accumulated); de f32 [nv, d] = d loss / d e (overwritten;    */
+/* rows no sample points at: 0).  d <= 256, 0 <= num_negatives <= 63.  The gradient rows of the samples  */
+/* are summed in fp64 (a sample may be many anchors' negative: terms that cancel).                        */
 size_t gp_infonce_workspace_bytes(int64_t num_samples, int32_t d);
 int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel,
                        int64_t num_samples, const int64_t *point_to_batch, int64_t num_anchors,
@@ -603,7 +605,12 @@ int gp_conv_wgrad_f16x3(const void *x_hi, const void *x_lo, int64_t ld_x, const 
 int gp_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int64_t step, void *stream);
 /* K nearest other points of each query row (faiss.IndexFlatL2.search(K+1)[:,1:], affinity_module.py:1157-1166), */
-/* order (d^2 in fp64 of the fp32 coordinates, row id); *flag_dev != 0: degenerate duplicates, result invalid.   */
+/* order (d^2 in fp64 of the fp32 coordinates, row id).  What is dropped is column 0 of that order, the lowest    */
+/* (d^2, id) entry -- the query row itself unless a coincident point has a lower id: then THAT point is dropped   */
+/* and the query's own row stays in its list.  1 <= k <= 1023, k + 1 <= n < 2^31 (otherwise GP_EINVAL, nothing is */
+/* launched); queries may repeat.  *flag_dev is cleared by every call; != 0 afterwards: some query has more than  */
+/* 2048 points inside the distance bin of its (k+1)-th neighbour (massively duplicated points) -- the contents of */
+/* out, all rows, are then unspecified.                                                                            */
 int gp_knn_points_f32(const float *xyz, int64_t n, const int64_t *queries, int64_t num_queries, int32_t k,
                       int64_t *out, int32_t *flag_dev, void *stream);
 /* The sampler's selections on the anchors x points similarity (sample_contrastive_pairs_hybrid, affinity_module.py:1116-1124):    */

@@ -17,7 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from extent_fence import INT_VIEW, POISON, assert_intact, fence_in, fenced, unwritten
+from extent_fence import INT_VIEW, POISON, Arena, assert_intact, bits, fence_in, fenced, run, unwritten
 from oracle import affinity as o_aff
 from oracle import metric as o_metric
 from oracle import student as o_student
@@ -58,68 +58,6 @@ def S():
 def up(a, dtype=None):
     t = torch.as_tensor(np.ascontiguousarray(a)) if not torch.is_tensor(a) else a
     return (t.to(dtype) if dtype is not None else t).cuda().contiguous()
-
-
-# ------------------------------------------------------------------------------------------ the two runs of a case
-class Arena:
-    """Hands a case its arrays: plain ones (contiguous, exactly sized; outputs start as the poison too, so what a kernel leaves
-    unwritten compares equal) or fenced ones.  pitch=None: an array the ABI takes without a leading dimension -- one flat fence
-    around all of it."""
-
-    def __init__(self, fence):
-        self.fence, self.fences = fence, []
-
-    def _keep(self, v, name):
-        v.fence.name = name or f"#{len(self.fences)}"
-        self.fences.append(v.fence)
-
-    def inp(self, t, pitch=None, name=None):
-        t = t.cuda()
-        if not self.fence:
-            return t.contiguous().clone()
-        if pitch is None or t.dim() == 1:
-            v = fence_in(t.contiguous().reshape(-1))
-            self._keep(v, name)
-            return v.view(t.shape)
-        v = fence_in(t, pitch)
-        self._keep(v, name)
-        return v
-
-    def out(self, shape, dtype, pitch=None, name=None):
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        if not self.fence:
-            return torch.full(shape, POISON["out"][dtype], dtype=INT_VIEW[dtype], device="cuda").view(dtype)
-        if pitch is None or len(shape) == 1:
-            v = fenced(int(np.prod(shape)), None, dtype, device="cuda")
-            self._keep(v, name)
-            return v.view(shape)
-        v = fenced(shape[0], shape[1], dtype, pitch=pitch, device="cuda")
-        self._keep(v, name)
-        return v
-
-
-def bits(t):
-    return t.contiguous().view(INT_VIEW[t.dtype])
-
-
-def run(case):
-    """case(arena) -> {name: output tensor}.  Runs it plain and fenced; the fences must be intact and the outputs the same bits.
-    Returns the plain run's outputs."""
-    got = []
-    for fence in (False, True):
-        a = Arena(fence)
-        outs = case(a)
-        torch.cuda.synchronize()
-        assert_intact(*a.fences)
-        got.append({k: v.clone() for k, v in outs.items()})
-    for k in got[0]:
-        x, y = bits(got[0][k]), bits(got[1][k])
-        assert x.shape == y.shape, k
-        if not torch.equal(x, y):
-            at = (x != y).nonzero()[0].tolist()
-            raise AssertionError(f"{k}: the fenced call differs from the plain call, first at {at}: {got[1][k][tuple(at)].item()} "
-                                 f"instead of {got[0][k][tuple(at)].item()} ({int((x != y).sum())} elements)")
-    return got[0]
 
 
 def whole(t, what):
