@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GP_LIB") or os.path.join(_HERE, "libgeopurify_hip.so")      # (GP_LIB: another build of the library, for same-box A/B runs)
 
 _P = c_void_p  # every device pointer travels as void*
+GP_KNN_MAX_K = 127  # include/geopurify_hip.h: K+1 <= 128
 
 # name -> (restype, [argtypes])  -- mirrors include/geopurify_hip.h one to one
 SIGNATURES = {
@@ -61,6 +62,8 @@ SIGNATURES = {
     "gp_embed_head_f16x3": (c_int32, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_int32, c_float, c_int32, _P, c_int64, _P, _P, c_float, _P, _P]),
     "gp_knn_workspace_bytes": (c_size_t, [c_int64]),
     "gp_knn_lattice": (c_int32, [_P, _P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "gp_knn_batched_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_knn_batched": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
     "gp_affinity_softmax": (c_int32, [_P, c_int64, c_int32, _P, c_int32, c_int64, c_float, _P, _P]),
     "gp_affinity_softmax_scatter": (c_int32, [_P, c_int64, c_int32, _P, c_int32, c_int64, c_float, _P, _P, _P, _P, _P]),
     "gp_pool_ell": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int64, c_int32, _P, c_int64, _P]),

@@ -13,17 +13,6 @@ namespace {
 
 constexpr uint64_t kMorton48 = (1ull << 48) - 1;
 
-// inverse of gp_morton3 for one axis: the bits at 3i (i < 21) of m, packed
-__device__ __forceinline__ uint32_t compact3(uint64_t m) {
-    m &= 0x1249249249249249ull;
-    m = (m ^ (m >> 2)) & 0x10c30c30c30c30c3ull;
-    m = (m ^ (m >> 4)) & 0x100f00f00f00f00full;
-    m = (m ^ (m >> 8)) & 0x1f0000ff0000ffull;
-    m = (m ^ (m >> 16)) & 0x1f00000000ffffull;
-    m = (m ^ (m >> 32)) & 0x1fffffull;
-    return (uint32_t)m;
-}
-
 __global__ void init_kernel(int32_t *__restrict__ mm, int32_t *__restrict__ status) {
     if (threadIdx.x < 3) mm[threadIdx.x] = INT32_MAX;
     else if (threadIdx.x < 6) mm[threadIdx.x] = INT32_MIN;
@@ -106,9 +95,9 @@ __global__ void kernel_map_sorted_kernel(const uint64_t *__restrict__ keys, int6
     if (k != 13) {
         const uint64_t key = keys[i];
         const uint64_t m = key & kMorton48;
-        const int x = (int)compact3(m) + (k % 3) - 1;
-        const int y = (int)compact3(m >> 1) + (k / 3 % 3) - 1;
-        const int z = (int)compact3(m >> 2) + (k / 9) - 1;
+        const int x = (int)gp_compact3(m) + (k % 3) - 1;
+        const int y = (int)gp_compact3(m >> 1) + (k / 3 % 3) - 1;
+        const int z = (int)gp_compact3(m >> 2) + (k / 9) - 1;
         r = -1;
         if ((uint32_t)x <= 65535u && (uint32_t)y <= 65535u && (uint32_t)z <= 65535u) {
             const uint64_t q = (key & ~kMorton48) | gp_morton3((uint32_t)x, (uint32_t)y, (uint32_t)z);

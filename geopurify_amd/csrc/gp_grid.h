@@ -40,6 +40,16 @@ __host__ __device__ __forceinline__ uint64_t gp_morton3(uint32_t x, uint32_t y, 
     uint64_t hi = gp_spread3_10(x >> 20) | (gp_spread3_10(y >> 20) << 1) | (gp_spread3_10(z >> 20) << 2);
     return lo | (mid << 30) | (hi << 60);
 }
+// inverse of gp_morton3 for one axis: the bits at 3i (i < 21) of m, packed (y: m >> 1, z: m >> 2)
+__host__ __device__ __forceinline__ uint32_t gp_compact3(uint64_t m) {
+    m &= 0x1249249249249249ull;
+    m = (m ^ (m >> 2)) & 0x10c30c30c30c30c3ull;
+    m = (m ^ (m >> 4)) & 0x100f00f00f00f00full;
+    m = (m ^ (m >> 8)) & 0x1f0000ff0000ffull;
+    m = (m ^ (m >> 16)) & 0x1f00000000ffffull;
+    m = (m ^ (m >> 32)) & 0x1fffffull;
+    return (uint32_t)m;
+}
 __device__ __forceinline__ uint32_t gp_local9(int x, int y, int z) {
     return (uint32_t)gp_morton3(x & 7, y & 7, z & 7);
 }

@@ -628,6 +628,33 @@ def knn_lattice(grid, coords_sorted, ids, k):
     return nbr
 
 
+def knn_batched(keys_sorted, ids, k, nbr=None, status=None, workspace=None):
+    """Exact kNN inside every batch entry (gp_knn_batched): keys_sorted (u64 held in an i64 [nv]) and ids = perm (i32 [nv]) as
+    coords_order_batched returns them -> (nbr i32 [nv,k] of SORTED-row numbers in (d^2, id) order, status i32 [4] = (queries whose
+    entry holds k or fewer voxels -- their rows are -1 --, the lowest such batch index or -1, its voxel count, mask of the axes with a
+    decoded coordinate of 32768 or more: lists undefined)), both on the device, no sync.  nbr / status / workspace: optional
+    caller-owned contiguous buffers (the workspace uint8 of at least gp_knn_batched_workspace_bytes(nv))."""
+    lib = _lib.load()
+    _chk(keys_sorted, torch.int64, "keys")
+    _chk(ids, torch.int32, "ids")
+    nv, k = keys_sorted.shape[0], int(k)
+    if keys_sorted.dim() != 1 or ids.shape != (nv,):
+        raise ValueError(f"knn_batched: expected keys [nv] and ids [nv], got {list(keys_sorted.shape)} and {list(ids.shape)}")
+    dev = keys_sorted.device
+    if nbr is None:
+        nbr = torch.empty((nv, max(k, 0)), dtype=torch.int32, device=dev)
+    elif _chk(nbr, torch.int32, "nbr").shape != (nv, k):
+        raise ValueError(f"knn_batched: expected nbr [{nv}, {k}], got {list(nbr.shape)}")
+    if status is None:
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+    elif _chk(status, torch.int32, "status").shape != (4,):
+        raise ValueError(f"knn_batched: expected status [4], got {list(status.shape)}")
+    ws = _ws(lib.gp_knn_batched_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_knn_batched(_ptr(keys_sorted), _ptr(ids), nv, k, _ptr(nbr), _ptr(status), _ptr(ws), ws.numel(), _stream()),
+          "gp_knn_batched")
+    return nbr, status
+
+
 def affinity_softmax(e, nbr, sharpen=20.0, d=None, into=None):
     """into: a PoolCs whose structure is built (pool_cs_plan(structure=True)): the weights also go straight into its fragment
     arrays -- the operator is complete when this returns (no pool_cs_fill)."""

@@ -1,18 +1,27 @@
-"""Quantisation of batched point clouds on the device: points in, unique voxels and an inverse map out, with autograd back to the
-points.  The step the reference writes by hand in front of the student (models/affinity_module.py:1192-1212: torch.unique(...,
+"""Batched point clouds on the device, the second way into the library beside the reference's 20-tuple: quantisation (points in,
+unique voxels and an inverse map out, with autograd back to the points), per-entry exact kNN, and the purifying step itself over
+ME-style SparseTensors.
+
+Quantisation is the step the reference writes by hand in front of the student (models/affinity_module.py:1192-1212: torch.unique(...,
 return_inverse=True) + torch_scatter.scatter_mean + ME.SparseTensor(features, batched_coordinates), then
-s_output.F[sample_to_voxel_map]) and every MinkowskiEngine user gets from SparseTensor(quantization_mode=...).
+s_output.F[sample_to_voxel_map]) and every MinkowskiEngine user gets from SparseTensor(quantization_mode=...).  The purifying step is
+evaluate_scene's (:1547-1587): exact kNN, sharpened cosine affinity, 19 applications of the operator -- here for every batch entry at
+once, entries never mixing.  The full chain, per-point features of several scenes in, purified per-point features out:
 
     q = quantize(coordinates, features, mode="average")         # coordinates [N,4] = batch, x, y, z; duplicates allowed
-    y = student(SparseTensor(features=q.features, coordinates=q.coordinates))
+    x = SparseTensor(features=q.features, coordinates=q.coordinates)
+    y = affinity_pool(x, student(x))                            # or purify(student, x, feature_dim=D): the two calls in one
     per_point = y.F[q.inverse_mapping]
 
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
+The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
+pooling families of HotPath, applied in the key order.
 """
 import torch
 
 from . import ops
+from ._lib import GP_KNN_MAX_K
 
 MODES = ("average", "subsample")
 COLLISIONS = ("differ", "count", "first")
@@ -161,3 +170,165 @@ def quantize(coordinates, features=None, labels=None, *, mode="average", quantiz
         if L is not None:
             labs = ops.segment_labels(L.to(torch.int64).contiguous(), q, ignore_label, collision)
     return Quantized(q.coordinates, feats, labs, q.inverse, q.unique_index, q.counts)
+
+
+# ------------------------------------------------------------------------------------------ per-entry kNN, affinity, pooling
+def _check_coordinates(who, C):
+    if not torch.is_tensor(C) or C.dim() != 2 or C.shape[1] != 4:
+        raise ValueError(f"{who}: coordinates must be [N, 4] (batch, x, y, z), got "
+                         f"{list(C.shape) if torch.is_tensor(C) else type(C).__name__}")
+    if C.dtype.is_floating_point or C.dtype.is_complex or C.dtype == torch.bool:
+        raise ValueError(f"{who}: coordinates must be integers, got {C.dtype}")
+    if not C.is_cuda:
+        raise ValueError(f"{who}: coordinates must be a CUDA tensor (got {C.device}); there is no CPU path")
+    if C.shape[0] == 0:
+        raise ValueError(f"{who}: empty coordinate set")
+
+
+def _check_k(who, k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= GP_KNN_MAX_K:
+        raise ValueError(f"{who}: K={k!r} outside 1..{GP_KNN_MAX_K}")
+
+
+def _ordered_knn(who, C, k, same_as=None):
+    """The checked coordinates C in the sorted order of ops.coords_order_batched -> (perm, rank i32 [N], nbr i32 [N,k] of sorted-row
+    numbers).  Every refusal is raised from ONE status read-back (before it: the int32 range read-back of coordinates that are not
+    int32 already).  same_as: a second coordinate tensor of C's shape that must equal C."""
+    with torch.cuda.device(C.device):
+        C = C.detach()
+        if C.dtype != torch.int32:
+            # (range-checked before the cast: an int64 coordinate beyond int32 must not wrap into a valid one)
+            lo, hi = ops.readback(torch.stack(torch.aminmax(C)).to(torch.int64))
+            if lo < -2 ** 31 or hi >= 2 ** 31:
+                raise ValueError(f"{who}: coordinates outside the int32 range ({lo} .. {hi})")
+            C = C.to(torch.int32)
+        C = C.contiguous()
+        perm, rank, keys, order_status = ops.coords_order_batched(C)
+        nbr, knn_status = ops.knn_batched(keys, perm, k)
+        xyz = C[:, 1:]
+        extent = (xyz.amax(0).to(torch.int64) - xyz.amin(0).to(torch.int64) + 1)
+        differ = (same_as.to(torch.int64) != C.to(torch.int64)).sum() if same_as is not None else torch.zeros((), dtype=torch.int64, device=C.device)
+        st = ops.readback(torch.cat([order_status.to(torch.int64), knn_status.to(torch.int64), extent, differ.reshape(1)]))
+    dups, bad_batch, bad_axes, short_rows, short_batch, short_count, axes15 = st[:7]
+    extent, differ = st[7:10], st[10]
+    if differ:
+        raise ValueError(f"{who}: the embeddings' coordinates differ from x.C in {differ} elements (both must be the same rows in the same order)")
+    # (range first: a row whose batch index is out of range has a meaningless key, which may equal another row's)
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index outside 0..65535")
+    if bad_axes:
+        axes = [n for a, n in enumerate("xyz") if bad_axes >> a & 1]
+        raise ValueError(f"{who}: coordinate extent of 65536 or more along {', '.join(axes)} (16 bits per axis)")
+    if dups:
+        raise ValueError(f"{who}: {dups} duplicate coordinate rows (MinkowskiEngine would merge them; quantise first)")
+    wide = [n for a, n in enumerate("xyz") if extent[a] >= 32768 or axes15 >> a & 1]
+    if wide:
+        raise ValueError(f"{who}: coordinate extent of 32768 or more along {', '.join(wide)} ({'/'.join(str(e) for e in extent)} voxels; "
+                         "squared distances must stay below 2^32)")
+    if short_rows:
+        raise ValueError(f"{who}: batch entry {short_batch} holds {short_count} voxels, K={k} neighbours need more than K "
+                         f"({short_rows} rows are in such entries)")
+    return perm, rank, nbr
+
+
+def knn(coordinates, k):
+    """Exact k nearest voxels inside each batch entry.  coordinates: integer [N,4] = batch, x, y, z on the GPU, any row order, unique
+    rows.  -> int64 [N,k] of INPUT row numbers in the input's row order: row i lists the k nearest rows of i's entry in (d^2, row)
+    order, itself dropped (the rule of ops.knn_lattice and the oracle; rows of other entries never appear, also where entries overlap).
+    ValueError for duplicate rows, a batch index outside 0..65535, an axis extent of 32768 or more (over all entries), an entry of k or
+    fewer voxels, k outside 1..127.  One status read-back (and a range read-back before it unless the coordinates are int32)."""
+    _check_k("knn", k)
+    _check_coordinates("knn", coordinates)
+    perm, rank, nbr = _ordered_knn("knn", coordinates, k)
+    with torch.cuda.device(coordinates.device):
+        # sorted rows -> input rows, then the lists into the input's row order
+        return perm.long()[nbr.long()].index_select(0, rank.long())
+
+
+_MODE_OF_FAMILY = {"cs": "mfma_cs", "chain": "mfma_chain", "mfma": "mfma", "mfma_persist": "mfma_persist", "tiles": "tiles", "ell": "ell"}
+
+
+def pool_family(D, K, num_iters, pool_mode="auto"):
+    """The pooling kernel family affinity_pool runs at width D: pipeline.resolve_pool_mode's choice at D padded to a multiple of 4, with
+    HotPath's default tile and block heights -- the column-sliced matrix-core kernels at 256 / 512 / 768 columns, the fp32 tiles at
+    multiples of 512 they do not take -- and the ELL kernel for every other width (the 64-wide tile kernel is config P's own)."""
+    from .pipeline import resolve_pool_mode
+    Dp = (D + 3) // 4 * 4
+    family = resolve_pool_mode(pool_mode, Dp, K, num_iters, 8, 64)
+    return "ell" if family == "tiles" and Dp % 512 else family
+
+
+def affinity_pool(x, embeddings, *, K=96, sharpen=20.0, num_iters=19, normalize=True, pool_mode="auto"):
+    """The purifying step of evaluate_scene (models/affinity_module.py:1547-1587) over a batched SparseTensor, every batch entry by
+    itself.  x: an ME-style SparseTensor (.F [N,D] floating, .C integer [N,4] = batch, x, y, z in any row order, unique rows);
+    embeddings: a SparseTensor with the same .C (the student's output) or a tensor [N,d].  Per entry: E = normalize(E) when
+    `normalize`, w = softmax_j(sharpen * <E_i, E_nbr(i,j)>) over the K exact nearest voxels of the entry, then num_iters applications
+    of the row-stochastic operator (num_iters=0 returns the features).  -> type(x)(features=Y, coordinates=x.C), Y fp32 [N,D] in x's
+    row order.
+    Like the reference's @torch.no_grad() evaluate_scene this takes NO gradients: inputs that require grad are detached, Y never
+    requires grad.
+    Inside: the sorted order of ops.coords_order_batched, ops.knn_batched, ops.l2norm_rows_, ops.affinity_softmax and HotPath's pooling
+    (pool_family(D, K, num_iters, pool_mode); the operator is built in the key order).  ValueError, all before any pooling kernel and
+    from one status read-back: see knn; also num_iters < 0, shape / dtype / device mismatches, embeddings whose coordinates differ."""
+    from .pipeline import HotPath
+    who = "affinity_pool"
+    if not (hasattr(x, "F") and hasattr(x, "C")):
+        raise ValueError(f"{who}: x must be a SparseTensor (an object with .F and .C), got {type(x).__name__}")
+    Fe, C = x.F, x.C
+    _check_k(who, K)
+    if isinstance(num_iters, bool) or not isinstance(num_iters, int) or num_iters < 0:
+        raise ValueError(f"{who}: num_iters={num_iters!r} must be an integer >= 0")
+    _check_coordinates(who, C)
+    n = C.shape[0]
+    if not torch.is_tensor(Fe) or Fe.dim() != 2 or Fe.shape[0] != n or Fe.shape[1] < 1:
+        raise ValueError(f"{who}: features must be [N, D] with N = {n} coordinate rows, got "
+                         f"{list(Fe.shape) if torch.is_tensor(Fe) else type(Fe).__name__}")
+    E, CE = (embeddings.F, embeddings.C) if hasattr(embeddings, "F") and hasattr(embeddings, "C") else (embeddings, None)
+    if not torch.is_tensor(E) or E.dim() != 2 or E.shape[0] != n or E.shape[1] < 1:
+        raise ValueError(f"{who}: embeddings must be [N, d] with N = {n} coordinate rows, got "
+                         f"{list(E.shape) if torch.is_tensor(E) else type(E).__name__}")
+    if not (Fe.dtype.is_floating_point and E.dtype.is_floating_point):
+        raise ValueError(f"{who}: features and embeddings must be floating point, got {Fe.dtype} / {E.dtype}")
+    if not (Fe.is_cuda and E.is_cuda) or Fe.device != C.device or E.device != C.device:
+        raise ValueError(f"{who}: features, embeddings and coordinates must be CUDA tensors on one device (got {Fe.device} / {E.device} / "
+                         f"{C.device}); there is no CPU path")
+    if CE is not None and CE is not C:
+        if not torch.is_tensor(CE) or CE.shape != C.shape or CE.device != C.device or CE.dtype.is_floating_point:
+            raise ValueError(f"{who}: the embeddings' coordinates must be x.C ({list(C.shape)} integers on {C.device}), got "
+                             f"{list(CE.shape) if torch.is_tensor(CE) else type(CE).__name__}")
+    else:
+        CE = None
+    D = Fe.shape[1]
+    family = pool_family(D, K, num_iters, pool_mode)                  # (an unknown or inadmissible mode raises here)
+    perm, rank, nbr = _ordered_knn(who, C, K, same_as=CE)
+    with torch.cuda.device(C.device), torch.no_grad():
+        dev = C.device
+        perm64, Dp = perm.long(), (D + 3) // 4 * 4
+        # rows into the key order (ops.gather_rows); the feature columns D .. Dp-1 are zero padding for the row loads of the kernels
+        X = torch.zeros((n, Dp), dtype=torch.float32, device=dev) if Dp != D else torch.empty((n, D), dtype=torch.float32, device=dev)
+        ops.gather_rows(_rows_f32(Fe.detach()), D, perm64, out=X)
+        Es = ops.gather_rows(_rows_f32(E.detach()), E.shape[1], perm64)
+        if normalize:
+            ops.l2norm_rows_(Es)
+        w = ops.affinity_softmax(Es, nbr, float(sharpen))
+        hp = HotPath(None, (1, 1), K=K, sharpen=float(sharpen), num_iters=num_iters, device=dev, pool_mode=_MODE_OF_FAMILY[family])
+        out = hp._pool(X, nbr, w, n, Dp)
+        if hp._chain_ops:
+            hp.pool_chain_check()                                        # (a chained launch, selected by name: never hand out rows of one that gave up)
+        Y = ops.gather_rows(out, D, rank.long())
+    return type(x)(features=Y, coordinates=x.C)
+
+
+def purify(student, x, *, feature_dim=None, **kw):
+    """student(x) in eval mode under no_grad, then affinity_pool on x.F[:, :feature_dim] with the embeddings it gave (the reference pools
+    all columns and slices [:, :512] afterwards; a column never influences another, so the geometry columns are left out before).
+    The student's training flag is restored afterwards.  kw: affinity_pool's options.  -> type(x)(features=Y, coordinates=x.C)."""
+    was = student.training
+    student.eval()
+    try:
+        with torch.no_grad():
+            e = student(x)
+    finally:
+        student.train(was)
+    feats = x.F if feature_dim is None else x.F[:, :int(feature_dim)]
+    return affinity_pool(type(x)(features=feats, coordinates=x.C), e, **kw)

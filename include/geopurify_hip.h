@@ -265,6 +265,20 @@ int gp_rows_renumber_i32(const int32_t *nbr, int64_t nv, int32_t k, const int32_
 size_t gp_knn_workspace_bytes(int64_t nv);
 int gp_knn_lattice(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv,
                    int32_t k, int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream);
+/* Row 10 over batched coordinates: the same rule inside every batch entry.  keys_sorted u64 [nv] are the sorted keys of             */
+/* gp_coords_order_batched (batch << 48 | morton(xyz - min)), ids i32 [nv] the tie-break id of each sorted row (its perm: ties then     */
+/* resolve by the input's row order inside each entry; NULL: the row number).  nbr i32 [nv,K] holds SORTED-ROW numbers: the K+1         */
+/* smallest by (d^2, id) among the rows of the query's own entry, self dropped, in that order; exact for every input.  Rows of          */
+/* different entries never appear in each other's lists, also where two entries occupy the same coordinates.  No coordinate array       */
+/* is read: coordinates are decoded from the keys, 8^3 cells (key >> 9) are found by binary search in a cell table built per call,      */
+/* rings 1 and 3 as gp_knn_lattice, then an exhaustive scan of the query's entry alone.  1 <= K <= GP_KNN_MAX_K, 1 <= nv < 2^31.        */
+/* status i32 [4] (device, written by the call): [0] queries whose entry holds K or fewer voxels -- their nbr rows are filled with -1; */
+/* [1] the lowest such batch index (-1: none); [2] its voxel count; [3] mask of the axes on which a decoded coordinate is 32768 or     */
+/* more: the (d^2 << 32 | id) key needs d^2 < 2^32, so with a nonzero mask the lists are undefined (the call still returns, and         */
+/* stores only row numbers of the query's entry or -1).  No host sync, nothing read or written outside the given extents.              */
+size_t gp_knn_batched_workspace_bytes(int64_t nv);
+int gp_knn_batched(const uint64_t *keys_sorted, const int32_t *ids, int64_t nv, int32_t k, int32_t *nbr, int32_t *status,
+                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Row 11: cosine affinity + sharpened softmax (models/affinity_module.py:1559-1572).             */
