@@ -67,6 +67,14 @@ SIGNATURES = {
     "gp_affinity_softmax": (c_int32, [_P, c_int64, c_int32, _P, c_int32, c_int64, c_float, _P, _P]),
     "gp_affinity_softmax_scatter": (c_int32, [_P, c_int64, c_int32, _P, c_int32, c_int64, c_float, _P, _P, _P, _P, _P]),
     "gp_pool_ell": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int64, c_int32, _P, c_int64, _P]),
+    "gp_pool_transpose_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_pool_transpose_build": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "gp_pool_ell_transpose": (c_int32, [_P, c_int64, _P, _P, _P, c_int32, c_int64, c_int32, _P, c_int64, _P]),
+    "gp_pool_ell_wgrad": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, c_int64, c_int32, _P, c_int32, _P]),
+    "gp_affinity_softmax_backward_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_affinity_softmax_backward": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, c_int32, c_int64, c_float, _P, _P, _P, c_int64, _P,
+                                               c_size_t, _P]),
+    "gp_l2norm_rows_backward": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int64, _P, c_int64, _P]),
     "gp_pool_tiles_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_pool_tiles_count": (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P]),
     "gp_pool_tiles_fill": (c_int32, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),

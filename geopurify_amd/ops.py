@@ -708,6 +708,110 @@ def pool_ell(x, nbr, w, d, out):
     return out
 
 
+# ------------------------------------------------------------------------------------------ the backward of affinity + pooling
+def _flat_nk(t, dtype, nv, k, name):
+    """an [nv, k] array the ABI takes without a leading dimension"""
+    if _chk(t, dtype, name).shape != (nv, k):
+        raise ValueError(f"{name}: expected [{nv}, {k}], got {list(t.shape)}")
+    return t
+
+
+def _rows(t, name, n=None, d=None):
+    """fp32 rows [n, d] with unit column stride (the row stride travels as the leading dimension)"""
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected CUDA fp32 rows with unit column stride, got {t.dtype} {list(t.shape)} strides {t.stride()}")
+    if (n is not None and t.shape[0] != n) or (d is not None and t.shape[1] != d):
+        raise ValueError(f"{name}: expected [{n}, {d}], got {list(t.shape)}")
+    return t
+
+
+def pool_transpose_build(nbr, tr_off=None, tr_slot=None, workspace=None):
+    """The inverted index of the neighbour lists nbr i32 [nv,k] (gp_pool_transpose_build) -> (tr_off i64 [nv+1], tr_slot i32 [nv*k]):
+    tr_slot[tr_off[m]:tr_off[m+1]] = the flat slots i*k+j with nbr[i,j] == m, ascending.  No sync.  tr_off / tr_slot / workspace:
+    optional caller-owned contiguous buffers (the workspace uint8 of at least gp_pool_transpose_workspace_bytes(nv, k))."""
+    lib = _lib.load()
+    _chk(nbr, torch.int32, "nbr")
+    if nbr.dim() != 2:
+        raise ValueError(f"pool_transpose_build: expected nbr [nv, k], got {list(nbr.shape)}")
+    nv, k = nbr.shape
+    dev = nbr.device
+    if tr_off is None:
+        tr_off = torch.empty(nv + 1, dtype=torch.int64, device=dev)
+    elif _chk(tr_off, torch.int64, "tr_off").shape != (nv + 1,):
+        raise ValueError(f"pool_transpose_build: expected tr_off [{nv + 1}], got {list(tr_off.shape)}")
+    if tr_slot is None:
+        tr_slot = torch.empty(nv * k, dtype=torch.int32, device=dev)
+    elif _chk(tr_slot, torch.int32, "tr_slot").shape != (nv * k,):
+        raise ValueError(f"pool_transpose_build: expected tr_slot [{nv * k}], got {list(tr_slot.shape)}")
+    ws = _ws(lib.gp_pool_transpose_workspace_bytes(nv, int(k)), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_pool_transpose_build(_ptr(nbr), nv, int(k), _ptr(tr_off), _ptr(tr_slot), _ptr(ws), ws.numel(), _stream()),
+          "gp_pool_transpose_build")
+    return tr_off, tr_slot
+
+
+def pool_ell_transpose(g, tr_off, tr_slot, w, k, out):
+    """out[m] = sum_p w[slot_p] * g[slot_p // k] over the inverted list of m, in list order (gp_pool_ell_transpose): the transposed
+    application of pool_ell's operator.  g / out fp32 [nv, d] with any row stride that is a multiple of 4; w fp32 [nv, k]."""
+    lib = _lib.load()
+    nv, d = _rows(g, "g").shape
+    _rows(out, "out", nv, d)
+    _chk(tr_off, torch.int64, "tr_off"), _chk(tr_slot, torch.int32, "tr_slot"), _chk(w, torch.float32, "w")
+    if tr_off.shape != (nv + 1,) or tr_slot.numel() != w.numel():
+        raise ValueError(f"pool_ell_transpose: expected tr_off [{nv + 1}] and one slot per weight, got {list(tr_off.shape)} / "
+                         f"{tr_slot.numel()} / {w.numel()}")
+    check(lib.gp_pool_ell_transpose(_ptr(g), g.stride(0), _ptr(tr_off), _ptr(tr_slot), _ptr(w), int(k), nv, int(d), _ptr(out),
+                                    out.stride(0), _stream()), "gp_pool_ell_transpose")
+    return out
+
+
+def pool_ell_wgrad(g, x_prev, nbr, dw, accumulate):
+    """dw[i,j] (+)= <g[i], x_prev[nbr[i,j]]> (gp_pool_ell_wgrad); accumulate=False overwrites.  g / x_prev fp32 [nv, d] with any row
+    stride that is a multiple of 4; dw fp32 [nv, k]."""
+    lib = _lib.load()
+    nv, d = _rows(g, "g").shape
+    _rows(x_prev, "x_prev", nv, d)
+    _chk(nbr, torch.int32, "nbr")
+    k = nbr.shape[1] if nbr.dim() == 2 else -1
+    _flat_nk(nbr, torch.int32, nv, k, "nbr"), _flat_nk(dw, torch.float32, nv, k, "dw")
+    check(lib.gp_pool_ell_wgrad(_ptr(g), g.stride(0), _ptr(x_prev), x_prev.stride(0), _ptr(nbr), int(k), nv, int(d), _ptr(dw),
+                                int(bool(accumulate)), _stream()), "gp_pool_ell_wgrad")
+    return dw
+
+
+def affinity_softmax_backward(e_unit, nbr, w, dw, sharpen, tr_off, tr_slot, out=None, workspace=None):
+    """The backward of affinity_softmax on unit rows (gp_affinity_softmax_backward) -> de_unit fp32 [nv, d]: the gather term over the
+    row's own list, then the transposed term over its inverted list, both in fixed order.  out / workspace: optional caller-owned
+    buffers (out with any row stride that is a multiple of 4; workspace of gp_affinity_softmax_backward_workspace_bytes(nv, k))."""
+    lib = _lib.load()
+    nv, d = _rows(e_unit, "e_unit").shape
+    _chk(nbr, torch.int32, "nbr")
+    k = nbr.shape[1] if nbr.dim() == 2 else -1
+    _flat_nk(nbr, torch.int32, nv, k, "nbr"), _flat_nk(w, torch.float32, nv, k, "w"), _flat_nk(dw, torch.float32, nv, k, "dw")
+    _chk(tr_off, torch.int64, "tr_off"), _chk(tr_slot, torch.int32, "tr_slot")
+    if tr_off.shape != (nv + 1,) or tr_slot.numel() != nv * k:
+        raise ValueError(f"affinity_softmax_backward: expected tr_off [{nv + 1}] and tr_slot [{nv * k}], got {list(tr_off.shape)} / "
+                         f"{list(tr_slot.shape)}")
+    out = torch.empty((nv, d), dtype=torch.float32, device=e_unit.device) if out is None else _rows(out, "out", nv, d)
+    ws = (_ws(lib.gp_affinity_softmax_backward_workspace_bytes(nv, int(k)), e_unit.device) if workspace is None
+          else _chk(workspace, torch.uint8, "workspace"))
+    check(lib.gp_affinity_softmax_backward(_ptr(e_unit), e_unit.stride(0), int(d), _ptr(nbr), _ptr(w), _ptr(dw), int(k), nv, float(sharpen),
+                                           _ptr(tr_off), _ptr(tr_slot), _ptr(out), out.stride(0), _ptr(ws), ws.numel(), _stream()),
+          "gp_affinity_softmax_backward")
+    return out
+
+
+def l2norm_rows_backward(e_raw, de_unit, out=None):
+    """The backward of l2norm_rows_ (gp_l2norm_rows_backward): e_raw the rows before the normalisation, de_unit the gradient of the
+    unit rows -> de_raw fp32 [n, d] (F.normalize's autograd, its 1e-12 clamp included)."""
+    lib = _lib.load()
+    n, d = _rows(e_raw, "e_raw").shape
+    _rows(de_unit, "de_unit", n, d)
+    out = torch.empty((n, d), dtype=torch.float32, device=e_raw.device) if out is None else _rows(out, "out", n, d)
+    check(lib.gp_l2norm_rows_backward(_ptr(e_raw), e_raw.stride(0), _ptr(de_unit), de_unit.stride(0), int(d), n, _ptr(out), out.stride(0),
+                                      _stream()), "gp_l2norm_rows_backward")
+    return out
+
+
 class PoolTiles:
     """Affinity operator re-blocked into tiles of r rows (built once per scene, applied many times)."""
 

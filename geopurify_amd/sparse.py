@@ -13,6 +13,11 @@ once, entries never mixing.  The full chain, per-point features of several scene
     y = affinity_pool(x, student(x))                            # or purify(student, x, feature_dim=D): the two calls in one
     per_point = y.F[q.inverse_mapping]
 
+Every link carries gradients when asked to: affinity_pool(x, student(x), differentiable=True) -- or purify(student, x,
+differentiable=True) -- puts y.F into the autograd graph, so a loss on the purified features reaches the student's parameters, x.F and
+through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
+l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene.
+
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -258,15 +263,83 @@ def pool_family(D, K, num_iters, pool_mode="auto"):
     return "ell" if family == "tiles" and Dp % 512 else family
 
 
-def affinity_pool(x, embeddings, *, K=96, sharpen=20.0, num_iters=19, normalize=True, pool_mode="auto"):
+GRAD_EMBED_WIDTHS = (16, 32, 64, 128)                       # gp_affinity_softmax's
+
+
+class _PoolGrad(torch.autograd.Function):
+    """affinity_pool(differentiable=True) behind the checks: feats [N,D], emb [N,d] in the input's row order -> Y fp32 [N,D].
+    Forward: num_iters single applications of ops.pool_ell into one stack [T, N, Dp] of fp32 rows (X_0 .. X_{T-1}, which the weight
+    gradient reads).  Backward, in the sorted key order, with G_T = dY and for t = T .. 1:
+        dw[i,j] += <G_t[i], X_{t-1}[nbr[i,j]]>                       ops.pool_ell_wgrad
+        G_{t-1}[m] = sum over (i,j) with nbr[i,j] = m of w[i,j] G_t[i]  ops.pool_ell_transpose over ops.pool_transpose_build's index
+    then d feats = G_0, and d emb through ops.affinity_softmax_backward and ops.l2norm_rows_backward.  The lists are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, feats, emb, perm64, rank64, nbr, K, sharpen, num_iters, normalize):
+        dev = feats.device
+        n, D = feats.shape
+        Dp, T = (D + 3) // 4 * 4, num_iters
+        stack = torch.empty((T, n, Dp), dtype=torch.float32, device=dev)
+        if Dp != D:
+            stack[0].zero_()                                             # (the padding columns D .. Dp-1 of X_0; every later X_t is written whole)
+        ops.gather_rows(_rows_f32(feats.detach()), D, perm64, out=stack[0])
+        e_raw = ops.gather_rows(_rows_f32(emb.detach()), emb.shape[1], perm64)
+        e_unit = ops.l2norm_rows_(e_raw.clone()) if normalize else e_raw
+        w = ops.affinity_softmax(e_unit, nbr, sharpen)
+        for t in range(1, T):
+            ops.pool_ell(stack[t - 1], nbr, w, Dp, stack[t])
+        out = torch.empty((n, Dp), dtype=torch.float32, device=dev)
+        ops.pool_ell(stack[T - 1], nbr, w, Dp, out)
+        ctx.save_for_backward(stack, w, nbr, e_raw, e_unit, perm64, rank64)
+        ctx.args = (D, Dp, T, K, sharpen, normalize, feats.dtype, emb.dtype)
+        return ops.gather_rows(out, D, rank64)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_y):
+        stack, w, nbr, e_raw, e_unit, perm64, rank64 = ctx.saved_tensors
+        D, Dp, T, K, sharpen, normalize, f_dtype, e_dtype = ctx.args
+        need_x, need_e = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dev = w.device
+        n = w.shape[0]
+        with torch.cuda.device(dev):
+            g = torch.zeros((n, Dp), dtype=torch.float32, device=dev) if Dp != D else torch.empty((n, D), dtype=torch.float32, device=dev)
+            ops.gather_rows(_rows_f32(d_y), D, perm64, out=g)
+            tr_off, tr_slot = ops.pool_transpose_build(nbr)
+            dw = torch.empty((n, K), dtype=torch.float32, device=dev) if need_e else None
+            spare = torch.empty_like(g) if need_x or (need_e and T > 1) else None
+            for t in range(T, 0, -1):
+                if need_e:
+                    ops.pool_ell_wgrad(g, stack[t - 1], nbr, dw, accumulate=t < T)
+                if need_x or (need_e and t > 1):
+                    ops.pool_ell_transpose(g, tr_off, tr_slot, w, K, spare)
+                    g, spare = spare, g
+            d_feats = ops.gather_rows(g, D, rank64).to(f_dtype) if need_x else None
+            d_emb = None
+            if need_e:
+                de = ops.affinity_softmax_backward(e_unit, nbr, w, dw, sharpen, tr_off, tr_slot)
+                if normalize:
+                    de = ops.l2norm_rows_backward(e_raw, de)
+                d_emb = ops.gather_rows(de, de.shape[1], rank64).to(e_dtype)
+        return d_feats, d_emb, None, None, None, None, None, None, None
+
+
+def affinity_pool(x, embeddings, *, K=96, sharpen=20.0, num_iters=19, normalize=True, pool_mode="auto", differentiable=False):
     """The purifying step of evaluate_scene (models/affinity_module.py:1547-1587) over a batched SparseTensor, every batch entry by
     itself.  x: an ME-style SparseTensor (.F [N,D] floating, .C integer [N,4] = batch, x, y, z in any row order, unique rows);
     embeddings: a SparseTensor with the same .C (the student's output) or a tensor [N,d].  Per entry: E = normalize(E) when
     `normalize`, w = softmax_j(sharpen * <E_i, E_nbr(i,j)>) over the K exact nearest voxels of the entry, then num_iters applications
     of the row-stochastic operator (num_iters=0 returns the features).  -> type(x)(features=Y, coordinates=x.C), Y fp32 [N,D] in x's
     row order.
-    Like the reference's @torch.no_grad() evaluate_scene this takes NO gradients: inputs that require grad are detached, Y never
-    requires grad.
+    Like the reference's @torch.no_grad() evaluate_scene this takes NO gradients by default: inputs that require grad are detached, Y
+    never requires grad.
+    differentiable=True: Y is part of the autograd graph whenever grad mode is on and x.F or the embeddings require grad (otherwise the
+    call is the default one).  Gradients reach x.F and the embeddings (a tensor or a SparseTensor's .F) in their row order and dtype;
+    the neighbour lists are discrete and not differentiated; no double backward.  num_iters=0: Y carries x.F's values with the identity
+    gradient, the embeddings receive none.  The forward then is num_iters single applications of ops.pool_ell that keep X_0 .. X_{T-1}
+    for the weight gradient in one fp32 stack of T * N * Dp * 4 bytes (Dp = D padded to a multiple of 4; 5.2 GB at 134k voxels x 512 x
+    19) -- there is no recompute mode.  The matrix-core families keep no fp32 intermediates: pool_mode other than "auto" / "ell"
+    together with differentiable=True is a ValueError, as is an embedding width outside 16 / 32 / 64 / 128, both before any kernel.
     Inside: the sorted order of ops.coords_order_batched, ops.knn_batched, ops.l2norm_rows_, ops.affinity_softmax and HotPath's pooling
     (pool_family(D, K, num_iters, pool_mode); the operator is built in the key order).  ValueError, all before any pooling kernel and
     from one status read-back: see knn; also num_iters < 0, shape / dtype / device mismatches, embeddings whose coordinates differ."""
@@ -299,8 +372,20 @@ def affinity_pool(x, embeddings, *, K=96, sharpen=20.0, num_iters=19, normalize=
     else:
         CE = None
     D = Fe.shape[1]
+    if differentiable:
+        if pool_mode not in ("auto", "ell"):
+            raise ValueError(f"{who}: pool_mode={pool_mode!r} with differentiable=True: the matrix-core families keep no fp32 intermediates, "
+                             "gradients run on pool_mode='auto' or 'ell'")
+        if E.shape[1] not in GRAD_EMBED_WIDTHS:
+            raise ValueError(f"{who}: differentiable=True takes embeddings of width {' / '.join(map(str, GRAD_EMBED_WIDTHS))}, got {E.shape[1]}")
     family = pool_family(D, K, num_iters, pool_mode)                  # (an unknown or inadmissible mode raises here)
     perm, rank, nbr = _ordered_knn(who, C, K, same_as=CE)
+    if differentiable and torch.is_grad_enabled() and (Fe.requires_grad or E.requires_grad):
+        if num_iters == 0:
+            return type(x)(features=Fe.to(torch.float32) if Fe.dtype != torch.float32 else Fe.clone(), coordinates=x.C)
+        with torch.cuda.device(C.device):
+            Y = _PoolGrad.apply(Fe, E, perm.long(), rank.long(), nbr, K, float(sharpen), num_iters, bool(normalize))
+        return type(x)(features=Y, coordinates=x.C)
     with torch.cuda.device(C.device), torch.no_grad():
         dev = C.device
         perm64, Dp = perm.long(), (D + 3) // 4 * 4
@@ -319,10 +404,15 @@ def affinity_pool(x, embeddings, *, K=96, sharpen=20.0, num_iters=19, normalize=
     return type(x)(features=Y, coordinates=x.C)
 
 
-def purify(student, x, *, feature_dim=None, **kw):
+def purify(student, x, *, feature_dim=None, differentiable=False, **kw):
     """student(x) in eval mode under no_grad, then affinity_pool on x.F[:, :feature_dim] with the embeddings it gave (the reference pools
     all columns and slices [:, :512] afterwards; a column never influences another, so the geometry columns are left out before).
-    The student's training flag is restored afterwards.  kw: affinity_pool's options.  -> type(x)(features=Y, coordinates=x.C)."""
+    The student's training flag is restored afterwards.  kw: affinity_pool's options.  -> type(x)(features=Y, coordinates=x.C).
+    differentiable=True: the student is called as the caller left it -- its mode and the grad state untouched -- and its output feeds
+    affinity_pool(..., differentiable=True): a loss on Y reaches the student's parameters and x.F."""
+    feats = x.F if feature_dim is None else x.F[:, :int(feature_dim)]
+    if differentiable:
+        return affinity_pool(type(x)(features=feats, coordinates=x.C), student(x), differentiable=True, **kw)
     was = student.training
     student.eval()
     try:
@@ -330,5 +420,4 @@ def purify(student, x, *, feature_dim=None, **kw):
             e = student(x)
     finally:
         student.train(was)
-    feats = x.F if feature_dim is None else x.F[:, :int(feature_dim)]
     return affinity_pool(type(x)(features=feats, coordinates=x.C), e, **kw)

@@ -298,6 +298,35 @@ int gp_affinity_softmax_scatter(const float *e, int64_t ld_e, int32_t d, const i
 int gp_pool_ell(const float *x, int64_t ld_x, const int32_t *nbr, const float *w, int32_t k,
                 int64_t nv, int32_t d, float *y, int64_t ld_y, void *stream);
 
+/* The backward of rows 11 + 12 (models/affinity_module.py:1564-1587), for a loss on the pooled features.  No float atomics: every    */
+/* sum runs over a list in a fixed order, the results are bitwise reproducible.  All pitches in floats, multiples of 4 and >= d;      */
+/* fp32 row matrices 16-byte aligned; 1 <= k <= 128; nv * k < 2^31; outputs alias no input.                                           */
+/* The inverted index of the lists (models/affinity_module.py:1564-1587: the transpose of the operator torch.sparse.mm applies):      */
+/* tr_slot[tr_off[m] .. tr_off[m+1]) = the slots i * k + j with nbr[i,j] == m, ascending.  tr_off i64 [nv+1], tr_slot i32 [nv*k]       */
+/* (slots whose id lies outside 0..nv-1 come behind tr_off[nv], in no list).  In-degree count, scan, stable radix sort.               */
+size_t gp_pool_transpose_workspace_bytes(int64_t nv, int32_t k);
+int gp_pool_transpose_build(const int32_t *nbr, int64_t nv, int32_t k, int64_t *tr_off, int32_t *tr_slot, void *workspace,
+                            size_t workspace_bytes, void *stream);
+/* One application of the transposed operator (models/affinity_module.py:1564-1587):                                                  */
+/* out[m,0:d] = sum_p w[slot_p] * g[slot_p / k, 0:d] over the list of m in list order; an empty list writes an exact zero row.        */
+int gp_pool_ell_transpose(const float *g, int64_t ld_g, const int64_t *tr_off, const int32_t *tr_slot, const float *w, int32_t k,
+                          int64_t nv, int32_t d, float *out, int64_t ld_out, void *stream);
+/* The gradient of the weights from one application (models/affinity_module.py:1564-1587): dw[i,j] = <g[i], x_prev[nbr[i,j]]>,        */
+/* added to dw when accumulate != 0.  An id outside 0..nv-1 gives 0.                                                                  */
+int gp_pool_ell_wgrad(const float *g, int64_t ld_g, const float *x_prev, int64_t ld_x, const int32_t *nbr, int32_t k, int64_t nv,
+                      int32_t d, float *dw, int32_t accumulate, void *stream);
+/* The backward of gp_affinity_softmax (models/affinity_module.py:1564-1587) on unit rows e_unit:                                     */
+/* da[i,j] = sharpen * w[i,j] * (dw[i,j] - sum_k w[i,k] dw[i,k]);                                                                      */
+/* de_unit[i] = sum_j da[i,j] e_unit[nbr[i,j]] + sum over the inverted list of i of da[slot] e_unit[slot / k], in that order.          */
+size_t gp_affinity_softmax_backward_workspace_bytes(int64_t nv, int32_t k);
+int gp_affinity_softmax_backward(const float *e_unit, int64_t ld_e, int32_t d, const int32_t *nbr, const float *w, const float *dw,
+                                 int32_t k, int64_t nv, float sharpen, const int64_t *tr_off, const int32_t *tr_slot, float *de_unit,
+                                 int64_t ld_de, void *workspace, size_t workspace_bytes, void *stream);
+/* The backward of gp_l2norm_rows (F.normalize's, models/affinity_module.py:1564-1587): with u = e / |e|,                              */
+/* de_raw = (de_unit - u <u, de_unit>) / |e|, and de_unit / 1e-12 where |e| < 1e-12.                                                   */
+int gp_l2norm_rows_backward(const float *e_raw, int64_t ld_e, const float *de_unit, int64_t ld_du, int32_t d, int64_t n,
+                            float *de_raw, int64_t ld_de, void *stream);
+
 /* Fast path of the same operator, re-blocked once per scene for the 19 applications: tiles of r     */
 /* Morton-adjacent rows (r in {4,8,16}); per tile the union of its rows' neighbours and a dense        */
 /* [union, r] weight block.  count: tile_off i64 [ntiles+1] (exclusive scan; last = total entries,     */
