@@ -147,6 +147,9 @@ SIGNATURES = {
     "gp_sampler_select": (c_int32, [_P, c_int64, c_int64, c_int64, _P, c_int32, _P, _P, _P]),
     "gp_normalize_split_f16": (c_int32, [_P, c_int64, c_int32, c_int64, c_int64, c_float, _P, _P, c_int64, _P]),
     "gp_iou_hist_i64": (c_int32, [_P, _P, c_int64, c_int32, POINTER(c_int64), c_int32, _P, _P]),
+    "gp_nn1_batched_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_nn1_batched": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "gp_iou_hist_batched_i64": (c_int32, [_P, _P, c_int64, _P, _P, c_int64, c_int32, c_int32, POINTER(c_int64), c_int32, _P, _P]),
     "gp_fused_decode_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gp_fused_decode": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
 }

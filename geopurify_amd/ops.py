@@ -1271,6 +1271,60 @@ def iou_hist(pred, target, num_classes, ignore_ids, counts):
     return counts
 
 
+def nn1_batched(keys_sorted, ids, ref_mask, query_mask, axes=7, nn=None, status=None, workspace=None):
+    """Masked exact 1-NN inside every batch entry (gp_nn1_batched): keys_sorted (u64 held in an i64 [nv]) and ids = perm (i32 [nv], or
+    None: the row number) as coords_order_batched returns them, ref_mask / query_mask u8 [nv] in SORTED-row order, axes the mask of
+    the axes that count (bit 0 = x, 1 = y, 2 = z) -> (nn i32 [nv]: for a query the SORTED row of the reference of its own entry with the
+    smallest (d^2, id), -1 for other rows and for queries whose entry has no reference; status i32 [4] = (queries, references, queries
+    left at -1, mask of the axes with a decoded coordinate of 32768 or more: nn undefined)), both on the device, no sync.
+    nn / status / workspace: optional caller-owned contiguous buffers (the workspace uint8 of at least
+    gp_nn1_batched_workspace_bytes(nv))."""
+    lib = _lib.load()
+    _chk(keys_sorted, torch.int64, "keys")
+    nv = keys_sorted.shape[0]
+    if keys_sorted.dim() != 1:
+        raise ValueError(f"nn1_batched: expected keys [nv], got {list(keys_sorted.shape)}")
+    for t, dtype, name in ((ids, torch.int32, "ids"), (ref_mask, torch.uint8, "ref_mask"), (query_mask, torch.uint8, "query_mask")):
+        if t is not None and _chk(t, dtype, name).shape != (nv,):
+            raise ValueError(f"nn1_batched: expected {name} [{nv}], got {list(t.shape)}")
+    dev = keys_sorted.device
+    if nn is None:
+        nn = torch.empty(nv, dtype=torch.int32, device=dev)
+    elif _chk(nn, torch.int32, "nn").shape != (nv,):
+        raise ValueError(f"nn1_batched: expected nn [{nv}], got {list(nn.shape)}")
+    if status is None:
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+    elif _chk(status, torch.int32, "status").shape != (4,):
+        raise ValueError(f"nn1_batched: expected status [4], got {list(status.shape)}")
+    ws = _ws(lib.gp_nn1_batched_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_nn1_batched(_ptr(keys_sorted), _ptr(ids), _ptr(ref_mask), _ptr(query_mask), nv, int(axes), _ptr(nn), _ptr(status),
+                             _ptr(ws), ws.numel(), _stream()), "gp_nn1_batched")
+    return nn, status
+
+
+def iou_hist_batched(pred, coords, target, num_batches, num_classes, ignore_ids, counts, index=None):
+    """counts i64 [B,3,C] += the (intersection, output, target) histograms of iou_hist, separated by batch entry
+    (gp_iou_hist_batched_i64): pred i64 [rows] per voxel row, coords i32 [rows,4] for the batch index, target i64 [n]; index i64 [n]
+    (a quantiser's inverse_mapping) makes item p use row index[p]; None is the identity with n = rows.  No sync."""
+    lib = _lib.load()
+    _chk(pred, torch.int64, "pred")
+    _chk(coords, torch.int32, "coords")
+    _chk(target, torch.int64, "target")
+    _chk(counts, torch.int64, "counts")
+    rows, n = pred.shape[0], target.shape[0]
+    if pred.dim() != 1 or coords.shape != (rows, 4) or target.dim() != 1:
+        raise ValueError(f"iou_hist_batched: expected pred [rows], coords [rows, 4], target [n], got {list(pred.shape)}, "
+                         f"{list(coords.shape)}, {list(target.shape)}")
+    if index is not None and _chk(index, torch.int64, "index").shape != (n,):
+        raise ValueError(f"iou_hist_batched: expected index [{n}], got {list(index.shape)}")
+    if counts.numel() != int(num_batches) * 3 * int(num_classes):
+        raise ValueError(f"iou_hist_batched: expected counts [{num_batches}, 3, {num_classes}], got {list(counts.shape)}")
+    ig = (ctypes.c_int64 * max(len(ignore_ids), 1))(*[int(v) for v in ignore_ids])
+    check(lib.gp_iou_hist_batched_i64(_ptr(pred), _ptr(coords), rows, _ptr(target), _ptr(index), n, int(num_batches), int(num_classes),
+                                      ig, len(ignore_ids), _ptr(counts), _stream()), "gp_iou_hist_batched_i64")
+    return counts
+
+
 # ------------------------------------------------------------------------------------------ SURVEY 8f-1: training step
 def col_stats(y, c=None):
     """mean, biased variance of the rows of y fp32 [nv, >=c] (BatchNorm1d training statistics)."""

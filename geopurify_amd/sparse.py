@@ -12,16 +12,18 @@ once, entries never mixing.  The full chain, per-point features of several scene
     x = SparseTensor(features=q.features, coordinates=q.coordinates)
     y = affinity_pool(x, student(x))                            # or purify(student, x, feature_dim=D): the two calls in one
     per_point = y.F[q.inverse_mapping]
+    seg = segment(y, text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)   # labels per point, (I, O, T) counts per scene
 
 Every link carries gradients when asked to: affinity_pool(x, student(x), differentiable=True) -- or purify(student, x,
 differentiable=True) -- puts y.F into the autograd graph, so a loss on the purified features reaches the student's parameters, x.F and
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
-l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene.
+l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene; segment (labels and counts) never does.
 
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
-pooling families of HotPath, applied in the key order.
+pooling families of HotPath, applied in the key order.  segment is the per-scene tail of run/validation.py:413-439 for all entries at
+once: ops.classify_argmax(_gemm), the zero-row fill by ops.nn1_batched inside each entry, ops.iou_hist_batched.
 """
 import torch
 
@@ -421,3 +423,138 @@ def purify(student, x, *, feature_dim=None, differentiable=False, **kw):
     finally:
         student.train(was)
     return affinity_pool(type(x)(features=feats, coordinates=x.C), e, **kw)
+
+
+# ------------------------------------------------------------------------------------------ labels and per-entry IoU counts
+FILLS = {"xyz": 7, "yz": 6, None: 0}                        # the axis mask of ops.nn1_batched (0: no fill)
+MAX_COUNT_ELEMENTS = 2 ** 27
+
+
+class Segmentation:
+    """pred i64 (per voxel in the input's row order, or per point with an inverse_mapping), zero bool [N] (rows with sum |F| == 0),
+    filled_from i64 [N] (the input row whose label a filled row took, -1 elsewhere), counts i64 [B,3,C] = (I, O, T) per batch entry or
+    None, unfilled int (zero rows of entries without a non-zero row: they keep their arg-max)."""
+
+    def __init__(self, pred, zero, filled_from, counts, unfilled):
+        self.pred, self.zero, self.filled_from, self.counts, self.unfilled = pred, zero, filled_from, counts, unfilled
+
+
+def _is_int_tensor(t):
+    return torch.is_tensor(t) and not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+def segment(y, text_features, logit_scale=1.0, *, labels=None, num_classes=None, ignore_labels=(255,), fill="xyz", inverse_mapping=None):
+    """The per-scene tail of run/validation.py:413-439 over a batched SparseTensor, every batch entry by itself: classify each row
+    against the text embeddings (both normalised, arg-max, first maximum on ties), give rows whose feature is all zero the label of the
+    nearest non-zero row OF THEIR ENTRY, count intersection / output / target per entry.
+    y: an ME-style SparseTensor (.F [N,D] floating, .C integer [N,4] = batch, x, y, z in any row order, unique rows); text_features
+    [C,D].  fill: "xyz" -- the nearest in all three coordinates --, "yz" -- the reference's slice quirk (:422-423: columns 1:4 of an
+    [N,3] tensor) --, or None; ties by (d^2, input row), as validation.scene_tail and knn.  labels: i64 [N] per voxel, or [P] per point
+    when inverse_mapping ([P], a quantiser's point -> voxel map) is given; counts are then over points, each in the entry of its
+    voxel, and pred is per point.  counts has B = highest batch index + 1 blocks (absent entries stay zero), C = num_classes (default:
+    the text rows) columns; counts.sum(0) is what sharding.summarize takes.  -> Segmentation.  No gradients: inputs are detached.
+    Inside: ops.coords_order_batched, ops.classify_argmax_gemm (more than 32 classes at D % 32 == 0) or ops.classify_argmax on the rows
+    as they lie, ops.nn1_batched on the zero flags in sorted order, ops.iou_hist_batched.  ValueError from ONE status read-back
+    (and a range read-back before it unless the coordinates are int32): see knn; also text_features not [C, D], num_classes outside
+    1..4096, more than 4 ignore labels, labels / inverse_mapping of the wrong length or dtype, an inverse_mapping value outside
+    0..N-1, an unknown fill, B * 3 * C above 2^27."""
+    who = "segment"
+    if not (hasattr(y, "F") and hasattr(y, "C")):
+        raise ValueError(f"{who}: y must be a SparseTensor (an object with .F and .C), got {type(y).__name__}")
+    Fe, C, T = y.F, y.C, text_features
+    if fill not in FILLS:
+        raise ValueError(f"{who}: fill={fill!r}, expected one of {tuple(FILLS)}")
+    _check_coordinates(who, C)
+    n = C.shape[0]
+    if not torch.is_tensor(Fe) or Fe.dim() != 2 or Fe.shape[0] != n or Fe.shape[1] < 1:
+        raise ValueError(f"{who}: features must be [N, D] with N = {n} coordinate rows, got "
+                         f"{list(Fe.shape) if torch.is_tensor(Fe) else type(Fe).__name__}")
+    D = Fe.shape[1]
+    if not torch.is_tensor(T) or T.dim() != 2 or T.shape[0] < 1 or T.shape[1] != D:
+        raise ValueError(f"{who}: text_features must be [C, D] with D = {D} feature columns, got "
+                         f"{list(T.shape) if torch.is_tensor(T) else type(T).__name__}")
+    if not (Fe.dtype.is_floating_point and T.dtype.is_floating_point):
+        raise ValueError(f"{who}: features and text_features must be floating point, got {Fe.dtype} / {T.dtype}")
+    if not (Fe.is_cuda and T.is_cuda) or Fe.device != C.device or T.device != C.device:
+        raise ValueError(f"{who}: features, text_features and coordinates must be CUDA tensors on one device (got {Fe.device} / {T.device} / "
+                         f"{C.device}); there is no CPU path")
+    nc = T.shape[0] if num_classes is None else num_classes
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 4096:
+        raise ValueError(f"{who}: num_classes={nc!r} outside 1..4096")
+    ignore = [int(v) for v in ignore_labels]
+    if len(ignore) > 4:
+        raise ValueError(f"{who}: {len(ignore)} ignore labels, at most 4")
+    inv = inverse_mapping
+    if inv is not None and (not _is_int_tensor(inv) or inv.dim() != 1 or inv.shape[0] < 1 or inv.device != C.device):
+        raise ValueError(f"{who}: inverse_mapping must be an integer tensor [P] on {C.device}, got "
+                         f"{(list(inv.shape), inv.dtype, str(inv.device)) if torch.is_tensor(inv) else type(inv).__name__}")
+    items = n if inv is None else inv.shape[0]
+    if labels is not None and (not _is_int_tensor(labels) or labels.dim() != 1 or labels.shape[0] != items or labels.device != C.device):
+        raise ValueError(f"{who}: labels must be an integer tensor [{items}] ({'one per point of inverse_mapping' if inv is not None else 'one per voxel'}) "
+                         f"on {C.device}, got {(list(labels.shape), labels.dtype, str(labels.device)) if torch.is_tensor(labels) else type(labels).__name__}")
+    axes = FILLS[fill]
+    dev = C.device
+    with torch.cuda.device(dev), torch.no_grad():
+        C = C.detach()
+        if C.dtype != torch.int32:
+            # (range-checked before the cast: an int64 coordinate beyond int32 must not wrap into a valid one)
+            lo, hi = ops.readback(torch.stack(torch.aminmax(C)).to(torch.int64))
+            if lo < -2 ** 31 or hi >= 2 ** 31:
+                raise ValueError(f"{who}: coordinates outside the int32 range ({lo} .. {hi})")
+            C = C.to(torch.int32)
+        C = C.contiguous()
+        perm, rank, keys, order_status = ops.coords_order_batched(C)
+        feats = _rows_f32(Fe.detach())
+        text_norm = torch.nn.functional.normalize(T.detach().float(), dim=-1).contiguous()
+        if text_norm.shape[0] > 32 and D % 32 == 0:                       # validation.scene_tail's choice
+            pred, zero = ops.classify_argmax_gemm(feats, text_norm)
+        else:
+            pred, zero = ops.classify_argmax(feats, text_norm, float(logit_scale))
+        if axes:
+            zero_sorted = zero.index_select(0, perm.long())
+            nn, fill_status = ops.nn1_batched(keys, perm, 1 - zero_sorted, zero_sorted, axes)
+        else:
+            nn, fill_status = None, torch.zeros(4, dtype=torch.int32, device=dev)
+        xyz = C[:, 1:]
+        extent = (xyz.amax(0).to(torch.int64) - xyz.amin(0).to(torch.int64) + 1)
+        if inv is not None:
+            inv = inv.detach().to(torch.int64).contiguous()
+            bad_inv = ((inv < 0) | (inv >= n)).sum().reshape(1)
+        else:
+            bad_inv = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = ops.readback(torch.cat([order_status.to(torch.int64), fill_status.to(torch.int64), extent, C[:, 0].amax().to(torch.int64).reshape(1),
+                                     bad_inv]))
+        dups, bad_batch, bad_axes = st[:3]
+        unfilled, axes15 = st[5], st[6]
+        extent, top_batch, bad_inv = st[7:10], st[10], st[11]
+        # (range first: a row whose batch index is out of range has a meaningless key, which may equal another row's)
+        if bad_batch:
+            raise ValueError(f"{who}: {bad_batch} rows have a batch index outside 0..65535")
+        if bad_axes:
+            names = [a for i, a in enumerate("xyz") if bad_axes >> i & 1]
+            raise ValueError(f"{who}: coordinate extent of 65536 or more along {', '.join(names)} (16 bits per axis)")
+        if dups:
+            raise ValueError(f"{who}: {dups} duplicate coordinate rows (MinkowskiEngine would merge them; quantise first)")
+        wide = [a for i, a in enumerate("xyz") if extent[i] >= 32768 or axes15 >> i & 1]
+        if wide:
+            raise ValueError(f"{who}: coordinate extent of 32768 or more along {', '.join(wide)} ({'/'.join(str(e) for e in extent)} voxels; "
+                             "squared distances must stay below 2^32)")
+        if bad_inv:
+            raise ValueError(f"{who}: {bad_inv} inverse_mapping values outside 0..{n - 1}")
+        B = top_batch + 1
+        if labels is not None and B * 3 * nc > MAX_COUNT_ELEMENTS:
+            raise ValueError(f"{who}: counts [{B}, 3, {nc}] would hold more than 2^27 elements (the highest batch index is {top_batch})")
+        if nn is not None:
+            # sorted rows -> input rows, in the input's row order; a filled row takes the label its source was classified with
+            nn_in = nn.index_select(0, rank.long()).long()
+            filled_from = torch.where(nn_in >= 0, perm.long()[nn_in.clamp(min=0)], nn_in)
+            pred = torch.where(filled_from >= 0, pred[filled_from.clamp(min=0)], pred)
+        else:
+            filled_from = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        counts = None
+        if labels is not None:
+            counts = torch.zeros((B, 3, nc), dtype=torch.int64, device=dev)
+            ops.iou_hist_batched(pred, C, labels.detach().to(torch.int64).contiguous(), B, nc, ignore, counts, index=inv)
+        if inv is not None:
+            pred = pred.index_select(0, inv)
+    return Segmentation(pred, zero.bool(), filled_from, counts, int(unfilled))

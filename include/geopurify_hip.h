@@ -575,6 +575,30 @@ int gp_rows_argmax(const float *logits, int64_t ld, int32_t c, int64_t n, const 
 int gp_iou_hist_i64(const int64_t *pred, const int64_t *target, int64_t n, int32_t num_classes,
                     const int64_t *ignore_ids_host, int32_t num_ignore, int64_t *counts,
                     void *stream);
+/* The zero-row fill of run/validation.py:417-431 (KDTree over the non-zero rows, k = 1) over BATCHED coordinates: masked exact 1-NN    */
+/* inside every batch entry.  keys_sorted u64 [nv] and ids i32 [nv] as gp_knn_batched takes them (NULL ids: the row number);            */
+/* ref_mask / query_mask u8 [nv] in SORTED-row order (non-zero = set).  nn i32 [nv]: for a query row the SORTED-ROW number of the        */
+/* reference row of the SAME entry that minimises (d^2, id), d^2 the integer squared distance over the axes of `axes` (bit 0 = x,       */
+/* 1 = y, 2 = z; 1..7 -- 6 is the reference's slice quirk, :422-423); -1 for rows that are no queries and for queries whose entry       */
+/* holds no reference.  Equal d^2: the lower id wins; a row set in both masks finds itself; rows of other entries never win, also       */
+/* where entries occupy the same coordinates.  No coordinate array is read.  Rings 1 and 3 over an 8^3 cell table of the reference      */
+/* keys, accepted only at d^2 strictly below (8R+1)^2, then a scan of the entry's references; axes != 7 scans at once.                  */
+/* 1 <= nv < 2^31.  status i32 [4] (device, written by the call): [0] queries; [1] reference rows; [2] queries left at -1 (their entry  */
+/* has no reference); [3] mask of the axes on which a decoded coordinate is 32768 or more: the (d^2 << 32 | id) key needs d^2 < 2^32,  */
+/* so with a nonzero mask nn is undefined (the call still returns, and stores only rows of the query's entry or -1).  No host sync,   */
+/* integer arithmetic only, nothing read or written outside the given extents.                                                          */
+size_t gp_nn1_batched_workspace_bytes(int64_t nv);
+int gp_nn1_batched(const uint64_t *keys_sorted, const int32_t *ids, const uint8_t *ref_mask, const uint8_t *query_mask, int64_t nv,
+                   int32_t axes, int32_t *nn, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+/* counts i64 [B,3,C] += the histograms of gp_iou_hist_i64 (util/util.py:160-177) separated by batch entry, in one pass.  Item p of n  */
+/* takes pred[r] and the batch index coords[r,0] of row r = index[p] (index i64 [n]: the per-point form through a quantiser's inverse  */
+/* map; NULL: r = p and n must equal rows), coords i32 [rows,4], and target[p].  Same ignore-id overwrite (at most 4 ids), values      */
+/* outside 0..C-1 dropped; an item whose row is outside 0..rows-1 or whose batch index is outside 0..B-1 is counted nowhere.           */
+/* 1 <= B <= 65536, 1 <= C <= 4096, 1 <= rows < 2^31.  Integer atomics only (LDS counters when B*3*C <= 12288, else 64-bit atomics on  */
+/* counts): the result does not depend on arrival order.                                                                               */
+int gp_iou_hist_batched_i64(const int64_t *pred, const int32_t *coords, int64_t rows, const int64_t *target, const int64_t *index,
+                            int64_t n, int32_t num_batches, int32_t num_classes, const int64_t *ignore_ids_host, int32_t num_ignore,
+                            int64_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* training step of the student (models/affinity_module.py:1138-1237,                */
