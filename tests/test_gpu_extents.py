@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from extent_fence import INT_VIEW, POISON, Arena, assert_intact, bits, fence_in, fenced, run, unwritten
+from lattice_cases import rcb_reference
 from oracle import affinity as o_aff
 from oracle import metric as o_metric
 from oracle import student as o_student
@@ -786,33 +787,6 @@ def test_kernel_map_build(ops, lib, nv):
         return {"nbr_map": nm}
 
     assert np.array_equal(run(case)["nbr_map"].cpu().numpy(), g["nm"])        # test_morton_grid_kernel_map: the oracle's map, exact
-
-
-def rcb_reference(cs, chunk, leaf):
-    """gp_rcb_order restated (csrc/rcb.hip): inside every chunk, a segment longer than a leaf is sorted along the axis of its largest
-    extent (ties: the lower axis; equal coordinates keep their order) and cut at ceil(len / 2 / leaf) * leaf rows."""
-    nv = len(cs)
-    sigma = np.empty(nv, np.int64)
-    for base in range(0, nv, chunk):
-        n = min(chunk, nv - base)
-        order, segs, more = np.arange(n), [(0, n)], n > leaf
-        while more:
-            new, more = [], False
-            for start, ln in segs:
-                if ln <= leaf:
-                    new.append((start, ln))
-                    continue
-                idx = order[start:start + ln]
-                p = cs[base + idx].astype(np.int64)
-                ax = int(np.argmax(p.max(0) - p.min(0)))
-                order[start:start + ln] = idx[np.argsort(p[:, ax], kind="stable")]
-                half = (ln // 2 + leaf - 1) // leaf * leaf
-                half = ln // 2 if half >= ln else half
-                new += [(start, half), (start + half, ln - half)]
-                more |= half > leaf or ln - half > leaf
-            segs = new
-        sigma[base:base + n] = base + order
-    return sigma
 
 
 # rcb_chunk_kernel: a chunk of 1024 rows per workgroup, leaves of 128; 1025 and 1151 leave a last chunk of 1 and of 127 rows
