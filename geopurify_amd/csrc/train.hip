@@ -445,8 +445,10 @@ __global__ void nce_normalize_kernel(const float *__restrict__ e, int64_t ld, co
 // and +p a / T many times, terms that cancel (all samples equal: to zero), and fp32 atomics left the rounding of the LARGEST partial
 // sum behind -- 1.07e-6 where the gradient is 0 and the bound 1e-6 (tests/test_gpu_train_edges.py, all_equal_map).  The products
 // g_j * a of two floats are exact in fp64, so what remains is the rounding of g and of the final sum.
+// w (optional, gp_infonce_weighted_fwd_bwd): anchor a counts w[a] times instead of 1 / na; l (optional): its own loss l[a].
 __global__ void nce_anchor_kernel(const float *__restrict__ en, int d, const int64_t *__restrict__ p2b, int64_t na, int nneg,
-                                  float inv_t, float *__restrict__ loss, double *__restrict__ den) {
+                                  float inv_t, float *__restrict__ loss, double *__restrict__ den, const float *__restrict__ w,
+                                  float *__restrict__ l) {
     int64_t a = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     if (a >= na) return;
     int lane = gp_lane();
@@ -470,8 +472,11 @@ __global__ void nce_anchor_kernel(const float *__restrict__ en, int d, const int
     float den_s = gp_wave_sum(ex);
     float p = ex / den_s;
     float l0 = __shfl(logit, 0, 64);
-    if (lane == 0) atomicAdd(loss, (mx + logf(den_s) - l0) / (float)na);
-    float g = lane < nl ? (p - (lane == 0 ? 1.f : 0.f)) * inv_t / (float)na : 0.f;       // d loss / d (a . e_j)
+    const float la = mx + logf(den_s) - l0;
+    if (lane == 0) atomicAdd(loss, w ? la * w[a] : la / (float)na);
+    if (lane == 0 && l) l[a] = la;
+    const float gl = (p - (lane == 0 ? 1.f : 0.f)) * inv_t;
+    float g = lane < nl ? (w ? gl * w[a] : gl / (float)na) : 0.f;       // d loss / d (a . e_j)
     double ga[4] = {0.0, 0.0, 0.0, 0.0};
     for (int j = 0; j < nl; ++j) {
         int64_t ij = __shfl(mine, j, 64);
@@ -770,8 +775,12 @@ __device__ __forceinline__ void sr_walk(const float *__restrict__ row, int n, bo
 }
 template <int LG>
 __global__ void __launch_bounds__(SR_NT, 8)
-sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n, const int64_t *__restrict__ anchor, int k,
-                      int64_t *__restrict__ positive, int64_t *__restrict__ macro) {
+sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n_all, const int64_t *__restrict__ anchor, int k,
+                      int64_t *__restrict__ positive, int64_t *__restrict__ macro, const int64_t *__restrict__ row_off,
+                      const int32_t *__restrict__ row_len, const int32_t *__restrict__ row_base) {
+    // row_off (optional, with row_len and row_base; gp_sampler_select_segments): row b is the row_len[b] floats at sim + row_off[b],
+    // element j of it stands for index row_base[b] + j -- anchor[b] and the results are such indices.  Without it: row b = sim + b ld,
+    // n_all elements, base 0.
     constexpr int lg = LG;
     __shared__ __align__(16) unsigned long long cand[SR_CAP];
     __shared__ unsigned gmin[SR_GROUPS];
@@ -781,9 +790,11 @@ sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n, const in
     __shared__ int s_cnt, s_pos, s_bin, s_acc, s_done;
     unsigned *hist = reinterpret_cast<unsigned *>(cand);                 // [SR_BINS]: the rare path's, before the candidates are collected
     const int tid = threadIdx.x, lane = tid & 63;
-    const float *row = sim + (int64_t)blockIdx.x * ld;
-    const bool vec = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(sim) & 15) == 0);
-    const int anc = (int)anchor[blockIdx.x];
+    const float *row = row_off ? sim + row_off[blockIdx.x] : sim + (int64_t)blockIdx.x * ld;
+    const bool vec = row_off ? (reinterpret_cast<uintptr_t>(row) & 15) == 0 : (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(sim) & 15) == 0);
+    const int n = row_off ? row_len[blockIdx.x] : n_all;
+    const int64_t base = row_off ? row_base[blockIdx.x] : 0;
+    const int anc = (int)(anchor[blockIdx.x] - base);
     const int n4 = (n + 3) >> 2, ngroups = (n4 + (1 << lg) - 1) >> lg;
     // ---- the sweep
     unsigned tmin = 0xffffffffu, tmaxk = 0u;
@@ -863,7 +874,7 @@ sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n, const in
     __syncthreads();
     const unsigned bound = s_bound;
     const int pos = s_pos;
-    if (tid == 0) positive[blockIdx.x] = pos;
+    if (tid == 0) positive[blockIdx.x] = base + pos;
     // ---- collect the elements at or below the bound
     sr_walk<LG>(row, n, vec, gmin, ngroups, bound, [&](int i, unsigned kx) {
         if (kx <= bound && i != anc && i != pos) {
@@ -924,7 +935,7 @@ sampler_select_kernel(const float *__restrict__ sim, int64_t ld, int n, const in
             rank += (c2.x < me) + (c2.y < me);
         }
         if (u < cnt) rank += cand[u] < me;
-        if (rank < k) macro[(int64_t)blockIdx.x * k + rank] = (int64_t)(unsigned)(me & 0xffffffffu);
+        if (rank < k) macro[(int64_t)blockIdx.x * k + rank] = base + (int64_t)(unsigned)(me & 0xffffffffu);
     }
 }
 
@@ -1111,15 +1122,16 @@ extern "C" size_t gp_infonce_workspace_bytes(int64_t num_samples, int32_t d) {
            gp_align_up((size_t)num_samples * sizeof(float), 256);
 }
 
-// loss (device scalar, overwritten) and dE [nv, d] (overwritten) of the InfoNCE of affinity_module.py:1219-1233
-extern "C" int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel, int64_t num_samples,
-                                  const int64_t *point_to_batch, int64_t num_anchors, int32_t num_negatives, float temperature,
-                                  float *loss, float *de, int64_t ld_de, void *workspace, size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(e && sample_to_voxel && point_to_batch && loss && de && workspace, "gp_infonce_fwd_bwd: null argument");
-    GP_CHECK_ARG(nv > 0 && num_samples > 0 && num_anchors > 0 && d > 0 && d <= 256, "gp_infonce_fwd_bwd: bad shape (d <= 256)");
-    GP_CHECK_ARG(num_negatives >= 0 && num_negatives < 64, "gp_infonce_fwd_bwd: 1 + negatives must fit one wave (<= 64)");
-    GP_CHECK_ARG(temperature > 0.f, "gp_infonce_fwd_bwd: temperature must be positive");
-    if (workspace_bytes < gp_infonce_workspace_bytes(num_samples, d)) { gp_set_error("gp_infonce_fwd_bwd: workspace too small"); return GP_ENOMEM; }
+// loss (device scalar, overwritten) and dE [nv, d] (overwritten) of the InfoNCE of affinity_module.py:1219-1233; weights (optional):
+// loss = sum_a weights[a] l_a instead of the mean; anchor_loss (optional): l_a
+static int infonce_launch(const char *who, const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel, int64_t num_samples,
+                          const int64_t *point_to_batch, int64_t num_anchors, int32_t num_negatives, float temperature, const float *weights,
+                          float *loss, float *anchor_loss, float *de, int64_t ld_de, void *workspace, size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(e && sample_to_voxel && point_to_batch && loss && de && workspace, "%s: null argument", who);
+    GP_CHECK_ARG(nv > 0 && num_samples > 0 && num_anchors > 0 && d > 0 && d <= 256, "%s: bad shape (d <= 256)", who);
+    GP_CHECK_ARG(num_negatives >= 0 && num_negatives < 64, "%s: 1 + negatives must fit one wave (<= 64)", who);
+    GP_CHECK_ARG(temperature > 0.f, "%s: temperature must be positive", who);
+    if (workspace_bytes < gp_infonce_workspace_bytes(num_samples, d)) { gp_set_error("%s: workspace too small", who); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);
     GpCarver cv(workspace, workspace_bytes);
     float *en = cv.take<float>(num_samples * d);
@@ -1130,10 +1142,26 @@ extern "C" int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int3
     GP_CHECK_HIP(hipMemset2DAsync(de, (size_t)ld_de * sizeof(float), 0, (size_t)d * sizeof(float), (size_t)nv, s));
     nce_normalize_kernel<<<(unsigned)((num_samples * 64 + 255) / 256), 256, 0, s>>>(e, ld_e, sample_to_voxel, num_samples, d, en, norm);
     nce_anchor_kernel<<<(unsigned)((num_anchors * 64 + 255) / 256), 256, 0, s>>>(en, d, point_to_batch, num_anchors, num_negatives,
-                                                                                 1.0f / temperature, loss, den);
+                                                                                 1.0f / temperature, loss, den, weights, anchor_loss);
     nce_scatter_kernel<<<(unsigned)((num_samples * 64 + 255) / 256), 256, 0, s>>>(en, den, norm, sample_to_voxel, num_samples, d, de, ld_de);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+extern "C" int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel, int64_t num_samples,
+                                  const int64_t *point_to_batch, int64_t num_anchors, int32_t num_negatives, float temperature,
+                                  float *loss, float *de, int64_t ld_de, void *workspace, size_t workspace_bytes, void *stream_) {
+    return infonce_launch("gp_infonce_fwd_bwd", e, ld_e, nv, d, sample_to_voxel, num_samples, point_to_batch, num_anchors, num_negatives, temperature,
+                          nullptr, loss, nullptr, de, ld_de, workspace, workspace_bytes, stream_);
+}
+// the same with loss = sum_a weights[a] l_a (weights f32 [A]: 1 / A gives the mean) and the anchors' own losses l_a in anchor_loss f32 [A];
+// the reduction over batch entries of geopurify_amd.sparse.info_nce is a choice of weights
+extern "C" int gp_infonce_weighted_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel, int64_t num_samples,
+                                           const int64_t *point_to_batch, int64_t num_anchors, int32_t num_negatives, float temperature,
+                                           const float *weights, float *loss, float *anchor_loss, float *de, int64_t ld_de, void *workspace,
+                                           size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(weights && anchor_loss, "gp_infonce_weighted_fwd_bwd: null argument");
+    return infonce_launch("gp_infonce_weighted_fwd_bwd", e, ld_e, nv, d, sample_to_voxel, num_samples, point_to_batch, num_anchors, num_negatives,
+                          temperature, weights, loss, anchor_loss, de, ld_de, workspace, workspace_bytes, stream_);
 }
 
 // torch.optim.AdamW step on one flat fp32 tensor; step >= 1
@@ -1177,7 +1205,28 @@ extern "C" int gp_sampler_select(const float *sim, int64_t ld, int64_t num_ancho
     int lg = 0;                                             // 4 << lg elements per group: the fewest that fit the row's groups into LDS
     while ((((n + 3) >> 2) + (1 << lg) - 1) >> lg > SR_GROUPS) ++lg;
     hipStream_t s = gp_stream(stream_);
-#define SR_LAUNCH(L) case L: sampler_select_kernel<L><<<(unsigned)num_anchors, SR_NT, 0, s>>>(sim, ld, (int)n, anchor_idx, k, positive, macro); break;
+#define SR_LAUNCH(L) case L: sampler_select_kernel<L><<<(unsigned)num_anchors, SR_NT, 0, s>>>(sim, ld, (int)n, anchor_idx, k, positive, macro, nullptr, nullptr, nullptr); break;
+    switch (lg) { SR_LAUNCH(0) SR_LAUNCH(1) SR_LAUNCH(2) SR_LAUNCH(3) SR_LAUNCH(4) SR_LAUNCH(5) SR_LAUNCH(6) default: break; }
+#undef SR_LAUNCH
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+// The same selections over ragged rows (the similarity of gp_sim_segments_f16x3): row a is the row_len[a] floats at sim + row_off[a]
+// and stands for the indices row_base[a] .. row_base[a] + row_len[a] - 1; anchor_idx and the results are such indices.  max_len: the
+// longest row (it picks the group size for all rows).
+extern "C" int gp_sampler_select_segments(const float *sim, const int64_t *row_off, const int32_t *row_len, const int32_t *row_base,
+                                          int64_t num_anchors, int64_t max_len, const int64_t *anchor_idx, int32_t k, int64_t *positive,
+                                          int64_t *macro, void *stream_) {
+    GP_CHECK_ARG(sim && row_off && row_len && row_base && anchor_idx && positive && macro && num_anchors > 0,
+                 "gp_sampler_select_segments: null/empty argument");
+    GP_CHECK_ARG(k >= 1 && k < SR_NT && k <= SR_CAP && max_len >= (int64_t)k + 2 && max_len <= (int64_t)SR_GROUPS * 256,
+                 "gp_sampler_select_segments: k=%d, max_len=%lld out of range (1 <= k < %d, k + 2 <= max_len <= %d)", k, (long long)max_len, SR_NT,
+                 SR_GROUPS * 256);
+    int lg = 0;
+    while ((((max_len + 3) >> 2) + (1 << lg) - 1) >> lg > SR_GROUPS) ++lg;
+    hipStream_t s = gp_stream(stream_);
+#define SR_LAUNCH(L) case L: sampler_select_kernel<L><<<(unsigned)num_anchors, SR_NT, 0, s>>>(sim, 0, 0, anchor_idx, k, positive, macro, row_off, row_len, row_base); break;
     switch (lg) { SR_LAUNCH(0) SR_LAUNCH(1) SR_LAUNCH(2) SR_LAUNCH(3) SR_LAUNCH(4) SR_LAUNCH(5) SR_LAUNCH(6) default: break; }
 #undef SR_LAUNCH
     GP_CHECK_LAUNCH();

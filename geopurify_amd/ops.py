@@ -1441,6 +1441,28 @@ def infonce_fwd_bwd(e, sample_to_voxel, point_to_batch, num_anchors, num_negativ
     return loss, de
 
 
+def infonce_weighted_fwd_bwd(e, sample_to_voxel, point_to_batch, num_anchors, num_negatives, temperature, weights):
+    """(loss 0-d, per-anchor losses f32 [A], d loss / d e) of loss = sum_a weights[a] l_a (gp_infonce_weighted_fwd_bwd)"""
+    lib = _lib.load()
+    nv, d = e.shape
+    ns = sample_to_voxel.shape[0]
+    _chk(e, torch.float32, "e")
+    _chk(sample_to_voxel, torch.int64, "sample_to_voxel")
+    _chk(point_to_batch, torch.int64, "point_to_batch")
+    _chk(weights, torch.float32, "weights")
+    if point_to_batch.shape != (num_anchors * (2 + num_negatives),) or weights.shape != (num_anchors,):
+        raise ValueError(f"infonce_weighted_fwd_bwd: expected point_to_batch [{num_anchors * (2 + num_negatives)}] and weights [{num_anchors}], got "
+                         f"{list(point_to_batch.shape)} and {list(weights.shape)}")
+    loss = torch.empty((), dtype=torch.float32, device=e.device)
+    anchor_loss = torch.empty(num_anchors, dtype=torch.float32, device=e.device)
+    de = torch.empty((nv, d), dtype=torch.float32, device=e.device)
+    ws = _ws(lib.gp_infonce_workspace_bytes(ns, d), e.device)
+    check(lib.gp_infonce_weighted_fwd_bwd(_ptr(e), e.stride(0), nv, int(d), _ptr(sample_to_voxel), ns, _ptr(point_to_batch), int(num_anchors),
+                                          int(num_negatives), float(temperature), _ptr(weights), _ptr(loss), _ptr(anchor_loss), _ptr(de),
+                                          de.stride(0), _ptr(ws), ws.numel(), _stream()), "gp_infonce_weighted_fwd_bwd")
+    return loss, anchor_loss, de
+
+
 def adamw_step_(param, grad, exp_avg, exp_avg_sq, lr, step, weight_decay=1e-2, betas=(0.9, 0.999), eps=1e-8):
     lib = _lib.load()
     for t in (param, grad, exp_avg, exp_avg_sq):
@@ -1475,6 +1497,65 @@ def sampler_select(sim, anchor_indices, k, n=None):
     check(lib.gp_sampler_select(_ptr(sim), sim.stride(0), A, int(n), _ptr(anchor_indices), int(k), _ptr(positive), _ptr(macro), _stream()),
           "gp_sampler_select")
     return positive, macro
+
+
+def _segment_rows(who, a, *ts):
+    for name, t, dt in ts:
+        _chk(t, dt, name)
+        if t.shape != (a,):
+            raise ValueError(f"{who}: expected {name} [{a}], got {list(t.shape)}")
+
+
+def sim_segments(hi, lo, anchor_row, seg_first, seg_len, row_off, max_len, out):
+    """The anchors' similarity rows, each against its own batch entry, into the ragged fp32 buffer `out` (gp_sim_segments_f16x3):
+    out[row_off[a] + j] = <x[anchor_row[a]], x[seg_first[a] + j]>, j < seg_len[a], x = hi + lo (normalize_split_f16 planes, width a
+    multiple of 32).  anchor_row / seg_first / seg_len i32 [A] with the anchors grouped by entry, row_off i64 [A] multiples of 4;
+    max_len: the largest seg_len (host int).  Floats of `out` outside the extents are not written."""
+    lib = _lib.load()
+    _chk(out, torch.float32, "out")
+    for name, t in (("hi", hi), ("lo", lo)):
+        if t.dtype != torch.float16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"sim_segments: expected {name} as CUDA float16 rows [n, d] with unit column stride, got {t.dtype} {list(t.shape)}")
+    a = anchor_row.shape[0]
+    _segment_rows("sim_segments", a, ("anchor_row", anchor_row, torch.int32), ("seg_first", seg_first, torch.int32), ("seg_len", seg_len, torch.int32),
+                  ("row_off", row_off, torch.int64))
+    if hi.shape != lo.shape or hi.stride(0) != lo.stride(0) or out.dim() != 1:
+        raise ValueError(f"sim_segments: expected hi and lo [n, d] of one row stride and a flat out, got {list(hi.shape)}, {list(lo.shape)}, {list(out.shape)}")
+    check(lib.gp_sim_segments_f16x3(_ptr(hi), _ptr(lo), hi.stride(0), hi.shape[1], _ptr(anchor_row), _ptr(seg_first), _ptr(seg_len), _ptr(row_off),
+                                    a, int(max_len), _ptr(out), _stream()), "gp_sim_segments_f16x3")
+    return out
+
+
+def sampler_select_segments(sim, row_off, row_len, row_base, anchor_idx, k, max_len):
+    """positive i64 [A], macro i64 [A, k] of the ragged rows of sim (gp_sampler_select_segments: sampler_select's kernel with a row
+    descriptor): row a = sim[row_off[a] : row_off[a] + row_len[a]], element j standing for index row_base[a] + j; anchor_idx and the
+    results are such indices.  sim is not written."""
+    lib = _lib.load()
+    _chk(sim, torch.float32, "sim")
+    a = anchor_idx.shape[0]
+    _segment_rows("sampler_select_segments", a, ("row_off", row_off, torch.int64), ("row_len", row_len, torch.int32), ("row_base", row_base, torch.int32),
+                  ("anchor_idx", anchor_idx, torch.int64))
+    positive = torch.empty(a, dtype=torch.int64, device=sim.device)
+    macro = torch.empty((a, k), dtype=torch.int64, device=sim.device)
+    check(lib.gp_sampler_select_segments(_ptr(sim), _ptr(row_off), _ptr(row_len), _ptr(row_base), a, int(max_len), _ptr(anchor_idx), int(k),
+                                         _ptr(positive), _ptr(macro), _stream()), "gp_sampler_select_segments")
+    return positive, macro
+
+
+def sampler_micro_segments(sim, row_off, seg_first, seg_len, nbr, positive, num_micro):
+    """micro i64 [A, num_micro]: of nbr i32 [A, K] (key rows) the num_micro of lowest similarity in the anchor's ragged row, ascending
+    by (value, slot); a neighbour equal to positive[a] counts as +inf (gp_sampler_micro_segments)."""
+    lib = _lib.load()
+    _chk(sim, torch.float32, "sim"), _chk(nbr, torch.int32, "nbr")
+    a = positive.shape[0]
+    _segment_rows("sampler_micro_segments", a, ("row_off", row_off, torch.int64), ("seg_first", seg_first, torch.int32), ("seg_len", seg_len, torch.int32),
+                  ("positive", positive, torch.int64))
+    if nbr.dim() != 2 or nbr.shape[0] != a:
+        raise ValueError(f"sampler_micro_segments: expected nbr [{a}, K], got {list(nbr.shape)}")
+    micro = torch.empty((a, num_micro), dtype=torch.int64, device=sim.device)
+    check(lib.gp_sampler_micro_segments(_ptr(sim), _ptr(row_off), _ptr(seg_first), _ptr(seg_len), _ptr(nbr), nbr.stride(0), nbr.shape[1],
+                                        _ptr(positive), a, int(num_micro), _ptr(micro), _stream()), "gp_sampler_micro_segments")
+    return micro
 
 
 def normalize_split_f16(x, n_pad=None, eps=1e-12):

@@ -14,6 +14,12 @@ once, entries never mixing.  The full chain, per-point features of several scene
     per_point = y.F[q.inverse_mapping]
     seg = segment(y, text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)   # labels per point, (I, O, T) counts per scene
 
+and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
+
+    pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
+    loss = info_nce(student(pairs.subset(x)), pairs)            # or contrastive_loss(student, x, teacher): the three calls in one
+    loss.backward()
+
 Every link carries gradients when asked to: affinity_pool(x, student(x), differentiable=True) -- or purify(student, x,
 differentiable=True) -- puts y.F into the autograd graph, so a loss on the purified features reaches the student's parameters, x.F and
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
@@ -23,7 +29,9 @@ The indices come from ops.quantize_batched (the key and order of ops.coords_orde
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
 pooling families of HotPath, applied in the key order.  segment is the per-scene tail of run/validation.py:413-439 for all entries at
-once: ops.classify_argmax(_gemm), the zero-row fill by ops.nn1_batched inside each entry, ops.iou_hist_batched.
+once: ops.classify_argmax(_gemm), the zero-row fill by ops.nn1_batched inside each entry, ops.iou_hist_batched.  sample_pairs is
+ops.normalize_split_f16 on the teacher rows in the key order, then per chunk of anchors ops.sim_segments (the similarity inside each
+anchor's entry, a ragged buffer), ops.sampler_select_segments and ops.sampler_micro_segments; info_nce is ops.infonce_weighted_fwd_bwd.
 """
 import torch
 
@@ -197,10 +205,12 @@ def _check_k(who, k):
         raise ValueError(f"{who}: K={k!r} outside 1..{GP_KNN_MAX_K}")
 
 
-def _ordered_knn(who, C, k, same_as=None):
+def _ordered_knn(who, C, k, same_as=None, extra=None, lists=True):
     """The checked coordinates C in the sorted order of ops.coords_order_batched -> (perm, rank i32 [N], nbr i32 [N,k] of sorted-row
     numbers).  Every refusal is raised from ONE status read-back (before it: the int32 range read-back of coordinates that are not
-    int32 already).  same_as: a second coordinate tensor of C's shape that must equal C."""
+    int32 already).  same_as: a second coordinate tensor of C's shape that must equal C.
+    extra: a function (perm, rank, keys) -> (i64 [m] device tensor, anything): its words ride in the same read-back, and the result is
+    (perm, rank, nbr, keys, the m words as ints, the anything).  lists=False: no kNN (nbr is None), the caller has lists of its own."""
     with torch.cuda.device(C.device):
         C = C.detach()
         if C.dtype != torch.int32:
@@ -211,11 +221,15 @@ def _ordered_knn(who, C, k, same_as=None):
             C = C.to(torch.int32)
         C = C.contiguous()
         perm, rank, keys, order_status = ops.coords_order_batched(C)
-        nbr, knn_status = ops.knn_batched(keys, perm, k)
+        if lists:
+            nbr, knn_status = ops.knn_batched(keys, perm, k)
+        else:
+            nbr, knn_status = None, torch.zeros(4, dtype=torch.int32, device=C.device)
+        words, kept = extra(perm, rank, keys) if extra is not None else (torch.zeros(0, dtype=torch.int64, device=C.device), None)
         xyz = C[:, 1:]
         extent = (xyz.amax(0).to(torch.int64) - xyz.amin(0).to(torch.int64) + 1)
         differ = (same_as.to(torch.int64) != C.to(torch.int64)).sum() if same_as is not None else torch.zeros((), dtype=torch.int64, device=C.device)
-        st = ops.readback(torch.cat([order_status.to(torch.int64), knn_status.to(torch.int64), extent, differ.reshape(1)]))
+        st = ops.readback(torch.cat([order_status.to(torch.int64), knn_status.to(torch.int64), extent, differ.reshape(1), words]))
     dups, bad_batch, bad_axes, short_rows, short_batch, short_count, axes15 = st[:7]
     extent, differ = st[7:10], st[10]
     if differ:
@@ -235,7 +249,7 @@ def _ordered_knn(who, C, k, same_as=None):
     if short_rows:
         raise ValueError(f"{who}: batch entry {short_batch} holds {short_count} voxels, K={k} neighbours need more than K "
                          f"({short_rows} rows are in such entries)")
-    return perm, rank, nbr
+    return (perm, rank, nbr) if extra is None else (perm, rank, nbr, keys, st[11:], kept)
 
 
 def knn(coordinates, k):
@@ -558,3 +572,284 @@ def segment(y, text_features, logit_scale=1.0, *, labels=None, num_classes=None,
         if inv is not None:
             pred = pred.index_select(0, inv)
     return Segmentation(pred, zero.bool(), filled_from, counts, int(unfilled))
+
+
+# ------------------------------------------------------------------------------------------ contrastive pairs and InfoNCE
+SIM_ROW_PAD = 4                                             # floats: the ragged rows start 16-byte aligned
+MAX_ENTRY_ROWS = 12288 * 256                                # gp_sampler_select_segments: the longest row its groups hold
+MAX_CHUNK_ANCHORS = 65535 * 64                              # gp_sim_segments_f16x3: anchor tiles per launch
+REDUCTIONS = ("anchor", "entry")
+
+
+class ContrastivePairs:
+    """The sampler's result, everything as INPUT row numbers: anchor i64 [A], positive i64 [A], negative i64 [A, Nn] (the macro
+    negatives ascending by (similarity, key row), then the micro ones ascending by (similarity, slot in the neighbour list)), entry
+    i64 [A] (the batch index of each anchor), num_rows = N and num_entries = the highest batch index + 1.
+    rows i64 [S] (the sorted unique sampled rows) and index i64 [A * (2 + Nn)] (positions in rows of cat(anchor, positive,
+    negative.flatten()): the reference's all_sampled_indices and point_to_batch_map, :1196) are made on first use by one torch.unique
+    -- which reads S back, as the reference's does."""
+
+    def __init__(self, anchor, positive, negative, entry, num_rows, num_entries):
+        self.anchor, self.positive, self.negative, self.entry = anchor, positive, negative, entry
+        self.num_rows, self.num_entries = int(num_rows), int(num_entries)
+        self._rows = self._index = None
+
+    def _unique(self):
+        if self._rows is None:
+            self._rows, self._index = torch.unique(torch.cat([self.anchor, self.positive, self.negative.flatten()]), return_inverse=True)
+        return self._rows, self._index
+
+    @property
+    def rows(self):
+        return self._unique()[0]
+
+    @property
+    def index(self):
+        return self._unique()[1]
+
+    def subset(self, x):
+        """the sampled rows of x as a SparseTensor (the reference's :1192-1212 for voxels that are their own samples): row s of it is
+        row rows[s] of x; gradients of its features reach x.F"""
+        if not (hasattr(x, "F") and hasattr(x, "C")) or x.C.shape[0] != self.num_rows or x.F.shape[0] != self.num_rows:
+            raise ValueError(f"ContrastivePairs.subset: x must be the SparseTensor of {self.num_rows} rows the pairs were sampled on")
+        rows = self.rows
+        return type(x)(features=x.F.index_select(0, rows), coordinates=x.C.index_select(0, rows))
+
+
+def _is_count(v, lo):
+    return not isinstance(v, bool) and isinstance(v, int) and v >= lo
+
+
+def sample_pairs(coordinates, teacher, *, K=96, num_anchors=4096, num_negatives=63, num_macro=48, anchor_indices=None, neighbors=None,
+                 generator=None, sim_budget_bytes=2 ** 33):
+    """sample_contrastive_pairs_hybrid (models/affinity_module.py:1099-1136) for every batch entry of a SparseTensor's coordinates at
+    once, entries never mixing.  coordinates: integer [N,4] = batch, x, y, z on the GPU, any row order, unique rows; teacher: floating
+    [N,Dt], one row per coordinate row.  For an anchor a of entry b, with s_j = <Fn_a, Fn_j>, Fn = F.normalize(teacher, dim=1), over the
+    rows j of entry b only:
+      positive[a] = arg-max of s_j over j != a;
+      negative[a] = the num_macro rows of lowest s_j other than a and positive[a], ascending, then the num_negatives - num_macro lowest
+                    of the anchor's K nearest voxels (row a of knn(coordinates, K), a neighbour equal to positive[a] counting as +inf --
+                    the reference's in-place mark, :1125-1133), ascending by (value, slot in the list).
+    Ties go to the lowest KEY row (the order of ops.coords_order_batched: batch, then Morton code), not to the lowest input row: the
+    result then depends on the voxels alone, so permuting the input rows permutes the result and nothing else.  -0 counts as +0, NaN
+    orders above +inf (gp_sampler_select).
+    anchor_indices: i64 [A] input rows, any count, order and entry; without it min(num_anchors, N_b // 3) rows of every entry are drawn
+    without replacement (:1108-1112) on the device -- one torch.rand(N, generator=generator) sorted inside the entries, no loop over
+    entries -- and come grouped by entry.  neighbors: i64 [A,K] input rows given together with anchor_indices, used instead of the kNN
+    (K is then its width).
+    The similarities live in a ragged fp32 buffer (one row of N_b floats per anchor, ops.sim_segments) of at most sim_budget_bytes:
+    anchors are processed in chunks that fit; the result does not depend on the chunking.  -> ContrastivePairs.
+    Host syncs: ONE status read-back, which also carries the anchor and row counts that size the buffer (and a range read-back before
+    it unless the coordinates are int32).  ValueError, all before any kernel of the sampler: what knn refuses; not 1 <= num_macro <=
+    num_negatives <= 63 or num_negatives - num_macro > K - 1; an entry that holds an anchor with fewer than num_macro + 2 rows;
+    anchors or neighbours outside 0..N-1; a neighbour in another entry than its anchor; a teacher of the wrong shape, dtype or device;
+    a budget too small for one anchor row."""
+    who = "sample_pairs"
+    C, T, AI, NB = coordinates, teacher, anchor_indices, neighbors
+    if NB is not None:
+        if AI is None:
+            raise ValueError(f"{who}: neighbors are given per anchor, together with anchor_indices")
+        if not _is_int_tensor(NB) or NB.dim() != 2 or NB.shape[1] < 1:
+            raise ValueError(f"{who}: neighbors must be an integer tensor [A, K], got "
+                             f"{(list(NB.shape), NB.dtype) if torch.is_tensor(NB) else type(NB).__name__}")
+        K = NB.shape[1]
+    _check_k(who, K)
+    if not (_is_count(num_macro, 1) and _is_count(num_negatives, 1) and num_macro <= num_negatives <= 63):
+        raise ValueError(f"{who}: num_macro={num_macro!r}, num_negatives={num_negatives!r}: expected 1 <= num_macro <= num_negatives <= 63")
+    num_micro = num_negatives - num_macro
+    if num_micro > K - 1:
+        raise ValueError(f"{who}: {num_micro} local negatives (num_negatives - num_macro) need K - 1 >= {num_micro} neighbours, K={K}")
+    if not _is_count(num_anchors, 1):
+        raise ValueError(f"{who}: num_anchors={num_anchors!r} must be an integer >= 1")
+    if not _is_count(sim_budget_bytes, 1):
+        raise ValueError(f"{who}: sim_budget_bytes={sim_budget_bytes!r} must be an integer >= 1")
+    _check_coordinates(who, C)
+    n = C.shape[0]
+    dev = C.device
+    if not torch.is_tensor(T) or T.dim() != 2 or T.shape[0] != n or T.shape[1] < 1:
+        raise ValueError(f"{who}: teacher must be [N, Dt] with N = {n} coordinate rows, got "
+                         f"{list(T.shape) if torch.is_tensor(T) else type(T).__name__}")
+    if not T.dtype.is_floating_point:
+        raise ValueError(f"{who}: teacher must be floating point, got {T.dtype}")
+    if T.device != dev:
+        raise ValueError(f"{who}: teacher and coordinates must be CUDA tensors on one device (got {T.device} / {dev}); there is no CPU path")
+    if AI is not None:
+        if not _is_int_tensor(AI) or AI.dim() != 1 or AI.shape[0] < 1 or AI.device != dev:
+            raise ValueError(f"{who}: anchor_indices must be an integer tensor [A] on {dev}, got "
+                             f"{(list(AI.shape), AI.dtype, str(AI.device)) if torch.is_tensor(AI) else type(AI).__name__}")
+        if NB is not None and (NB.shape[0] != AI.shape[0] or NB.device != dev):
+            raise ValueError(f"{who}: neighbors must be [{AI.shape[0]}, K] (one list per anchor) on {dev}, got {list(NB.shape)} on {NB.device}")
+    pad = lambda v: (v + (SIM_ROW_PAD - 1)) // SIM_ROW_PAD * SIM_ROW_PAD
+
+    def extra(perm, rank, keys):
+        """entry bounds of every key row, the anchors' descriptors when they are given, and the status words"""
+        eb = (keys >> 48) & 0xFFFF                                        # the batch index of every key row, ascending
+        first = torch.searchsorted(eb, eb)
+        size = torch.searchsorted(eb, eb, right=True) - first
+        zero = torch.zeros((), dtype=torch.int64, device=dev)
+        bad_a = bad_n = other = zero
+        if AI is not None:
+            a_in = AI.detach().to(torch.int64)
+            bad_a = ((a_in < 0) | (a_in >= n)).sum()
+            a_key = rank.long()[a_in.clamp(0, n - 1)]
+            a_first, a_len = first[a_key], size[a_key]
+            count, floats, longest, shortest = zero + a_in.shape[0], pad(a_len).sum(), a_len.max(), a_len.min()
+            nb_key = None
+            if NB is not None:
+                nb_in = NB.detach().to(torch.int64)
+                bad_n = ((nb_in < 0) | (nb_in >= n)).sum()
+                nb_key = rank.long()[nb_in.clamp(0, n - 1)]
+                other = (first[nb_key] != a_first.unsqueeze(1)).sum()
+        else:
+            a_key = nb_key = None
+            head = first == torch.arange(n, device=dev)                   # one row per entry
+            take = torch.clamp(size // 3, max=num_anchors) * head          # :1108: min(num_anchors, N_b // 3) anchors of the entry
+            on = take > 0
+            count, floats = take.sum(), (take * pad(size)).sum()
+            longest = torch.where(on, size, zero).max()
+            shortest = torch.where(on, size, zero + n).min()
+        words = torch.stack([bad_a, bad_n, other, count, floats, longest, shortest, eb[-1], size.min()])
+        return words, (eb, first, size, a_key, nb_key)
+
+    perm, rank, nbr, keys, words, (eb, first, size, a_key, nb_key) = _ordered_knn(who, C, K, extra=extra, lists=NB is None)
+    bad_a, bad_n, other, A, floats, longest, shortest, top_batch, smallest = words
+    if NB is not None and smallest <= K:                                  # (what the kNN refuses when the lists are its own)
+        raise ValueError(f"{who}: a batch entry holds {smallest} voxels, K={K} neighbours need more than K")
+    if bad_a:
+        raise ValueError(f"{who}: {bad_a} anchor_indices outside 0..{n - 1}")
+    if bad_n:
+        raise ValueError(f"{who}: {bad_n} neighbors outside 0..{n - 1}")
+    if other:
+        raise ValueError(f"{who}: {other} neighbors lie in another batch entry than their anchor")
+    if A == 0:
+        raise ValueError(f"{who}: no entry holds 3 voxels or more: nothing to draw anchors from")
+    if shortest < num_macro + 2:
+        raise ValueError(f"{who}: a batch entry that holds an anchor has {shortest} voxels, num_macro={num_macro} negatives beside the anchor "
+                         f"and its positive need at least {num_macro + 2}")
+    if longest > MAX_ENTRY_ROWS:
+        raise ValueError(f"{who}: a batch entry that holds an anchor has {longest} voxels, more than the {MAX_ENTRY_ROWS} a row of the selection takes")
+    chunk = min(sim_budget_bytes // 4 // pad(longest), MAX_CHUNK_ANCHORS)
+    if chunk < 1:
+        raise ValueError(f"{who}: sim_budget_bytes={sim_budget_bytes} is less than one anchor's row of {longest} similarities "
+                         f"({4 * pad(longest)} bytes)")
+    with torch.cuda.device(dev), torch.no_grad():
+        perm64 = perm.long()
+        if a_key is None:
+            # the draw: rows by (entry, a uniform number); the first min(num_anchors, N_b // 3) of every entry are its anchors
+            u = torch.rand(n, device=dev, generator=generator)
+            by_u = torch.argsort(u)
+            order = by_u[torch.argsort(eb[by_u], stable=True)]
+            place = torch.arange(n, device=dev) - first[order]
+            chosen = place < torch.clamp(size[order] // 3, max=num_anchors)
+            a_sorted = order[torch.argsort(~chosen, stable=True)[:A]]     # (A is known from the read-back: no second sync)
+            back = None
+        else:
+            by_key = torch.argsort(a_key)                                 # anchors grouped by entry, as the similarity kernel takes them
+            a_sorted = a_key[by_key]
+            back = torch.empty_like(by_key)
+            back[by_key] = torch.arange(A, device=dev)
+        a_first, a_len = first[a_sorted].to(torch.int32), size[a_sorted].to(torch.int32)
+        a_row = a_sorted.to(torch.int32)
+        offs = torch.cumsum(pad(size[a_sorted]), 0)
+        offs = torch.cat([offs.new_zeros(1), offs])                       # [A + 1]: the rows' starts as if all were in one buffer
+        if num_micro:
+            lists = nbr.index_select(0, a_sorted) if nb_key is None else nb_key.index_select(0, by_key).to(torch.int32)
+            lists = lists.contiguous()
+        Dt = T.shape[1]
+        Dp = (Dt + 31) // 32 * 32
+        Tk = torch.zeros((n, Dp), dtype=torch.float32, device=dev) if Dp != Dt else torch.empty((n, Dt), dtype=torch.float32, device=dev)
+        ops.gather_rows(_rows_f32(T.detach()), Dt, perm64, out=Tk)         # the teacher rows in the key order, zero columns up to Dp
+        hi, lo = ops.normalize_split_f16(Tk)
+        del Tk
+        buf = torch.empty(min(floats, chunk * pad(longest)), dtype=torch.float32, device=dev)
+        positive = torch.empty(A, dtype=torch.int64, device=dev)
+        negative = torch.empty((A, num_negatives), dtype=torch.int64, device=dev)
+        for a0 in range(0, A, chunk):
+            a1 = min(a0 + chunk, A)
+            off = (offs[a0:a1] - offs[a0]).contiguous()
+            sl = slice(a0, a1)
+            ops.sim_segments(hi, lo, a_row[sl], a_first[sl], a_len[sl], off, longest, buf)
+            pos, macro = ops.sampler_select_segments(buf, off, a_len[sl], a_first[sl], a_sorted[sl], num_macro, longest)
+            positive[sl] = pos
+            negative[sl, :num_macro] = macro
+            if num_micro:
+                negative[sl, num_macro:] = ops.sampler_micro_segments(buf, off, a_first[sl], a_len[sl], lists[sl], pos, num_micro)
+        # key rows -> input rows, and the anchors back into the caller's order
+        anchor, entry = perm64[a_sorted], eb[a_sorted]
+        positive, negative = perm64[positive], perm64[negative]
+        if back is not None:
+            anchor, entry, positive, negative = anchor[back], entry[back], positive[back], negative[back]
+    return ContrastivePairs(anchor, positive, negative, entry, n, top_batch + 1)
+
+
+class _InfoNCE(torch.autograd.Function):
+    """loss = sum_a w_a l_a and dE by ops.infonce_weighted_fwd_bwd in the forward pass; backward hands g * dE to the embeddings"""
+
+    @staticmethod
+    def forward(ctx, E, s2v, index, A, Nn, temperature, w):
+        loss, per_anchor, dE = ops.infonce_weighted_fwd_bwd(_rows_f32(E.detach()), s2v, index, A, Nn, temperature, w)
+        ctx.save_for_backward(dE)
+        ctx.dtype = E.dtype
+        ctx.mark_non_differentiable(per_anchor)
+        return loss, per_anchor
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        (dE,) = ctx.saved_tensors
+        return (g * dE).to(ctx.dtype), None, None, None, None, None, None
+
+
+def info_nce(embeddings, pairs, *, temperature=0.07, reduction="anchor"):
+    """The InfoNCE of SonataXAffinityTrainer.forward (models/affinity_module.py:1219-1233) over the pairs of sample_pairs: per anchor
+    the cross entropy of (<a, p>, <a, n_1>, ...) / temperature on the normalised embeddings, target 0.  embeddings: a SparseTensor or
+    a floating tensor of width <= 256 with S = len(pairs.rows) rows (the student's output on pairs.subset(x)) or N rows (on all of x).
+    reduction "anchor": the mean over all anchors -- with one entry the reference's loss; "entry": the mean, over the entries that have
+    anchors, of each entry's mean -- what one scene per rank under DDP averages to.  -> 0-d fp32 loss under autograd (backward hands
+    g * dE to the embeddings; no double backward); loss.per_entry: fp32 [num_entries], every entry's mean, detached, NaN for an entry
+    without anchors.  ValueError before any kernel: a row count that is neither S nor N, a width above 256, an unknown reduction, a
+    temperature that is not positive."""
+    who = "info_nce"
+    if not isinstance(pairs, ContrastivePairs):
+        raise ValueError(f"{who}: pairs must be the ContrastivePairs of sample_pairs, got {type(pairs).__name__}")
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"{who}: reduction={reduction!r}, expected one of {REDUCTIONS}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0:
+        raise ValueError(f"{who}: temperature={temperature!r} must be positive")
+    E = embeddings.F if hasattr(embeddings, "F") and hasattr(embeddings, "C") else embeddings
+    if not torch.is_tensor(E) or E.dim() != 2 or not E.dtype.is_floating_point:
+        raise ValueError(f"{who}: embeddings must be a SparseTensor or a floating tensor [rows, d], got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    dev = pairs.anchor.device
+    if E.device != dev:
+        raise ValueError(f"{who}: embeddings and pairs must be on one device (got {E.device} / {dev}); there is no CPU path")
+    if not 1 <= E.shape[1] <= 256:
+        raise ValueError(f"{who}: embedding width {E.shape[1]} outside 1..256")
+    S, N = pairs.rows.shape[0], pairs.num_rows
+    if E.shape[0] not in (S, N):
+        raise ValueError(f"{who}: embeddings have {E.shape[0]} rows, expected S = {S} (the rows of pairs.subset) or N = {N} (all rows)")
+    A, Nn = pairs.negative.shape
+    with torch.cuda.device(dev):
+        # (S == N: every row was sampled, rows is 0..N-1 and both readings are the same)
+        s2v = pairs.rows if E.shape[0] == N else torch.arange(S, device=dev)
+        counts = torch.zeros(pairs.num_entries, dtype=torch.float32, device=dev).index_add_(
+            0, pairs.entry, torch.ones(A, dtype=torch.float32, device=dev))
+        if reduction == "anchor":
+            w = torch.full((A,), 1.0 / A, dtype=torch.float32, device=dev)
+        else:
+            w = 1.0 / ((counts > 0).sum() * counts[pairs.entry])
+        loss, per_anchor = _InfoNCE.apply(E, s2v.contiguous(), pairs.index.contiguous(), A, Nn, float(temperature), w.contiguous())
+        loss.per_entry = torch.zeros_like(counts).index_add_(0, pairs.entry, per_anchor.detach()) / counts
+    return loss
+
+
+def contrastive_loss(student, x, teacher, *, subset=True, temperature=0.07, reduction="anchor", **kw):
+    """sample_pairs on x.C and the teacher rows, the student on the sampled rows (subset=True: pairs.subset(x), as the reference's
+    forward runs it on the sampled voxels only, :1192-1212) or on all of x, info_nce on what it returns.  The student is called as the
+    caller left it: its mode and the grad state untouched.  kw: sample_pairs's options.  -> the loss of info_nce, with loss.pairs."""
+    if not (hasattr(x, "F") and hasattr(x, "C")):
+        raise ValueError(f"contrastive_loss: x must be a SparseTensor (an object with .F and .C), got {type(x).__name__}")
+    pairs = sample_pairs(x.C, teacher, **kw)
+    loss = info_nce(student(pairs.subset(x) if subset else x), pairs, temperature=temperature, reduction=reduction)
+    loss.pairs = pairs
+    return loss

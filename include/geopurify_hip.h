@@ -657,6 +657,14 @@ int gp_infonce_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, cons
                        int64_t num_samples, const int64_t *point_to_batch, int64_t num_anchors,
                        int32_t num_negatives, float temperature, float *loss, float *de, int64_t ld_de,
                        void *workspace, size_t workspace_bytes, void *stream);
+/* The same InfoNCE (affinity_module.py:1219-1233) with a weight per anchor: loss = sum_a weights[a] l_a (weights f32 [A]; 1 / A   */
+/* each is the mean of gp_infonce_fwd_bwd), de follows, and anchor_loss f32 [A] receives the l_a.  The reductions over the batch    */
+/* entries of a SparseTensor ("anchor": 1 / A; "entry": 1 / (entries with anchors x anchors of a's entry)) are choices of weights.  */
+/* Same limits, same workspace, same fp64 gradient accumulation.                                                                     */
+int gp_infonce_weighted_fwd_bwd(const float *e, int64_t ld_e, int64_t nv, int32_t d, const int64_t *sample_to_voxel,
+                                int64_t num_samples, const int64_t *point_to_batch, int64_t num_anchors, int32_t num_negatives,
+                                float temperature, const float *weights, float *loss, float *anchor_loss, float *de, int64_t ld_de,
+                                void *workspace, size_t workspace_bytes, void *stream);
 /* Weight gradient of a 3x3x3 layer on the matrix cores: dW[k] = X[in_k]^T dY[out_k] (f16 hi/lo operands, fp32    */
 /* accumulate).  x_hi/x_lo f16 [nv, ld_x >= cin_pad]; y_hi/y_lo f16 [nv+1, ld_y >= cout] with row nv all zero;       */
 /* pair_in/pair_out i32: per offset its (input row, output row) pairs padded to a multiple of 32 with (0, nv);      */
@@ -687,6 +695,29 @@ int gp_knn_points_f32(const float *xyz, int64_t n, const int64_t *queries, int64
 /* 1 <= k < 1024, k + 2 <= n <= 3 145 728 (12 288 groups of at most 256 elements in LDS).  -0 counts as +0; NaNs order above +inf.        */
 int gp_sampler_select(const float *sim, int64_t ld, int64_t num_anchors, int64_t n, const int64_t *anchor_idx, int32_t k,
                       int64_t *positive, int64_t *macro, void *stream);
+/* The sampler over a batched SparseTensor (affinity_module.py:1099-1136 for several scenes at once): rows live in the key order of    */
+/* gp_coords_order_batched, so a batch entry is one contiguous row range, and an anchor is compared with the rows of ITS entry only.  */
+/* The similarity (affinity_module.py:1113-1115) is a ragged fp32 buffer: anchor a owns the seg_len[a] floats at out + row_off[a],    */
+/* out[row_off[a] + j] = <x[anchor_row[a]], x[seg_first[a] + j]> with x = hi + lo, the f16 planes [*, ld_h] of                        */
+/* gp_normalize_split_f16 (d % 32 == 0: pad with zero columns), three products hi.hi + hi.lo + lo.hi accumulated in fp32 on           */
+/* v_mfma_f32_16x16x32_f16.  The anchors must be grouped by entry (equal seg_first consecutive); row_off[a] % 4 == 0 (16-byte        */
+/* aligned rows) and the extents [row_off[a], row_off[a] + seg_len[a]) must not overlap; floats between them are not written.        */
+/* max_len = the largest seg_len; at most 65535 * 64 anchors per call.                                                                */
+int gp_sim_segments_f16x3(const void *hi, const void *lo, int64_t ld_h, int32_t d, const int32_t *anchor_row, const int32_t *seg_first,
+                          const int32_t *seg_len, const int64_t *row_off, int64_t num_anchors, int64_t max_len, float *out,
+                          void *stream);
+/* gp_sampler_select (affinity_module.py:1116-1124) over such ragged rows: row a = the row_len[a] floats at sim + row_off[a], element */
+/* j standing for index row_base[a] + j; anchor_idx, positive and macro are such indices (global key rows).  Same kernel, same order  */
+/* rules.  1 <= k < 1024, every row_len >= k + 2, max_len = the largest row_len <= 3 145 728.                                        */
+int gp_sampler_select_segments(const float *sim, const int64_t *row_off, const int32_t *row_len, const int32_t *row_base,
+                               int64_t num_anchors, int64_t max_len, const int64_t *anchor_idx, int32_t k, int64_t *positive,
+                               int64_t *macro, void *stream);
+/* The local negatives (affinity_module.py:1125-1133): micro[a, 0:num_micro] = the entries of nbr[a, 0:k] (i32 key rows, leading      */
+/* dimension ld_nbr) with the num_micro lowest similarities in anchor a's ragged row, ascending by (value, slot in the list); an      */
+/* entry equal to positive[a] counts as +inf (the reference's in-place mark).  1 <= num_micro <= k <= 128.                           */
+int gp_sampler_micro_segments(const float *sim, const int64_t *row_off, const int32_t *seg_first, const int32_t *seg_len,
+                              const int32_t *nbr, int64_t ld_nbr, int32_t k, const int64_t *positive, int64_t num_anchors,
+                              int32_t num_micro, int64_t *micro, void *stream);
 /* F.normalize(x, p=2, dim=1) (affinity_module.py:1114) written as the f16 hi/lo planes of the similarity GEMM's operands:            */
 /* hi + lo = x[r] / max(|x[r]|_2, eps) for r < n; rows n <= r < n_pad of the planes are zero.  d % 4 == 0, x 16-byte aligned.         */
 int gp_normalize_split_f16(const float *x, int64_t ld_x, int32_t d, int64_t n, int64_t n_pad, float eps, void *hi, void *lo,
