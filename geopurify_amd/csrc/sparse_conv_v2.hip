@@ -927,8 +927,71 @@ __device__ __forceinline__ void conv_gather_sum_q24(const unsigned char *__restr
     }
 }
 
-template <bool WIDE /* cout > 512: a second register set for columns 512 .. */, bool NO_CENTRE = false /* tuning twin: see knob 3, 256 */>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+// The pipelined row walk of conv_phase2_q24_kernel (WALK != 0) keeps TWO batches of partial rows per wave: the one being decoded and the
+// first batch of the wave's NEXT row, whose loads were issued a row earlier.  A batch is statically indexed registers: per partial row the
+// lane's 16-byte piece, its 8-byte piece and the exponents.  The position of a partial row is wave-uniform: it is read with v_readlane into
+// an SGPR (the lane index comes from the ballot mask), so a load takes a scalar row base + the lane's constant 32-bit offset, and the row's
+// NQ = cout / 128 exponent bytes (4 at 512 columns: one aligned word; 2 at 256: half of one) come as ONE scalar load of the aligned word
+// that holds them, the lane picking its quarter's byte with v_perm.  Reads only: nothing is stored through the scalar unit.  The decode is
+// that of conv_gather_sum_q24, operation for operation.
+#ifndef GP_P2_NL
+#define GP_P2_NL 4              // partial rows per batch (the sweep: profiles/conv_phase2_walk.log)
+#endif
+#ifndef GP_P2_WAVES
+#define GP_P2_WAVES 4           // waves per SIMD of the pipelined walk; gp_sparse_conv_f16x3 sizes the resident grid from it
+#endif
+template <int NL, int NQ>
+__device__ __forceinline__ void q24_batch_issue(u32x4 (&th)[NL], u32x2 (&tl)[NL], unsigned (&te)[NL], unsigned (&tsel)[NL], int &cnt,
+                                                const unsigned char *__restrict__ pb, const unsigned char *__restrict__ pb_e, int mypos,
+                                                unsigned long long &m, unsigned off16, unsigned off8, bool act, int pair_base) {
+    const int left = __builtin_popcountll(m);
+    cnt = left < NL ? left : NL;
+#pragma unroll
+    for (int i = 0; i < NL; ++i)
+        if (i < cnt) {                                       // wave-uniform: no load is issued for a slot without a partial row
+            const int k = __builtin_ctzll(m);
+            m &= m - 1;
+            // (byte offsets fit 32 bits: the host checks every chunk before the first launch)
+            const unsigned pos = (unsigned)(__builtin_amdgcn_readlane(mypos, k) - pair_base);
+            const unsigned char *row = pb + (size_t)(pos * (unsigned)(NQ * 384));
+            const unsigned eo = pos * (unsigned)NQ;          // NQ divides 4: the row's exponent bytes lie inside one aligned word
+            te[i] = *reinterpret_cast<const unsigned *>(pb_e + (size_t)(eo & ~3u));
+            tsel[i] = 0x0c0c0c00u | (eo & 3u);               // v_perm selector of the row's first exponent byte (+ the lane's quarter)
+            if (act) {
+                th[i] = *reinterpret_cast<const u32x4 *>(row + off16);
+                tl[i] = *reinterpret_cast<const u32x2 *>(row + off8);
+            }
+        }
+}
+// one partial row's 24 bytes of this lane (h: the 16-byte piece, l: the 8-byte piece; e: the quarter's exponent byte) added into a[8].
+// (The pieces come BY VALUE: read element-wise through the array references, the two batches stayed in scratch memory.)
+__device__ __forceinline__ void q24_row_decode(const u32x4 h, const u32x2 l, unsigned e, float (&a)[8]) {
+    const float s = e == 255u ? __uint_as_float(0x7fc00000u) : __uint_as_float((e - 21u) << 23);   // 2^(E - 148)
+    const unsigned d0 = h.x, d1 = h.y, d2 = h.z, d3 = h.w, d4 = l.x, d5 = l.y;
+    const unsigned u0 = __builtin_amdgcn_perm(0u, d0, 0x0c020100u), u1 = __builtin_amdgcn_perm(d1, d0, 0x0c050403u);
+    const unsigned u2 = __builtin_amdgcn_perm(d2, d1, 0x0c040302u), u3 = __builtin_amdgcn_perm(0u, d2, 0x0c030201u);
+    const unsigned u4 = __builtin_amdgcn_perm(0u, d3, 0x0c020100u), u5 = __builtin_amdgcn_perm(d4, d3, 0x0c050403u);
+    const unsigned u6 = __builtin_amdgcn_perm(d5, d4, 0x0c040302u), u7 = __builtin_amdgcn_perm(0u, d5, 0x0c030201u);
+    a[0] = fmaf((float)u0 - 4194304.f, s, a[0]);
+    a[1] = fmaf((float)u1 - 4194304.f, s, a[1]);
+    a[2] = fmaf((float)u2 - 4194304.f, s, a[2]);
+    a[3] = fmaf((float)u3 - 4194304.f, s, a[3]);
+    a[4] = fmaf((float)u4 - 4194304.f, s, a[4]);
+    a[5] = fmaf((float)u5 - 4194304.f, s, a[5]);
+    a[6] = fmaf((float)u6 - 4194304.f, s, a[6]);
+    a[7] = fmaf((float)u7 - 4194304.f, s, a[7]);
+}
+template <int NL>
+__device__ __forceinline__ void q24_batch_decode(const u32x4 (&th)[NL], const u32x2 (&tl)[NL], const unsigned (&te)[NL], const unsigned (&tsel)[NL],
+                                                 int cnt, unsigned q, bool act, float (&a)[8]) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i)
+        if (i < cnt && act) q24_row_decode(th[i], tl[i], __builtin_amdgcn_perm(0u, te[i], tsel[i] + q), a);
+}
+
+template <bool WIDE /* cout > 512: a second register set for columns 512 .. */, bool NO_CENTRE = false /* tuning twin: see knob 3, 256 */,
+          int WALK = 0 /* 0: one row at a time (the reference walk); pipelined across rows: 1 at cout = 256, 2 at cout = 512 */>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WALK ? GP_P2_WAVES : 4, WALK ? GP_P2_WAVES : 4)))
 conv_phase2_q24_kernel(const unsigned char *__restrict__ pb, int64_t e_off, const int32_t *__restrict__ pair_pos, int64_t nv,
                        int kv, int cout, const float *__restrict__ scale, const float *__restrict__ shift,
                        const float *__restrict__ residual, int64_t ld_res, int relu, float *__restrict__ y, int64_t ld_y,
@@ -961,6 +1024,115 @@ conv_phase2_q24_kernel(const unsigned char *__restrict__ pb, int64_t e_off, cons
             sc0[h * 4] = a.x; sc0[h * 4 + 1] = a.y; sc0[h * 4 + 2] = a.z; sc0[h * 4 + 3] = a.w;
             sh0[h * 4] = b.x; sh0[h * 4 + 1] = b.y; sh0[h * 4 + 2] = b.z; sh0[h * 4 + 3] = b.w;
         }
+    }
+    if constexpr (WALK != 0) {
+        // The pipelined walk (columns [0, 512) only: the wide form keeps the reference walk).  While row u is decoded, reduced and stored, the
+        // first batch of the wave's next row u + W is in flight, and the positions of row u + 2 W are being loaded.  Per row:
+        //   decode the landed batch (+ further batches of a row with more than NL partial rows, as in the reference walk) -> ONE wait for
+        //   everything outstanding (the next row's batch, issued a row ago) -> epilogue, stores -> issue row u + 2 W into the freed batch.
+        // The wait stands BEFORE the stores and the new loads, so it never waits for what was just issued, and every count it depends on is
+        // static.  Nothing is loaded for a row at or beyond row_end (its positions are all -1), nor for a slot without a partial row.
+        static_assert(!WIDE && !NO_CENTRE, "the pipelined walk is for cout = 256 and 512");
+        constexpr int NQ = 2 * WALK, NL = GP_P2_NL;                                            // NQ = cout / 128: the host picks WALK by it
+        const int c = lane * 8;
+        const bool act = c < NQ * 128;
+        const unsigned q = (unsigned)c >> 7, f = ((unsigned)c >> 3) & 15u;                     // quarter, lane in it
+        const unsigned off16 = q * 384u + f * 16u, off8 = q * 384u + 256u + f * 8u;            // the lane's two pieces inside a partial row
+        const unsigned char *pb_e = pb + e_off;
+        const unsigned long long kvmask = (kv >= 64) ? ~0ull : ((1ull << kv) - 1ull);
+        auto load_pos = [&](int64_t r) { return (lane < kv && r < row_end) ? pair_pos[(int64_t)lane * nv + r] : -1; };
+        auto wait_all = [] { __builtin_amdgcn_s_waitcnt(0x0f70); };                               // s_waitcnt vmcnt(0)
+        u32x4 thA[NL], thB[NL];
+        u32x2 tlA[NL], tlB[NL];
+        unsigned teA[NL], teB[NL], tselA[NL], tselB[NL];
+        int cntA, cntB;
+        int posA = mypos_next, posB = load_pos(u + n_waves);
+        unsigned long long mA = __ballot(posA >= 0) & kvmask;
+        q24_batch_issue<NL, NQ>(thA, tlA, teA, tselA, cntA, pb, pb_e, posA, mA, off16, off8, act, pair_base);
+        wait_all();
+        unsigned long long mB = __ballot(posB >= 0) & kvmask;
+        q24_batch_issue<NL, NQ>(thB, tlB, teB, tselB, cntB, pb, pb_e, posB, mB, off16, off8, act, pair_base);
+        int pos2 = load_pos(u + 2 * n_waves);
+        // one row: th / tl / te hold its first batch (landed), posX / mX its positions and the partial rows not yet loaded
+        auto row = [&](u32x4 (&th)[NL], u32x2 (&tl)[NL], unsigned (&te)[NL], unsigned (&tsel)[NL], int &cnt, int &posX, unsigned long long &mX) __attribute__((always_inline)) {
+            // the residual of this row, asked for ahead of the decode (fp32 rows OR split planes: the host checks that it is one of them)
+            u32x4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
+            float ri = 1.f;
+            if (act) {
+                if (residual) {
+                    r0 = *reinterpret_cast<const u32x4 *>(residual + u * ld_res + c);
+                    r1 = *reinterpret_cast<const u32x4 *>(residual + u * ld_res + c + 4);
+                } else if (res_hi) {
+                    const _Float16 *rph = r_il ? res_hi + u * ld_rh + ((c >> 5) << 6) + (c & 31) : res_hi + u * ld_rh + c;
+                    const _Float16 *rpl = r_il ? rph + 32 : res_lo + u * ld_rh + c;
+                    r0 = *reinterpret_cast<const u32x4 *>(rph);
+                    r1 = *reinterpret_cast<const u32x4 *>(rpl);
+                    if (res_inv) ri = res_inv[u];
+                }
+            }
+            float a[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a[j] = 0.f;
+            q24_batch_decode<NL>(th, tl, te, tsel, cnt, q, act, a);
+            while (mX) {
+                q24_batch_issue<NL, NQ>(th, tl, te, tsel, cnt, pb, pb_e, posX, mX, off16, off8, act, pair_base);
+                q24_batch_decode<NL>(th, tl, te, tsel, cnt, q, act, a);
+            }
+            wait_all();                                          // the next row's batch, the residual, the positions of row u + 2 W
+            float amax = 0.f;
+            if (act) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] = a[j] * sc0[j] + sh0[j];
+                if (residual) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { a[j] += __uint_as_float(r0[j]); a[j + 4] += __uint_as_float(r1[j]); }
+                }
+                if (res_hi) {
+                    const f16x8 rh = __builtin_bit_cast(f16x8, r0), rl = __builtin_bit_cast(f16x8, r1);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) a[j] += ((float)rh[j] + (float)rl[j]) * ri;
+                }
+                if (relu) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) a[j] = fmaxf(a[j], 0.f);
+                }
+                if (y) {
+                    *reinterpret_cast<float4 *>(y + u * ld_y + c) = make_float4(a[0], a[1], a[2], a[3]);
+                    *reinterpret_cast<float4 *>(y + u * ld_y + c + 4) = make_float4(a[4], a[5], a[6], a[7]);
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(a[j]));
+            }
+            float s = 1.f;
+            if (rowscale) {                                      // (see conv_phase2_kernel)
+                amax = gp_wave_max(amax);
+                s = gp_pow2_for(amax);
+                if (lane == 0) y_inv_scale[u] = 1.f / s;
+            }
+            if (y_hi && act) {
+                f16x8 h, l;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) gp_split_f16(a[j] * s, h, l, j);
+                _Float16 *ph = y_il ? y_hi + u * ld_yh + ((c >> 5) << 6) + (c & 31) : y_hi + u * ld_yh + c;
+                _Float16 *pl = y_il ? ph + 32 : y_lo + u * ld_yh + c;
+                *reinterpret_cast<f16x8 *>(ph) = h;
+                *reinterpret_cast<f16x8 *>(pl) = l;
+            }
+            // this batch is free: the first batch of row u + 2 W goes into it, and the positions of row u + 3 W are asked for
+            posX = pos2;
+            mX = __ballot(posX >= 0) & kvmask;
+            q24_batch_issue<NL, NQ>(th, tl, te, tsel, cnt, pb, pb_e, posX, mX, off16, off8, act, pair_base);
+            pos2 = load_pos(u + 3 * n_waves);
+        };
+        for (;;) {
+            row(thA, tlA, teA, tselA, cntA, posA, mA);
+            u += n_waves;
+            if (u >= row_end) break;
+            row(thB, tlB, teB, tselB, cntB, posB, mB);
+            u += n_waves;
+            if (u >= row_end) break;
+        }
+        return;
     }
     for (; u < row_end; u += n_waves) {
         const int mypos = mypos_next;
@@ -1300,7 +1472,7 @@ extern "C" int gp_sparse_conv_f16x3(const float *x, int64_t ld_x, const void *x_
                                     const int32_t *chunk_pair_off_host, const float *x_row_inv_scale, float *y_row_inv_scale,
                                     const void *res_hi, const void *res_lo, int64_t ld_rh, const float *res_row_inv_scale, int32_t w_blocked,
                                     int32_t plane_flags, void *stream_) {
-    GP_CHECK_ARG(plane_flags >= 0 && plane_flags < 32, "gp_sparse_conv_f16x3: plane_flags is a mask of 1 (x interleaved), 2 (y interleaved), 4 (residual interleaved), 8 (fp32 partial rows), 16 (one dense offset: phase 1 writes y)");
+    GP_CHECK_ARG(plane_flags >= 0 && plane_flags < 64, "gp_sparse_conv_f16x3: plane_flags is a mask of 1 (x interleaved), 2 (y interleaved), 4 (residual interleaved), 8 (fp32 partial rows), 16 (one dense offset: phase 1 writes y), 32 (phase 2 walks one row at a time)");
     // bit 4: ONE offset whose map holds every output row (a gather-GEMM: the training sampler's anchors x points similarity): pair p IS
     // output row p, nothing is summed, so phase 1 stores its fp32 rows straight into y and phase 2 (a 2 x 2.4 GB round trip there) is not run
     const bool direct = (plane_flags & 16) != 0;
@@ -1420,11 +1592,18 @@ extern "C" int gp_sparse_conv_f16x3(const float *x, int64_t ld_x, const void *x_
         int64_t p2_res = (int64_t)gp_cu_count() * p2_wg_per_cu;
         // (the 24-bit kernel: 4 waves per SIMD at 128 registers -- 4 workgroups per CU are one resident round)
         if (q24 && p2_wg_per_cu == 6) p2_res = (int64_t)gp_cu_count() * 4;
+        // bit 5 of plane_flags ASKS for the reference walk (one row per wave at a time): what the pipelined walk is compared with, bit for
+        // bit, and the A side of an in-library A/B.  The wide form (cout > 512) and the centre-less tuning twin keep the reference walk: a
+        // second batch beside the wide form's two accumulator sets does not fit its registers.
+        const bool p2_pipe = q24 && cout <= 512 && !(plane_flags & 32) && !(g_conv_ablate & 256);
+        if (p2_pipe) p2_res = (int64_t)gp_cu_count() * GP_P2_WAVES;     // (GP_P2_WAVES waves per SIMD = as many 4-wave workgroups per CU)
         const unsigned p2_grid = (unsigned)((p2_res > 0 && p2_res < p2_full) ? p2_res : p2_full);
 #define P2Q_ARGS reinterpret_cast<const unsigned char *>(partial), q_e_off, pair_pos, nv, kv, cout, scale, shift, residual, ld_res, \
                  relu, y, ld_y, static_cast<_Float16 *>(y_hi), static_cast<_Float16 *>(y_lo), ld_yh, row_begin, row_count, pair_base, y_row_inv_scale, \
                  static_cast<const _Float16 *>(res_hi), static_cast<const _Float16 *>(res_lo), ld_rh, res_row_inv_scale, plane_flags
-        if (q24 && cout <= 512 && (g_conv_ablate & 256)) conv_phase2_q24_kernel<false, true><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);
+        if (p2_pipe && cout == 512) conv_phase2_q24_kernel<false, false, 2><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);
+        else if (p2_pipe) conv_phase2_q24_kernel<false, false, 1><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);       // (cout = 256: cout is a multiple of TN)
+        else if (q24 && cout <= 512 && (g_conv_ablate & 256)) conv_phase2_q24_kernel<false, true><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);
         else if (q24 && cout > 512) conv_phase2_q24_kernel<true><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);
         else if (q24) conv_phase2_q24_kernel<false><<<p2_grid, 256, 0, s>>>(P2Q_ARGS);
 #undef P2Q_ARGS

@@ -522,7 +522,8 @@ def pow2_scale(x, d=None):
 
 
 def sparse_conv_f16x3(x, pairs, w_hi, w_lo, scale=None, shift=None, residual=None, relu=False, out=None,
-                      x_split=None, out_split=None, x_row_inv=None, out_row_inv=None, want_f32=True, fp32_partials=False, dense_single_offset=False):
+                      x_split=None, out_split=None, x_row_inv=None, out_row_inv=None, want_f32=True, fp32_partials=False, dense_single_offset=False,
+                      reference_walk=False):
     """x fp32 [nv, >=cin] and/or x_split=(hi, lo) f16 (pre-split operand -> LDS-DMA path);
     out_split=(hi, lo) f16 buffers to also receive the split output.  x_row_inv fp32 [nv]: the per-row inverse scales of
     a row-scaled x_split; out_row_inv fp32 [nv]: receive the output's (out_split is then row-scaled).
@@ -535,7 +536,9 @@ def sparse_conv_f16x3(x, pairs, w_hi, w_lo, scale=None, shift=None, residual=Non
     are checked against; also what a call takes by itself when a chunk's 24-bit rows would pass 4 GiB) -- an explicit argument of the
     call (plane_flags bit 3), not a process-wide switch.
     dense_single_offset=True (plane_flags bit 4): kv = 1 and every output row has its pair -- a gather-GEMM; phase 1 writes the fp32 output
-    itself, no partial rows, no phase 2."""
+    itself, no partial rows, no phase 2.
+    reference_walk=True (plane_flags bit 5): phase 2 over the 24-bit partial rows walks its output rows one at a time -- the form that
+    the pipelined walk (the default up to 512 columns) is compared with bit for bit; an argument of the call, not a process-wide switch."""
     lib = _lib.load()
     res_planes = residual if isinstance(residual, (tuple, list)) else None
     if res_planes is not None:
@@ -557,7 +560,7 @@ def sparse_conv_f16x3(x, pairs, w_hi, w_lo, scale=None, shift=None, residual=Non
     yh, yl = out_split if out_split is not None else (None, None)
     # interleaved rows ([K step][hi 32 | lo 32], ONE tensor of 2 x channels halfs per row): given as (tensor, None)
     plane_flags = (1 if (xh is not None and xl is None) else 0) | (2 if (yh is not None and yl is None) else 0) | \
-                  (4 if (rh is not None and rl is None) else 0) | (8 if fp32_partials else 0) | (16 if dense_single_offset else 0)
+                  (4 if (rh is not None and rl is None) else 0) | (8 if fp32_partials else 0) | (16 if dense_single_offset else 0) | (32 if reference_walk else 0)
     check(lib.gp_sparse_conv_f16x3(_ptr(x), x.stride(0) if x is not None else 0, _ptr(xh), _ptr(xl),
                                    xh.stride(0) if xh is not None else 0, _ptr(pairs.pair_in), _ptr(pairs.pair_pos),
                                    _ptr(pairs.pair_off), _ptr(pairs.tile_start), _ptr(pairs.tile_desc), pairs.nseg, pairs.num_pairs, nv, kv, _ptr(w_hi), _ptr(w_lo), cin, cout,
