@@ -155,6 +155,15 @@ SIGNATURES = {
     "gp_nn1_batched_workspace_bytes": (c_size_t, [c_int64]),
     "gp_nn1_batched": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
     "gp_iou_hist_batched_i64": (c_int32, [_P, _P, c_int64, _P, _P, c_int64, c_int32, c_int32, POINTER(c_int64), c_int32, _P, _P]),
+    "gp_sparse_conv_tiles": (c_int32, [POINTER(c_int32)]),
+    "gp_segment_loss_col_step": (c_int32, []),
+    "gp_segment_loss_unit_rows": (c_int32, [_P, c_int64, c_int32, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "gp_segment_loss_items_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gp_segment_loss_items": (c_int32, [_P, _P, c_int64, _P, _P, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, _P, _P, _P, _P, _P, _P,
+                                        _P, c_size_t, _P]),
+    "gp_segment_loss_rows": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "gp_segment_loss_reduce_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_segment_loss_reduce": (c_int32, [_P, _P, c_int64, _P, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "gp_fused_decode_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gp_fused_decode": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
 }

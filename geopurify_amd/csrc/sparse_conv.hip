@@ -214,3 +214,11 @@ extern "C" int gp_sparse_conv(const float *x, int64_t ld_x, const int32_t *nbr_m
     GP_CHECK_LAUNCH();
     return GP_OK;
 }
+
+extern "C" int gp_sparse_conv_tiles(int32_t *tiles) {
+    GP_CHECK_ARG(tiles, "gp_sparse_conv_tiles: null argument");
+    tiles[0] = BM;
+    tiles[1] = BN;
+    tiles[2] = BK;
+    return GP_OK;
+}

@@ -1328,6 +1328,128 @@ def iou_hist_batched(pred, coords, target, num_batches, num_classes, ignore_ids,
     return counts
 
 
+# ------------------------------------------------------------------------------------------ cross-entropy of rows against text embeddings
+SEGMENT_LOSS_MAX_ENTRIES = 65536                            # entry_cnt / entry_w of gp_segment_loss_items
+SEGMENT_LOSS_REDUCTIONS = {"item": 0, "entry": 1}
+
+
+def sparse_conv_tiles():
+    """(row tile, column tile -- cout is a multiple of it --, channel step -- cin is a multiple of it --) of gp_sparse_conv, asked of
+    the library (gp_sparse_conv_tiles): what a caller pads its operands to, and where the tests put their edge cases"""
+    t = (ctypes.c_int32 * 3)()
+    check(_lib.load().gp_sparse_conv_tiles(t), "gp_sparse_conv_tiles")
+    return tuple(int(v) for v in t)
+
+
+def segment_loss_col_step():
+    """columns per lane step of the row kernels of gp_segment_loss_* (asked of the library)"""
+    return int(_lib.load().gp_segment_loss_col_step())
+
+
+def segment_loss_unit_rows(y, d=None, u=None, zero=None):
+    """(u fp32 [n, d_pad] = the unit rows of y fp32 [n, >= d] (y / max(|y|, 1e-12), zero columns d .. d_pad-1), zero u8 [n] =
+    (sum |y_i| == 0)) (gp_segment_loss_unit_rows).  u: optional caller-owned rows, their width is d_pad; default d padded to the GEMM's
+    channel step."""
+    lib = _lib.load()
+    n = _rows(y, "y").shape[0]
+    d = y.shape[1] if d is None else int(d)
+    if u is None:
+        kp = sparse_conv_tiles()[2]
+        u = torch.empty((n, (d + kp - 1) // kp * kp), dtype=torch.float32, device=y.device)
+    _rows(u, "u", n)
+    zero = torch.empty(n, dtype=torch.uint8, device=y.device) if zero is None else _chk(zero, torch.uint8, "zero")
+    if zero.shape != (n,):
+        raise ValueError(f"segment_loss_unit_rows: expected zero [{n}], got {list(zero.shape)}")
+    check(lib.gp_segment_loss_unit_rows(_ptr(y), y.stride(0), d, n, _ptr(u), u.stride(0), u.shape[1], _ptr(zero), _stream()),
+          "gp_segment_loss_unit_rows")
+    return u, zero
+
+
+class SegmentLossItems:
+    """The valid items of gp_segment_loss_items: row_valid u8 [n] (per-voxel labels) or item_off i64 [n+1] + item_id i32 [p] (per-point
+    labels), entry_cnt i64 [65536], entry_w fp32 [65536], status i64 [4] = (bad batch rows, bad index items, top batch, V)."""
+
+    def __init__(self, row_valid, item_off, item_id, entry_cnt, entry_w, status):
+        self.row_valid, self.item_off, self.item_id = row_valid, item_off, item_id
+        self.entry_cnt, self.entry_w, self.status = entry_cnt, entry_w, status
+
+
+def segment_loss_items(coords, zero, labels, num_classes, ignore_ids, reduction, index=None, buffers=None, workspace=None):
+    """gp_segment_loss_items: coords i32 [n,4], zero u8 [n], labels i64 [p], index i64 [p] or None (p == n) -> SegmentLossItems, no
+    sync.  buffers: optional dict of caller-owned outputs by attribute name; workspace: uint8 of at least
+    gp_segment_loss_items_workspace_bytes(n, p) (only read with an index)."""
+    lib = _lib.load()
+    _chk(coords, torch.int32, "coords"), _chk(zero, torch.uint8, "zero"), _chk(labels, torch.int64, "labels")
+    n, p = zero.shape[0], labels.shape[0]
+    if coords.shape != (n, 4) or zero.dim() != 1 or labels.dim() != 1:
+        raise ValueError(f"segment_loss_items: expected coords [n, 4], zero [n], labels [p], got {list(coords.shape)}, {list(zero.shape)}, "
+                         f"{list(labels.shape)}")
+    if index is not None and _chk(index, torch.int64, "index").shape != (p,):
+        raise ValueError(f"segment_loss_items: expected index [{p}], got {list(index.shape)}")
+    if index is None and p != n:
+        raise ValueError(f"segment_loss_items: {p} labels for {n} rows and no index")
+    dev, B = coords.device, SEGMENT_LOSS_MAX_ENTRIES
+    want = {"entry_cnt": (torch.int64, (B,)), "entry_w": (torch.float32, (B,)), "status": (torch.int64, (4,))}
+    want.update({"row_valid": (torch.uint8, (n,))} if index is None else {"item_off": (torch.int64, (n + 1,)), "item_id": (torch.int32, (p,))})
+    got = {}
+    for name, (dtype, shape) in want.items():
+        t = (buffers or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif _chk(t, dtype, name).shape != shape:
+            raise ValueError(f"segment_loss_items: expected {name} {list(shape)}, got {list(t.shape)}")
+        got[name] = t
+    ws = None
+    if index is not None:
+        ws = _ws(lib.gp_segment_loss_items_workspace_bytes(n, p), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    ig = (ctypes.c_int64 * max(len(ignore_ids), 1))(*[int(v) for v in ignore_ids])
+    check(lib.gp_segment_loss_items(_ptr(coords), _ptr(zero), n, _ptr(labels), _ptr(index), p, int(num_classes), ig, len(ignore_ids),
+                                    SEGMENT_LOSS_REDUCTIONS[reduction], _ptr(got.get("row_valid")), _ptr(got.get("item_off")),
+                                    _ptr(got.get("item_id")), _ptr(got["entry_cnt"]), _ptr(got["entry_w"]), _ptr(got["status"]),
+                                    _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "gp_segment_loss_items")
+    return SegmentLossItems(got.get("row_valid"), got.get("item_off"), got.get("item_id"), got["entry_cnt"], got["entry_w"], got["status"])
+
+
+def segment_loss_rows(z, num_classes, coords, items, labels, row0, g, lse, term):
+    """The row kernel (gp_segment_loss_rows) over the chunk of rows row0 .. row0 + r - 1: z fp32 [r, >= c] the chunk's logits, g fp32
+    [r, c_pad] (its width is c_pad) the chunk's own, or None: lse and term alone (the forward); coords i32 [n,4], lse fp32 [n], term
+    f64 [n] and the items the whole arrays."""
+    lib = _lib.load()
+    r = _rows(z, "z").shape[0]
+    if g is not None:
+        _rows(g, "g", r)
+    _chk(coords, torch.int32, "coords"), _chk(labels, torch.int64, "labels"), _chk(lse, torch.float32, "lse"), _chk(term, torch.float64, "term")
+    n = coords.shape[0]
+    if not 0 <= row0 <= n - r or lse.shape != (n,) or term.shape != (n,):
+        raise ValueError(f"segment_loss_rows: rows {row0} .. {row0 + r - 1} of {n}, lse {list(lse.shape)}, term {list(term.shape)}")
+    per_row = items.item_off is None
+    c_pad, ld_g = (g.shape[1], g.stride(0)) if g is not None else (int(num_classes), 0)
+    check(lib.gp_segment_loss_rows(_ptr(z), z.stride(0), r, int(num_classes), c_pad, _ptr(coords[row0:]),
+                                   _ptr(items.row_valid[row0:]) if per_row else None, None if per_row else _ptr(items.item_off[row0:]),
+                                   None if per_row else _ptr(items.item_id), _ptr(labels[row0:]) if per_row else _ptr(labels),
+                                   _ptr(items.entry_w), _ptr(g), ld_g, _ptr(lse[row0:]), _ptr(term[row0:]), _stream()),
+          "gp_segment_loss_rows")
+    return g
+
+
+def segment_loss_reduce(term, coords, entry_cnt, num_entries, reduction, loss=None, per_entry=None, workspace=None):
+    """(loss fp32 0-d, per_entry fp32 [num_entries]) from the rows' terms f64 [n] in a fixed order (gp_segment_loss_reduce)."""
+    lib = _lib.load()
+    _chk(term, torch.float64, "term"), _chk(coords, torch.int32, "coords"), _chk(entry_cnt, torch.int64, "entry_cnt")
+    n, dev = term.shape[0], term.device
+    if coords.shape != (n, 4) or entry_cnt.shape[0] < num_entries:
+        raise ValueError(f"segment_loss_reduce: expected coords [{n}, 4] and at least {num_entries} entry counts, got {list(coords.shape)}, "
+                         f"{list(entry_cnt.shape)}")
+    loss = torch.empty((), dtype=torch.float32, device=dev) if loss is None else _chk(loss, torch.float32, "loss")
+    per_entry = torch.empty(num_entries, dtype=torch.float32, device=dev) if per_entry is None else _chk(per_entry, torch.float32, "per_entry")
+    if per_entry.shape != (num_entries,):
+        raise ValueError(f"segment_loss_reduce: expected per_entry [{num_entries}], got {list(per_entry.shape)}")
+    ws = _ws(lib.gp_segment_loss_reduce_workspace_bytes(n, int(num_entries)), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_segment_loss_reduce(_ptr(term), _ptr(coords), n, _ptr(entry_cnt), int(num_entries), SEGMENT_LOSS_REDUCTIONS[reduction],
+                                     _ptr(loss), _ptr(per_entry), _ptr(ws), ws.numel(), _stream()), "gp_segment_loss_reduce")
+    return loss, per_entry
+
+
 # ------------------------------------------------------------------------------------------ SURVEY 8f-1: training step
 def col_stats(y, c=None):
     """mean, biased variance of the rows of y fp32 [nv, >=c] (BatchNorm1d training statistics)."""

@@ -20,6 +20,11 @@ and the objective the student is trained with (models/affinity_module.py:1099-11
     loss = info_nce(student(pairs.subset(x)), pairs)            # or contrastive_loss(student, x, teacher): the three calls in one
     loss.backward()
 
+and the loss on the purified features, labels per voxel or per point, ground truth or the VLM's own segment(x, ...).pred:
+
+    loss = segment_loss(purify(student, x, differentiable=True), text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)
+    loss.backward()                                             # or purified_loss(student, x, text, scale, labels=...): the two calls in one
+
 Every link carries gradients when asked to: affinity_pool(x, student(x), differentiable=True) -- or purify(student, x,
 differentiable=True) -- puts y.F into the autograd graph, so a loss on the purified features reaches the student's parameters, x.F and
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
@@ -31,7 +36,9 @@ The neighbour lists come from ops.knn_batched over the same sorted keys; affinit
 pooling families of HotPath, applied in the key order.  segment is the per-scene tail of run/validation.py:413-439 for all entries at
 once: ops.classify_argmax(_gemm), the zero-row fill by ops.nn1_batched inside each entry, ops.iou_hist_batched.  sample_pairs is
 ops.normalize_split_f16 on the teacher rows in the key order, then per chunk of anchors ops.sim_segments (the similarity inside each
-anchor's entry, a ragged buffer), ops.sampler_select_segments and ops.sampler_micro_segments; info_nce is ops.infonce_weighted_fwd_bwd.
+anchor's entry, a ragged buffer), ops.sampler_select_segments and ops.sampler_micro_segments; info_nce is ops.infonce_weighted_fwd_bwd.  segment_loss is
+ops.segment_loss_unit_rows and ops.segment_loss_items, then per chunk of rows the exact-fp32 GEMM of ops.sparse_conv around
+ops.segment_loss_rows, ops.segment_loss_reduce and ops.l2norm_rows_backward.
 """
 import torch
 
@@ -572,6 +579,200 @@ def segment(y, text_features, logit_scale=1.0, *, labels=None, num_classes=None,
         if inv is not None:
             pred = pred.index_select(0, inv)
     return Segmentation(pred, zero.bool(), filled_from, counts, int(unfilled))
+
+
+# ------------------------------------------------------------------------------------------ cross-entropy against text embeddings
+LOSS_REDUCTIONS = ("item", "entry")
+_LOSS_OPTIONS = ("ignore_labels", "inverse_mapping", "reduction", "logits_budget_bytes")
+
+
+def _pad_to(v, m):
+    return (v + m - 1) // m * m
+
+
+class _TextProducts:
+    """The operands of the loss's two products on ops.sparse_conv's exact-fp32 matrix-core GEMM (one dense offset): the normalised text
+    rows as [Dp, Cp] for Z = s U T^T and as [Cp, Dq] for dU = s G T, zero padded to the kernel's tiles (Dp = D to 32, Cp = C to 128,
+    Dq = D to 128), with s as the epilogue's per-column scale."""
+
+    def __init__(self, text_features, scale, D):
+        T = torch.nn.functional.normalize(text_features.detach().float(), dim=-1)
+        C, dev = T.shape[0], T.device
+        self.C, self.D = C, D
+        _, cp, kp = ops.sparse_conv_tiles()
+        self.Dp, self.Cp, self.Dq = _pad_to(D, kp), _pad_to(C, cp), _pad_to(D, cp)
+        self.to_logits = torch.zeros((self.Dp, self.Cp), dtype=torch.float32, device=dev)
+        self.to_logits[:D, :C] = T.t()
+        self.to_rows = torch.zeros((self.Cp, self.Dq), dtype=torch.float32, device=dev)
+        self.to_rows[:C, :D] = T
+        self.scale = scale.to(torch.float32).reshape(1).expand(max(self.Cp, self.Dq)).contiguous()
+
+    def logits(self, u_rows, out):
+        """out[r, Cp] = s * u_rows @ T^T (columns C .. Cp-1 are zeros)"""
+        return ops.sparse_conv(u_rows, None, self.to_logits, scale=self.scale, out=out)
+
+    def rows(self, g, out):
+        """out[r, Dq] = s * g @ T"""
+        return ops.sparse_conv(g, None, self.to_rows, scale=self.scale, out=out)
+
+
+class _SegmentLoss(torch.autograd.Function):
+    """The loss and dY are both made by segment_loss's forward kernels; backward hands g * dY to y.F"""
+
+    @staticmethod
+    def forward(ctx, feats, loss, d_feats):
+        ctx.save_for_backward(d_feats)
+        ctx.dtype = feats.dtype
+        return loss.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (d_feats,) = ctx.saved_tensors
+        return (g * d_feats).to(ctx.dtype), None, None
+
+
+def segment_loss(y, text_features, logit_scale=1.0, *, labels, ignore_labels=(255,), inverse_mapping=None, reduction="item",
+                 logits_budget_bytes=2 ** 30):
+    """The differentiable twin of segment: the classification cross-entropy of y.F against the text embeddings, forward and gradient on
+    HIP kernels, deterministic.  y: an ME-style SparseTensor (.F [N,D] floating of any dtype and row stride, .C integer [N,4]; only the
+    batch column is used, the rows are taken as they lie); text_features [C,D], 1 <= C <= 4096; labels: integer [N] per voxel, or [P]
+    per point when inverse_mapping ([P], a quantiser's point -> voxel map) is given, exactly as segment takes them -- ground truth, or
+    segment(x_unpurified, ...).pred for the label-free objective.  With u_i = y_i / max(|y_i|, 1e-12), t_c = normalize(text_c) and
+    s = logit_scale: z_ic = s <u_i, t_c> (its arg-max is segment's pred on non-zero rows), lse_i = log sum_c exp(z_ic), and
+        loss = sum over the valid items p of w_b(p) (lse_i(p) - z_i(p),l_p).
+    An item (a voxel, or a point with row i(p) = inverse_mapping[p]) is valid when 0 <= l_p < C, l_p is none of ignore_labels (at most
+    4) and row i(p) is not a zero row (sum |y_i| == 0: segment's zero flag).  reduction "item": w = 1 / V over all V valid items
+    (F.cross_entropy's mean); "entry": w_b = 1 / (E V_b), the mean over the E entries that hold valid items of each entry's mean
+    (info_nce's "entry").  No valid item: the loss is 0.0 and every gradient exactly zero.
+    -> 0-d fp32 loss under autograd with respect to y.F only (the gradient in y.F's dtype, rows without valid items exactly +0.0; no
+    double backward); loss.per_entry fp32 [B], every entry's mean, detached, NaN for an entry without valid items, B = the highest
+    batch index + 1; loss.valid i64 [B].  The text embeddings and logit_scale are the frozen VLM's: one that requires grad while grad
+    mode is on is a ValueError.
+    Inside: ops.segment_loss_unit_rows, ops.segment_loss_items (per point: a CSR of the valid items by row), then per chunk of rows
+    Z = s U T^T on ops.sparse_conv's exact-fp32 matrix-core GEMM, ops.segment_loss_rows (stable softmax, G = w (m softmax - cnt), lse,
+    the row's term) and dU = s G T on the same GEMM, ops.segment_loss_reduce (fixed-order fp64) and ops.l2norm_rows_backward.  The
+    logits and G exist for one chunk at a time, at most logits_budget_bytes for the two (G only when a gradient is wanted: a call
+    under no_grad, or on features that do not require grad, stores none); the result does not depend on the chunking.
+    ValueError before any kernel or from the ONE status read-back (which also carries the highest batch index and V): shape / dtype /
+    device mismatches, CPU tensors, an unknown reduction, more than 4 ignore labels, C outside 1..4096, a logit_scale that is not
+    finite and positive, a batch index outside 0..65535, an inverse_mapping value outside 0..N-1."""
+    who = "segment_loss"
+    if not (hasattr(y, "F") and hasattr(y, "C")):
+        raise ValueError(f"{who}: y must be a SparseTensor (an object with .F and .C), got {type(y).__name__}")
+    Fe, C, T = y.F, y.C, text_features
+    if reduction not in LOSS_REDUCTIONS:
+        raise ValueError(f"{who}: reduction={reduction!r}, expected one of {LOSS_REDUCTIONS}")
+    _check_coordinates(who, C)
+    n = C.shape[0]
+    if not torch.is_tensor(Fe) or Fe.dim() != 2 or Fe.shape[0] != n or Fe.shape[1] < 1:
+        raise ValueError(f"{who}: features must be [N, D] with N = {n} coordinate rows, got "
+                         f"{list(Fe.shape) if torch.is_tensor(Fe) else type(Fe).__name__}")
+    D = Fe.shape[1]
+    if not torch.is_tensor(T) or T.dim() != 2 or T.shape[0] < 1 or T.shape[1] != D:
+        raise ValueError(f"{who}: text_features must be [C, D] with D = {D} feature columns, got "
+                         f"{list(T.shape) if torch.is_tensor(T) else type(T).__name__}")
+    if not (Fe.dtype.is_floating_point and T.dtype.is_floating_point):
+        raise ValueError(f"{who}: features and text_features must be floating point, got {Fe.dtype} / {T.dtype}")
+    if not (Fe.is_cuda and T.is_cuda) or Fe.device != C.device or T.device != C.device:
+        raise ValueError(f"{who}: features, text_features and coordinates must be CUDA tensors on one device (got {Fe.device} / {T.device} / "
+                         f"{C.device}); there is no CPU path")
+    nc = T.shape[0]
+    if not 1 <= nc <= 4096:
+        raise ValueError(f"{who}: {nc} text rows (classes) outside 1..4096")
+    ignore = [int(v) for v in ignore_labels]
+    if len(ignore) > 4:
+        raise ValueError(f"{who}: {len(ignore)} ignore labels, at most 4")
+    S = logit_scale
+    if torch.is_tensor(S):
+        if S.numel() != 1 or not S.dtype.is_floating_point or S.device != C.device:
+            raise ValueError(f"{who}: a tensor logit_scale must be one floating point value on {C.device}, got {list(S.shape)} {S.dtype} on {S.device}")
+    elif isinstance(S, bool) or not isinstance(S, (int, float)) or not (S > 0 and S < float("inf")):
+        raise ValueError(f"{who}: logit_scale={S!r} must be finite and positive")
+    if torch.is_grad_enabled() and (T.requires_grad or (torch.is_tensor(S) and S.requires_grad)):
+        raise ValueError(f"{who}: text_features and logit_scale are not differentiated (the frozen VLM's); detach them, or the gradient "
+                         "would be dropped silently")
+    inv = inverse_mapping
+    if inv is not None and (not _is_int_tensor(inv) or inv.dim() != 1 or inv.shape[0] < 1 or inv.device != C.device):
+        raise ValueError(f"{who}: inverse_mapping must be an integer tensor [P] on {C.device}, got "
+                         f"{(list(inv.shape), inv.dtype, str(inv.device)) if torch.is_tensor(inv) else type(inv).__name__}")
+    items = n if inv is None else inv.shape[0]
+    if not _is_int_tensor(labels) or labels.dim() != 1 or labels.shape[0] != items or labels.device != C.device:
+        raise ValueError(f"{who}: labels must be an integer tensor [{items}] ({'one per point of inverse_mapping' if inv is not None else 'one per voxel'}) "
+                         f"on {C.device}, got {(list(labels.shape), labels.dtype, str(labels.device)) if torch.is_tensor(labels) else type(labels).__name__}")
+    if not _is_count(logits_budget_bytes, 1):
+        raise ValueError(f"{who}: logits_budget_bytes={logits_budget_bytes!r} must be an integer >= 1")
+    dev = C.device
+    need_grad = torch.is_grad_enabled() and Fe.requires_grad
+    with torch.cuda.device(dev), torch.no_grad():
+        C = C.detach()
+        bad_range = torch.zeros(1, dtype=torch.int64, device=dev)
+        if C.dtype != torch.int32:
+            # (only the batch column is read: one outside int32 is outside 0..65535 too and must not wrap into it)
+            batch = C[:, 0]
+            bad_range = ((batch < 0) | (batch > 65535)).sum().reshape(1)
+            C = torch.cat([batch.clamp(-1, 65536).reshape(-1, 1), torch.zeros_like(C[:, 1:])], 1).to(torch.int32)
+        C = C.contiguous()
+        s_dev = S.detach().to(torch.float32).reshape(1) if torch.is_tensor(S) else torch.full((1,), float(S), dtype=torch.float32, device=dev)
+        bad_scale = (~(torch.isfinite(s_dev) & (s_dev > 0))).to(torch.int64)
+        tp = _TextProducts(T, s_dev, D)
+        feats = _rows_f32(Fe.detach())
+        U, zero = ops.segment_loss_unit_rows(feats, D)
+        lab = labels.detach().to(torch.int64).contiguous()
+        if inv is not None:
+            inv = inv.detach().to(torch.int64).contiguous()
+        it = ops.segment_loss_items(C, zero, lab, nc, ignore, reduction, index=inv)
+        bad_batch, bad_inv, top_batch, V, bad_range, bad_scale = ops.readback(torch.cat([it.status, bad_range, bad_scale]))
+        if bad_batch or bad_range:
+            raise ValueError(f"{who}: {max(bad_batch, bad_range)} rows have a batch index outside 0..65535")
+        if bad_inv:
+            raise ValueError(f"{who}: {bad_inv} inverse_mapping values outside 0..{n - 1}")
+        if bad_scale:
+            raise ValueError(f"{who}: logit_scale must be finite and positive")
+        B = top_batch + 1
+        valid = it.entry_cnt[:B].clone()
+        if V == 0:
+            loss = torch.zeros((), dtype=torch.float32, device=dev)
+            per_entry = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+            d_feats = torch.zeros((n, D), dtype=torch.float32, device=dev) if need_grad else None
+        else:
+            chunk = max(1, min(n, logits_budget_bytes // ((8 if need_grad else 4) * tp.Cp), (2 ** 31 - 1) // tp.Cp))
+            Z = torch.empty((chunk, tp.Cp), dtype=torch.float32, device=dev)
+            G = torch.empty((chunk, tp.Cp), dtype=torch.float32, device=dev) if need_grad else None   # (forward only: no G is stored)
+            lse = torch.empty(n, dtype=torch.float32, device=dev)
+            term = torch.empty(n, dtype=torch.float64, device=dev)
+            dU = torch.empty((n, tp.Dq), dtype=torch.float32, device=dev) if need_grad else None
+            for r0 in range(0, n, chunk):
+                r = min(chunk, n - r0)
+                tp.logits(U[r0:r0 + r], Z[:r])
+                ops.segment_loss_rows(Z[:r], nc, C, it, lab, r0, G[:r] if need_grad else None, lse, term)
+                if need_grad:
+                    tp.rows(G[:r], dU[r0:r0 + r])
+            loss, per_entry = ops.segment_loss_reduce(term, C, it.entry_cnt, B, reduction)
+            d_feats = None
+            if need_grad:
+                # the backward of the row normalisation on the padded rows (zero columns change neither the norm nor the products)
+                raw = feats
+                if tp.Dp != D:
+                    raw = torch.zeros((n, tp.Dp), dtype=torch.float32, device=dev)
+                    raw[:, :D] = feats
+                d_feats = ops.l2norm_rows_backward(raw, dU[:, :tp.Dp])[:, :D]
+    if need_grad:
+        with torch.cuda.device(dev):
+            loss = _SegmentLoss.apply(Fe, loss, d_feats)
+    loss.per_entry, loss.valid = per_entry, valid
+    return loss
+
+
+def purified_loss(student, x, text_features, logit_scale=1.0, *, labels, feature_dim=None, **kw):
+    """purify(student, x, feature_dim=feature_dim, differentiable=True) followed by segment_loss on what it returns: the objective
+    DESIGN.md 5.7 built the differentiable pooling for.  kw is split by name: ignore_labels, inverse_mapping, reduction and
+    logits_budget_bytes are segment_loss's, everything else affinity_pool's.  -> the loss of segment_loss, with loss.purified."""
+    loss_kw = {k: kw.pop(k) for k in _LOSS_OPTIONS if k in kw}
+    purified = purify(student, x, feature_dim=feature_dim, differentiable=True, **kw)
+    loss = segment_loss(purified, text_features, logit_scale, labels=labels, **loss_kw)
+    loss.purified = purified
+    return loss
 
 
 # ------------------------------------------------------------------------------------------ contrastive pairs and InfoNCE

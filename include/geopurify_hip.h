@@ -147,6 +147,9 @@ int gp_sparse_conv(const float *x, int64_t ld_x, const int32_t *nbr_map, int64_t
                    const float *w, int32_t kv, int32_t cin, int32_t cout,
                    const float *scale, const float *shift, const float *residual, int64_t ld_res,
                    int32_t relu, float *y, int64_t ld_y, void *stream);
+/* tiles i32 [3] (host) = gp_sparse_conv's row tile, its column tile (cout is a multiple of it) and its channel step (cin is a      */
+/* multiple of it): what a caller pads dense operands to.                                                                          */
+int gp_sparse_conv_tiles(int32_t *tiles);
 /* Fast path of the same convolution on the f16 matrix cores with fp32-class accuracy (operands     */
 /* split x = hi + lo in f16, products hi*hi + hi*lo + lo*hi accumulated in fp32; relative error of   */
 /* a product <= 2^-21).  gp_conv_pairs_build compacts the kernel map once per scene: pair_in i32     */
@@ -601,6 +604,48 @@ int gp_nn1_batched(const uint64_t *keys_sorted, const int32_t *ids, const uint8_
 int gp_iou_hist_batched_i64(const int64_t *pred, const int32_t *coords, int64_t rows, const int64_t *target, const int64_t *index,
                             int64_t n, int32_t num_batches, int32_t num_classes, const int64_t *ignore_ids_host, int32_t num_ignore,
                             int64_t *counts, void *stream);
+/* Classification cross-entropy of SparseTensor rows against text embeddings, forward and gradient (the differentiable twin of the     */
+/* labelling above): u_i = y_i / max(|y_i|, 1e-12), z_ic = s <u_i, t_c>, lse_i = log sum_c exp(z_ic),                                   */
+/*   loss = sum over the valid items p of w_b(p) (lse_i(p) - z_i(p),l_p),   dz_ic = w_b(i) (m_i softmax_ic - cnt_ic).                  */
+/* The products Z = U T^T and dU = s G T are gp_sparse_conv's (kv = 1); the four calls below stand around them.  No float atomics:      */
+/* two calls give the same bits.  Nothing is read or written outside the given extents.  Every call refuses an output whose extent      */
+/* overlaps an input's or another output's (labels and item_id of gp_segment_loss_rows' per-point form, whose lengths are no argument,  */
+/* count from their first element on).  gp_segment_loss_col_step: the columns per lane step of the row kernels (64).                    */
+int32_t gp_segment_loss_col_step(void);
+/* gp_segment_loss_unit_rows: u f32 [n, ld_u >= d_pad] = the unit rows of y f32 [n, ld_y >= d] with zeros in the columns d .. d_pad-1,   */
+/* zero u8 [n] = (sum |y_i| == 0), the zero flag of gp_classify_argmax.  1 <= n < 2^31.                                                 */
+int gp_segment_loss_unit_rows(const float *y, int64_t ld_y, int32_t d, int64_t n, float *u, int64_t ld_u, int32_t d_pad, uint8_t *zero,
+                              void *stream);
+/* gp_segment_loss_items: the valid items.  Item q of p takes the row r = index[q] (index i64 [p], a quantiser's inverse map; NULL:    */
+/* r = q and p must equal n) and the label labels[q]; it is valid when 0 <= label < c, the label is none of the ignore ids (at most 4), */
+/* r is inside 0..n-1, zero[r] is clear and the batch index coords[r,0] (coords i32 [n,4]) is inside 0..65535.  With an index:           */
+/* item_off i64 [n+1] and item_id i32 [p] receive the CSR of the valid items by row, item numbers ascending inside a row (integer        */
+/* counts + a scan + a stable sort; the tail of item_id holds the invalid items); without: row_valid u8 [n].  entry_cnt i64 [65536] =    */
+/* the valid items V_b per batch entry, entry_w f32 [65536] = 1 / V (reduction 0, "item") or 1 / (E V_b) (1, "entry": E the entries      */
+/* with V_b > 0), 0 where V_b = 0.  status i64 [4] (device, written by the call): [0] rows with a batch index outside 0..65535, [1]      */
+/* items with a row outside 0..n-1, [2] the highest batch index inside the range, [3] V.  1 <= c <= 4096, 1 <= n, p < 2^31.  No sync.   */
+size_t gp_segment_loss_items_workspace_bytes(int64_t n, int64_t p);
+int gp_segment_loss_items(const int32_t *coords, const uint8_t *zero, int64_t n, const int64_t *labels, const int64_t *index, int64_t p,
+                          int32_t c, const int64_t *ignore_ids_host, int32_t num_ignore, int32_t reduction, uint8_t *row_valid,
+                          int64_t *item_off, int32_t *item_id, int64_t *entry_cnt, float *entry_w, int64_t *status, void *workspace,
+                          size_t workspace_bytes, void *stream);
+/* gp_segment_loss_rows: the row kernel over a chunk of r rows of logits z f32 [r, ld_z >= c], one wave per row.  coords, row_valid,    */
+/* item_off, lse and term are the chunk's own rows (pointers advanced to its first row; item_off's values stay positions in the whole   */
+/* item_id); labels is indexed by item number (with item_off + item_id) or by chunk row (both NULL: the item of a row is the row        */
+/* itself where row_valid is set).  g f32 [r, ld_g >= c_pad] = w_b(i) (m_i softmax_ic - cnt_ic) with exact zeros in the columns         */
+/* c .. c_pad-1 (the softmax with the row maximum subtracted; the counts come off as integers in list order before the weight, so one   */
+/* class gives exactly 0), lse f32 [r], term f64 [r] = m_i lse_i - sum over the row's items of z_i,l.  A row without items stores       */
+/* zeros and reads no logits.  g NULL: lse and term alone (the forward), no g is stored.  1 <= c <= 4096, r * ld < 2^31, pitches         */
+/* multiples of 4, z / g 16-byte aligned.                                                                                               */
+int gp_segment_loss_rows(const float *z, int64_t ld_z, int64_t r, int32_t c, int32_t c_pad, const int32_t *coords, const uint8_t *row_valid,
+                         const int64_t *item_off, const int32_t *item_id, const int64_t *labels, const float *entry_w, float *g,
+                         int64_t ld_g, float *lse, double *term, void *stream);
+/* gp_segment_loss_reduce: loss f32 (device scalar, overwritten) = sum_b w_b S_b and per_entry f32 [num_entries] = S_b / V_b (NaN where  */
+/* V_b = 0), S_b the fp64 sum of term over the rows of entry b in a fixed order (rows sorted by entry, a strided sum per thread, a tree   */
+/* over the threads), w_b in fp64 from entry_cnt as above.  num_entries = the highest batch index + 1, 1..65536; 1 <= n < 2^31.           */
+size_t gp_segment_loss_reduce_workspace_bytes(int64_t n, int32_t num_entries);
+int gp_segment_loss_reduce(const double *term, const int32_t *coords, int64_t n, const int64_t *entry_cnt, int32_t num_entries,
+                           int32_t reduction, float *loss, float *per_entry, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* training step of the student (models/affinity_module.py:1138-1237,                */
