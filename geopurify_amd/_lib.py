@@ -166,6 +166,11 @@ SIGNATURES = {
     "gp_segment_loss_reduce": (c_int32, [_P, _P, c_int64, _P, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "gp_fused_decode_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gp_fused_decode": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_batched_col_chunk": (c_int32, []),
+    "gp_lift_batched_transpose": (c_int32, [_P, c_int32, c_int32, c_int64, _P, _P]),
+    "gp_lift_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_lift_batched": (c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_double, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

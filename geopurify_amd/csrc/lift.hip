@@ -4,6 +4,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_project.h"
 
 namespace {
 
@@ -28,16 +29,6 @@ __global__ void lift_dense_accum_kernel(const float *__restrict__ feat2d, int d,
 // F.interpolate(bilinear, align_corners=True) and then samples it at the visible pixels; here the resize is evaluated
 // only at those pixels.  Arithmetic follows torch's CPU kernel to the bit: source = scale*i in fp32, lambda clipped to
 // [0,1], value = fma(w0, a, w1*b) per axis (rows of the two source lines first, then the two lines).
-__device__ __forceinline__ void bilinear_tap(float scale, int64_t i, int in_size, int &i0, int &i1, float &w0, float &w1) {
-    float real = scale * (float)i;
-    int f = (int)floorf(real);
-    i0 = f < in_size - 1 ? f : in_size - 1;
-    float lam = real - (float)i0;
-    lam = lam < 0.f ? 0.f : (lam > 1.f ? 1.f : lam);
-    i1 = i0 + 1 < in_size - 1 ? i0 + 1 : in_size - 1;
-    w0 = 1.f - lam;
-    w1 = lam;
-}
 __global__ void lift_dense_bilinear_accum_kernel(const float *__restrict__ feat, int d, int h, int w, float scale_h,
                                                  float scale_w, const int64_t *__restrict__ pt,
                                                  const int64_t *__restrict__ x, const int64_t *__restrict__ y, int64_t n_v,

@@ -1,0 +1,491 @@
+// The 2D -> 3D lift over BATCHED point clouds (geopurify_amd/sparse.py: lift): for every batch entry b, with its points the rows of
+// batch b in ascending row order and its views the views with view_entry == b in ascending view index,
+//     n_v      = #points of the view's entry that project_point sees in view v                    (view_count)
+//     keep_v   = n_v != 0 && n_v >= min_visible && n_v <= max_visible                             (view_keep)
+//     sum_p    = fp32 sum over the kept views that see p, in ascending v, of the sampled feature column
+//     out_p    = sum_p / (cnt_p == 0 ? 1e-6 : cnt_p),  seen_p = cnt_p > 0                         (features, seen, count)
+//     nn_p     = for an unseen p of an entry with seen points: the seen point of ITS entry that minimises (d^2, row), else -1
+// -- models/affinity_module.py:404-452 with fusion_util.py:45-147 and data_loader_ablation.py:254-288, for all entries and all views
+// in one sequence of launches.  The per-scene path (gp_views_visible_lists, one gp_lift_dense_accum launch per view that
+// read-modify-writes [N,D] sums, gp_lift_dense_finish, gp_nn1_masked_f64) computes the same bits one scene at a time.
+//
+// Structure: (1) rows and views sorted stably by entry (rocPRIM radix sort on 17-bit keys; a bad index sorts behind every entry) and
+// the two offset tables by binary search, one thread per entry; (2) the per-view counts: every (view, point of its entry) pair is
+// projected, counted per lane, reduced over the wave, one integer atomic per wave and view; (3) the fused lift: one wave per point,
+// lane l projects the point through the l-th view of a group of 64 of its entry, a 64-bit ballot is the visible-and-kept mask, its
+// set bits are walked in ascending view order with all lanes striding the channels and accumulating in registers; the row is divided
+// and stored once.  No float atomics and no read-modify-write of the sums: the fp32 add order is the sequential index_add_'s.  The
+// maps are read PIXEL-MAJOR ([V, h*w, D]: one contiguous row of 4 D bytes per sample); (4) the fill: references (seen rows) and
+// queries (unseen rows of entries that have seen ones) compacted in the entry-sorted order, so an entry's references are one
+// contiguous run; a block of 256 queries streams the runs of its queries' entries through LDS tiles, each query comparing only inside
+// its own run.
+//
+// Bounds: a batch or view entry index is range-checked before every table access (0..65535; the tables hold 65538 words); sorted
+// positions come from the offset tables (inside 0..n / 0..nviews by construction of the lower bounds); a pixel is read only after
+// project_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0; bilinear taps are clamped to the map; channel indices are
+// guarded by c < d.  All offsets are 64-bit.
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "gp_common.h"
+#include "gp_project.h"
+
+namespace {
+
+constexpr int LB_MAX_ENTRIES = 65536;
+constexpr int LB_KEY_BITS = 17;                                  // keys 0 .. 65536 (65536: no valid entry)
+constexpr int LB_TABLE = LB_MAX_ENTRIES + 2;                     // off[b] for b = 0 .. 65537: off[65536] = first bad row, off[65537] = n
+constexpr int LB_COLS_PER_LANE = 8;
+constexpr int LB_COL_CHUNK = GP_WAVE * LB_COLS_PER_LANE;         // channels one pass of the lift kernel holds in registers
+constexpr int LB_TILE = 1024;                                    // references per LDS tile of the fill
+
+enum { ST_BAD_BATCH = 0, ST_BAD_VIEW = 1, ST_NONFINITE = 2, ST_TOP_BATCH = 3, ST_SEEN = 4, ST_QUERIES = 5, ST_WORDS = 8 };
+
+inline bool lb_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// the entry of a point row (its batch column), -1 when it is no integer in 0..65535 (NaN included)
+__device__ __forceinline__ int lb_entry_of(double b) {
+    return (b >= 0.0 && b <= 65535.0 && b == floor(b)) ? (int)b : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ entry tables
+__global__ void __launch_bounds__(256) lb_row_keys_kernel(const double *__restrict__ points, int64_t n, uint32_t *__restrict__ keys,
+                                                          int32_t *__restrict__ rows, unsigned long long *__restrict__ status) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const bool live = r < n;
+    bool nonfinite = false, bad = false;
+    int b = -1;
+    if (live) {
+        const double *P = points + r * 4;
+        nonfinite = !(fabs(P[0]) < INFINITY && fabs(P[1]) < INFINITY && fabs(P[2]) < INFINITY && fabs(P[3]) < INFINITY);
+        b = lb_entry_of(P[0]);
+        bad = b < 0 && fabs(P[0]) < INFINITY;
+        keys[r] = b >= 0 ? (uint32_t)b : (uint32_t)LB_MAX_ENTRIES;
+        rows[r] = (int32_t)r;
+    }
+    const int nbad = __popcll(__ballot(bad)), nnf = __popcll(__ballot(nonfinite));
+    int top = b;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o, 64));
+    if (gp_lane() == 0) {
+        if (nbad) atomicAdd(status + ST_BAD_BATCH, (unsigned long long)nbad);
+        if (nnf) atomicAdd(status + ST_NONFINITE, (unsigned long long)nnf);
+        if (top >= 0) atomicMax(status + ST_TOP_BATCH, (unsigned long long)top);
+    }
+}
+
+__global__ void __launch_bounds__(256) lb_view_keys_kernel(const int64_t *__restrict__ view_entry, int nviews, uint32_t *__restrict__ keys,
+                                                           int32_t *__restrict__ views, unsigned long long *__restrict__ status) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (v < nviews) {
+        const int64_t e = view_entry[v];
+        bad = (uint64_t)e >= (uint64_t)LB_MAX_ENTRIES;
+        keys[v] = bad ? (uint32_t)LB_MAX_ENTRIES : (uint32_t)e;
+        views[v] = v;
+    }
+    const int nbad = __popcll(__ballot(bad));
+    if (gp_lane() == 0 && nbad) atomicAdd(status + ST_BAD_VIEW, (unsigned long long)nbad);
+}
+
+// off[b] = the first sorted position whose key is >= b, b = 0 .. 65537 (keys are <= 65536, so off[65537] = n)
+__global__ void __launch_bounds__(256) lb_offsets_kernel(const uint32_t *__restrict__ keys_sorted, int64_t n, int32_t *__restrict__ off) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= LB_TABLE) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys_sorted[mid] < (uint32_t)b) lo = mid + 1;
+        else hi = mid;
+    }
+    off[b] = (int32_t)lo;
+}
+
+// ------------------------------------------------------------------------------------------------ per-view counts and the drop rule
+// blockIdx.y = view; the blocks of a view stride the rows of its entry.  Integer atomics: the counts do not depend on arrival order.
+__global__ void __launch_bounds__(256) lb_counts_kernel(const double *__restrict__ points, const int32_t *__restrict__ entry_rows,
+                                                        const int32_t *__restrict__ entry_off, const int64_t *__restrict__ view_entry,
+                                                        const double *__restrict__ w2c, const double *__restrict__ intr,
+                                                        const double *__restrict__ depth, int W, int H, int cut, double tau,
+                                                        unsigned long long *__restrict__ view_count) {
+    const int v = blockIdx.y;
+    const int64_t e = view_entry[v];
+    if ((uint64_t)e >= (uint64_t)LB_MAX_ENTRIES) return;             // (block-uniform)
+    const int64_t r0 = entry_off[e], r1 = entry_off[e + 1];
+    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+    const double *dv = depth ? depth + (int64_t)v * W * H : nullptr;
+    int local = 0;
+    for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r1; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *P = points + (int64_t)entry_rows[i] * 4;
+        long long ui, vi;
+        local += project_point(P[1], P[2], P[3], M, M + 4, M + 8, K[0], K[1], K[2], K[3], dv, W, H, cut, tau, ui, vi) ? 1 : 0;
+    }
+    local = gp_wave_sum_i(local);
+    if (gp_lane() == 0 && local) atomicAdd(view_count + v, (unsigned long long)local);
+}
+
+// the view-drop rule of the loader (data_loader_ablation.py:254-255, 280-288)
+__global__ void lb_keep_kernel(const unsigned long long *__restrict__ view_count, int nviews, int64_t min_visible, int64_t max_visible,
+                               uint8_t *__restrict__ keep) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nviews) return;
+    const int64_t nv = (int64_t)view_count[v];
+    keep[v] = (nv != 0 && nv >= min_visible && nv <= max_visible) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------ [V, D, hw] -> [V, hw, D]
+__global__ void __launch_bounds__(256) lb_transpose_kernel(const float *__restrict__ src, int rows, int64_t cols, float *__restrict__ dst) {
+    __shared__ float tile[64][65];
+    const int64_t vo = (int64_t)blockIdx.z * rows * cols;
+    const int64_t bx = (int64_t)blockIdx.x * 64;
+    const int by = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int r = ty; r < 64; r += 4) {
+        const int row = by + r;
+        const int64_t col = bx + tx;
+        tile[r][tx] = (row < rows && col < cols) ? src[vo + (int64_t)row * cols + col] : 0.f;
+    }
+    __syncthreads();
+    for (int r = ty; r < 64; r += 4) {
+        const int64_t orow = bx + r;
+        const int ocol = by + tx;
+        if (orow < cols && ocol < rows) dst[vo + orow * rows + ocol] = tile[tx][r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the fused lift
+// One wave per point.  BILINEAR: the map is [h, w] and the pixel indexes the [H, W] image the reference resizes the map to
+// (F.interpolate(bilinear, align_corners=True)); the resize is evaluated at the sampled pixel with the arithmetic of
+// lift_dense_bilinear_accum_kernel.  Otherwise (h, w) == (H, W) and the pixel's row is added as it is.
+template <bool BILINEAR>
+__global__ void __launch_bounds__(256) lb_lift_kernel(const double *__restrict__ points, int64_t n, const float *__restrict__ feat, int d, int h,
+                                                      int w, float scale_h, float scale_w, const int32_t *__restrict__ entry_views,
+                                                      const int32_t *__restrict__ view_off, const double *__restrict__ w2c,
+                                                      const double *__restrict__ intr, const double *__restrict__ depth, int W, int H, int cut,
+                                                      double tau, const uint8_t *__restrict__ keep, float *__restrict__ out, int64_t ld_out,
+                                                      uint8_t *__restrict__ seen, int32_t *__restrict__ count, int64_t *__restrict__ nn) {
+    const int64_t p = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;     // (the same for the whole wave: every exit is wave-uniform)
+    if (p >= n) return;
+    const int lane = gp_lane();
+    const double *P = points + p * 4;
+    const double x = P[1], y = P[2], z = P[3];
+    const int b = lb_entry_of(P[0]);
+    int v0 = 0, v1 = 0;
+    if (b >= 0) { v0 = view_off[b]; v1 = view_off[b + 1]; }
+    const int64_t map = (int64_t)h * w * d;
+    float *orow = out + p * ld_out;
+    int cnt = 0;
+    for (int c0 = 0; c0 < d; c0 += LB_COL_CHUNK) {
+        float acc[LB_COLS_PER_LANE];
+#pragma unroll
+        for (int k = 0; k < LB_COLS_PER_LANE; ++k) acc[k] = 0.f;
+        int seen_by = 0;
+        for (int g = v0; g < v1; g += GP_WAVE) {
+            int v = 0, px = 0, py = 0;
+            bool vis = false;
+            if (g + lane < v1) {
+                v = entry_views[g + lane];
+                if (keep[v]) {
+                    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+                    long long ui, vi;
+                    vis = project_point(x, y, z, M, M + 4, M + 8, K[0], K[1], K[2], K[3], depth ? depth + (int64_t)v * W * H : nullptr, W, H,
+                                        cut, tau, ui, vi);
+                    px = (int)ui;
+                    py = (int)vi;
+                }
+            }
+            unsigned long long m = __ballot(vis);
+            seen_by += __popcll(m);
+            while (m) {                                              // ascending view index: the entry's views are sorted stably
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int vj = __shfl(v, j, 64), col = __shfl(px, j, 64), row = __shfl(py, j, 64);
+                const float *f = feat + (int64_t)vj * map;
+                if (BILINEAR) {
+                    int r0, r1, q0, q1;
+                    float wr0, wr1, wc0, wc1;
+                    bilinear_tap(scale_h, row, h, r0, r1, wr0, wr1);
+                    bilinear_tap(scale_w, col, w, q0, q1, wc0, wc1);
+                    const float *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
+                    const float *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+#pragma unroll
+                    for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                        const int c = c0 + lane + k * GP_WAVE;
+                        if (c < d) {
+                            const float top = __builtin_fmaf(wc0, f00[c], wc1 * f01[c]);
+                            const float bot = __builtin_fmaf(wc0, f10[c], wc1 * f11[c]);
+                            acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                        }
+                    }
+                } else {
+                    const float *fr = f + ((int64_t)row * w + col) * d;
+#pragma unroll
+                    for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                        const int c = c0 + lane + k * GP_WAVE;
+                        if (c < d) acc[k] += fr[c];
+                    }
+                }
+            }
+        }
+        cnt = seen_by;                                               // (every column chunk sees the same views)
+        const float den = cnt == 0 ? 1e-6f : (float)cnt;
+#pragma unroll
+        for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+            const int c = c0 + lane + k * GP_WAVE;
+            if (c < d) orow[c] = acc[k] / den;
+        }
+    }
+    if (lane == 0) {
+        seen[p] = cnt > 0 ? 1 : 0;
+        count[p] = cnt;
+        if (nn) nn[p] = -1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the fill
+// sorted position s: ref[s] = the row is seen; qry[s] = unseen, in a valid entry (decided later whether that entry has references)
+__global__ void __launch_bounds__(256) lb_fill_flags_kernel(const uint32_t *__restrict__ keys_sorted, const int32_t *__restrict__ entry_rows,
+                                                            const uint8_t *__restrict__ seen, int64_t n, int32_t *__restrict__ ref,
+                                                            int32_t *__restrict__ qry) {
+    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (s > n) return;
+    int r = 0, q = 0;
+    if (s < n && keys_sorted[s] < (uint32_t)LB_MAX_ENTRIES) {
+        r = seen[entry_rows[s]] ? 1 : 0;
+        q = 1 - r;
+    }
+    ref[s] = r;
+    qry[s] = q;
+}
+
+// rs / qs: the exclusive scans of the flags over n + 1 elements (rs[n] = references, qs[n] = unseen rows of valid entries)
+__global__ void __launch_bounds__(256) lb_fill_compact_kernel(const double *__restrict__ points, const int32_t *__restrict__ entry_rows,
+                                                              const int32_t *__restrict__ ref, const int32_t *__restrict__ qry,
+                                                              const int32_t *__restrict__ rs, const int32_t *__restrict__ qs, int64_t n,
+                                                              float *__restrict__ rxyz, int32_t *__restrict__ rrow, int32_t *__restrict__ qpos,
+                                                              unsigned long long *__restrict__ status) {
+    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    if (ref[s]) {
+        const int64_t j = rs[s], row = entry_rows[s];
+        const double *P = points + row * 4;
+        rxyz[j * 3] = (float)P[1];
+        rxyz[j * 3 + 1] = (float)P[2];
+        rxyz[j * 3 + 2] = (float)P[3];
+        rrow[j] = (int32_t)row;
+    }
+    if (qry[s]) qpos[qs[s]] = (int32_t)s;
+    if (s == n - 1) status[ST_SEEN] = (unsigned long long)rs[n];
+}
+
+// 256 queries (compacted, in the entry-sorted order) per block.  A query's references are the run [rs[entry_off[b]], rs[entry_off[b+1]])
+// of its entry b; the block streams the union of its queries' runs -- one contiguous range, since both lists are entry-sorted --
+// through LDS, every query comparing inside its own run only.  d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over the fp32-rounded xyz, the
+// first strict minimum wins and a run ascends by row: the (d^2, row) rule of gp_nn1_masked_f64.
+__global__ void __launch_bounds__(256) lb_fill_kernel(const double *__restrict__ points, const uint32_t *__restrict__ keys_sorted,
+                                                      const int32_t *__restrict__ entry_rows, const int32_t *__restrict__ entry_off,
+                                                      const int32_t *__restrict__ rs, const int32_t *__restrict__ qs, int64_t n,
+                                                      const float *__restrict__ rxyz, const int32_t *__restrict__ rrow,
+                                                      const int32_t *__restrict__ qpos, int64_t *__restrict__ nn,
+                                                      unsigned long long *__restrict__ status) {
+    __shared__ double sx[LB_TILE], sy[LB_TILE], sz[LB_TILE];
+    __shared__ int s_lo, s_hi, s_filled;
+    const int64_t nq = qs[n];
+    if ((int64_t)blockIdx.x * 256 >= nq) return;                     // (block-uniform)
+    if (threadIdx.x == 0) { s_lo = INT32_MAX; s_hi = 0; s_filled = 0; }
+    __syncthreads();
+    const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int r0 = 0, r1 = 0;
+    int64_t row = -1;
+    double qx = 0, qy = 0, qz = 0;
+    if (qi < nq) {
+        const int64_t s = qpos[qi];
+        const uint32_t b = keys_sorted[s];                           // < 65536: only rows of valid entries are queries
+        r0 = rs[entry_off[b]];
+        r1 = rs[entry_off[b + 1]];
+        row = entry_rows[s];
+        const double *P = points + row * 4;
+        qx = (double)(float)P[1]; qy = (double)(float)P[2]; qz = (double)(float)P[3];
+        if (r1 > r0) { atomicMin(&s_lo, r0); atomicMax(&s_hi, r1); }
+    }
+    __syncthreads();
+    const int lo = s_lo, hi = s_hi;
+    double best = INFINITY;
+    int bi = -1;
+    for (int t0 = lo; t0 < hi; t0 += LB_TILE) {
+        const int tn = hi - t0 < LB_TILE ? hi - t0 : LB_TILE;
+        __syncthreads();
+        for (int j = threadIdx.x; j < tn; j += 256) {
+            sx[j] = rxyz[(int64_t)(t0 + j) * 3]; sy[j] = rxyz[(int64_t)(t0 + j) * 3 + 1]; sz[j] = rxyz[(int64_t)(t0 + j) * 3 + 2];
+        }
+        __syncthreads();
+        const int j0 = r0 > t0 ? r0 - t0 : 0, j1 = r1 - t0 < tn ? r1 - t0 : tn;
+        for (int j = j0; j < j1; ++j) {
+            const double dx = qx - sx[j], dy = qy - sy[j], dz = qz - sz[j];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 < best) { best = d2; bi = t0 + j; }
+        }
+    }
+    if (bi >= 0) {
+        nn[row] = rrow[bi];
+        atomicAdd(&s_filled, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_filled) atomicAdd(status + ST_QUERIES, (unsigned long long)s_filled);
+}
+
+size_t lb_sort_bytes(int64_t n) {
+    size_t t = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0,
+                                    LB_KEY_BITS, 0);
+    return t;
+}
+
+size_t lb_scan_bytes(int64_t n) {
+    size_t t = 0;
+    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
+    return t;
+}
+
+struct LbWork {
+    uint32_t *k0, *k1, *vk0, *vk1;
+    int32_t *r0, *entry_rows, *w0, *entry_views, *entry_off, *view_off, *ref, *qry, *rs, *qs, *rrow, *qpos;
+    float *rxyz;
+    char *tmp;
+    size_t tmp_bytes;
+    LbWork(GpCarver &cv, int64_t n, int32_t nviews) {
+        const size_t a = lb_sort_bytes(n), b = lb_sort_bytes(nviews), c = lb_scan_bytes(n + 1);
+        tmp_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
+        k0 = cv.take<uint32_t>(n);
+        k1 = cv.take<uint32_t>(n);
+        r0 = cv.take<int32_t>(n);
+        entry_rows = cv.take<int32_t>(n);
+        vk0 = cv.take<uint32_t>(nviews);
+        vk1 = cv.take<uint32_t>(nviews);
+        w0 = cv.take<int32_t>(nviews);
+        entry_views = cv.take<int32_t>(nviews);
+        entry_off = cv.take<int32_t>(LB_TABLE);
+        view_off = cv.take<int32_t>(LB_TABLE);
+        ref = cv.take<int32_t>(n + 1);
+        qry = cv.take<int32_t>(n + 1);
+        rs = cv.take<int32_t>(n + 1);
+        qs = cv.take<int32_t>(n + 1);
+        rrow = cv.take<int32_t>(n);
+        qpos = cv.take<int32_t>(n);
+        rxyz = cv.take<float>(3 * n);
+        tmp = cv.take<char>(tmp_bytes);
+    }
+};
+
+}  // namespace
+
+extern "C" int32_t gp_lift_batched_col_chunk(void) { return LB_COL_CHUNK; }
+
+extern "C" int gp_lift_batched_transpose(const float *src, int32_t nviews, int32_t d, int64_t hw, float *dst, void *stream_) {
+    GP_CHECK_ARG(src && dst, "gp_lift_batched_transpose: null argument");
+    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535 && d >= 1 && hw >= 1 && hw < (1ll << 31), "gp_lift_batched_transpose: %d views of %d x %lld",
+                 nviews, d, (long long)hw);
+    GP_CHECK_ARG((hw + 63) / 64 < (1ll << 31) && (d + 63) / 64 <= 65535, "gp_lift_batched_transpose: %d channels exceed the grid", d);
+    {
+        const size_t bytes = (size_t)nviews * (size_t)d * (size_t)hw * 4;
+        GP_CHECK_ARG(!lb_overlap(dst, bytes, src, bytes), "gp_lift_batched_transpose: dst overlaps src");
+    }
+    lb_transpose_kernel<<<dim3((unsigned)((hw + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)nviews), 256, 0, gp_stream(stream_)>>>(src, d, hw,
+                                                                                                                                       dst);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+extern "C" size_t gp_lift_batched_workspace_bytes(int64_t n, int32_t nviews) {
+    if (n <= 0 || n >= (1ll << 31) || nviews < 1 || nviews > 65535) return 0;
+    GpCarver cv(nullptr, 0);
+    LbWork k(cv, n, nviews);
+    return cv.off;
+}
+
+extern "C" int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t d, int32_t h, int32_t w, const int64_t *view_entry,
+                               const double *w2c, const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                               int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible, int32_t fill,
+                               float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn,
+                               int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(points && feat && view_entry && w2c && intrinsics && out && seen && count && view_count && view_keep && status && workspace,
+                 "gp_lift_batched: null argument");
+    GP_CHECK_ARG(n > 0 && n < (1ll << 31), "gp_lift_batched: n=%lld outside 1..2^31-1", (long long)n);
+    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_batched: %d views outside 1..65535", nviews);
+    GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_out >= d, "gp_lift_batched: d=%d, map %d x %d, image %d x %d, ld_out=%lld",
+                 d, h, w, height, width, (long long)ld_out);
+    GP_CHECK_ARG(bilinear == 0 || bilinear == 1, "gp_lift_batched: bilinear=%d (0 nearest, 1 bilinear)", bilinear);
+    GP_CHECK_ARG(bilinear || (h == height && w == width), "gp_lift_batched: the nearest mode samples the map itself: map %d x %d, image %d x %d", h, w,
+                 height, width);
+    GP_CHECK_ARG(cut_bound >= 0, "gp_lift_batched: cut_bound=%d must not be negative", cut_bound);
+    GP_CHECK_ARG(fill == 0 || nn, "gp_lift_batched: the fill writes nn");
+    {
+        // every output against every input and every other output, over their whole extents
+        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * 4;
+        const void *in[] = {points, feat, view_entry, w2c, intrinsics, depth};
+        const size_t in_bytes[] = {(size_t)n * 32, maps, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32, (size_t)nviews * px * 8};
+        const void *o[] = {out, seen, count, view_count, view_keep, nn, status, workspace};
+        const size_t o_bytes[] = {(size_t)((n - 1) * ld_out + d) * 4, (size_t)n, (size_t)n * 4, (size_t)nviews * 8, (size_t)nviews, (size_t)n * 8,
+                                  (size_t)ST_WORDS * 8, workspace_bytes};
+        for (int a = 0; a < 8; ++a) {
+            for (int i = 0; i < 6; ++i)
+                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_batched: an output overlaps an input");
+            for (int q = a + 1; q < 8; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_batched: two outputs overlap");
+        }
+    }
+    GpCarver cv(workspace, workspace_bytes);
+    LbWork k(cv, n, nviews);
+    if (!cv.ok()) {
+        gp_set_error("gp_lift_batched: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
+    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
+    GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
+    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
+    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
+    // (1) entry tables
+    lb_row_keys_kernel<<<nb, 256, 0, s>>>(points, n, k.k0, k.r0, st);
+    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, k.vk0, k.w0, st);
+    GP_CHECK_LAUNCH();
+    size_t io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, k.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));          // (stable)
+    io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.vk0, k.vk1, k.w0, k.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));  // (stable)
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.k1, n, k.entry_off);
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.vk1, nviews, k.view_off);
+    // (2) per-view counts and the drop rule
+    lb_counts_kernel<<<dim3(nb < 64 ? nb : 64, (unsigned)nviews), 256, 0, s>>>(points, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, depth,
+                                                                                width, height, cut_bound, vis_thres, vc);
+    lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
+    GP_CHECK_LAUNCH();
+    // (3) the fused lift
+    // area_pixel_compute_scale<float>(in, out, align_corners=true): (in-1)/(out-1) in fp32, 0 for a single output pixel
+    const float sh = height > 1 ? (float)(h - 1) / (float)(height - 1) : 0.f;
+    const float sw = width > 1 ? (float)(w - 1) / (float)(width - 1) : 0.f;
+    const unsigned lb = (unsigned)((n * 64 + 255) / 256);
+    if (bilinear)
+        lb_lift_kernel<true><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
+                                                cut_bound, vis_thres, view_keep, out, ld_out, seen, count, nn);
+    else
+        lb_lift_kernel<false><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
+                                                 cut_bound, vis_thres, view_keep, out, ld_out, seen, count, nn);
+    GP_CHECK_LAUNCH();
+    // (4) the fill
+    const unsigned nb1 = (unsigned)((n + 1 + 255) / 256);
+    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(k.k1, k.entry_rows, seen, n, k.ref, k.qry);
+    GP_CHECK_LAUNCH();
+    io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.ref, k.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.qry, k.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, k.entry_rows, k.ref, k.qry, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, st);
+    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.k1, k.entry_rows, k.entry_off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, st);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}

@@ -6,20 +6,12 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_project.h"
 
 namespace {
 
 struct Mat34 { double m[3][4]; };
 struct Mat44 { double m[4][4]; };
-
-__device__ __forceinline__ double dot4_blas(const double *r, double x, double y, double z) {
-    // acc = r0*x ; acc = fma(r1,y,acc) ; acc = fma(r2,z,acc) ; acc = fma(r3,1,acc)
-    double acc = r[0] * x;
-    acc = fma(r[1], y, acc);
-    acc = fma(r[2], z, acc);
-    acc = fma(r[3], 1.0, acc);
-    return acc;
-}
 
 __global__ void vox_affine_kernel(const double *__restrict__ c, int64_t n, Mat34 R, double *__restrict__ out,
                                   long long *__restrict__ mn) {
@@ -112,30 +104,6 @@ __global__ void vox_emit_kernel(const double *__restrict__ c, const int64_t *__r
         *nv_dev = v + 1;
         if (seg_start) seg_start[v + 1] = n;
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// one point through one view: pixel (vi = row, ui = column) and the visibility decision of fusion_util.py:99-147 / :45-82
-__device__ __forceinline__ bool project_point(double x, double y, double z, const double *m0, const double *m1, const double *m2,
-                                              double fx, double fy, double cx, double cy, const double *__restrict__ depth,
-                                              int W, int H, int cut, double tau, long long &ui, long long &vi) {
-    double p0 = dot4_blas(m0, x, y, z), p1 = dot4_blas(m1, x, y, z), p2 = dot4_blas(m2, x, y, z);
-    double u = (p0 * fx) / p2 + cx;
-    double v = (p1 * fy) / p2 + cy;
-    double ur = rint(u), vr = rint(v);
-    bool finite = (fabs(ur) < 9.0e15) && (fabs(vr) < 9.0e15);      // also false for NaN
-    ui = finite ? (long long)ur : -1;
-    vi = finite ? (long long)vr : -1;
-    bool inside = finite && ui >= cut && vi >= cut && ui < (long long)W - cut && vi < (long long)H - cut;
-    if (depth) {
-        if (inside) {
-            double d = depth[vi * W + ui];
-            inside = fabs(d - p2) <= tau * d;
-        }
-    } else {
-        inside = inside && (p2 > 0.0);
-    }
-    return inside;
 }
 
 // ---- all views of a scene in one launch per step (instead of V x {project, flags, scan, compact}):

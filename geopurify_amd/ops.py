@@ -1450,6 +1450,79 @@ def segment_loss_reduce(term, coords, entry_cnt, num_entries, reduction, loss=No
     return loss, per_entry
 
 
+# ------------------------------------------------------------------------------------------ the lift over batched point clouds
+def lift_batched_col_chunk():
+    """channels one pass of gp_lift_batched's lift kernel holds in registers (asked of the library)"""
+    return int(_lib.load().gp_lift_batched_col_chunk())
+
+
+def lift_batched_transpose(maps, out=None):
+    """maps fp32 [V, D, h, w] contiguous (NCHW) -> the pixel-major copy fp32 [V, h*w, D] that gp_lift_batched reads"""
+    lib = _lib.load()
+    _chk(maps, torch.float32, "maps")
+    if maps.dim() != 4:
+        raise ValueError(f"lift_batched_transpose: expected maps [V, D, h, w], got {list(maps.shape)}")
+    v, d, h, w = maps.shape
+    if out is None:
+        out = torch.empty((v, h * w, d), dtype=torch.float32, device=maps.device)
+    elif _chk(out, torch.float32, "out").shape != (v, h * w, d):
+        raise ValueError(f"lift_batched_transpose: expected out [{v}, {h * w}, {d}], got {list(out.shape)}")
+    check(lib.gp_lift_batched_transpose(_ptr(maps), v, d, h * w, _ptr(out), _stream()), "gp_lift_batched_transpose")
+    return out
+
+
+class LiftBatched:
+    """What gp_lift_batched writes: out fp32 [n, D] (before the fill), seen u8 [n], count i32 [n], view_count i64 [V], view_keep u8 [V],
+    nn i64 [n] or None (the seen row an unseen row takes, -1 elsewhere), status i64 [8] = (bad batch rows, bad view entries, non-finite
+    rows, top batch, seen rows, filled rows, 0, 0)."""
+
+    def __init__(self, out, seen, count, view_count, view_keep, nn, status):
+        self.out, self.seen, self.count, self.view_count, self.view_keep, self.nn, self.status = out, seen, count, view_count, view_keep, nn, status
+
+
+def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, image_hw, bilinear, cut_bound, vis_thres, min_visible,
+                 max_visible, fill=True, buffers=None, workspace=None):
+    """gp_lift_batched, no sync: points f64 [n,4]; maps_pm fp32 [V, h*w, D] pixel-major with map_hw = (h, w); view_entry i64 [V]; w2c f64
+    [V,4,4]; intrinsics f64 [V,4]; depth f64 [V,H,W] or None; image_hw = (H, W).  -> LiftBatched.  buffers: optional dict of
+    caller-owned outputs by attribute name (out: fp32 rows of any pitch); workspace: uint8 of at least
+    gp_lift_batched_workspace_bytes(n, V)."""
+    lib = _lib.load()
+    _chk(points, torch.float64, "points"), _chk(maps_pm, torch.float32, "maps_pm"), _chk(view_entry, torch.int64, "view_entry")
+    _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
+    (h, w), (H, W) = map_hw, image_hw
+    n, dev = points.shape[0], points.device
+    if points.dim() != 2 or points.shape[1] != 4 or maps_pm.dim() != 3 or maps_pm.shape[1] != h * w:
+        raise ValueError(f"lift_batched: expected points [n, 4] and maps_pm [V, {h * w}, D], got {list(points.shape)}, {list(maps_pm.shape)}")
+    nv, _, d = maps_pm.shape
+    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
+        raise ValueError(f"lift_batched: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
+                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
+        raise ValueError(f"lift_batched: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    want = {"seen": (torch.uint8, (n,)), "count": (torch.int32, (n,)), "view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,)),
+            "status": (torch.int64, (8,))}
+    if fill:
+        want["nn"] = (torch.int64, (n,))
+    got = {}
+    for name, (dtype, shape) in want.items():
+        t = (buffers or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif _chk(t, dtype, name).shape != shape:
+            raise ValueError(f"lift_batched: expected {name} {list(shape)}, got {list(t.shape)}")
+        got[name] = t
+    out = (buffers or {}).get("out")
+    out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
+    need = lib.gp_lift_batched_workspace_bytes(n, nv)
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_batched(_ptr(points), n, _ptr(maps_pm), d, int(h), int(w), _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv,
+                              int(H), int(W), 1 if bilinear else 0, int(cut_bound), float(vis_thres), int(min_visible), int(max_visible),
+                              1 if fill else 0, _ptr(out), out.stride(0), _ptr(got["seen"]), _ptr(got["count"]), _ptr(got["view_count"]),
+                              _ptr(got["view_keep"]), _ptr(got.get("nn")), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()),
+          "gp_lift_batched")
+    return LiftBatched(out, got["seen"], got["count"], got["view_count"], got["view_keep"], got.get("nn"), got["status"])
+
+
 # ------------------------------------------------------------------------------------------ SURVEY 8f-1: training step
 def col_stats(y, c=None):
     """mean, biased variance of the rows of y fp32 [nv, >=c] (BatchNorm1d training statistics)."""

@@ -6,9 +6,11 @@ Quantisation is the step the reference writes by hand in front of the student (m
 return_inverse=True) + torch_scatter.scatter_mean + ME.SparseTensor(features, batched_coordinates), then
 s_output.F[sample_to_voxel_map]) and every MinkowskiEngine user gets from SparseTensor(quantization_mode=...).  The purifying step is
 evaluate_scene's (:1547-1587): exact kNN, sharpened cosine affinity, 19 applications of the operator -- here for every batch entry at
-once, entries never mixing.  The full chain, per-point features of several scenes in, purified per-point features out:
+once, entries never mixing.  The full chain, the points, poses, depths and VLM feature maps of several scenes in, purified per-point
+features out:
 
-    q = quantize(coordinates, features, mode="average")         # coordinates [N,4] = batch, x, y, z; duplicates allowed
+    lifted = lift(points, Views(maps, view_entry, world_to_camera, intrinsics, depth))   # points [N,4] = batch, world x, y, z
+    q = quantize(points, lifted.features, mode="average", quantization_size=voxel)       # duplicates allowed
     x = SparseTensor(features=q.features, coordinates=q.coordinates)
     y = affinity_pool(x, student(x))                            # or purify(student, x, feature_dim=D): the two calls in one
     per_point = y.F[q.inverse_mapping]
@@ -30,6 +32,9 @@ differentiable=True) -- puts y.F into the autograd graph, so a loss on the purif
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
 l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene; segment (labels and counts) never does.
 
+lift is the reference's lift_lseg_features (models/affinity_module.py:404-452) with the point -> pixel mapping of
+models/utils/fusion_util.py:45-147 and the loader's view-drop rule (dataset/data_loader_ablation.py:254-288), for all entries and all
+views in one call of ops.lift_batched, then ops.gather_rows for the fill.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -103,6 +108,131 @@ class _Subsample(torch.autograd.Function):
         g = ops.gather_rows(_rows_f32(d_out), d_out.shape[1], q.inverse)
         chosen = q.unique_index.index_select(0, q.inverse) == torch.arange(q.n, device=g.device)
         return torch.where(chosen.unsqueeze(1), g, torch.zeros((), dtype=g.dtype, device=g.device)).to(ctx.dtype), None
+
+
+# ------------------------------------------------------------------------------------------ the 2D -> 3D lift
+LIFT_MODES = ("nearest", "bilinear")
+
+
+class Views:
+    """The views of a batch of scenes: features fp32 [V,D,h,w] (the frozen VLM's maps, NCHW contiguous or torch.channels_last; other
+    floating dtypes are upcast), view_entry integer [V] (the batch entry a view looks at), world_to_camera fp64 [V,4,4], intrinsics fp64
+    [V,4] = fx, fy, cx, cy at the image size, depth fp64 [V,H,W] or None (None: a point is visible where it projects inside the image
+    with p_z > 0), image_shape = (H, W) shared by all views (default: the maps' (h, w)).
+    world_to_camera is the row-major world->camera matrix: the transpose of the reference's world_view_transform, or the inverse of a
+    camera-to-world matrix.  lift checks the fields."""
+
+    def __init__(self, features, view_entry, world_to_camera, intrinsics, depth=None, image_shape=None):
+        self.features, self.view_entry, self.world_to_camera, self.intrinsics = features, view_entry, world_to_camera, intrinsics
+        self.depth, self.image_shape = depth, image_shape
+
+
+class Lifted:
+    """features fp32 [N,D] in the points' row order, seen bool [N] (some kept view sees the point), count i32 [N] (the kept views that
+    see it), view_count i64 [V] (the points of its entry a view sees), view_keep bool [V] (the view passed the drop rule)."""
+
+    def __init__(self, features, seen, count, view_count, view_keep):
+        self.features, self.seen, self.count, self.view_count, self.view_keep = features, seen, count, view_count, view_keep
+
+
+def _shape_of(t):
+    return list(t.shape) if torch.is_tensor(t) else type(t).__name__
+
+
+def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
+    """The 2D -> 3D lift of the reference (models/affinity_module.py:404-452, models/utils/fusion_util.py:45-147,
+    dataset/data_loader_ablation.py:254-288) for several scenes at once, entries never mixing.  points: floating (fp64 or fp32) [N,4] =
+    batch index (integral, 0..65535), world x, y, z, on the GPU, in any row order; views: a Views.  Per entry b -- its points the rows
+    with batch b in ascending row order, its views those with view_entry == b in ascending view index:
+      1. a point is visible in a view when it projects inside [cut_bound, W - cut_bound) x [cut_bound, H - cut_bound) (pixels rounded
+         half to even) and |depth - p_z| <= vis_thres * depth there (without depths: p_z > 0);
+      2. view_keep[v] = n_v != 0 and n_v >= min_visible and n_v <= max_visible (None: no upper bound), n_v = view_count[v];
+      3. the sampled feature columns of the kept views that see a point are summed in fp32 in ascending v;
+      4. features = sum / (count == 0 ? 1e-6 : count), seen = count > 0;
+      5. with fill, in an entry that has both seen and unseen points every unseen point takes the row of the seen point OF ITS ENTRY
+         that minimises (d^2, row number), d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over the fp32-rounded xyz.
+    mode "nearest" samples the map's own pixel and needs (h, w) == image_shape; "bilinear" is the LSeg form: F.interpolate(bilinear,
+    align_corners=True) of the [h,w] map to image_shape, evaluated at the sampled pixels only.  An entry without views, or with nothing
+    seen, keeps zero rows; a view whose entry has no points has view_count 0.  The result is the same bits as HotPath.lift_dense /
+    lift_lseg on each scene by itself.  -> Lifted.  No gradients: the VLM is frozen and the reference lifts under no_grad, so maps that
+    require grad are refused and the points are detached.
+    Inside: ops.lift_batched (the entry tables, the per-view counts, the fused lift kernel over pixel-major maps -- a channels_last
+    tensor is read in place, an NCHW one goes through ops.lift_batched_transpose once --, the per-entry masked 1-NN) and
+    ops.gather_rows.  ValueError before any kernel: shape / dtype / device mismatches, CPU tensors, an unknown mode, maps that require
+    grad, more than 65535 views, N >= 2^31; from the ONE status read-back, taken after the last launch (no buffer is sized by what it
+    carries): rows whose batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates."""
+    who = "lift"
+    if mode not in LIFT_MODES:
+        raise ValueError(f"{who}: mode={mode!r}, expected one of {LIFT_MODES}")
+    if not isinstance(views, Views):
+        raise ValueError(f"{who}: views must be a Views, got {type(views).__name__}")
+    P, Fm, E, M, K, Dp = points, views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    if not torch.is_tensor(Fm) or Fm.dim() != 4 or min(Fm.shape) < 1:
+        raise ValueError(f"{who}: views.features must be [V, D, h, w] with V, D, h, w >= 1, got {_shape_of(Fm)}")
+    if not Fm.dtype.is_floating_point:
+        raise ValueError(f"{who}: views.features must be floating point, got {Fm.dtype}")
+    V, D, h, w = Fm.shape
+    if V > 65535:
+        raise ValueError(f"{who}: {V} views, at most 65535")
+    if not _is_int_tensor(E) or E.shape != (V,):
+        raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
+        raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
+    if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
+        raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
+                         f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+    shape = (h, w) if views.image_shape is None else tuple(views.image_shape)
+    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+        raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers, got {views.image_shape!r}")
+    H, W = shape
+    if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
+        raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
+                         f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+    if mode == "nearest" and (h, w) != (H, W):
+        raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
+        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
+    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
+        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    if Fm.requires_grad:
+        raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
+                         "no_grad); detach them")
+    tensors = [P, Fm, E, M, K] + ([Dp] if Dp is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    dev = P.device
+    with torch.cuda.device(dev), torch.no_grad():
+        pts = P.detach().to(torch.float64).contiguous()
+        maps = Fm.detach().to(torch.float32)
+        if maps.is_contiguous(memory_format=torch.channels_last):
+            maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)          # (a view: channels_last is pixel-major already)
+        else:
+            maps_pm = ops.lift_batched_transpose(maps.contiguous())
+        r = ops.lift_batched(pts, maps_pm, (h, w), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous(),
+                             None if Dp is None else Dp.detach().contiguous(), (H, W), mode == "bilinear", cut_bound, float(vis_thres),
+                             min_visible, 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1), fill=bool(fill))
+        feats = r.out
+        if fill:
+            feats = ops.gather_rows(r.out, D, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
+        bad_batch, bad_view, nonfinite = ops.readback(r.status)[:3]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    return Lifted(feats, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
 
 
 def _voxel_size(quantization_size, like):

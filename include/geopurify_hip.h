@@ -789,6 +789,52 @@ int gp_fused_decode(const uint8_t *mask_chunk, int64_t n, const uint8_t *row_kee
                     void *out, uint8_t *mask_out, int64_t *n_sel, void *workspace, size_t workspace_bytes,
                     void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The 2D -> 3D lift over BATCHED point clouds: models/affinity_module.py:404-452 (sample each view  */
+/* at the visible pixels, mean over views, unseen points take the nearest seen point) with the       */
+/* point -> pixel mapping of models/utils/fusion_util.py:45-147 and the view-drop rule of            */
+/* dataset/data_loader_ablation.py:254-288, for every batch entry and every view in one sequence of  */
+/* launches; entries never mix.  It replaces, per scene, gp_views_visible_lists, one                 */
+/* gp_lift_dense_accum / gp_lift_dense_bilinear_accum launch per view, gp_lift_dense_finish and      */
+/* gp_nn1_masked_f64, and gives the same bits.                                                       */
+/* points f64 [n,4] = batch index, world x, y, z, in any row order.  Entry b's points are the rows   */
+/* with batch b in ascending row order, its views the v with view_entry[v] == b in ascending v.      */
+/* feat f32 [nviews, h*w, d], PIXEL-MAJOR (a channels_last [V,d,h,w] tensor as it lies; an NCHW one    */
+/* through gp_lift_batched_transpose); view_entry i64 [nviews]; w2c f64 [nviews,16] row-major          */
+/* world->camera, worded as gp_project_points_f64 words it (the transpose of the reference's          */
+/* world_view_transform, or the inverse of a camera-to-world matrix); intrinsics f64 [nviews,4] = fx,  */
+/* fy, cx, cy at the image size; depth f64 [nviews,height,width] or NULL (NULL: the p_z > 0 test).     */
+/* bilinear = 0: the maps are images (h == height, w == width) and a pixel's row is taken as it is;   */
+/* 1: F.interpolate(bilinear, align_corners=True) of the [h,w] map to the image, evaluated at the      */
+/* sampled pixels with gp_lift_dense_bilinear_accum's arithmetic.                                     */
+/*   view_count i64 [nviews]: the points of the view's entry that the view sees;                      */
+/*   view_keep u8 [nviews] = view_count != 0 && min_visible <= view_count <= max_visible;             */
+/*   count i32 [n]: the kept views that see the point; seen u8 [n] = count > 0;                        */
+/*   out f32 [n, ld_out >= d]: the fp32 sum over those views in ascending v of the sampled column,     */
+/*     divided by (count == 0 ? 1e-6 : count) -- zeros for an unseen point;                           */
+/*   nn i64 [n] (fill != 0; nullable otherwise): for an unseen point of an entry that has seen points  */
+/*     the seen row OF ITS ENTRY that minimises (d^2, row), d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over */
+/*     the fp32-rounded xyz (gp_nn1_masked_f64's rule), -1 elsewhere.  out is not rewritten: the       */
+/*     caller gathers rows by nn (gp_gather_rows);                                                    */
+/*   status i64 [8]: [0] rows whose batch index is no integer in 0..65535, [1] views whose entry is    */
+/*     outside 0..65535, [2] rows with a non-finite value, [3] the highest valid batch index, [4] seen */
+/*     rows, [5] filled rows.  Rows and views counted in [0] / [1] belong to no entry (count 0, zero   */
+/*     rows, nn -1, view_count 0); nothing is read or written outside the extents whatever they hold.  */
+/* No float atomics: two calls give the same bits.  1 <= n < 2^31, 1 <= nviews <= 65535, d >= 1,      */
+/* cut_bound >= 0.  No output may overlap an input or another output (GP_EINVAL).                     */
+/* gp_lift_batched_col_chunk: the channels one pass of the lift kernel holds in registers (wider rows  */
+/* take several passes).                                                                              */
+int32_t gp_lift_batched_col_chunk(void);
+/* src f32 [nviews, d, hw] (NCHW maps) -> dst f32 [nviews, hw, d]; dst must not overlap src.          */
+int gp_lift_batched_transpose(const float *src, int32_t nviews, int32_t d, int64_t hw, float *dst, void *stream);
+size_t gp_lift_batched_workspace_bytes(int64_t n, int32_t nviews);
+int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t d, int32_t h, int32_t w,
+                    const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
+                    int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres,
+                    int64_t min_visible, int64_t max_visible, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
+                    int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn, int64_t *status,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
