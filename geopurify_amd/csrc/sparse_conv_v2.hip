@@ -614,9 +614,9 @@ conv_phase1_dma_body(const _Float16 *__restrict__ x_hi, const _Float16 *__restri
     // ---- epilogue: accumulators straight to the partial buffer (no LDS staging: that made every slice's LDS reads wait for the
     //      previous slice's stores -- one vector-memory counter -- 4 store round trips per tile, a third of the kernel's time).
     // PARTIAL ROWS ARE STORED AS 24-BIT BLOCK FLOATING POINT (round 5): per pair row and 128-column quarter (= what one wave owns) an
-    // exponent byte E and per element u = rint(v * 2^(148 - E)) + 2^22 in three bytes, |v * 2^(148 - E)| < 2^22 for every element of
+    // exponent byte E and per element u = rint(v * 2^(148 - E)) + 2^22 in three bytes, |v * 2^(148 - E)| <= 2^22 - 1/2 (0 <= u <= 2^23) for every element of
     // the quarter -- 3 + 1/128 bytes instead of 4 per element of the round trip phase 1 -> Infinity Cache -> phase 2 (2 x 2.0 GB per
-    // 512 -> 512 layer in fp32).  Encoding costs ONE fused multiply-add per element: t = fma(acc, s, 1.5 * 2^23) lies in [2^23, 2^24),
+    // 512 -> 512 layer in fp32).  Encoding costs ONE fused multiply-add per element: t = fma(acc, s, 1.5 * 2^23) lies in [2^23, 2^24],
     // where floats are the integers, so the hardware's round-to-nearest-even IS the quantisation and the three low bytes of t's bit
     // pattern ARE u; eight elements = 24 bytes per lane, packed by six byte permutes.  The rounding is half a unit of 2^(E - 148): between
     // 2^-23 and 2^-22 of the quarter's largest magnitude per partial row -- no more than the NEXT rounding on the path (phase 2 splits

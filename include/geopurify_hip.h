@@ -163,7 +163,9 @@ int gp_sparse_conv_tiles(int32_t *tiles);
 /* when chunked) for the partial rows between the two phases -- fp32 rows on the register-staged path   */
 /* (x fp32), 24-bit block floating point on the LDS-DMA path (x_hi / x_lo; 3 bytes per element + one    */
 /* exponent byte per (pair row, 128 columns): rounded within 2^-22 of the quarter's largest magnitude,   */
-/* the rounding of the f16 hi + lo split that follows; an Inf / NaN activation row makes the output      */
+/* the rounding of the f16 hi + lo split that follows; an element is u = rint(v 2^(148 - E)) + 2^22 with  */
+/* 0 <= u <= 2^23, both ends reached, and E is clamped to >= 22: values below 2^-104 stay below 2^-104; */
+/* an Inf / NaN activation row makes the output      */
 /* rows that gather it NaN -- so does ONE overflowing element of a partial row: its whole 128-column    */
 /* quarter is marked, where fp32 rows kept Inf in that element and finite neighbours.  The 24-bit rows   */
 /* use 32-bit byte offsets: a call whose largest chunk holds pairs * cout * 3 >= 4 GiB runs on fp32     */

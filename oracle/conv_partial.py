@@ -3,12 +3,19 @@ the build's sparse convolution (geopurify_amd/csrc/sparse_conv_v2.hip, DESIGN.md
 convolution is MinkowskiEngine's (affinity_module.py:36-66) -- so this restates the build's own stated format, in numpy, for the tests
 to hold the kernels to byte for byte.
 
-Per pair row and 128-column quarter:  E  = exponent field of (largest |v| of the quarter, one unit in the last place added) -- an
+A pair row is a row of accumulators a times its input row's power of two 2^e (e = 0 without row scales): v = a 2^e.
+Per pair row and 128-column quarter:  Em = exponent field of (largest |a| of the quarter, one unit in the last place added) -- an
                                            all-ones mantissa takes the next exponent;  255 when the quarter holds an Inf or a NaN
-                                      u  = rint(v * 2^(148 - E)) + 2^22      (round half to even; 0 < u < 2^23), three little-endian bytes
+                                      E  = max(Em + e, 22), the stored byte;  255 when Em = 255 or Em + e > 254 (phase 2 writes NaN)
+                                      u  = rint(a * 2^(148 - Em)) + 2^22     (round half to even), three little-endian bytes, 0 <= u <= 2^23:
+                                           |a| 2^(148 - Em) <= 2^22 - 1/2 over the quarter, and a largest magnitude with mantissa 0x7ffffe sits AT
+                                           2^22 - 1/2, which rounds to even: u = 2^23, its negative twin u = 0.  2^23 fits the three bytes and
+                                           decodes to the next power of two, still within half a unit of the value.
+                                           (Em < 21: the multiplier stops at 2^127, the largest finite power of two.)
 A quarter's 384 bytes: the first 16 bytes of its 16 lanes (lane f = columns 8 f .. 8 f + 7, 24 bytes), then their last 8.
 The exponent bytes follow the rows of the chunk at the next multiple of 16 bytes.  Decoded value = (u - 2^22) * 2^(E - 148): within half a
-unit, 2^(E - 149) <= 2^-22 of the quarter's largest magnitude.  (The kernel clamps E to >= 22: values below 2^-104 -- not restated.)
+unit, 2^(E - 149) <= 2^-22 of the quarter's largest magnitude, wherever Em + e >= 22.  Below the clamp (Em + e < 22: every |v| of the quarter
+below 2^-105) the decoded value is v times a power of two >= 1 and stays below 2^-104 in magnitude: an all-zero quarter is E = 22, u = 2^22.
 """
 import numpy as np
 
@@ -25,14 +32,32 @@ def exponents(v):
     return np.where(nan | (E >= 255), 255, E)
 
 
-def encode(v):
-    """v f32 [P, cout] -> (rows uint8 [P * cout * 3], E uint8 [P * cout / 128]) in the kernel's layout (finite quarters only)"""
+def stored_exponents(v, row_exp=None):
+    """accumulators v f32 [P, cout], row_exp int [P] (the input rows' e, default 0) -> the stored bytes E int64 [P, cout / 128]"""
+    Em = exponents(v)
+    e = np.zeros(v.shape[0], np.int64) if row_exp is None else np.asarray(row_exp, np.int64)
+    Es = np.maximum(Em + e[:, None], 22)
+    return np.where((Em == 255) | (Es > 254), 255, Es)
+
+
+def units(v):
+    """accumulators v f32 [P, cout] (finite) -> u int64 [P, cout / 128, 128]"""
+    P, cout = v.shape
+    Em = exponents(v)
+    assert (Em < 255).all(), "the restatement of u covers finite accumulators"
+    mult = np.exp2(np.minimum(275 - Em, 254) - 127.0)                   # 2^(148 - Em), at most 2^127
+    u = np.rint(v.reshape(P, cout // QUARTER, QUARTER).astype(np.float64) * mult[:, :, None]).astype(np.int64) + (1 << 22)
+    assert u.min() >= 0 and u.max() <= (1 << 23)
+    return u
+
+
+def encode(v, row_exp=None):
+    """accumulators v f32 [P, cout] (finite), row_exp int [P] (default 0) -> (rows uint8 [P * cout * 3], E uint8 [P * cout / 128]) in the
+    kernel's layout"""
     P, cout = v.shape
     nq = cout // QUARTER
-    E = exponents(v)
-    assert (E >= 22).all() and (E < 255).all(), "the restatement covers finite quarters above 2^-104"
-    u = np.rint(v.reshape(P, nq, QUARTER).astype(np.float64) * np.exp2(148.0 - E)[:, :, None]).astype(np.int64) + (1 << 22)
-    assert u.min() > 0 and u.max() < (1 << 23)
+    E = stored_exponents(v, row_exp)
+    u = units(v)
     lanes = u.reshape(P, nq, 16, 8)
     b = np.stack([(lanes >> (8 * t)) & 255 for t in range(3)], axis=-1).astype(np.uint8).reshape(P, nq, 16, 24)
     rows = np.concatenate([b[..., :16].reshape(P, nq, 256), b[..., 16:].reshape(P, nq, 128)], axis=2).reshape(-1)
