@@ -171,6 +171,14 @@ SIGNATURES = {
     "gp_lift_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_lift_batched": (c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_double, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_batched_lists_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_lift_masks_batched_lists": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_double, c_int64, c_int64,
+                                              c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_batched_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
+                                                         c_int64]),
+    "gp_lift_masks_batched": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32,
+                                        _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
+                                        _P, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

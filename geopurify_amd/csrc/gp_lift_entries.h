@@ -1,0 +1,221 @@
+// Device code shared by the lifts over BATCHED point clouds (lift_batched.hip: gp_lift_batched; lift_masks_batched.hip): the
+// entry tables (rows and views sorted stably by entry, offsets by binary search), the per-view counts with the view-drop rule, and
+// the per-entry scene-level fill (references and queries compacted in the entry-sorted order).  One definition for both.
+#pragma once
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "gp_common.h"
+#include "gp_project.h"
+
+namespace {
+
+constexpr int LB_MAX_ENTRIES = 65536;
+constexpr int LB_KEY_BITS = 17;                                  // keys 0 .. 65536 (65536: no valid entry)
+constexpr int LB_TABLE = LB_MAX_ENTRIES + 2;                     // off[b] for b = 0 .. 65537: off[65536] = first bad row, off[65537] = n
+constexpr int LB_TILE = 1024;                                    // references per LDS tile of the fill
+
+enum { ST_BAD_BATCH = 0, ST_BAD_VIEW = 1, ST_NONFINITE = 2, ST_TOP_BATCH = 3, ST_SEEN = 4, ST_QUERIES = 5, ST_WORDS = 8 };
+
+inline bool lb_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// the entry of a point row (its batch column), -1 when it is no integer in 0..65535 (NaN included)
+__device__ __forceinline__ int lb_entry_of(double b) {
+    return (b >= 0.0 && b <= 65535.0 && b == floor(b)) ? (int)b : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ entry tables
+__global__ void __launch_bounds__(256) lb_row_keys_kernel(const double *__restrict__ points, int64_t n, uint32_t *__restrict__ keys,
+                                                          int32_t *__restrict__ rows, unsigned long long *__restrict__ status) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const bool live = r < n;
+    bool nonfinite = false, bad = false;
+    int b = -1;
+    if (live) {
+        const double *P = points + r * 4;
+        nonfinite = !(fabs(P[0]) < INFINITY && fabs(P[1]) < INFINITY && fabs(P[2]) < INFINITY && fabs(P[3]) < INFINITY);
+        b = lb_entry_of(P[0]);
+        bad = b < 0 && fabs(P[0]) < INFINITY;
+        keys[r] = b >= 0 ? (uint32_t)b : (uint32_t)LB_MAX_ENTRIES;
+        rows[r] = (int32_t)r;
+    }
+    const int nbad = __popcll(__ballot(bad)), nnf = __popcll(__ballot(nonfinite));
+    int top = b;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o, 64));
+    if (gp_lane() == 0) {
+        if (nbad) atomicAdd(status + ST_BAD_BATCH, (unsigned long long)nbad);
+        if (nnf) atomicAdd(status + ST_NONFINITE, (unsigned long long)nnf);
+        if (top >= 0) atomicMax(status + ST_TOP_BATCH, (unsigned long long)top);
+    }
+}
+
+__global__ void __launch_bounds__(256) lb_view_keys_kernel(const int64_t *__restrict__ view_entry, int nviews, uint32_t *__restrict__ keys,
+                                                           int32_t *__restrict__ views, unsigned long long *__restrict__ status) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (v < nviews) {
+        const int64_t e = view_entry[v];
+        bad = (uint64_t)e >= (uint64_t)LB_MAX_ENTRIES;
+        keys[v] = bad ? (uint32_t)LB_MAX_ENTRIES : (uint32_t)e;
+        views[v] = v;
+    }
+    const int nbad = __popcll(__ballot(bad));
+    if (gp_lane() == 0 && nbad) atomicAdd(status + ST_BAD_VIEW, (unsigned long long)nbad);
+}
+
+// off[b] = the first sorted position whose key is >= b, b = 0 .. 65537 (keys are <= 65536, so off[65537] = n)
+__global__ void __launch_bounds__(256) lb_offsets_kernel(const uint32_t *__restrict__ keys_sorted, int64_t n, int32_t *__restrict__ off) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= LB_TABLE) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys_sorted[mid] < (uint32_t)b) lo = mid + 1;
+        else hi = mid;
+    }
+    off[b] = (int32_t)lo;
+}
+
+// ------------------------------------------------------------------------------------------------ per-view counts and the drop rule
+// blockIdx.y = view; the blocks of a view stride the rows of its entry.  Integer atomics: the counts do not depend on arrival order.
+__global__ void __launch_bounds__(256) lb_counts_kernel(const double *__restrict__ points, const int32_t *__restrict__ entry_rows,
+                                                        const int32_t *__restrict__ entry_off, const int64_t *__restrict__ view_entry,
+                                                        const double *__restrict__ w2c, const double *__restrict__ intr,
+                                                        const double *__restrict__ depth, int W, int H, int cut, double tau,
+                                                        unsigned long long *__restrict__ view_count) {
+    const int v = blockIdx.y;
+    const int64_t e = view_entry[v];
+    if ((uint64_t)e >= (uint64_t)LB_MAX_ENTRIES) return;             // (block-uniform)
+    const int64_t r0 = entry_off[e], r1 = entry_off[e + 1];
+    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+    const double *dv = depth ? depth + (int64_t)v * W * H : nullptr;
+    int local = 0;
+    for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r1; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *P = points + (int64_t)entry_rows[i] * 4;
+        long long ui, vi;
+        local += project_point(P[1], P[2], P[3], M, M + 4, M + 8, K[0], K[1], K[2], K[3], dv, W, H, cut, tau, ui, vi) ? 1 : 0;
+    }
+    local = gp_wave_sum_i(local);
+    if (gp_lane() == 0 && local) atomicAdd(view_count + v, (unsigned long long)local);
+}
+
+// the view-drop rule of the loader (data_loader_ablation.py:254-255, 280-288)
+__global__ void lb_keep_kernel(const unsigned long long *__restrict__ view_count, int nviews, int64_t min_visible, int64_t max_visible,
+                               uint8_t *__restrict__ keep) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nviews) return;
+    const int64_t nv = (int64_t)view_count[v];
+    keep[v] = (nv != 0 && nv >= min_visible && nv <= max_visible) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the fill
+// sorted position s: ref[s] = the row is seen; qry[s] = unseen, in a valid entry (decided later whether that entry has references)
+__global__ void __launch_bounds__(256) lb_fill_flags_kernel(const uint32_t *__restrict__ keys_sorted, const int32_t *__restrict__ entry_rows,
+                                                            const uint8_t *__restrict__ seen, int64_t n, int32_t *__restrict__ ref,
+                                                            int32_t *__restrict__ qry) {
+    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (s > n) return;
+    int r = 0, q = 0;
+    if (s < n && keys_sorted[s] < (uint32_t)LB_MAX_ENTRIES) {
+        r = seen[entry_rows[s]] ? 1 : 0;
+        q = 1 - r;
+    }
+    ref[s] = r;
+    qry[s] = q;
+}
+
+// rs / qs: the exclusive scans of the flags over n + 1 elements (rs[n] = references, qs[n] = unseen rows of valid entries)
+__global__ void __launch_bounds__(256) lb_fill_compact_kernel(const double *__restrict__ points, const int32_t *__restrict__ entry_rows,
+                                                              const int32_t *__restrict__ ref, const int32_t *__restrict__ qry,
+                                                              const int32_t *__restrict__ rs, const int32_t *__restrict__ qs, int64_t n,
+                                                              float *__restrict__ rxyz, int32_t *__restrict__ rrow, int32_t *__restrict__ qpos,
+                                                              unsigned long long *__restrict__ status) {
+    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    if (ref[s]) {
+        const int64_t j = rs[s], row = entry_rows[s];
+        const double *P = points + row * 4;
+        rxyz[j * 3] = (float)P[1];
+        rxyz[j * 3 + 1] = (float)P[2];
+        rxyz[j * 3 + 2] = (float)P[3];
+        rrow[j] = (int32_t)row;
+    }
+    if (qry[s]) qpos[qs[s]] = (int32_t)s;
+    if (s == n - 1) status[ST_SEEN] = (unsigned long long)rs[n];
+}
+
+// 256 queries (compacted, in the entry-sorted order) per block.  A query's references are the run [rs[entry_off[b]], rs[entry_off[b+1]])
+// of its entry b; the block streams the union of its queries' runs -- one contiguous range, since both lists are entry-sorted --
+// through LDS, every query comparing inside its own run only.  d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over the fp32-rounded xyz, the
+// first strict minimum wins and a run ascends by row: the (d^2, row) rule of gp_nn1_masked_f64.
+__global__ void __launch_bounds__(256) lb_fill_kernel(const double *__restrict__ points, const uint32_t *__restrict__ keys_sorted,
+                                                      const int32_t *__restrict__ entry_rows, const int32_t *__restrict__ entry_off,
+                                                      const int32_t *__restrict__ rs, const int32_t *__restrict__ qs, int64_t n,
+                                                      const float *__restrict__ rxyz, const int32_t *__restrict__ rrow,
+                                                      const int32_t *__restrict__ qpos, int64_t *__restrict__ nn,
+                                                      unsigned long long *__restrict__ status) {
+    __shared__ double sx[LB_TILE], sy[LB_TILE], sz[LB_TILE];
+    __shared__ int s_lo, s_hi, s_filled;
+    const int64_t nq = qs[n];
+    if ((int64_t)blockIdx.x * 256 >= nq) return;                     // (block-uniform)
+    if (threadIdx.x == 0) { s_lo = INT32_MAX; s_hi = 0; s_filled = 0; }
+    __syncthreads();
+    const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int r0 = 0, r1 = 0;
+    int64_t row = -1;
+    double qx = 0, qy = 0, qz = 0;
+    if (qi < nq) {
+        const int64_t s = qpos[qi];
+        const uint32_t b = keys_sorted[s];                           // < 65536: only rows of valid entries are queries
+        r0 = rs[entry_off[b]];
+        r1 = rs[entry_off[b + 1]];
+        row = entry_rows[s];
+        const double *P = points + row * 4;
+        qx = (double)(float)P[1]; qy = (double)(float)P[2]; qz = (double)(float)P[3];
+        if (r1 > r0) { atomicMin(&s_lo, r0); atomicMax(&s_hi, r1); }
+    }
+    __syncthreads();
+    const int lo = s_lo, hi = s_hi;
+    double best = INFINITY;
+    int bi = -1;
+    for (int t0 = lo; t0 < hi; t0 += LB_TILE) {
+        const int tn = hi - t0 < LB_TILE ? hi - t0 : LB_TILE;
+        __syncthreads();
+        for (int j = threadIdx.x; j < tn; j += 256) {
+            sx[j] = rxyz[(int64_t)(t0 + j) * 3]; sy[j] = rxyz[(int64_t)(t0 + j) * 3 + 1]; sz[j] = rxyz[(int64_t)(t0 + j) * 3 + 2];
+        }
+        __syncthreads();
+        const int j0 = r0 > t0 ? r0 - t0 : 0, j1 = r1 - t0 < tn ? r1 - t0 : tn;
+        for (int j = j0; j < j1; ++j) {
+            const double dx = qx - sx[j], dy = qy - sy[j], dz = qz - sz[j];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 < best) { best = d2; bi = t0 + j; }
+        }
+    }
+    if (bi >= 0) {
+        nn[row] = rrow[bi];
+        atomicAdd(&s_filled, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_filled) atomicAdd(status + ST_QUERIES, (unsigned long long)s_filled);
+}
+
+size_t lb_sort_bytes(int64_t n) {
+    size_t t = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0,
+                                    LB_KEY_BITS, 0);
+    return t;
+}
+
+size_t lb_scan_bytes(int64_t n) {
+    size_t t = 0;
+    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
+    return t;
+}
+
+}  // namespace

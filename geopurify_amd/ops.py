@@ -1523,6 +1523,135 @@ def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, im
     return LiftBatched(out, got["seen"], got["count"], got["view_count"], got["view_keep"], got.get("nn"), got["status"])
 
 
+# ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
+def _outputs(who, want, buffers, dev):
+    """the named outputs: the caller's (checked) or fresh ones"""
+    got = {}
+    for name, (dtype, shape) in want.items():
+        t = (buffers or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif _chk(t, dtype, name).shape != shape:
+            raise ValueError(f"{who}: expected {name} {list(shape)}, got {list(t.shape)}")
+        got[name] = t
+    return got
+
+
+class LiftMasksLists:
+    """What gp_lift_masks_batched_lists writes: the view-major entries pt / x / y i64 [total] (global point row, pixel row, pixel
+    column), view i32 [total], view_off i64 [V+1], view_count i64 [V], view_keep u8 [V], status i64 [8] = (bad batch rows, bad view
+    entries, non-finite rows, top batch, 0, entries that did not fit, entries in all, the most views of one entry); total and max_views
+    are the two sizes, read back."""
+
+    def __init__(self, pt, x, y, view, view_off, view_count, view_keep, status, total, max_views):
+        self.pt, self.x, self.y, self.view, self.view_off, self.view_count, self.view_keep = pt, x, y, view, view_off, view_count, view_keep
+        self.status, self.total, self.max_views = status, total, max_views
+
+
+def lift_masks_batched_lists(points, view_entry, w2c, intrinsics, depth, image_hw, cut_bound, vis_thres, min_visible, max_visible, buffers=None,
+                             workspace=None, total=None):
+    """The visible lists of all views of all entries: points f64 [n,4]; view_entry i64 [V]; w2c f64 [V,4,4]; intrinsics f64 [V,4]; depth
+    f64 [V,H,W] or None; image_hw = (H, W).  -> LiftMasksLists.  Two calls of gp_lift_masks_batched_lists around ONE read-back (ops.readback
+    of the counting call's status: the entries in all size the arrays); total: the count when the caller knows it already (no read-back,
+    max_views is None then).  buffers: optional dict of caller-owned outputs by attribute name (pt, x, y, view need total); workspace:
+    uint8 of at least gp_lift_masks_batched_lists_workspace_bytes(n, V)."""
+    lib = _lib.load()
+    who = "lift_masks_batched_lists"
+    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c")
+    _chk(intrinsics, torch.float64, "intrinsics")
+    H, W = image_hw
+    n, nv, dev = points.shape[0], view_entry.shape[0], points.device
+    if points.dim() != 2 or points.shape[1] != 4 or view_entry.dim() != 1 or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
+        raise ValueError(f"{who}: expected points [n, 4], view_entry [V], w2c [V, 4, 4], intrinsics [V, 4], got {list(points.shape)}, "
+                         f"{list(view_entry.shape)}, {list(w2c.shape)}, {list(intrinsics.shape)}")
+    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
+        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    got = _outputs(who, {"view_off": (torch.int64, (nv + 1,)), "view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,)),
+                         "status": (torch.int64, (8,))}, buffers, dev)
+    need = lib.gp_lift_masks_batched_lists_workspace_bytes(n, nv)
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+
+    def call(cap, ent):
+        check(lib.gp_lift_masks_batched_lists(_ptr(points), n, _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv, int(H), int(W),
+                                              int(cut_bound), float(vis_thres), int(min_visible), int(max_visible), int(cap), _ptr(ent.get("pt")),
+                                              _ptr(ent.get("x")), _ptr(ent.get("y")), _ptr(ent.get("view")), _ptr(got["view_off"]),
+                                              _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(got["status"]), _ptr(ws), ws.numel(),
+                                              _stream()), "gp_lift_masks_batched_lists")
+
+    max_views = None
+    if total is None:
+        call(0, {})
+        sizes = readback(got["status"])
+        total, max_views = int(sizes[6]), int(sizes[7])
+    ent = {}
+    if total > 0:
+        ent = _outputs(who, {"pt": (torch.int64, (total,)), "x": (torch.int64, (total,)), "y": (torch.int64, (total,)),
+                             "view": (torch.int32, (total,))}, buffers, dev)
+        call(total, ent)
+    return LiftMasksLists(ent.get("pt"), ent.get("x"), ent.get("y"), ent.get("view"), got["view_off"], got["view_count"], got["view_keep"],
+                          got["status"], total, max_views)
+
+
+class LiftMasksBatched:
+    """What gp_lift_masks_batched writes: out fp32 [n, d] (before the scene-level fill), seen u8 [n], count i32 [n], nn i64 [n] or None,
+    seg i32 [total] (every entry's segment after the in-view fill, -1 = none), status i64 [8] = (bad batch rows, bad view entries,
+    non-finite rows, top batch, seen rows, filled rows, entries that are not what the lists promise, views beyond words x 64)."""
+
+    def __init__(self, out, seen, count, nn, seg, status):
+        self.out, self.seen, self.count, self.nn, self.seg, self.status = out, seen, count, nn, seg, status
+
+
+def lift_masks_batched(points, view_entry, pred_masks, scores, taps, out_hw, ent, view_off, view_keep, total, words, f_seg, logit_seg, fill=True,
+                       fill_cap=None, buffers=None, workspace=None):
+    """gp_lift_masks_batched, no sync: from view-major entries to the fused rows.  points f64 [n,4]; view_entry i64 [V]; pred_masks f32
+    [V,Q,h,w]; scores f32 [V,Q]; taps = (x0 i32 [W], wx f32 [W,4], y0 i32 [H], wy f32 [H,4]); out_hw = (H, W); ent = (pt, x, y i64
+    [>= total], view i32 [>= total]) -- lift_masks_batched_lists' or the caller's own: entries of a view contiguous, rows ascending inside
+    it --; view_off i64 [V+1]; view_keep u8 [V]; words >= ceil(most views of one entry / 64); f_seg f32 [V,Q,d], logit_seg f32 [V,Q,C]
+    (segment_tables; d a multiple of 4).  -> LiftMasksBatched.  buffers: optional dict of caller-owned outputs by attribute name (out:
+    fp32 rows of a pitch that is a multiple of 4); workspace: uint8 of at least gp_lift_masks_batched_workspace_bytes(...)."""
+    lib = _lib.load()
+    who = "lift_masks_batched"
+    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry"), _chk(pred_masks, torch.float32, "pred_masks")
+    _chk(scores, torch.float32, "scores"), _chk(view_off, torch.int64, "view_off"), _chk(view_keep, torch.uint8, "view_keep")
+    _chk(f_seg, torch.float32, "f_seg"), _chk(logit_seg, torch.float32, "logit_seg")
+    tx0, twx, ty0, twy = taps
+    _chk(tx0, torch.int32, "tap_x0"), _chk(twx, torch.float32, "tap_wx"), _chk(ty0, torch.int32, "tap_y0"), _chk(twy, torch.float32, "tap_wy")
+    pt, x, y, view = ent
+    _chk(pt, torch.int64, "ent_pt"), _chk(x, torch.int64, "ent_x"), _chk(y, torch.int64, "ent_y"), _chk(view, torch.int32, "ent_view")
+    H, W = out_hw
+    n, dev, total = points.shape[0], points.device, int(total)
+    if points.dim() != 2 or points.shape[1] != 4 or pred_masks.dim() != 4 or view_entry.shape != (pred_masks.shape[0],):
+        raise ValueError(f"{who}: expected points [n, 4], pred_masks [V, Q, h, w], view_entry [V], got {list(points.shape)}, "
+                         f"{list(pred_masks.shape)}, {list(view_entry.shape)}")
+    nv, Q, h, w = pred_masks.shape
+    if scores.shape != (nv, Q) or view_off.shape != (nv + 1,) or view_keep.shape != (nv,):
+        raise ValueError(f"{who}: expected scores [{nv}, {Q}], view_off [{nv + 1}], view_keep [{nv}], got {list(scores.shape)}, "
+                         f"{list(view_off.shape)}, {list(view_keep.shape)}")
+    if tx0.shape != (W,) or twx.shape != (W, 4) or ty0.shape != (H,) or twy.shape != (H, 4):
+        raise ValueError(f"{who}: expected taps ([{W}], [{W}, 4], [{H}], [{H}, 4]), got {[list(t.shape) for t in taps]}")
+    if total < 1 or any(t.dim() != 1 or t.shape[0] < total for t in ent):
+        raise ValueError(f"{who}: expected four entry arrays of at least total = {total} >= 1 elements, got {[list(t.shape) for t in ent]}")
+    if f_seg.dim() != 3 or f_seg.shape[:2] != (nv, Q) or logit_seg.dim() != 3 or logit_seg.shape[:2] != (nv, Q):
+        raise ValueError(f"{who}: expected f_seg [{nv}, {Q}, d] and logit_seg [{nv}, {Q}, C], got {list(f_seg.shape)}, {list(logit_seg.shape)}")
+    d, C = f_seg.shape[2], logit_seg.shape[2]
+    want = {"seen": (torch.uint8, (n,)), "count": (torch.int32, (n,)), "seg": (torch.int32, (total,)), "status": (torch.int64, (8,))}
+    if fill:
+        want["nn"] = (torch.int64, (n,))
+    got = _outputs(who, want, buffers, dev)
+    out = (buffers or {}).get("out")
+    out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
+    if fill_cap is None:
+        fill_cap = min(total, max(total // 4, 65536))
+    need = lib.gp_lift_masks_batched_workspace_bytes(n, nv, Q, h, w, int(H), int(W), total, int(words), int(fill_cap))
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_masks_batched(_ptr(points), n, _ptr(view_entry), nv, _ptr(pred_masks), Q, h, w, _ptr(scores), _ptr(tx0), _ptr(twx), _ptr(ty0),
+                                    _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y), _ptr(view), _ptr(view_off), _ptr(view_keep), total,
+                                    int(words), int(fill_cap), _ptr(f_seg), _ptr(logit_seg), d, C, 1 if fill else 0, _ptr(out), out.stride(0),
+                                    _ptr(got["seen"]), _ptr(got["count"]), _ptr(got.get("nn")), _ptr(got["seg"]), _ptr(got["status"]), _ptr(ws),
+                                    ws.numel(), _stream()), "gp_lift_masks_batched")
+    return LiftMasksBatched(out, got["seen"], got["count"], got.get("nn"), got["seg"], got["status"])
+
+
 # ------------------------------------------------------------------------------------------ SURVEY 8f-1: training step
 def col_stats(y, c=None):
     """mean, biased variance of the rows of y fp32 [nv, >=c] (BatchNorm1d training statistics)."""

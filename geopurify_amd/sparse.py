@@ -16,6 +16,11 @@ features out:
     per_point = y.F[q.inverse_mapping]
     seg = segment(y, text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)   # labels per point, (I, O, T) counts per scene
 
+or, from the X-Decoder form of the VLM's outputs (masks, class logits, mask embeddings: the reference's default lift), the same chain with
+
+    lifted = lift_masks(points, MaskViews(pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth,
+                                          image_shape=(H, W)), text_embed, logit_scale)   # -> .features, .text_features (normalised)
+
 and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
 
     pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
@@ -35,6 +40,9 @@ l2norm_rows_backward).  The default takes no gradients, like the reference's eva
 lift is the reference's lift_lseg_features (models/affinity_module.py:404-452) with the point -> pixel mapping of
 models/utils/fusion_util.py:45-147 and the loader's view-drop rule (dataset/data_loader_ablation.py:254-288), for all entries and all
 views in one call of ops.lift_batched, then ops.gather_rows for the fill.
+lift_masks is the reference's lift_xdecoder_features (models/affinity_module.py:455-714: per-view mask-embedding lift, in-view nearest
+fill, consensus top-3 fusion, scene-level fill) with the same mapping and drop rule, for all entries and any number of views per entry:
+ops.lift_masks_batched_lists (ordered visible lists), ops.segment_tables, ops.lift_masks_batched, ops.gather_rows; two read-backs.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -233,6 +241,187 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     if bad_view:
         raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
     return Lifted(feats, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
+
+
+# ------------------------------------------------------------------------------------------ the mask-embedding lift
+MAX_QUERIES = 1024                                          # gp_lift_masks_batched: a view's scores are sorted in LDS
+_TABLE_ROWS = 2 ** 24                                       # rows of one ops.segment_tables launch
+
+
+class MaskViews:
+    """The views of a batch of scenes with the X-Decoder form of the VLM's outputs: pred_masks fp32 [V,Q,h,w] (mask logits), pred_logits
+    floating [V,Q,C+1] (class logits, the last column "no object"), mask_embed floating [V,Q,D]; view_entry, world_to_camera,
+    intrinsics, depth exactly as in Views; image_shape = (H, W), required: the reference's cfg.mask_shape, the size the masks are
+    resized to and the depths and intrinsics refer to (h <= H and w <= W).  Every view has the same number of queries Q.  lift_masks
+    checks the fields."""
+
+    def __init__(self, pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth=None, image_shape=None):
+        self.pred_masks, self.pred_logits, self.mask_embed = pred_masks, pred_logits, mask_embed
+        self.view_entry, self.world_to_camera, self.intrinsics, self.depth, self.image_shape = view_entry, world_to_camera, intrinsics, depth, image_shape
+
+
+class LiftedMasks:
+    """features fp32 [N,D] in the points' row order, seen bool [N], count i32 [N] (the kept views that see the point), view_count i64
+    [V], view_keep bool [V], text_features fp32 [C,D] (the NORMALISED text embeddings, as the reference returns them) and logit_scale."""
+
+    def __init__(self, features, seen, count, view_count, view_keep, text_features, logit_scale):
+        self.features, self.seen, self.count, self.view_count, self.view_keep = features, seen, count, view_count, view_keep
+        self.text_features, self.logit_scale = text_features, logit_scale
+
+
+_TAPS = {}
+
+
+def _tap_tables(h, w, H, W, device):
+    """bicubic.aa_bicubic_taps of both axes on the device, cached per (h, w, H, W, device).  The upload is from pinned memory and does
+    not wait; the pinned source is kept beside the device copy."""
+    key = (h, w, H, W, str(device))
+    if key not in _TAPS:
+        from .bicubic import aa_bicubic_taps
+        tx0, twx = aa_bicubic_taps(w, W)
+        ty0, twy = aa_bicubic_taps(h, H)
+        host = tuple(torch.from_numpy(a).pin_memory() for a in (tx0, twx, ty0, twy))
+        _TAPS[key] = (tuple(t.to(device, non_blocking=True) for t in host), host)
+    return _TAPS[key][0]
+
+
+def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
+    """The reference's default lift, lift_xdecoder_features (models/affinity_module.py:455-714), for several scenes at once, entries
+    never mixing and with no cap on the views of an entry.  points as for lift; views: a MaskViews; text_embed floating [C,D].  Per
+    entry b -- its points the rows with batch b in ascending row order, its views those with view_entry == b in ascending view index:
+      1. visibility, view_count and view_keep exactly as lift's steps 1-2;
+      2. score[v,q] = softmax(pred_logits[v,q])[:-1].max() (torch on the device);
+      3. the segment of a visible pixel of a kept view: the bicubic-antialias resize of pred_masks[v] to image_shape evaluated at that
+         pixel; over the queries with score > 0 the arg-max of score_q * sigmoid(logit_q), the smallest q among equal products; that q
+         if sigmoid(logit_q) >= 0.5, else none;
+      4. the in-view fill (:604-625): inside a kept view a point without a segment takes the segment of the point of that view that has
+         one and minimises (d^2, row), d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over the fp32-rounded xyz; a view where no point has a
+         segment keeps none;
+      5. f_seg = normalize(mask_embed), logit_seg = logit_scale * f_seg . normalize(text_embed);
+      6. fusion (:647-686) over a point's slots = its kept views that see it, in ascending view index: the consensus class is the
+         arg-max of the mean logits (the first maximum), the top-min(M,3) slots by that class's logit (the earlier slot among equals)
+         are combined with softmax weights; a slot without a segment carries a zero feature and zero logits;
+      7. count = the slots, seen = count > 0, unseen rows are zero; with fill an unseen point of an entry that has seen points takes
+         the row of the seen point of its entry minimising (d^2, row) -- lift's step 5;
+      8. text_features = normalize(text_embed): the reference returns those (:628 rebinds the name).
+    The rows are the same bits as HotPath.lift_masks' kernels on each scene by itself.  -> LiftedMasks.  No gradients: inputs that
+    require grad are refused and the points are detached.  Deterministic: no float atomics, no order that depends on arrival.
+    Inside: ops.lift_masks_batched_lists (entry tables, ordered visible lists), ops.segment_tables, ops.lift_masks_batched (segments,
+    in-view fill, point -> view lists over a bit set of ceil(most views of an entry / 64) words, fusion, per-entry 1-NN), ops.gather_rows.
+    D is padded to a multiple of 4 inside (the fusion kernel's rows).  ValueError before any kernel: shape / dtype / device mismatches,
+    CPU tensors, inputs that require grad, Q > 1024, more than 65535 views, masks larger than image_shape, N >= 2^31.  TWO read-backs:
+    the sizes after the counting pass (entries in all, the most views of an entry) and the status after the last launch (rows whose
+    batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates: ValueError)."""
+    who = "lift_masks"
+    if not isinstance(views, MaskViews):
+        raise ValueError(f"{who}: views must be a MaskViews, got {type(views).__name__}")
+    P, Pm, Pl, Em = points, views.pred_masks, views.pred_logits, views.mask_embed
+    E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    if not torch.is_tensor(Pm) or Pm.dim() != 4 or min(Pm.shape) < 1 or Pm.dtype != torch.float32:
+        raise ValueError(f"{who}: views.pred_masks must be fp32 [V, Q, h, w] with V, Q, h, w >= 1, got "
+                         f"{(list(Pm.shape), Pm.dtype) if torch.is_tensor(Pm) else type(Pm).__name__}")
+    V, Q, h, w = Pm.shape
+    if V > 65535:
+        raise ValueError(f"{who}: {V} views, at most 65535")
+    if Q > MAX_QUERIES:
+        raise ValueError(f"{who}: {Q} queries per view, at most {MAX_QUERIES} (a view's scores are sorted in LDS)")
+    if not torch.is_tensor(text_embed) or text_embed.dim() != 2 or min(text_embed.shape) < 1 or not text_embed.dtype.is_floating_point:
+        raise ValueError(f"{who}: text_embed must be floating point [C, D] with C, D >= 1, got "
+                         f"{(list(text_embed.shape), text_embed.dtype) if torch.is_tensor(text_embed) else type(text_embed).__name__}")
+    C, D = text_embed.shape
+    if not torch.is_tensor(Pl) or Pl.shape != (V, Q, C + 1) or not Pl.dtype.is_floating_point:
+        raise ValueError(f"{who}: views.pred_logits must be floating point [{V}, {Q}, {C + 1}] (C + 1 columns, the last \"no object\"), got "
+                         f"{(list(Pl.shape), Pl.dtype) if torch.is_tensor(Pl) else type(Pl).__name__}")
+    if not torch.is_tensor(Em) or Em.shape != (V, Q, D) or not Em.dtype.is_floating_point:
+        raise ValueError(f"{who}: views.mask_embed must be floating point [{V}, {Q}, {D}], got "
+                         f"{(list(Em.shape), Em.dtype) if torch.is_tensor(Em) else type(Em).__name__}")
+    if not _is_int_tensor(E) or E.shape != (V,):
+        raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
+        raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
+    if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
+        raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
+                         f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+    shape = () if views.image_shape is None else tuple(views.image_shape)
+    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+        raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers (the size the masks are resized to), got "
+                         f"{views.image_shape!r}")
+    H, W = shape
+    if h > H or w > W:
+        raise ValueError(f"{who}: masks of {h} x {w} are larger than image_shape {H} x {W}: the bicubic-antialias resize is evaluated for "
+                         "up-sampling only")
+    if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
+        raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
+                         f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
+        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
+    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
+        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    if isinstance(logit_scale, bool) or not isinstance(logit_scale, (int, float)) or logit_scale != logit_scale:
+        raise ValueError(f"{who}: logit_scale={logit_scale!r} must be a number")
+    for name, t in (("views.pred_masks", Pm), ("views.pred_logits", Pl), ("views.mask_embed", Em), ("text_embed", text_embed)):
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
+                             "no_grad); detach them")
+    tensors = [P, Pm, Pl, Em, text_embed, E, M, K] + ([Dp] if Dp is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points, text_embed and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    dev = P.device
+    with torch.cuda.device(dev), torch.no_grad():
+        pts = P.detach().to(torch.float64).contiguous()
+        ve = E.detach().to(torch.int64).contiguous()
+        lists = ops.lift_masks_batched_lists(pts, ve, M.detach().contiguous(), K.detach().contiguous(),
+                                             None if Dp is None else Dp.detach().contiguous(), (H, W), cut_bound, float(vis_thres), min_visible,
+                                             2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1))    # (the first read-back)
+        text_norm = torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
+        status = lists.status
+        if lists.total == 0:
+            feats = torch.zeros((n, D), dtype=torch.float32, device=dev)
+            seen, count = torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        else:
+            scores = torch.softmax(Pl.detach().float(), dim=-1)[..., :-1].max(-1).values.contiguous()
+            # the fusion kernel moves rows as float4: tables and rows padded to a multiple of 4 columns (zeros add nothing to a norm or a
+            # dot product, and a lane's terms stay the lane's)
+            d4 = _pad_to(D, 4)
+            emb = torch.zeros((V * Q, d4), dtype=torch.float32, device=dev)
+            emb[:, :D] = Em.detach().float().reshape(V * Q, D)
+            text4 = torch.zeros((C, d4), dtype=torch.float32, device=dev)
+            text4[:, :D] = text_norm
+            f_seg = torch.empty((V, Q, d4), dtype=torch.float32, device=dev)
+            l_seg = torch.empty((V, Q, C), dtype=torch.float32, device=dev)
+            for r0 in range(0, V * Q, _TABLE_ROWS):
+                r1 = min(r0 + _TABLE_ROWS, V * Q)
+                ops.segment_tables(emb[r0:r1], text4, float(logit_scale), f_seg.view(V * Q, d4)[r0:r1], l_seg.view(V * Q, C)[r0:r1])
+            r = ops.lift_masks_batched(pts, ve, Pm.detach().contiguous(), scores, _tap_tables(h, w, H, W, dev), (H, W),
+                                       (lists.pt, lists.x, lists.y, lists.view), lists.view_off, lists.view_keep, lists.total,
+                                       max(1, -(-lists.max_views // 64)), f_seg, l_seg, fill=bool(fill))
+            feats = r.out
+            if fill:
+                feats = ops.gather_rows(r.out, d4, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
+            feats = feats[:, :D].contiguous() if d4 != D else feats
+            seen, count, status = r.seen.bool(), r.count, r.status
+        st = ops.readback(status)                                                # (the second read-back)
+    bad_batch, bad_view, nonfinite = st[:3]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    if lists.total and (st[6] or st[7]):
+        raise RuntimeError(f"{who}: the visible lists do not hold together ({st[6]} entries, {st[7]} views): the inputs changed during the call")
+    return LiftedMasks(feats, seen, count, lists.view_count, lists.view_keep.bool(), text_norm, logit_scale)
 
 
 def _voxel_size(quantization_size, like):

@@ -837,6 +837,64 @@ int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t 
                     int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn, int64_t *status,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The mask-embedding lift with top-3 fusion over BATCHED point clouds: models/affinity_module.py:455-714  */
+/* (lift_xdecoder_features) for every batch entry and every view in one sequence of launches, entries     */
+/* never mixing and with no cap on the views of an entry.  It replaces, per scene,                        */
+/* gp_views_visible_lists, gp_lift_masks_views (at most 128 views), gp_fuse_views_top3 and                */
+/* gp_nn1_masked_f64, and gives the same bits.  Points, entries, views and poses are worded as in         */
+/* gp_lift_batched.                                                                                       */
+/*                                                                                                        */
+/* gp_lift_masks_batched_lists: the visible lists of all views (fusion_util.py:45-147,                    */
+/* data_loader_ablation.py:254-288, affinity_module.py:495-517), view-major: a view tests the rows of its */
+/* own entry only and its entries ascend by row (count per block -> scan -> write: no atomic cursor).     */
+/*   view_count i64 [nviews], view_keep u8 [nviews]: as gp_lift_batched;                                   */
+/*   view_off i64 [nviews+1]: the first entry of every view, view_off[nviews] = the entries in all;        */
+/*   ent_pt / ent_x / ent_y i64 [cap], ent_view i32 [cap]: global point row, pixel row, pixel column and   */
+/*     view of every entry (dropped views included: gp_lift_masks_batched skips them by view_keep).        */
+/*     cap = 0 with null entry arrays: count only (the caller reads status[6] and calls again);            */
+/*     entries beyond cap are not written and counted in status[5];                                        */
+/*   status i64 [8]: [0]..[3] as gp_lift_batched, [5] entries that did not fit, [6] entries in all,        */
+/*     [7] the most views one entry has.                                                                   */
+/* 1 <= n < 2^31, 1 <= nviews <= 65535, cut_bound >= 0; no output may overlap an input or another output. */
+size_t gp_lift_masks_batched_lists_workspace_bytes(int64_t n, int32_t nviews);
+int gp_lift_masks_batched_lists(const double *points, int64_t n, const int64_t *view_entry, const double *w2c,
+                                const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                                int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible, int64_t cap,
+                                int64_t *ent_pt, int64_t *ent_x, int64_t *ent_y, int32_t *ent_view, int64_t *view_off,
+                                int64_t *view_count, uint8_t *view_keep, int64_t *status, void *workspace,
+                                size_t workspace_bytes, void *stream);
+/* gp_lift_masks_batched: from such entries (its own or a caller's: total entries, view_off i64 [nviews+1],*/
+/* keep u8 [nviews]) to the fused rows.  Per entry of a kept view the segment of gp_lift_masks_views       */
+/* (:526-592: the bicubic-antialias resize of pred_masks f32 [nviews,q,h,w] evaluated at the pixel, arg-max */
+/* over scores f32 [nviews,q] > 0 of score x sigmoid, first q among equals, none below sigmoid 0.5), the   */
+/* in-view fill (:604-625, (d^2, row) minimum inside the view), then per point its kept views in ascending */
+/* view index -- a bit set over the view's position inside its entry, `words` 64-bit words per point,      */
+/* words >= ceil(most views of one entry / 64) -- fused by gp_fuse_views_top3's kernel (:647-686) over      */
+/* f_seg f32 [nviews,q,d] and logit_seg f32 [nviews,q,c] (gp_segment_tables; d and ld_out multiples of 4), */
+/* and the scene-level fill of gp_lift_batched inside every entry (:687-696).                              */
+/*   out f32 [n, ld_out >= d]: the fused row, zeros for a point no kept view sees (before the fill);       */
+/*   seen u8 [n], count i32 [n] (the kept views that see the point), nn i64 [n] (fill != 0; as             */
+/*   gp_lift_batched: the caller gathers), seg i32 [total]: the segment of every entry after the in-view   */
+/*   fill, -1 = none;                                                                                      */
+/*   status i64 [8]: [0]..[5] as gp_lift_batched, [6] entries that are not what the lists promise (a view  */
+/*     that is not the one view_off puts the entry in, a point row outside 0..n-1 or of another batch      */
+/*     entry than the view's or not ascending inside the view, a pixel outside the image, a view_off that  */
+/*     does not ascend from 0 to total, a tap origin outside the mask), [7] views whose position inside    */
+/*     their entry is beyond words x 64.  Such entries and views take no part; nothing is read or written  */
+/*     outside the extents whatever the arrays hold.                                                       */
+/* fill_cap: as gp_lift_masks_views.  1 <= q <= 1024, 1 <= total < 2^31 - 1, 1 <= words <= 1024.           */
+size_t gp_lift_masks_batched_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
+                                             int32_t out_w, int64_t total, int32_t words, int64_t fill_cap);
+int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews,
+                          const float *pred_masks, int32_t q, int32_t h, int32_t w, const float *scores,
+                          const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0, const float *tap_wy,
+                          int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y,
+                          const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep, int64_t total, int32_t words,
+                          int64_t fill_cap, const float *f_seg, const float *logit_seg, int32_t d, int32_t c, int32_t fill,
+                          float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg, int64_t *status,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
