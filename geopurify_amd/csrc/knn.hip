@@ -22,7 +22,13 @@ struct KnnCfg {
     static constexpr int HB = (B + 63) / 64 * 64;
 };
 
-template <int R, int WAVES>
+// KEEP candidates per lane stay in registers between pass 1 and pass 2 (first ring only): blocks of up to 64 KEEP candidates are read
+// ONCE -- pass 2 emits from what pass 1 kept, no second cell search and no second coordinate load.  A kept candidate is one word:
+// min(d^2, 127) above its row (pass 2 asks d^2 < T and d^2 == T with T < B = 81 only), so rows must stay below 2^25.
+constexpr int KNN_KEEP = 32;
+constexpr int KNN_KEEP_ROW_BITS = 25;
+
+template <int R, int WAVES, bool KEEP = false>
 __global__ void __launch_bounds__(WAVES * 64)
 knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int32_t *__restrict__ ids, int64_t nv,
                 int k, int32_t *__restrict__ nbr, const int32_t *__restrict__ qlist,
@@ -82,7 +88,30 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
     };
 
     // ---- pass 1: histogram of d^2 over the candidates (two per lane and round: both coordinate loads in flight together)
-    for (int j0 = 0; j0 < total_c; j0 += 128) {
+    static_assert(!KEEP || KnnCfg<R>::B <= 127, "a kept candidate holds d^2 in 7 bits");
+    const bool kept = KEEP && total_c <= 64 * KNN_KEEP;            // (wave-uniform; larger blocks take the two-pass code below)
+    unsigned keep[KEEP ? KNN_KEEP : 1];
+    if constexpr (KEEP) {
+        if (kept) {
+#pragma unroll
+            for (int i = 0; i < KNN_KEEP; i += 2) {                  // fully unrolled: keep[] is indexed statically
+                if (i * 64 < total_c) {
+                    const int ja = i * 64 + lane, jb = ja + 64;
+                    const bool va = ja < total_c, vb = jb < total_c;
+                    const int64_t ra = va ? row_of(ja) : 0, rb = vb ? row_of(jb) : 0;
+                    const int ax = coords[ra * 3], ay = coords[ra * 3 + 1], az = coords[ra * 3 + 2];
+                    const int bx = coords[rb * 3], by = coords[rb * 3 + 1], bz = coords[rb * 3 + 2];
+                    const int da = (ax - qx) * (ax - qx) + (ay - qy) * (ay - qy) + (az - qz) * (az - qz);
+                    const int db = (bx - qx) * (bx - qx) + (by - qy) * (by - qy) + (bz - qz) * (bz - qz);
+                    if (va && da < B) atomicAdd(&hist[da], 1);
+                    if (vb && db < B) atomicAdd(&hist[db], 1);
+                    keep[i] = ((unsigned)(va ? min(da, 127) : 127) << KNN_KEEP_ROW_BITS) | (unsigned)ra;
+                    keep[i + 1] = ((unsigned)(vb ? min(db, 127) : 127) << KNN_KEEP_ROW_BITS) | (unsigned)rb;
+                }
+            }
+        }
+    }
+    for (int j0 = kept ? total_c : 0; j0 < total_c; j0 += 128) {
         const int ja = j0 + lane, jb = j0 + 64 + lane;
         const bool va = ja < total_c, vb = jb < total_c;
         const int64_t ra = va ? row_of(ja) : 0, rb = vb ? row_of(jb) : 0;
@@ -136,23 +165,32 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
     }
 
     // ---- pass 2: emit winners below T, collect ties at T
-    for (int j0 = 0; j0 < total_c; j0 += 64) {
+    auto emit = [&](int64_t r, int d2) {
+        if (d2 < T) {
+            int id = ids ? ids[r] : (int)r;
+            int p = atomicAdd(&s_cnt[wv][0], 1);
+            s_selkey[wv][p] = ((unsigned long long)(unsigned)d2 << 32) | (unsigned)id;
+            s_selrow[wv][p] = (int)r;
+        } else if (d2 == T) {
+            int id = ids ? ids[r] : (int)r;
+            int p = atomicAdd(&s_cnt[wv][1], 1);
+            s_tieid[wv][p] = id;
+            s_tierow[wv][p] = (int)r;
+        }
+    };
+    if constexpr (KEEP) {
+        if (kept) {
+#pragma unroll
+            for (int i = 0; i < KNN_KEEP; ++i)
+                if (i * 64 < total_c) emit((int64_t)(keep[i] & ((1u << KNN_KEEP_ROW_BITS) - 1u)), (int)(keep[i] >> KNN_KEEP_ROW_BITS));
+        }
+    }
+    for (int j0 = kept ? total_c : 0; j0 < total_c; j0 += 64) {
         const int j = j0 + lane;
         if (j < total_c) {
             const int64_t r = row_of(j);
             int ex = coords[r * 3] - qx, ey = coords[r * 3 + 1] - qy, ez = coords[r * 3 + 2] - qz;
-            int d2 = ex * ex + ey * ey + ez * ez;
-            if (d2 < T) {
-                int id = ids ? ids[r] : (int)r;
-                int p = atomicAdd(&s_cnt[wv][0], 1);
-                s_selkey[wv][p] = ((unsigned long long)(unsigned)d2 << 32) | (unsigned)id;
-                s_selrow[wv][p] = (int)r;
-            } else if (d2 == T) {
-                int id = ids ? ids[r] : (int)r;
-                int p = atomicAdd(&s_cnt[wv][1], 1);
-                s_tieid[wv][p] = id;
-                s_tierow[wv][p] = (int)r;
-            }
+            emit(r, ex * ex + ey * ey + ez * ez);
         }
     }
     gp_wave_sync();
@@ -250,8 +288,8 @@ extern "C" size_t gp_knn_workspace_bytes(int64_t nv) {
     return cv.off;
 }
 
-extern "C" int gp_knn_lattice(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv, int32_t k,
-                              int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream_) {
+static int knn_lattice(bool read_once, const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv, int32_t k,
+                       int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream_) {
     GP_CHECK_ARG(grid && coords && nbr && workspace, "gp_knn_lattice: null argument");
     GP_CHECK_ARG(k >= 1 && k <= GP_KNN_MAX_K, "gp_knn_lattice: k=%d not in 1..%d", k, GP_KNN_MAX_K);
     GP_CHECK_ARG(nv > k, "gp_knn_lattice: need more than k voxels (nv=%lld, k=%d)", (long long)nv, k);
@@ -264,12 +302,26 @@ extern "C" int gp_knn_lattice(const void *grid, const int32_t *coords, const int
     zero2_kernel<<<1, 64, 0, s>>>(counts, counts + 1);
     constexpr int W1 = 4, W3 = 2;
     // ring 1: all queries
-    knn_ring_kernel<1, W1><<<(int)((nv + W1 - 1) / W1), W1 * 64, 0, s>>>(grid, coords, ids, nv, k, nbr, nullptr, nullptr,
-                                                                      list_a, counts);
+    if (read_once && nv <= ((int64_t)1 << KNN_KEEP_ROW_BITS))
+        knn_ring_kernel<1, W1, true><<<(int)((nv + W1 - 1) / W1), W1 * 64, 0, s>>>(grid, coords, ids, nv, k, nbr, nullptr, nullptr,
+                                                                                list_a, counts);
+    else
+        knn_ring_kernel<1, W1><<<(int)((nv + W1 - 1) / W1), W1 * 64, 0, s>>>(grid, coords, ids, nv, k, nbr, nullptr, nullptr,
+                                                                          list_a, counts);
     // ring 3: failures of ring 1 (grid sized for the worst case; surplus waves exit immediately)
     knn_ring_kernel<3, W3><<<(int)((nv + W3 - 1) / W3), W3 * 64, 0, s>>>(grid, coords, ids, nv, k, nbr, list_a, counts,
                                                                       list_b, counts + 1);
     knn_exhaustive_kernel<<<1024, 256, 0, s>>>(coords, ids, nv, k, nbr, list_b, counts + 1);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_knn_lattice(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv, int32_t k,
+                              int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream_) {
+    return knn_lattice(true, grid, coords, ids, nv, k, nbr, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int gp_knn_lattice_two_pass(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv, int32_t k,
+                                       int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream_) {
+    return knn_lattice(false, grid, coords, ids, nv, k, nbr, workspace, workspace_bytes, stream_);
 }

@@ -222,15 +222,33 @@ __global__ void pv_fill_kernel(const int64_t *__restrict__ pt, const int32_t *__
     pv_seg[s] = seg[i];
 }
 
-// row 7: one wave per point
+// seen[p] = the point has a list, unseen[p] = it has none: the reference / query masks of the scene-level fill, from the list
+// offsets alone (so the fill's search can run before the fusion)
+__global__ void seen_masks_kernel(const int64_t *__restrict__ start, int64_t n, uint8_t *__restrict__ seen, uint8_t *__restrict__ unseen) {
+    int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const bool has = start[p + 1] > start[p];
+    seen[p] = has ? 1 : 0;
+    unseen[p] = has ? 0 : 1;
+}
+
+// row 7: one wave per point.  FILL: row p is fused from the list of point nn[p] where nn[p] >= 0 (the scene-level fill of a point
+// without a list: its nearest seen point), from its own list otherwise -- the same loops on another list, so a filled row has the
+// bits of the row it copies
+template <bool FILL>
 __global__ void fuse_top3_kernel(const int64_t *__restrict__ start, const int32_t *__restrict__ pv_view,
                                  const int32_t *__restrict__ pv_seg, int64_t n, const float *__restrict__ fseg,
                                  const float *__restrict__ lseg, int Q, int d, int C, float *__restrict__ out,
-                                 int64_t ld_out, uint8_t *__restrict__ seen) {
+                                 int64_t ld_out, uint8_t *__restrict__ seen, const int64_t *__restrict__ nn) {
     int64_t p = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     if (p >= n) return;
     int lane = gp_lane();
-    int64_t b = start[p], e = start[p + 1];
+    int64_t src = p;
+    if constexpr (FILL) {
+        const int64_t t = nn[p];
+        if (t >= 0 && t < n) src = t;
+    }
+    int64_t b = start[src], e = start[src + 1];
     int M = (int)(e - b);
     if (lane == 0 && seen) seen[p] = M > 0 ? 1 : 0;
     if (M == 0) {
@@ -529,8 +547,26 @@ extern "C" int gp_fuse_views_top3(const int64_t *pv_start, const int32_t *pv_vie
                                   float *out, int64_t ld_out, uint8_t *seen, void *stream_) {
     GP_CHECK_ARG(pv_start && pv_view && pv_seg && f_seg && logit_seg && out && n > 0, "gp_fuse_views_top3: null/empty argument");
     GP_CHECK_ARG(d % 4 == 0 && ld_out % 4 == 0, "gp_fuse_views_top3: d and ld_out must be multiples of 4");
-    fuse_top3_kernel<<<(int)((n * 64 + 255) / 256), 256, 0, gp_stream(stream_)>>>(pv_start, pv_view, pv_seg, n, f_seg,
-                                                                                logit_seg, q, d, c, out, ld_out, seen);
+    fuse_top3_kernel<false><<<(int)((n * 64 + 255) / 256), 256, 0, gp_stream(stream_)>>>(pv_start, pv_view, pv_seg, n, f_seg,
+                                                                                       logit_seg, q, d, c, out, ld_out, seen, nullptr);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+extern "C" int gp_seen_masks(const int64_t *pv_start, int64_t n, uint8_t *seen, uint8_t *unseen, void *stream_) {
+    GP_CHECK_ARG(pv_start && seen && unseen && n > 0, "gp_seen_masks: null/empty argument");
+    seen_masks_kernel<<<(int)((n + 255) / 256), 256, 0, gp_stream(stream_)>>>(pv_start, n, seen, unseen);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+extern "C" int gp_fuse_views_top3_fill(const int64_t *pv_start, const int32_t *pv_view, const int32_t *pv_seg, int64_t n,
+                                       const float *f_seg, const float *logit_seg, int32_t q, int32_t d, int32_t c,
+                                       const int64_t *nn, float *out, int64_t ld_out, void *stream_) {
+    GP_CHECK_ARG(pv_start && pv_view && pv_seg && f_seg && logit_seg && nn && out && n > 0, "gp_fuse_views_top3_fill: null/empty argument");
+    GP_CHECK_ARG(d % 4 == 0 && ld_out % 4 == 0, "gp_fuse_views_top3_fill: d and ld_out must be multiples of 4");
+    fuse_top3_kernel<true><<<(int)((n * 64 + 255) / 256), 256, 0, gp_stream(stream_)>>>(pv_start, pv_view, pv_seg, n, f_seg,
+                                                                                      logit_seg, q, d, c, out, ld_out, nullptr, nn);
     GP_CHECK_LAUNCH();
     return GP_OK;
 }

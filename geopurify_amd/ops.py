@@ -277,6 +277,25 @@ def scatter_mean_csr(src, d, order, seg_start, nv, out, col0=0, row_map=None):
     return out
 
 
+def voxel_rows_operands(f, d, geo, dg, order, seg_start, nv, cin_pad, row_map=None, want_scale=True):
+    """Row 8 and its operands in one pass (gp_voxel_rows_operands): X f32 [nv, cin_pad] = voxel means of f[:, :d] | geo[:, :dg] | zeros,
+    written through row_map; (rows, None, row_inv) = split_f16(X, cin_pad, per_row=True, interleaved=True); sc = pow2_scale(X, d)
+    (None unless want_scale).  Returns (X, (rows, None, row_inv), sc), the bits of those calls."""
+    lib = _lib.load()
+    _chk(f, torch.float32, "f")
+    _chk(geo, torch.float32, "geo")
+    dev = f.device
+    X = torch.empty((nv, cin_pad), dtype=torch.float32, device=dev)
+    rows = torch.empty((nv, 2 * cin_pad), dtype=torch.float16, device=dev)
+    rinv = torch.empty(nv, dtype=torch.float32, device=dev)
+    sc = torch.empty(2, dtype=torch.float32, device=dev) if want_scale else None
+    ws = _ws(256, dev) if want_scale else None
+    check(lib.gp_voxel_rows_operands(_ptr(f), f.stride(0), int(d), _ptr(geo), geo.stride(0), int(dg), _ptr(order), _ptr(seg_start), int(nv),
+                                     _ptr(row_map), _ptr(X), X.stride(0), int(cin_pad), _ptr(rows), rows.stride(0), _ptr(rinv), _ptr(sc),
+                                     _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "gp_voxel_rows_operands")
+    return X, (rows, None, rinv), sc
+
+
 def gather_rows(src, d, index, out=None, row_map=None):
     lib = _lib.load()
     n = index.shape[0]
@@ -620,14 +639,15 @@ def embed_head_f16x3(x_split, w_hi, w_lo, out_scale, x_row_inv=None, normalize=T
     return (out, (eh, el)) if planes else out
 
 
-def knn_lattice(grid, coords_sorted, ids, k):
+def knn_lattice(grid, coords_sorted, ids, k, two_pass=False):
+    """two_pass: gp_knn_lattice_two_pass, the form that reads every candidate twice (tests, timing); the same lists"""
     lib = _lib.load()
     nv = coords_sorted.shape[0]
     dev = coords_sorted.device
     ws = _ws(lib.gp_knn_workspace_bytes(nv), dev)
     nbr = torch.empty((nv, k), dtype=torch.int32, device=dev)
-    check(lib.gp_knn_lattice(_ptr(grid.buf), _ptr(coords_sorted), _ptr(ids), nv, int(k), _ptr(nbr), _ptr(ws),
-                             ws.numel(), _stream()), "gp_knn_lattice")
+    fn, name = (lib.gp_knn_lattice_two_pass, "gp_knn_lattice_two_pass") if two_pass else (lib.gp_knn_lattice, "gp_knn_lattice")
+    check(fn(_ptr(grid.buf), _ptr(coords_sorted), _ptr(ids), nv, int(k), _ptr(nbr), _ptr(ws), ws.numel(), _stream()), name)
     return nbr
 
 
@@ -1145,6 +1165,27 @@ def fuse_views_top3(pv_start, pv_view, pv_seg, n, f_seg, logit_seg, out):
     check(lib.gp_fuse_views_top3(_ptr(pv_start), _ptr(pv_view), _ptr(pv_seg), int(n), _ptr(f_seg), _ptr(logit_seg),
                                  Q, d, C, _ptr(out), out.stride(0), _ptr(seen), _stream()), "gp_fuse_views_top3")
     return seen
+
+
+def seen_masks(pv_start, n):
+    """(seen, unseen) u8 [n] from the list offsets: seen[p] = the point has a list (gp_seen_masks)"""
+    lib = _lib.load()
+    _chk(pv_start, torch.int64, "pv_start")
+    seen = torch.empty(n, dtype=torch.uint8, device=pv_start.device)
+    unseen = torch.empty(n, dtype=torch.uint8, device=pv_start.device)
+    check(lib.gp_seen_masks(_ptr(pv_start), int(n), _ptr(seen), _ptr(unseen), _stream()), "gp_seen_masks")
+    return seen, unseen
+
+
+def fuse_views_top3_fill(pv_start, pv_view, pv_seg, n, f_seg, logit_seg, nn, out):
+    """fuse_views_top3 with the scene-level fill inside: row p from the list of nn[p] where nn[p] >= 0 (gp_fuse_views_top3_fill)"""
+    lib = _lib.load()
+    V, Q, d = f_seg.shape
+    C = logit_seg.shape[2]
+    _chk(nn, torch.int64, "nn")
+    check(lib.gp_fuse_views_top3_fill(_ptr(pv_start), _ptr(pv_view), _ptr(pv_seg), int(n), _ptr(f_seg), _ptr(logit_seg),
+                                      Q, d, C, _ptr(nn), _ptr(out), out.stride(0), _stream()), "gp_fuse_views_top3_fill")
+    return out
 
 
 def nn1(ref_xyz, query_xyz):

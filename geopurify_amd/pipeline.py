@@ -129,6 +129,13 @@ class StudentWeights:
             return None
         return ops.split_f16(x, self.cin_pad, per_row=True, interleaved=self.residual_from_planes and self.interleaved_rows)
 
+    def one_pass_input(self, F, geo):
+        """True when split_input's operand can come out of the voxel-mean pass itself (ops.voxel_rows_operands): the fast path's
+        interleaved rows, a width the one-wave-per-voxel kernel holds in registers, contiguous 16-byte-aligned feature rows"""
+        return (self.fast and self.residual_from_planes and self.interleaved_rows and self.cin_pad <= 1024 and F.shape[1] % 4 == 0
+                and F.dtype == torch.float32 and F.is_contiguous() and F.data_ptr() % 16 == 0
+                and geo.dtype == torch.float32 and geo.is_contiguous() and geo.shape[1] == self.cin - F.shape[1])
+
     def forward(self, x, nbr_map, pairs=None, x_split=None, mark=None, planes=False, plane_rows=None, raw=False):
         """x fp32 [Nv, >=cin_pad] (internal order).  Returns L2-normalised embeddings [Nv, embed] (raw=True: the output layer's rows
         before F.normalize -- what AffinityPredictor.forward returns on a SparseTensor).
@@ -542,11 +549,11 @@ class HotPath:
         dev = self.device
         N = batch.scene_coords.shape[0]
         F = torch.empty((N, D), dtype=torch.float32, device=dev)
-        seen = ops.fuse_views_top3(start, pvv, pvs, N, f_seg, l_seg, F)
-        # scene-level fill of never-seen points (:687-696)
-        nn = ops.nn1_masked(batch.scene_coords, seen, 1 - seen)
-        src = torch.where(nn >= 0, nn, torch.arange(N, device=dev))
-        F = ops.gather_rows(F, D, src)
+        # scene-level fill of never-seen points (:687-696), searched first -- who is seen shows in the list offsets -- and applied by
+        # the fusion itself: a never-seen point's row is fused from its nearest seen point's list, so F is written once
+        seen, unseen = ops.seen_masks(start, N)
+        nn = ops.nn1_masked(batch.scene_coords, seen, unseen)
+        ops.fuse_views_top3_fill(start, pvv, pvs, N, f_seg, l_seg, nn, F)
         # the reference returns the NORMALISED text embeddings (affinity_module.py:628 rebinds the name returned at :711)
         return F, text, logit_scale
 
@@ -602,10 +609,17 @@ class HotPath:
             segc = torch.zeros(Nv + 1, dtype=torch.int64, device=dev)
             segc[1:] = torch.bincount(batch.scene_inds_reconstruct, minlength=Nv).cumsum(0)
             batch.order, batch.seg_start = order, segc
-        X = torch.zeros((Nv, st.cin_pad), dtype=torch.float32, device=dev)
-        ops.scatter_mean_csr(F, D, batch.order, batch.seg_start, Nv, X, col0=0, row_map=rank)
-        ops.scatter_mean_csr(batch.scene_gauss_features, GEO_DIM, batch.order, batch.seg_start, Nv, X, col0=D,
-                             row_map=rank)
+        family = self._pool_family(D)
+        xs = sc = None
+        if st.one_pass_input(F, batch.scene_gauss_features):
+            # the means, the pad columns, the first layer's operand rows and the pooling planes' scale from one pass over the points
+            X, xs, sc = ops.voxel_rows_operands(F, D, batch.scene_gauss_features, GEO_DIM, batch.order, batch.seg_start, Nv, st.cin_pad,
+                                                row_map=rank, want_scale=family in ("cs", "chain"))
+        else:
+            X = torch.zeros((Nv, st.cin_pad), dtype=torch.float32, device=dev)
+            ops.scatter_mean_csr(F, D, batch.order, batch.seg_start, Nv, X, col0=0, row_map=rank)
+            ops.scatter_mean_csr(batch.scene_gauss_features, GEO_DIM, batch.order, batch.seg_start, Nv, X, col0=D,
+                                 row_map=rank)
         mark("scatter_mean")
         if batch.extent is not None:
             grid = ops.grid_build(cs, [0, 0, 0], batch.extent)
@@ -617,10 +631,10 @@ class HotPath:
         nbr = ops.knn_lattice(grid, cs, perm, self.K)
         mark("kNN")
         state = {"X": X, "rank": rank, "nbr_map": nbr_map, "pairs": pairs, "nbr": nbr, "Nv": Nv, "D": D, "pool": None,
-                 "xs": st.split_input(X)}                   # the first layer's pre-split operand (per-row scales)
-        family = self._pool_family(D)
+                 "xs": xs if xs is not None else st.split_input(X)}      # the first layer's pre-split operand (per-row scales)
         if family in ("cs", "chain"):
-            sc = ops.pow2_scale(X, D)
+            if sc is None:
+                sc = ops.pow2_scale(X, D)
             # "valid": the structure for the matrix-core affinity kernel (gp_affinity_cs_fragments: needs 128-wide embeddings and
             # K <= 96); True: the dst table of rounds 3-4 (affinity_block_kernel scatters its weights); False: the two-pass build
             how = self.pool_structure_ahead

@@ -206,6 +206,17 @@ int gp_pow2_scale(const float *x, int64_t ld_x, int32_t d, int64_t n, float *sca
 /* dst_row (nullable, i32 [n]): row r of x is written to row dst_row[r] of hi / lo / row_inv_scale (a permutation: gp_rcb_order).   */
 int gp_split_f16_scaled(const float *x, int64_t ld_x, int32_t d, int64_t n, void *hi, void *lo, int64_t ld_h,
                         const float *scale, float *row_inv_scale, const int32_t *dst_row, void *stream);
+/* gp_voxel_rows_operands: row 8 and what the first layer and the pooling take from it, in one pass (one wave per voxel).  Equal,  */
+/* bit for bit, to: x zeroed; gp_scatter_mean_csr(f, d, col0 = 0) and gp_scatter_mean_csr(geo, dg, col0 = d) into x through        */
+/* row_map; gp_split_f16_scaled(x, cin_pad, lo = NULL, row_inv_scale) (the interleaved row-scaled operand); gp_pow2_scale(x, d).   */
+/* x f32 [nv, ld_x >= cin_pad] is written whole (columns d + dg .. cin_pad - 1 are zeros), rows f16 [nv, ld_rows >= 2 cin_pad],   */
+/* row_inv_scale f32 [nv], all at row row_map[v] (nullable: v).  scale2 (nullable, 2 floats) <- [s, 1/s] of max |x[:, 0:d]|, then  */
+/* workspace >= 4 bytes.  d % 4 == 0, cin_pad % 32 == 0, d + dg <= cin_pad <= 1024; f and x 16-byte aligned with ld % 4 == 0.     */
+/* No host sync.                                                                                                                  */
+int gp_voxel_rows_operands(const float *f, int64_t ld_f, int32_t d, const float *geo, int64_t ld_geo, int32_t dg,
+                           const int64_t *order, const int64_t *seg_start, int64_t nv, const int32_t *row_map, float *x,
+                           int64_t ld_x, int32_t cin_pad, void *rows, int64_t ld_rows, float *row_inv_scale, float *scale2,
+                           void *workspace, size_t workspace_bytes, void *stream);
 int gp_sparse_conv_f16x3(const float *x, int64_t ld_x, const void *x_hi, const void *x_lo, int64_t ld_xh,
                          const int32_t *pair_in, const int32_t *pair_pos,
                          const int32_t *seg_off, const int32_t *tile_start, const int32_t *tile_desc,
@@ -272,6 +283,11 @@ int gp_rows_renumber_i32(const int32_t *nbr, int64_t nv, int32_t k, const int32_
 size_t gp_knn_workspace_bytes(int64_t nv);
 int gp_knn_lattice(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv,
                    int32_t k, int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream);
+/* gp_knn_lattice reads a query's candidates once where its first ring holds at most 2048 of them (and nv <= 2^25): their d^2   */
+/* and rows stay in registers between the histogram and the emit.  gp_knn_lattice_two_pass: the form that reads them twice (what   */
+/* larger blocks take inside gp_knn_lattice as well); same arguments, same lists -- kept for tests and timing.                     */
+int gp_knn_lattice_two_pass(const void *grid, const int32_t *coords, const int32_t *ids, int64_t nv,
+                            int32_t k, int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream);
 /* Row 10 over batched coordinates: the same rule inside every batch entry.  keys_sorted u64 [nv] are the sorted keys of             */
 /* gp_coords_order_batched (batch << 48 | morton(xyz - min)), ids i32 [nv] the tie-break id of each sorted row (its perm: ties then     */
 /* resolve by the input's row order inside each entry; NULL: the row number).  nbr i32 [nv,K] holds SORTED-ROW numbers: the K+1         */
@@ -533,6 +549,17 @@ int gp_pv_fill(const int64_t *pt, const int32_t *seg, int64_t n_v, int32_t view,
 int gp_fuse_views_top3(const int64_t *pv_start, const int32_t *pv_view, const int32_t *pv_seg,
                        int64_t n, const float *f_seg, const float *logit_seg, int32_t q, int32_t d,
                        int32_t c, float *out, int64_t ld_out, uint8_t *seen, void *stream);
+/* gp_seen_masks: seen[p] = (pv_start[p + 1] > pv_start[p]), unseen[p] = 1 - seen[p] (u8 [n] each): the reference and query   */
+/* masks of the scene-level fill (gp_nn1_masked_f64) from the list offsets alone, so that the search can run before the fusion. */
+int gp_seen_masks(const int64_t *pv_start, int64_t n, uint8_t *seen, uint8_t *unseen, void *stream);
+/* gp_fuse_views_top3_fill: gp_fuse_views_top3 with the scene-level fill (:687-696) applied while the row is made: row p is     */
+/* fused from the list of point nn[p] where 0 <= nn[p] < n (gp_nn1_masked_f64 over gp_seen_masks: the nearest seen point of a   */
+/* point without a list), from its own list otherwise.  Same kernel, same loops: out equals gp_fuse_views_top3 followed by      */
+/* gp_gather_rows(nn >= 0 ? nn : p) bit for bit, written once.  A point whose own list is empty and whose nn is -1 (no seen     */
+/* point anywhere) keeps a zero row.  nn i64 [n]; the other arguments and their alignment as in gp_fuse_views_top3.             */
+int gp_fuse_views_top3_fill(const int64_t *pv_start, const int32_t *pv_view, const int32_t *pv_seg,
+                            int64_t n, const float *f_seg, const float *logit_seg, int32_t q, int32_t d,
+                            int32_t c, const int64_t *nn, float *out, int64_t ld_out, void *stream);
 /* gp_nn1_fill_f64: exact 1-NN (fp64 distances on fp32 coordinates, lowest index on ties) from       */
 /* query points to reference points; writes nn[i] = index into ref.  (sklearn KDTree k=1,           */
 /* affinity_module.py:619-625,693-696; run/validation.py:425-430.)                                   */

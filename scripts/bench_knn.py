@@ -16,11 +16,19 @@ perm, rank = ops.morton_order(coords)
 cs = coords[perm.long()].contiguous()
 grid = ops.grid_build(cs)
 nbr = ops.knn_lattice(grid, cs, perm, 96)
+two = ops.knn_lattice(grid, cs, perm, 96, two_pass=True)
 torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(10):
-    ops.knn_lattice(grid, cs, perm, 96)
-e1.record()
-torch.cuda.synchronize()
-print(f"Nv={cs.shape[0]}  knn_lattice K=96: {e0.elapsed_time(e1) / 10:.3f} ms  checksum {int(nbr.long().sum())}")
+# the two forms of the first ring alternated in one process (gp_knn_lattice reads a query's candidates once, gp_knn_lattice_two_pass twice)
+ms = {False: [], True: []}
+for _ in range(5):
+    for two_pass in (False, True):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            ops.knn_lattice(grid, cs, perm, 96, two_pass=two_pass)
+        e1.record()
+        torch.cuda.synchronize()
+        ms[two_pass].append(e0.elapsed_time(e1) / 10)
+print(f"Nv={cs.shape[0]}  knn_lattice K=96: {min(ms[False]):.3f} ms  checksum {int(nbr.long().sum())}")
+print(f"  per round of 10 calls, ms: read-once {' '.join(f'{v:.3f}' for v in ms[False])} | two-pass {' '.join(f'{v:.3f}' for v in ms[True])}; "
+      f"lists equal: {bool(torch.equal(nbr, two))}")
