@@ -176,6 +176,15 @@ SIGNATURES = {
     "gp_lift_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_lift_batched": (c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_double, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_stream_state_bytes": (c_size_t, [c_int64]),
+    "gp_lift_stream_begin_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_lift_stream_begin": (c_int32, [_P, c_int64, c_int32, _P, c_size_t, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_stream_add_workspace_bytes": (c_size_t, [c_int32]),
+    "gp_lift_stream_add": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32,
+                                     c_int32, c_int32, c_double, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_stream_finish_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_lift_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int64, _P, _P, c_int32, _P, c_int64, _P, _P, _P, _P,
+                                        c_size_t, _P]),
     "gp_lift_masks_batched_lists_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_lift_masks_batched_lists": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_double, c_int64, c_int64,
                                               c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),

@@ -1,0 +1,449 @@
+// The 2D -> 3D lift over BATCHED point clouds, RESUMABLE (geopurify_amd/sparse.py: LiftStream): the views arrive in chunks, every
+// chunk's maps are read once and may then be freed, and the result after any number of chunks is the bits of gp_lift_batched on the
+// concatenation of the chunks -- the chunk loop of models/affinity_module.py:365-436 (sum_features / counter grown by index_add_ per
+// chunk of max_batch_size views) and its end :435-449 (divide, fill), for all entries at once.
+//     begin    the points' entry tables (rows sorted stably by entry, offsets), once, into the caller's STATE; sums = +0, count = 0,
+//              the status words (bad batch rows, non-finite rows, top batch)
+//     add      per chunk: the chunk's view table, n_v and keep_v of the chunk's views from each view's own count (the drop rule needs
+//              no other view), then for every point sum_p = (((sum_p + f_v1) + f_v2) + ...) over the chunk's kept views that see it,
+//              in ascending view index, cnt_p += their number
+//     finish   out_p = sum_p / (cnt_p == 0 ? 1e-6 : cnt_p), seen_p, the per-entry fill's nn_p; sums, counts and state are only read
+// Why the bits are gp_lift_batched's: a point's fp32 sum there starts from +0 and takes the kept views that see the point in ascending
+// view index, one add each; here the same adds happen in the same order, with a store and a reload of the fp32 partial sum between two
+// chunks, which changes no bit; the integer counts add up; keep_v depends on view v's own count alone; division and fill run once.
+//
+// The accumulating kernel is lb_lift_kernel's walk (lift_batched.hip): one wave per point, lane l projects the point through the l-th
+// view of a group of 64 of its entry's views IN THIS CHUNK, a 64-bit ballot is the visible-and-kept mask, its set bits are walked in
+// ascending order with all lanes striding the channels (pixel-major maps: 256 contiguous bytes per wave load).  The sum row is loaded
+// at the first set bit and stored only if there was one: a point that no kept view of the chunk sees costs its projection and no
+// row traffic.  One wave owns one point: the row's read-modify-write is its own, there are no float atomics.
+//
+// Bounds: a batch or view entry index is range-checked before every table access (0..65535; the tables hold 65538 words).  The state
+// is written by begin alone, but it is the caller's memory between calls, so nothing read from it is trusted: add's count kernel
+// clamps the two offsets to 0..n and skips a sorted row number outside 0..n-1 (and a row of another entry); finish copies the three
+// tables into its workspace with keys clamped to 0..65536, row numbers to 0..n-1 and offsets to 0..n, counts what it had to change in
+// status[6], and runs the fill of gp_lift_entries.h on the copies, whose indices then stay inside n / n+1 / 3n elements whatever the
+// state held.  The chunk's view table lies in add's own workspace (positions inside 0..nviews by construction of the lower bounds).
+// A pixel is read only after project_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0; bilinear taps are clamped to
+// the map; channel indices are guarded by c < d.  All offsets are 64-bit.
+#include "gp_lift_entries.h"
+
+namespace {
+
+constexpr int LS_COLS_PER_LANE = 8;
+constexpr int LS_COL_CHUNK = GP_WAVE * LS_COLS_PER_LANE;         // channels one pass holds in registers (gp_lift_batched's)
+enum { ST_BAD_STATE = 6 };
+
+struct LsState {                                                 // the caller's state buffer: written by begin, read by add and finish
+    uint32_t *keys;                                              // [n]   the rows' entries in sorted order (65536: no valid entry)
+    int32_t *rows;                                               // [n]   the row of every sorted position
+    int32_t *off;                                                // [LB_TABLE] the first sorted position of every entry
+    LsState(GpCarver &cv, int64_t n) {
+        keys = cv.take<uint32_t>(n);
+        rows = cv.take<int32_t>(n);
+        off = cv.take<int32_t>(LB_TABLE);
+    }
+};
+
+struct LsBeginWork {
+    uint32_t *k0;
+    int32_t *r0;
+    char *tmp;
+    size_t tmp_bytes;
+    LsBeginWork(GpCarver &cv, int64_t n) {
+        tmp_bytes = lb_sort_bytes(n);
+        k0 = cv.take<uint32_t>(n);
+        r0 = cv.take<int32_t>(n);
+        tmp = cv.take<char>(tmp_bytes);
+    }
+};
+
+struct LsAddWork {
+    uint32_t *vk0, *vk1;
+    int32_t *w0, *entry_views, *view_off;
+    char *tmp;
+    size_t tmp_bytes;
+    LsAddWork(GpCarver &cv, int32_t nviews) {
+        tmp_bytes = lb_sort_bytes(nviews);
+        vk0 = cv.take<uint32_t>(nviews);
+        vk1 = cv.take<uint32_t>(nviews);
+        w0 = cv.take<int32_t>(nviews);
+        entry_views = cv.take<int32_t>(nviews);
+        view_off = cv.take<int32_t>(LB_TABLE);
+        tmp = cv.take<char>(tmp_bytes);
+    }
+};
+
+struct LsFinishWork {
+    uint32_t *keys;
+    int32_t *rows, *off, *ref, *qry, *rs, *qs, *rrow, *qpos;
+    float *rxyz;
+    char *tmp;
+    size_t tmp_bytes;
+    LsFinishWork(GpCarver &cv, int64_t n) {
+        tmp_bytes = lb_scan_bytes(n + 1);
+        keys = cv.take<uint32_t>(n);
+        rows = cv.take<int32_t>(n);
+        off = cv.take<int32_t>(LB_TABLE);
+        ref = cv.take<int32_t>(n + 1);
+        qry = cv.take<int32_t>(n + 1);
+        rs = cv.take<int32_t>(n + 1);
+        qs = cv.take<int32_t>(n + 1);
+        rrow = cv.take<int32_t>(n);
+        qpos = cv.take<int32_t>(n);
+        rxyz = cv.take<float>(3 * n);
+        tmp = cv.take<char>(tmp_bytes);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ per-view counts over the state
+// lb_counts_kernel with every index of the state checked before use: blockIdx.y = view; the blocks of a view stride the sorted rows
+// of its entry.  Integer atomics: the counts do not depend on arrival order.
+__global__ void __launch_bounds__(256) ls_counts_kernel(const double *__restrict__ points, int64_t n, const int32_t *__restrict__ entry_rows,
+                                                        const int32_t *__restrict__ entry_off, const int64_t *__restrict__ view_entry,
+                                                        const double *__restrict__ w2c, const double *__restrict__ intr,
+                                                        const double *__restrict__ depth, int W, int H, int cut, double tau,
+                                                        unsigned long long *__restrict__ view_count) {
+    const int v = blockIdx.y;
+    const int64_t e = view_entry[v];
+    if ((uint64_t)e >= (uint64_t)LB_MAX_ENTRIES) return;             // (block-uniform)
+    int64_t r0 = entry_off[e], r1 = entry_off[e + 1];
+    r0 = r0 < 0 ? 0 : r0;
+    r1 = r1 > n ? n : r1;
+    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+    const double *dv = depth ? depth + (int64_t)v * W * H : nullptr;
+    int local = 0;
+    for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r1; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = entry_rows[i];
+        if ((uint64_t)row >= (uint64_t)n) continue;
+        const double *P = points + row * 4;
+        if (lb_entry_of(P[0]) != (int)e) continue;
+        long long ui, vi;
+        local += project_point(P[1], P[2], P[3], M, M + 4, M + 8, K[0], K[1], K[2], K[3], dv, W, H, cut, tau, ui, vi) ? 1 : 0;
+    }
+    local = gp_wave_sum_i(local);
+    if (gp_lane() == 0 && local) atomicAdd(view_count + v, (unsigned long long)local);
+}
+
+// ------------------------------------------------------------------------------------------------ the accumulating lift
+// One wave per point, over the views of the point's entry in this chunk.  BILINEAR as in lb_lift_kernel: the map is [h, w], the pixel
+// indexes the [H, W] image, and the resize is evaluated at the pixel with the arithmetic of lift_dense_bilinear_accum_kernel.
+template <bool BILINEAR>
+__global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict__ points, int64_t n, const float *__restrict__ feat, int d, int h,
+                                                       int w, float scale_h, float scale_w, const int32_t *__restrict__ entry_views,
+                                                       const int32_t *__restrict__ view_off, const double *__restrict__ w2c,
+                                                       const double *__restrict__ intr, const double *__restrict__ depth, int W, int H, int cut,
+                                                       double tau, const uint8_t *__restrict__ keep, float *__restrict__ sums, int64_t ld_sum,
+                                                       int32_t *__restrict__ count) {
+    const int64_t p = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;     // (the same for the whole wave: every exit is wave-uniform)
+    if (p >= n) return;
+    const int lane = gp_lane();
+    const double *P = points + p * 4;
+    const int b = lb_entry_of(P[0]);
+    if (b < 0) return;
+    const int v0 = view_off[b], v1 = view_off[b + 1];
+    if (v0 >= v1) return;                                            // the chunk holds no view of this entry
+    const double x = P[1], y = P[2], z = P[3];
+    const int64_t map = (int64_t)h * w * d;
+    float *srow = sums + p * ld_sum;
+    int cnt = 0;
+    for (int c0 = 0; c0 < d; c0 += LS_COL_CHUNK) {
+        float acc[LS_COLS_PER_LANE];
+#pragma unroll
+        for (int k = 0; k < LS_COLS_PER_LANE; ++k) acc[k] = 0.f;
+        int seen_by = 0;
+        for (int g = v0; g < v1; g += GP_WAVE) {
+            int v = 0, px = 0, py = 0;
+            bool vis = false;
+            if (g + lane < v1) {
+                v = entry_views[g + lane];
+                if (keep[v]) {
+                    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+                    long long ui, vi;
+                    vis = project_point(x, y, z, M, M + 4, M + 8, K[0], K[1], K[2], K[3], depth ? depth + (int64_t)v * W * H : nullptr, W, H,
+                                        cut, tau, ui, vi);
+                    px = (int)ui;
+                    py = (int)vi;
+                }
+            }
+            unsigned long long m = __ballot(vis);
+            if (m && !seen_by) {                                     // (wave-uniform) the first view that sees the point: continue its sum
+#pragma unroll
+                for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                    const int c = c0 + lane + k * GP_WAVE;
+                    if (c < d) acc[k] = srow[c];
+                }
+            }
+            seen_by += __popcll(m);
+            while (m) {                                              // ascending view index: the entry's views are sorted stably
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int vj = __shfl(v, j, 64), col = __shfl(px, j, 64), row = __shfl(py, j, 64);
+                const float *f = feat + (int64_t)vj * map;
+                if (BILINEAR) {
+                    int r0, r1, q0, q1;
+                    float wr0, wr1, wc0, wc1;
+                    bilinear_tap(scale_h, row, h, r0, r1, wr0, wr1);
+                    bilinear_tap(scale_w, col, w, q0, q1, wc0, wc1);
+                    const float *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
+                    const float *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+#pragma unroll
+                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                        const int c = c0 + lane + k * GP_WAVE;
+                        if (c < d) {
+                            const float top = __builtin_fmaf(wc0, f00[c], wc1 * f01[c]);
+                            const float bot = __builtin_fmaf(wc0, f10[c], wc1 * f11[c]);
+                            acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                        }
+                    }
+                } else {
+                    const float *fr = f + ((int64_t)row * w + col) * d;
+#pragma unroll
+                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                        const int c = c0 + lane + k * GP_WAVE;
+                        if (c < d) acc[k] += fr[c];
+                    }
+                }
+            }
+        }
+        cnt = seen_by;                                               // (every column chunk sees the same views)
+        if (!cnt) return;                                            // unseen by this chunk: the row is neither loaded nor stored
+#pragma unroll
+        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+            const int c = c0 + lane + k * GP_WAVE;
+            if (c < d) srow[c] = acc[k];
+        }
+    }
+    if (lane == 0) count[p] += cnt;
+}
+
+// ------------------------------------------------------------------------------------------------ the end
+// one wave per point: the row divided once, seen, nn = -1 (the fill overwrites the rows it fills)
+__global__ void __launch_bounds__(256) ls_divide_kernel(const float *__restrict__ sums, int64_t ld_sum, const int32_t *__restrict__ count,
+                                                        int64_t n, int d, float *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ seen,
+                                                        int64_t *__restrict__ nn) {
+    const int64_t p = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+    if (p >= n) return;
+    const int lane = gp_lane();
+    const int cnt = count[p];
+    const float den = cnt == 0 ? 1e-6f : (float)cnt;
+    const float *srow = sums + p * ld_sum;
+    float *orow = out + p * ld_out;
+    for (int c = lane; c < d; c += GP_WAVE) orow[c] = srow[c] / den;
+    if (lane == 0) {
+        seen[p] = cnt > 0 ? 1 : 0;
+        if (nn) nn[p] = -1;
+    }
+}
+
+// the state's tables into the workspace, every value forced into its range; status_out = the running words, [6] = values changed
+__global__ void __launch_bounds__(256) ls_tables_kernel(const uint32_t *__restrict__ keys, const int32_t *__restrict__ rows,
+                                                        const int32_t *__restrict__ off, int64_t n, uint32_t *__restrict__ keys_out,
+                                                        int32_t *__restrict__ rows_out, int32_t *__restrict__ off_out,
+                                                        unsigned long long *__restrict__ status_out) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    int nbad = 0;
+    if (i < n) {
+        const uint32_t k = keys[i];
+        const int32_t r = rows[i];
+        const bool ok = (uint64_t)(int64_t)r < (uint64_t)n;
+        nbad = (k > (uint32_t)LB_MAX_ENTRIES ? 1 : 0) + (ok ? 0 : 1);
+        keys_out[i] = k > (uint32_t)LB_MAX_ENTRIES ? (uint32_t)LB_MAX_ENTRIES : k;
+        rows_out[i] = ok ? r : 0;
+    }
+    if (i < LB_TABLE) {
+        const int64_t o = off[i];
+        nbad += (o < 0 || o > n) ? 1 : 0;
+        off_out[i] = (int32_t)(o < 0 ? 0 : (o > n ? n : o));
+    }
+    nbad = gp_wave_sum_i(nbad);
+    if (gp_lane() == 0 && nbad) atomicAdd(status_out + ST_BAD_STATE, (unsigned long long)nbad);
+}
+
+__global__ void ls_status_kernel(const int64_t *__restrict__ running, int64_t *__restrict__ status_out) {
+    const int i = threadIdx.x;
+    if (i < ST_WORDS) status_out[i] = i <= ST_TOP_BATCH ? running[i] : 0;
+}
+
+size_t ls_state_bytes(int64_t n) {
+    GpCarver cv(nullptr, 0);
+    LsState s(cv, n);
+    return cv.off;
+}
+
+bool ls_n_ok(int64_t n) { return n > 0 && n < (1ll << 31); }
+
+}  // namespace
+
+extern "C" size_t gp_lift_stream_state_bytes(int64_t n) { return ls_n_ok(n) ? ls_state_bytes(n) : 0; }
+
+extern "C" size_t gp_lift_stream_begin_workspace_bytes(int64_t n) {
+    if (!ls_n_ok(n)) return 0;
+    GpCarver cv(nullptr, 0);
+    LsBeginWork k(cv, n);
+    return cv.off;
+}
+
+extern "C" int gp_lift_stream_begin(const double *points, int64_t n, int32_t d, void *state, size_t state_bytes, float *sums, int64_t ld_sum,
+                                    int32_t *count, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(points && state && sums && count && status && workspace, "gp_lift_stream_begin: null argument");
+    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_begin: n=%lld outside 1..2^31-1", (long long)n);
+    GP_CHECK_ARG(d >= 1 && ld_sum >= d, "gp_lift_stream_begin: d=%d, ld_sum=%lld", d, (long long)ld_sum);
+    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_begin: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+    {
+        const void *o[] = {state, sums, count, status, workspace};
+        const size_t o_bytes[] = {state_bytes, (size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8, workspace_bytes};
+        for (int a = 0; a < 5; ++a) {
+            GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], points, (size_t)n * 32), "gp_lift_stream_begin: an output overlaps an input");
+            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_begin: two outputs overlap");
+        }
+    }
+    GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
+    LsState st(sv, n);
+    LsBeginWork k(cv, n);
+    if (!cv.ok()) {
+        gp_set_error("gp_lift_stream_begin: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
+    GP_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int32_t), s));
+    GP_CHECK_HIP(hipMemset2DAsync(sums, (size_t)ld_sum * 4, 0, (size_t)d * 4, (size_t)n, s));       // +0 in every sum, the pitch columns untouched
+    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, reinterpret_cast<unsigned long long *>(status));
+    GP_CHECK_LAUNCH();
+    size_t io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, st.keys, k.r0, st.rows, (size_t)n, 0, LB_KEY_BITS, s));             // (stable)
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(st.keys, n, st.off);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+extern "C" size_t gp_lift_stream_add_workspace_bytes(int32_t nviews) {
+    if (nviews < 1 || nviews > 65535) return 0;
+    GpCarver cv(nullptr, 0);
+    LsAddWork k(cv, nviews);
+    return cv.off;
+}
+
+extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const float *feat, int32_t d, int32_t h,
+                                  int32_t w, const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
+                                  int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres,
+                                  int64_t min_visible, int64_t max_visible, float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count,
+                                  uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(points && state && feat && view_entry && w2c && intrinsics && sums && count && view_count && view_keep && status && workspace,
+                 "gp_lift_stream_add: null argument");
+    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_add: n=%lld outside 1..2^31-1", (long long)n);
+    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_stream_add: %d views outside 1..65535", nviews);
+    GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_sum >= d,
+                 "gp_lift_stream_add: d=%d, map %d x %d, image %d x %d, ld_sum=%lld", d, h, w, height, width, (long long)ld_sum);
+    GP_CHECK_ARG(bilinear == 0 || bilinear == 1, "gp_lift_stream_add: bilinear=%d (0 nearest, 1 bilinear)", bilinear);
+    GP_CHECK_ARG(bilinear || (h == height && w == width), "gp_lift_stream_add: the nearest mode samples the map itself: map %d x %d, image %d x %d",
+                 h, w, height, width);
+    GP_CHECK_ARG(cut_bound >= 0, "gp_lift_stream_add: cut_bound=%d must not be negative", cut_bound);
+    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_add: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+    {
+        // every output against every input and every other output, over their whole extents
+        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * 4;
+        const void *in[] = {points, state, feat, view_entry, w2c, intrinsics, depth};
+        const size_t in_bytes[] = {(size_t)n * 32,      state_bytes,          maps, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32,
+                                   (size_t)nviews * px * 8};
+        const void *o[] = {sums, count, view_count, view_keep, status, workspace};
+        const size_t o_bytes[] = {(size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)nviews * 8, (size_t)nviews, (size_t)ST_WORDS * 8,
+                                  workspace_bytes};
+        for (int a = 0; a < 6; ++a) {
+            for (int i = 0; i < 7; ++i)
+                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_stream_add: an output overlaps an input");
+            for (int q = a + 1; q < 6; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_add: two outputs overlap");
+        }
+    }
+    GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
+    const LsState st(sv, n);
+    LsAddWork k(cv, nviews);
+    if (!cv.ok()) {
+        gp_set_error("gp_lift_stream_add: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
+    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
+    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
+    // (1) the chunk's view table; its bad entries join the running count
+    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, k.vk0, k.w0, reinterpret_cast<unsigned long long *>(status));
+    GP_CHECK_LAUNCH();
+    size_t io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.vk0, k.vk1, k.w0, k.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));  // (stable)
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.vk1, nviews, k.view_off);
+    // (2) the chunk's per-view counts and the drop rule
+    ls_counts_kernel<<<dim3(nb < 64 ? nb : 64, (unsigned)nviews), 256, 0, s>>>(points, n, st.rows, st.off, view_entry, w2c, intrinsics, depth, width,
+                                                                                height, cut_bound, vis_thres, vc);
+    lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
+    GP_CHECK_LAUNCH();
+    // (3) the accumulating lift
+    // area_pixel_compute_scale<float>(in, out, align_corners=true): (in-1)/(out-1) in fp32, 0 for a single output pixel
+    const float sh = height > 1 ? (float)(h - 1) / (float)(height - 1) : 0.f;
+    const float sw = width > 1 ? (float)(w - 1) / (float)(width - 1) : 0.f;
+    const unsigned lb = (unsigned)((n * 64 + 255) / 256);
+    if (bilinear)
+        ls_accum_kernel<true><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
+                                                 cut_bound, vis_thres, view_keep, sums, ld_sum, count);
+    else
+        ls_accum_kernel<false><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
+                                                  cut_bound, vis_thres, view_keep, sums, ld_sum, count);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+extern "C" size_t gp_lift_stream_finish_workspace_bytes(int64_t n) {
+    if (!ls_n_ok(n)) return 0;
+    GpCarver cv(nullptr, 0);
+    LsFinishWork k(cv, n);
+    return cv.off;
+}
+
+extern "C" int gp_lift_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes, const float *sums, int32_t d,
+                                     int64_t ld_sum, const int32_t *count, const int64_t *status, int32_t fill, float *out, int64_t ld_out,
+                                     uint8_t *seen, int64_t *nn, int64_t *status_out, void *workspace, size_t workspace_bytes, void *stream_) {
+    GP_CHECK_ARG(points && state && sums && count && status && out && seen && status_out && workspace, "gp_lift_stream_finish: null argument");
+    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_finish: n=%lld outside 1..2^31-1", (long long)n);
+    GP_CHECK_ARG(d >= 1 && ld_sum >= d && ld_out >= d, "gp_lift_stream_finish: d=%d, ld_sum=%lld, ld_out=%lld", d, (long long)ld_sum,
+                 (long long)ld_out);
+    GP_CHECK_ARG(fill == 0 || nn, "gp_lift_stream_finish: the fill writes nn");
+    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_finish: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+    {
+        const void *in[] = {points, state, sums, count, status};
+        const size_t in_bytes[] = {(size_t)n * 32, state_bytes, (size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8};
+        const void *o[] = {out, seen, nn, status_out, workspace};
+        const size_t o_bytes[] = {(size_t)((n - 1) * ld_out + d) * 4, (size_t)n, (size_t)n * 8, (size_t)ST_WORDS * 8, workspace_bytes};
+        for (int a = 0; a < 5; ++a) {
+            for (int i = 0; i < 5; ++i)
+                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_stream_finish: an output overlaps an input");
+            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_finish: two outputs overlap");
+        }
+    }
+    GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
+    const LsState st(sv, n);
+    LsFinishWork k(cv, n);
+    if (!cv.ok()) {
+        gp_set_error("gp_lift_stream_finish: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    unsigned long long *so = reinterpret_cast<unsigned long long *>(status_out);
+    const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
+    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
+    ls_status_kernel<<<1, 64, 0, s>>>(status, status_out);
+    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(st.keys, st.rows, st.off, n, k.keys, k.rows, k.off, so);
+    ls_divide_kernel<<<(unsigned)((n * 64 + 255) / 256), 256, 0, s>>>(sums, ld_sum, count, n, d, out, ld_out, seen, nn);
+    GP_CHECK_LAUNCH();
+    // the fill of gp_lift_batched, over the checked copies of the tables
+    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(k.keys, k.rows, seen, n, k.ref, k.qry);
+    GP_CHECK_LAUNCH();
+    size_t io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.ref, k.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.qry, k.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, k.rows, k.ref, k.qry, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, so);
+    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.keys, k.rows, k.off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, so);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}

@@ -1564,6 +1564,100 @@ def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, im
     return LiftBatched(out, got["seen"], got["count"], got["view_count"], got["view_keep"], got.get("nn"), got["status"])
 
 
+# ------------------------------------------------------------------------------------------ the same lift, the views in chunks
+class LiftStreamState:
+    """What a resumable lift keeps between its calls, all of it the caller's: points f64 [n,4], state u8 (the entry tables, written by
+    gp_lift_stream_begin alone), sums fp32 [n, D] rows of any pitch, count i32 [n], status i64 [8] (the running words: bad batch rows,
+    bad view entries so far, non-finite rows, top batch)."""
+
+    def __init__(self, points, state, sums, count, status):
+        self.points, self.state, self.sums, self.count, self.status = points, state, sums, count, status
+
+
+def lift_stream_begin(points, d, buffers=None, workspace=None):
+    """gp_lift_stream_begin, no sync: points f64 [n,4] -> LiftStreamState for rows of d channels (sums +0, counts 0).  buffers: optional
+    dict of caller-owned state / sums / count / status (state: uint8 of at least gp_lift_stream_state_bytes(n); sums: fp32 rows of any
+    pitch); workspace: uint8 of at least gp_lift_stream_begin_workspace_bytes(n)."""
+    lib = _lib.load()
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1 or int(d) < 1:
+        raise ValueError(f"lift_stream_begin: expected points [n >= 1, 4] and d >= 1, got {list(points.shape)}, d={d}")
+    n, dev, d = points.shape[0], points.device, int(d)
+    got = _outputs("lift_stream_begin", {"count": (torch.int32, (n,)), "status": (torch.int64, (8,))}, buffers, dev)
+    state = (buffers or {}).get("state")
+    state = _ws(lib.gp_lift_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")
+    sums = (buffers or {}).get("sums")
+    sums = torch.empty((n, d), dtype=torch.float32, device=dev) if sums is None else _rows(sums, "sums", n, d)
+    ws = _ws(lib.gp_lift_stream_begin_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_stream_begin(_ptr(points), n, d, _ptr(state), state.numel(), _ptr(sums), sums.stride(0), _ptr(got["count"]),
+                                   _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_lift_stream_begin")
+    return LiftStreamState(points, state, sums, got["count"], got["status"])
+
+
+def lift_stream_add_workspace_bytes(num_views):
+    return int(_lib.load().gp_lift_stream_add_workspace_bytes(int(num_views)))
+
+
+def lift_stream_finish_workspace_bytes(n):
+    return int(_lib.load().gp_lift_stream_finish_workspace_bytes(int(n)))
+
+
+def lift_stream_add(st, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, image_hw, bilinear, cut_bound, vis_thres, min_visible, max_visible,
+                    buffers=None, workspace=None):
+    """gp_lift_stream_add, no sync: one chunk of views onto the LiftStreamState st; the chunk's arrays as ops.lift_batched takes them
+    (maps_pm fp32 [V, h*w, D] pixel-major).  -> (view_count i64 [V], view_keep u8 [V]) of the chunk.  buffers: optional dict of
+    caller-owned view_count / view_keep; workspace: uint8 of at least gp_lift_stream_add_workspace_bytes(V)."""
+    lib = _lib.load()
+    who = "lift_stream_add"
+    _chk(maps_pm, torch.float32, "maps_pm"), _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c")
+    _chk(intrinsics, torch.float64, "intrinsics")
+    (h, w), (H, W) = map_hw, image_hw
+    n, d, dev = st.points.shape[0], st.sums.shape[1], st.points.device
+    if maps_pm.dim() != 3 or maps_pm.shape[1] != h * w or maps_pm.shape[2] != d:
+        raise ValueError(f"{who}: expected maps_pm [V, {h * w}, {d}], got {list(maps_pm.shape)}")
+    nv = maps_pm.shape[0]
+    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
+        raise ValueError(f"{who}: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
+                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
+        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    got = _outputs(who, {"view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,))}, buffers, dev)
+    ws = _ws(lib.gp_lift_stream_add_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_stream_add(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(maps_pm), d, int(h), int(w), _ptr(view_entry),
+                                 _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv, int(H), int(W), 1 if bilinear else 0, int(cut_bound),
+                                 float(vis_thres), int(min_visible), int(max_visible), _ptr(st.sums), st.sums.stride(0), _ptr(st.count),
+                                 _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(st.status), _ptr(ws), ws.numel(), _stream()),
+          "gp_lift_stream_add")
+    return got["view_count"], got["view_keep"]
+
+
+class LiftStreamFinish:
+    """What gp_lift_stream_finish writes: out fp32 [n, D] (before the fill), seen u8 [n], nn i64 [n] or None, status i64 [8] = (bad batch
+    rows, bad view entries, non-finite rows, top batch, seen rows, filled rows, values of the state outside their range, 0)."""
+
+    def __init__(self, out, seen, nn, status):
+        self.out, self.seen, self.nn, self.status = out, seen, nn, status
+
+
+def lift_stream_finish(st, fill=True, buffers=None, workspace=None):
+    """gp_lift_stream_finish, no sync: the LiftStreamState st as it stands -> LiftStreamFinish; st is not changed.  buffers: optional
+    dict of caller-owned out (fp32 rows of any pitch) / seen / nn / status; workspace: uint8 of at least
+    gp_lift_stream_finish_workspace_bytes(n)."""
+    lib = _lib.load()
+    n, d, dev = st.points.shape[0], st.sums.shape[1], st.points.device
+    want = {"seen": (torch.uint8, (n,)), "status": (torch.int64, (8,))}
+    if fill:
+        want["nn"] = (torch.int64, (n,))
+    got = _outputs("lift_stream_finish", want, buffers, dev)
+    out = (buffers or {}).get("out")
+    out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
+    ws = _ws(lib.gp_lift_stream_finish_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_stream_finish(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(st.sums), d, st.sums.stride(0), _ptr(st.count),
+                                    _ptr(st.status), 1 if fill else 0, _ptr(out), out.stride(0), _ptr(got["seen"]), _ptr(got.get("nn")),
+                                    _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_lift_stream_finish")
+    return LiftStreamFinish(out, got["seen"], got.get("nn"), got["status"])
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

@@ -16,6 +16,14 @@ features out:
     per_point = y.F[q.inverse_mapping]
     seg = segment(y, text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)   # labels per point, (I, O, T) counts per scene
 
+or, with the VLM producing its maps a batch of views at a time (the reference's own loop, :365-449), the same start without ever
+holding more than one batch of maps:
+
+    stream = LiftStream(points, feature_dim=D, mode="bilinear")
+    for maps, view_entry, world_to_camera, intrinsics, depth in vlm_batches:
+        stream.add(Views(maps, view_entry, world_to_camera, intrinsics, depth, image_shape=(H, W)))
+    lifted = stream.finish()                                    # the bits of lift on all the views; add / finish may go on
+
 or, from the X-Decoder form of the VLM's outputs (masks, class logits, mask embeddings: the reference's default lift), the same chain with
 
     lifted = lift_masks(points, MaskViews(pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth,
@@ -40,6 +48,8 @@ l2norm_rows_backward).  The default takes no gradients, like the reference's eva
 lift is the reference's lift_lseg_features (models/affinity_module.py:404-452) with the point -> pixel mapping of
 models/utils/fusion_util.py:45-147 and the loader's view-drop rule (dataset/data_loader_ablation.py:254-288), for all entries and all
 views in one call of ops.lift_batched, then ops.gather_rows for the fill.
+LiftStream is the same lift resumable over chunks of views: ops.lift_stream_begin (the entry tables, once), ops.lift_stream_add per chunk
+(fp32 sums continued in view order), ops.lift_stream_finish (divide and fill; a snapshot), ops.gather_rows.
 lift_masks is the reference's lift_xdecoder_features (models/affinity_module.py:455-714: per-view mask-embedding lift, in-view nearest
 fill, consensus top-3 fusion, scene-level fill) with the same mapping and drop rule, for all entries and any number of views per entry:
 ops.lift_masks_batched_lists (ordered visible lists), ops.segment_tables, ops.lift_masks_batched, ops.gather_rows; two read-backs.
@@ -147,6 +157,63 @@ def _shape_of(t):
     return list(t.shape) if torch.is_tensor(t) else type(t).__name__
 
 
+def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible):
+    """lift's argument checks, in lift's order; views None: those of the points and the options alone (LiftStream's construction).
+    -> (V, D, h, w, H, W), or None without views"""
+    if mode not in LIFT_MODES:
+        raise ValueError(f"{who}: mode={mode!r}, expected one of {LIFT_MODES}")
+    if views is not None and not isinstance(views, Views):
+        raise ValueError(f"{who}: views must be a Views, got {type(views).__name__}")
+    P = points
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    if views is not None:
+        Fm, E, M, K, Dp = views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        if not torch.is_tensor(Fm) or Fm.dim() != 4 or min(Fm.shape) < 1:
+            raise ValueError(f"{who}: views.features must be [V, D, h, w] with V, D, h, w >= 1, got {_shape_of(Fm)}")
+        if not Fm.dtype.is_floating_point:
+            raise ValueError(f"{who}: views.features must be floating point, got {Fm.dtype}")
+        V, D, h, w = Fm.shape
+        if V > 65535:
+            raise ValueError(f"{who}: {V} views, at most 65535")
+        if not _is_int_tensor(E) or E.shape != (V,):
+            raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
+                             f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+        if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
+            raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
+        if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
+            raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
+                             f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+        shape = (h, w) if views.image_shape is None else tuple(views.image_shape)
+        if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+            raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers, got {views.image_shape!r}")
+        H, W = shape
+        if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
+            raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
+                             f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+        if mode == "nearest" and (h, w) != (H, W):
+            raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
+        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
+    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
+        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    if views is not None and Fm.requires_grad:
+        raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
+                         "no_grad); detach them")
+    tensors = [P] + ([Fm, E, M, K] + ([Dp] if Dp is not None else []) if views is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    return (V, D, h, w, H, W) if views is not None else None
+
+
 def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
     """The 2D -> 3D lift of the reference (models/affinity_module.py:404-452, models/utils/fusion_util.py:45-147,
     dataset/data_loader_ablation.py:254-288) for several scenes at once, entries never mixing.  points: floating (fp64 or fp32) [N,4] =
@@ -170,55 +237,9 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     grad, more than 65535 views, N >= 2^31; from the ONE status read-back, taken after the last launch (no buffer is sized by what it
     carries): rows whose batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates."""
     who = "lift"
-    if mode not in LIFT_MODES:
-        raise ValueError(f"{who}: mode={mode!r}, expected one of {LIFT_MODES}")
-    if not isinstance(views, Views):
-        raise ValueError(f"{who}: views must be a Views, got {type(views).__name__}")
+    V, D, h, w, H, W = _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible)
     P, Fm, E, M, K, Dp = points, views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
-    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
-        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
-    if P.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
     n = P.shape[0]
-    if n == 0 or n >= 2 ** 31:
-        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
-    if not torch.is_tensor(Fm) or Fm.dim() != 4 or min(Fm.shape) < 1:
-        raise ValueError(f"{who}: views.features must be [V, D, h, w] with V, D, h, w >= 1, got {_shape_of(Fm)}")
-    if not Fm.dtype.is_floating_point:
-        raise ValueError(f"{who}: views.features must be floating point, got {Fm.dtype}")
-    V, D, h, w = Fm.shape
-    if V > 65535:
-        raise ValueError(f"{who}: {V} views, at most 65535")
-    if not _is_int_tensor(E) or E.shape != (V,):
-        raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
-                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-    if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
-        raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
-    if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
-        raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
-                         f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
-    shape = (h, w) if views.image_shape is None else tuple(views.image_shape)
-    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-        raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers, got {views.image_shape!r}")
-    H, W = shape
-    if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
-        raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
-                         f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
-    if mode == "nearest" and (h, w) != (H, W):
-        raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
-    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
-        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
-    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
-        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
-    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
-        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
-    if Fm.requires_grad:
-        raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
-                         "no_grad); detach them")
-    tensors = [P, Fm, E, M, K] + ([Dp] if Dp is not None else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
     dev = P.device
     with torch.cuda.device(dev), torch.no_grad():
         pts = P.detach().to(torch.float64).contiguous()
@@ -241,6 +262,123 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     if bad_view:
         raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
     return Lifted(feats, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
+
+
+class LiftStream:
+    """lift with the views arriving in chunks -- the reference's own loop (models/affinity_module.py:365-449: the VLM runs on
+    max_batch_size views at a time, every chunk is added into sum_features / counter and freed, one division and one fill at the end),
+    for several scenes at once.  Only one chunk's maps need to exist at a time:
+
+        stream = LiftStream(points, feature_dim=D, mode="bilinear")
+        for chunk in vlm_chunks:                                # a Views: views of any entries, any number of them
+            stream.add(chunk)                                   # no host synchronisation
+        lifted = stream.finish()                                # -> Lifted; the one status read-back
+
+    points and the options are lift's; every chunk is a Views as lift takes it.
+      1. After any sequence of add calls, finish(fill=f) returns what lift(points, Views(the chunks concatenated in the order added),
+         fill=f, ...) returns, bit for bit in features, seen, count, view_count and view_keep (the last two in arrival order).
+      2. A chunk need not be a slice of one global view list: an entry's views are taken in their order of arrival, which is all that
+         lift's rule 3 (the fp32 sum in ascending v) depends on.  view_keep follows from a view's own count (rule 2), so it is final
+         when the chunk is added.
+      3. finish is a snapshot: it writes new tensors from the sums and counts and changes neither, so add and finish may go on
+         alternating (the online use: a result after every chunk for one divide pass over [N, D] and the fill).
+      4. Maps of other floating dtypes are upcast per chunk; a channels_last chunk is read in place, an NCHW chunk is transposed into
+         one scratch buffer of the stream's that grows only when a chunk is larger than every chunk before it.  Apart from the
+         per-view count and keep vectors the stream holds nothing that grows with the views added: the state is the entry tables
+         (8 bytes per point), the fp32 sums [N, D] and the counts [N].
+    Why the bits are lift's: a point's sum starts from +0 and takes the kept views that see it in ascending order, one fp32 add each;
+    between two chunks the partial sum is stored and reloaded as fp32, which changes no bit.  A point that no kept view of a chunk
+    sees is neither read nor written by that chunk.
+    Inside: ops.lift_stream_begin at construction (the entry tables, once), per chunk ops.lift_batched_transpose (NCHW only) and
+    ops.lift_stream_add (the chunk's view table, the per-view counts and drop rule, the accumulating lift kernel), in finish
+    ops.lift_stream_finish (divide, seen, the per-entry masked 1-NN) and ops.gather_rows.
+    ValueError before any kernel of the call: lift's refusals, for points and options at construction and for the chunk at add; a
+    chunk whose D is not feature_dim, or whose (h, w), image_shape, presence of depth or device differ from the first chunk's; a chunk
+    that takes the views past 65535 in all (lift's limit); finish before any add.  A refused add leaves the stream as it was.  From
+    finish's ONE status read-back, with lift's messages and precedence: non-finite rows, rows whose batch index is no integer in
+    0..65535 (both counted once, at construction), views whose entry is outside 0..65535 (counted over all chunks).  Such rows and
+    views belong to no entry and change nobody else's result.  (RuntimeError from the same read-back: the entry tables hold values
+    outside their range, i.e. somebody wrote into the stream's state; the kernels force them into range before use.)"""
+
+    def __init__(self, points, feature_dim, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None):
+        who = "LiftStream"
+        _check_lift(who, points, None, mode, cut_bound, vis_thres, min_visible, max_visible)
+        if not _is_count(feature_dim, 1) or feature_dim >= 2 ** 31:
+            raise ValueError(f"{who}: feature_dim={feature_dim!r} must be a positive integer")
+        self.mode, self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = mode, cut_bound, vis_thres, min_visible, max_visible
+        self.feature_dim, self.num_views = int(feature_dim), 0
+        self._points, self._device = points, points.device
+        self._first = None                                      # ((h, w), (H, W), depth present) of the first chunk
+        self._view_count, self._view_keep = [], []
+        self._scratch = self._ws_add = self._ws_finish = None
+        with torch.cuda.device(self._device), torch.no_grad():
+            self._st = ops.lift_stream_begin(points.detach().to(torch.float64).contiguous(), self.feature_dim)
+
+    def _options(self):
+        return self.mode, self.cut_bound, self.vis_thres, self.min_visible, self.max_visible
+
+    def add(self, views):
+        """One chunk of views (a Views) onto the sums.  No host synchronisation."""
+        who = "LiftStream.add"
+        V, D, h, w, H, W = _check_lift(who, self._points, views, *self._options())
+        if D != self.feature_dim:
+            raise ValueError(f"{who}: the chunk's maps have {D} channels, the stream was built with feature_dim={self.feature_dim}")
+        this = ((h, w), (H, W), views.depth is not None)
+        if self._first is not None:
+            for name, a, b in zip(("(h, w)", "image_shape", "the presence of depth"), this, self._first):
+                if a != b:
+                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
+        if self.num_views + V > 65535:
+            raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
+        Fm, E, M, K, Dp = views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        with torch.cuda.device(self._device), torch.no_grad():
+            maps = Fm.detach().to(torch.float32)
+            if maps.is_contiguous(memory_format=torch.channels_last):
+                maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)      # (a view: channels_last is pixel-major already)
+            else:
+                if self._scratch is None or self._scratch.numel() < maps.numel():
+                    self._scratch = None                                    # (freed before the larger one is taken)
+                    self._scratch = torch.empty(maps.numel(), dtype=torch.float32, device=self._device)
+                maps_pm = ops.lift_batched_transpose(maps.contiguous(), out=self._scratch[:maps.numel()].view(V, h * w, D))
+            need = ops.lift_stream_add_workspace_bytes(V)
+            if self._ws_add is None or self._ws_add.numel() < need:
+                self._ws_add = None
+                self._ws_add = torch.empty(need, dtype=torch.uint8, device=self._device)
+            vc, vk = ops.lift_stream_add(self._st, maps_pm, (h, w), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(),
+                                         K.detach().contiguous(), None if Dp is None else Dp.detach().contiguous(), (H, W),
+                                         self.mode == "bilinear", self.cut_bound, float(self.vis_thres), self.min_visible,
+                                         2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1), workspace=self._ws_add)
+        self._first = this
+        self.num_views += V
+        self._view_count.append(vc)
+        self._view_keep.append(vk)
+
+    def finish(self, fill=True):
+        """-> Lifted over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
+        who = "LiftStream.finish"
+        if self._first is None:
+            raise ValueError(f"{who}: no views were added")
+        n, D, dev = self._points.shape[0], self.feature_dim, self._device
+        with torch.cuda.device(dev), torch.no_grad():
+            if self._ws_finish is None:
+                self._ws_finish = torch.empty(ops.lift_stream_finish_workspace_bytes(n), dtype=torch.uint8, device=dev)
+            r = ops.lift_stream_finish(self._st, fill=bool(fill), workspace=self._ws_finish)
+            feats = r.out
+            if fill:
+                feats = ops.gather_rows(r.out, D, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
+            count = self._st.count.clone()
+            view_count, view_keep = torch.cat(self._view_count), torch.cat(self._view_keep).bool()
+            status = ops.readback(r.status)
+        bad_batch, bad_view, nonfinite, bad_state = status[0], status[1], status[2], status[6]
+        if nonfinite:
+            raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+        if bad_batch:
+            raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+        if bad_view:
+            raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+        if bad_state:
+            raise RuntimeError(f"{who}: {bad_state} values of the stream's entry tables are out of range: the state was overwritten")
+        return Lifted(feats, r.seen.bool(), count, view_count, view_keep)
 
 
 # ------------------------------------------------------------------------------------------ the mask-embedding lift

@@ -865,6 +865,57 @@ int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t 
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* gp_lift_batched, RESUMABLE: the views arrive in chunks (the VLM's batches), every chunk's maps are  */
+/* read once, and after any number of chunks the result is the bits of gp_lift_batched on the          */
+/* concatenation of the chunks in the order added.  Points, views, poses, modes and the drop rule are  */
+/* worded as in gp_lift_batched; only the relative order of an entry's views matters, and that is the  */
+/* order of arrival.  The caller owns, between the calls: state (gp_lift_stream_state_bytes(n)), sums   */
+/* f32 [n, ld_sum >= d], count i32 [n] and the running status i64 [8].                                 */
+/*                                                                                                    */
+/* gp_lift_stream_begin: before the chunk loop of models/affinity_module.py:365-436 (its sum_features /  */
+/* counter = zeros).  The points' entry tables (rows sorted stably by entry, offsets) into state, which */
+/* no later call writes; sums = +0, count = 0; status [0] rows whose batch index is no integer in       */
+/* 0..65535, [2] rows with a non-finite value, [3] the highest valid batch index, the others 0.        */
+/*                                                                                                    */
+/* gp_lift_stream_add: one pass of the chunk loop, models/affinity_module.py:365-436 (fusion_util.py:   */
+/* 45-147, data_loader_ablation.py:254-288), for the nviews views of this chunk, of any entries:        */
+/*   view_count i64 [nviews], view_keep u8 [nviews]: as gp_lift_batched, of this chunk's views;          */
+/*   sums: every point's row continued with the sampled columns of the chunk's kept views that see it,  */
+/*     one fp32 add each in ascending view index; count += their number.  The row of a point that no    */
+/*     kept view of the chunk sees is neither read nor written.  No float atomics;                      */
+/*   status[1] += the chunk's views whose entry is outside 0..65535 (they belong to no entry).         */
+/* It does not synchronise and sizes nothing by device data.  feat f32 [nviews, h*w, d] pixel-major.   */
+/*                                                                                                    */
+/* gp_lift_stream_finish: the end, models/affinity_module.py:435-449.  Reads state, sums, count and     */
+/* status and changes none of them, so it may be called after every chunk:                              */
+/*   out f32 [n, ld_out >= d] = sums / (count == 0 ? 1e-6 : count); seen u8 [n] = count > 0;            */
+/*   nn i64 [n] (fill != 0; nullable otherwise): as gp_lift_batched, the caller gathers;                */
+/*   status_out i64 [8]: [0]..[3] the running status, [4] seen rows, [5] filled rows, [6] values of     */
+/*     state that lay outside their range (a state that gp_lift_stream_begin did not write for these    */
+/*     points; they are forced into range first: nothing is read or written outside the extents        */
+/*     whatever state holds, and add checks every row number and offset it takes from it as well).     */
+/* 1 <= n < 2^31, 1 <= nviews <= 65535 per chunk (the caller keeps the total within 65535 if it wants   */
+/* gp_lift_batched's limit), d >= 1, cut_bound >= 0.  No output may overlap an input or another output */
+/* (GP_EINVAL); sums, count and status are outputs of begin and add and inputs of finish.              */
+size_t gp_lift_stream_state_bytes(int64_t n);
+size_t gp_lift_stream_begin_workspace_bytes(int64_t n);
+int gp_lift_stream_begin(const double *points, int64_t n, int32_t d, void *state, size_t state_bytes, float *sums,
+                         int64_t ld_sum, int32_t *count, int64_t *status, void *workspace, size_t workspace_bytes,
+                         void *stream);
+size_t gp_lift_stream_add_workspace_bytes(int32_t nviews);
+int gp_lift_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const float *feat,
+                       int32_t d, int32_t h, int32_t w, const int64_t *view_entry, const double *w2c,
+                       const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                       int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible,
+                       float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count, uint8_t *view_keep,
+                       int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t gp_lift_stream_finish_workspace_bytes(int64_t n);
+int gp_lift_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes, const float *sums,
+                          int32_t d, int64_t ld_sum, const int32_t *count, const int64_t *status, int32_t fill, float *out,
+                          int64_t ld_out, uint8_t *seen, int64_t *nn, int64_t *status_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The mask-embedding lift with top-3 fusion over BATCHED point clouds: models/affinity_module.py:455-714  */
 /* (lift_xdecoder_features) for every batch entry and every view in one sequence of launches, entries     */
 /* never mixing and with no cap on the views of an entry.  It replaces, per scene,                        */
