@@ -193,6 +193,18 @@ SIGNATURES = {
     "gp_lift_masks_batched": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32,
                                         _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
                                         _P, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_stream_state_bytes": (c_size_t, [c_int64]),
+    "gp_lift_masks_stream_begin_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_lift_masks_stream_begin": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_stream_sizes_workspace_bytes": (c_size_t, [c_int32]),
+    "gp_lift_masks_stream_sizes": (c_int32, [c_int64, _P, c_size_t, _P, _P, _P, _P, c_int32, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_stream_add_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64]),
+    "gp_lift_masks_stream_add": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32,
+                                           c_int32, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P,
+                                           c_size_t, _P]),
+    "gp_lift_masks_stream_finish_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64, c_int32]),
+    "gp_lift_masks_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, _P, _P, c_int32, _P, _P, c_int64, c_int32, _P, _P, c_int32,
+                                              c_int32, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -26,37 +26,12 @@
 // state held.  The chunk's view table lies in add's own workspace (positions inside 0..nviews by construction of the lower bounds).
 // A pixel is read only after project_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0; bilinear taps are clamped to
 // the map; channel indices are guarded by c < d.  All offsets are 64-bit.
-#include "gp_lift_entries.h"
+#include "gp_lift_stream_state.h"
 
 namespace {
 
 constexpr int LS_COLS_PER_LANE = 8;
 constexpr int LS_COL_CHUNK = GP_WAVE * LS_COLS_PER_LANE;         // channels one pass holds in registers (gp_lift_batched's)
-enum { ST_BAD_STATE = 6 };
-
-struct LsState {                                                 // the caller's state buffer: written by begin, read by add and finish
-    uint32_t *keys;                                              // [n]   the rows' entries in sorted order (65536: no valid entry)
-    int32_t *rows;                                               // [n]   the row of every sorted position
-    int32_t *off;                                                // [LB_TABLE] the first sorted position of every entry
-    LsState(GpCarver &cv, int64_t n) {
-        keys = cv.take<uint32_t>(n);
-        rows = cv.take<int32_t>(n);
-        off = cv.take<int32_t>(LB_TABLE);
-    }
-};
-
-struct LsBeginWork {
-    uint32_t *k0;
-    int32_t *r0;
-    char *tmp;
-    size_t tmp_bytes;
-    LsBeginWork(GpCarver &cv, int64_t n) {
-        tmp_bytes = lb_sort_bytes(n);
-        k0 = cv.take<uint32_t>(n);
-        r0 = cv.take<int32_t>(n);
-        tmp = cv.take<char>(tmp_bytes);
-    }
-};
 
 struct LsAddWork {
     uint32_t *vk0, *vk1;
@@ -236,42 +211,10 @@ __global__ void __launch_bounds__(256) ls_divide_kernel(const float *__restrict_
     }
 }
 
-// the state's tables into the workspace, every value forced into its range; status_out = the running words, [6] = values changed
-__global__ void __launch_bounds__(256) ls_tables_kernel(const uint32_t *__restrict__ keys, const int32_t *__restrict__ rows,
-                                                        const int32_t *__restrict__ off, int64_t n, uint32_t *__restrict__ keys_out,
-                                                        int32_t *__restrict__ rows_out, int32_t *__restrict__ off_out,
-                                                        unsigned long long *__restrict__ status_out) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    int nbad = 0;
-    if (i < n) {
-        const uint32_t k = keys[i];
-        const int32_t r = rows[i];
-        const bool ok = (uint64_t)(int64_t)r < (uint64_t)n;
-        nbad = (k > (uint32_t)LB_MAX_ENTRIES ? 1 : 0) + (ok ? 0 : 1);
-        keys_out[i] = k > (uint32_t)LB_MAX_ENTRIES ? (uint32_t)LB_MAX_ENTRIES : k;
-        rows_out[i] = ok ? r : 0;
-    }
-    if (i < LB_TABLE) {
-        const int64_t o = off[i];
-        nbad += (o < 0 || o > n) ? 1 : 0;
-        off_out[i] = (int32_t)(o < 0 ? 0 : (o > n ? n : o));
-    }
-    nbad = gp_wave_sum_i(nbad);
-    if (gp_lane() == 0 && nbad) atomicAdd(status_out + ST_BAD_STATE, (unsigned long long)nbad);
-}
-
 __global__ void ls_status_kernel(const int64_t *__restrict__ running, int64_t *__restrict__ status_out) {
     const int i = threadIdx.x;
     if (i < ST_WORDS) status_out[i] = i <= ST_TOP_BATCH ? running[i] : 0;
 }
-
-size_t ls_state_bytes(int64_t n) {
-    GpCarver cv(nullptr, 0);
-    LsState s(cv, n);
-    return cv.off;
-}
-
-bool ls_n_ok(int64_t n) { return n > 0 && n < (1ll << 31); }
 
 }  // namespace
 

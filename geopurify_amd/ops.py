@@ -1684,12 +1684,14 @@ class LiftMasksLists:
 
 
 def lift_masks_batched_lists(points, view_entry, w2c, intrinsics, depth, image_hw, cut_bound, vis_thres, min_visible, max_visible, buffers=None,
-                             workspace=None, total=None):
+                             workspace=None, total=None, sizes=None):
     """The visible lists of all views of all entries: points f64 [n,4]; view_entry i64 [V]; w2c f64 [V,4,4]; intrinsics f64 [V,4]; depth
     f64 [V,H,W] or None; image_hw = (H, W).  -> LiftMasksLists.  Two calls of gp_lift_masks_batched_lists around ONE read-back (ops.readback
     of the counting call's status: the entries in all size the arrays); total: the count when the caller knows it already (no read-back,
-    max_views is None then).  buffers: optional dict of caller-owned outputs by attribute name (pt, x, y, view need total); workspace:
-    uint8 of at least gp_lift_masks_batched_lists_workspace_bytes(n, V)."""
+    max_views is None then).  sizes: a callable that takes the place of the read-back: called after the counting call with the dict of
+    view_off / view_count / view_keep / status, it returns (total, max_views) -- LiftMasksStream's, which reads its own sizes back and
+    may still name the entry arrays in buffers.  buffers: optional dict of caller-owned outputs by attribute name (pt, x, y, view need
+    total); workspace: uint8 of at least gp_lift_masks_batched_lists_workspace_bytes(n, V)."""
     lib = _lib.load()
     who = "lift_masks_batched_lists"
     _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c")
@@ -1716,8 +1718,11 @@ def lift_masks_batched_lists(points, view_entry, w2c, intrinsics, depth, image_h
     max_views = None
     if total is None:
         call(0, {})
-        sizes = readback(got["status"])
-        total, max_views = int(sizes[6]), int(sizes[7])
+        if sizes is None:
+            words = readback(got["status"])
+            total, max_views = int(words[6]), int(words[7])
+        else:
+            total, max_views = sizes(got)
     ent = {}
     if total > 0:
         ent = _outputs(who, {"pt": (torch.int64, (total,)), "x": (torch.int64, (total,)), "y": (torch.int64, (total,)),
@@ -1785,6 +1790,174 @@ def lift_masks_batched(points, view_entry, pred_masks, scores, taps, out_hw, ent
                                     _ptr(got["seen"]), _ptr(got["count"]), _ptr(got.get("nn")), _ptr(got["seg"]), _ptr(got["status"]), _ptr(ws),
                                     ws.numel(), _stream()), "gp_lift_masks_batched")
     return LiftMasksBatched(out, got["seen"], got["count"], got.get("nn"), got["seg"], got["status"])
+
+
+# ------------------------------------------------------------------------------------------ the same mask lift, the views in chunks
+class LiftMasksStreamState:
+    """What a resumable mask lift keeps between its calls besides the arrays that grow with the views (those are the caller's, see
+    lift_masks_stream_add): points f64 [n,4], state u8 (the entry tables and one view counter per entry: written by
+    gp_lift_masks_stream_begin, the counters advanced by gp_lift_masks_stream_add), status i64 [8] (the running words: bad batch rows, bad
+    view entries so far, non-finite rows, top batch, the most views of one entry, records, entries and counters that did not hold
+    together, positions beyond 65535)."""
+
+    def __init__(self, points, state, status):
+        self.points, self.state, self.status = points, state, status
+
+
+def lift_masks_stream_begin(points, buffers=None, workspace=None):
+    """gp_lift_masks_stream_begin, no sync: points f64 [n,4] -> LiftMasksStreamState.  buffers: optional dict of caller-owned state (uint8
+    of at least gp_lift_masks_stream_state_bytes(n)) / status; workspace: uint8 of at least gp_lift_masks_stream_begin_workspace_bytes(n)."""
+    lib = _lib.load()
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"lift_masks_stream_begin: expected points [n >= 1, 4], got {list(points.shape)}")
+    n, dev = points.shape[0], points.device
+    got = _outputs("lift_masks_stream_begin", {"status": (torch.int64, (8,))}, buffers, dev)
+    state = (buffers or {}).get("state")
+    state = _ws(lib.gp_lift_masks_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")
+    ws = _ws(lib.gp_lift_masks_stream_begin_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_masks_stream_begin(_ptr(points), n, _ptr(state), state.numel(), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()),
+          "gp_lift_masks_stream_begin")
+    return LiftMasksStreamState(points, state, got["status"])
+
+
+def lift_masks_stream_state_bytes(n):
+    return int(_lib.load().gp_lift_masks_stream_state_bytes(int(n)))
+
+
+def lift_masks_batched_lists_workspace_bytes(n, num_views):
+    return int(_lib.load().gp_lift_masks_batched_lists_workspace_bytes(int(n), int(num_views)))
+
+
+def lift_masks_stream_sizes_workspace_bytes(num_views):
+    return int(_lib.load().gp_lift_masks_stream_sizes_workspace_bytes(int(num_views)))
+
+
+def lift_masks_stream_add_workspace_bytes(n, num_views, Q, mask_hw, image_hw, total, fill_cap=None):
+    if fill_cap is None:
+        fill_cap = min(total, max(total // 4, 65536))
+    return int(_lib.load().gp_lift_masks_stream_add_workspace_bytes(int(n), int(num_views), int(Q), int(mask_hw[0]), int(mask_hw[1]),
+                                                                    int(image_hw[0]), int(image_hw[1]), int(total), int(fill_cap)))
+
+
+def lift_masks_stream_finish_workspace_bytes(n, num_views, total, words):
+    return int(_lib.load().gp_lift_masks_stream_finish_workspace_bytes(int(n), int(num_views), int(total), int(words)))
+
+
+def lift_masks_stream_sizes(st, view_entry, view_count, view_keep, buffers=None, workspace=None):
+    """gp_lift_masks_stream_sizes, no sync: a chunk's view_entry i64 [V] with the view_count i64 [V] / view_keep u8 [V] of
+    lift_masks_batched_lists' counting call -> sizes i64 [4] = (the chunk's visible entries, those of its kept views, the most views one
+    entry has once the chunk is added, 0).  st is not changed.  buffers: optional dict with a caller-owned sizes; workspace: uint8 of at
+    least gp_lift_masks_stream_sizes_workspace_bytes(V)."""
+    lib = _lib.load()
+    who = "lift_masks_stream_sizes"
+    _chk(view_entry, torch.int64, "view_entry"), _chk(view_count, torch.int64, "view_count"), _chk(view_keep, torch.uint8, "view_keep")
+    nv, n, dev = view_entry.shape[0], st.points.shape[0], st.points.device
+    if view_entry.dim() != 1 or view_count.shape != (nv,) or view_keep.shape != (nv,):
+        raise ValueError(f"{who}: expected view_entry, view_count, view_keep [V], got {list(view_entry.shape)}, {list(view_count.shape)}, "
+                         f"{list(view_keep.shape)}")
+    got = _outputs(who, {"sizes": (torch.int64, (4,))}, buffers, dev)
+    ws = _ws(lib.gp_lift_masks_stream_sizes_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_masks_stream_sizes(n, _ptr(st.state), st.state.numel(), _ptr(st.status), _ptr(view_entry), _ptr(view_count), _ptr(view_keep),
+                                         nv, _ptr(got["sizes"]), _ptr(ws), ws.numel(), _stream()), "gp_lift_masks_stream_sizes")
+    return got["sizes"]
+
+
+def lift_masks_stream_add(st, view_entry, pred_masks, scores, taps, out_hw, ent, view_off, view_keep, total, rec_row, rec_seg, rec_base, rec_off,
+                          view_pos, fill_cap=None, workspace=None):
+    """gp_lift_masks_stream_add, no sync: one chunk of views onto the LiftMasksStreamState st.  The chunk's arrays as
+    ops.lift_masks_batched takes them (view_entry i64 [V]; pred_masks f32 [V,Q,h,w]; scores f32 [V,Q]; taps; out_hw; ent = (pt, x, y,
+    view) and view_off i64 [V+1], view_keep u8 [V], total from lift_masks_batched_lists ON THE CHUNK).  What the caller keeps: rec_row /
+    rec_seg i32 [capacity] (the chunk's records go to rec_base ..), rec_off i64 [V+1] and view_pos i32 [V] (the chunk's slices of the
+    per-view arrays; rec_off[V] is the next chunk's rec_off[0]).  total = 0: nothing is visible in a kept view of the chunk -- pred_masks,
+    scores, ent, rec_row and rec_seg may be None, only view_pos, rec_off and the counters are written.  workspace: uint8 of at least
+    lift_masks_stream_add_workspace_bytes(...)."""
+    lib = _lib.load()
+    who = "lift_masks_stream_add"
+    _chk(view_entry, torch.int64, "view_entry"), _chk(view_off, torch.int64, "view_off"), _chk(view_keep, torch.uint8, "view_keep")
+    _chk(rec_off, torch.int64, "rec_off"), _chk(view_pos, torch.int32, "view_pos")
+    nv, n, dev, total = view_entry.shape[0], st.points.shape[0], st.points.device, int(total)
+    H, W = out_hw
+    if view_entry.dim() != 1 or view_off.shape != (nv + 1,) or view_keep.shape != (nv,) or rec_off.shape != (nv + 1,) or view_pos.shape != (nv,):
+        raise ValueError(f"{who}: expected view_entry [V], view_off [V + 1], view_keep [V], rec_off [V + 1], view_pos [V], got "
+                         f"{[list(t.shape) for t in (view_entry, view_off, view_keep, rec_off, view_pos)]}")
+    Q = h = w = 1
+    tx0 = twx = ty0 = twy = None
+    pt = x = y = view = None
+    cap = 0
+    if total:
+        _chk(pred_masks, torch.float32, "pred_masks"), _chk(scores, torch.float32, "scores")
+        _chk(rec_row, torch.int32, "rec_row"), _chk(rec_seg, torch.int32, "rec_seg")
+        tx0, twx, ty0, twy = taps
+        _chk(tx0, torch.int32, "tap_x0"), _chk(twx, torch.float32, "tap_wx"), _chk(ty0, torch.int32, "tap_y0"), _chk(twy, torch.float32, "tap_wy")
+        pt, x, y, view = ent
+        _chk(pt, torch.int64, "ent_pt"), _chk(x, torch.int64, "ent_x"), _chk(y, torch.int64, "ent_y"), _chk(view, torch.int32, "ent_view")
+        if pred_masks.dim() != 4 or pred_masks.shape[0] != nv or scores.shape != tuple(pred_masks.shape[:2]):
+            raise ValueError(f"{who}: expected pred_masks [{nv}, Q, h, w] and scores [{nv}, Q], got {list(pred_masks.shape)}, {list(scores.shape)}")
+        _, Q, h, w = pred_masks.shape
+        if tx0.shape != (W,) or twx.shape != (W, 4) or ty0.shape != (H,) or twy.shape != (H, 4):
+            raise ValueError(f"{who}: expected taps ([{W}], [{W}, 4], [{H}], [{H}, 4]), got {[list(t.shape) for t in taps]}")
+        if any(t.dim() != 1 or t.shape[0] < total for t in ent):
+            raise ValueError(f"{who}: expected four entry arrays of at least total = {total} elements, got {[list(t.shape) for t in ent]}")
+        if rec_row.dim() != 1 or rec_row.shape != rec_seg.shape:
+            raise ValueError(f"{who}: expected rec_row and rec_seg [capacity], got {list(rec_row.shape)}, {list(rec_seg.shape)}")
+        cap = rec_row.shape[0]
+    if fill_cap is None:
+        fill_cap = min(total, max(total // 4, 65536))
+    need = lib.gp_lift_masks_stream_add_workspace_bytes(n, nv, Q, h, w, int(H), int(W), total, int(fill_cap))
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_masks_stream_add(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(view_entry), nv, _ptr(pred_masks), Q, h, w,
+                                       _ptr(scores), _ptr(tx0), _ptr(twx), _ptr(ty0), _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y),
+                                       _ptr(view), _ptr(view_off), _ptr(view_keep), total, int(fill_cap), _ptr(rec_row), _ptr(rec_seg),
+                                       int(rec_base), max(cap, int(rec_base)), _ptr(rec_off), _ptr(view_pos), _ptr(st.status), _ptr(ws), ws.numel(),
+                                       _stream()), "gp_lift_masks_stream_add")
+
+
+class LiftMasksStreamFinish:
+    """What gp_lift_masks_stream_finish writes: out fp32 [n, d] (before the scene-level fill), seen u8 [n], count i32 [n], nn i64 [n] or
+    None, status i64 [8] = (bad batch rows, bad view entries, non-finite rows, top batch, seen rows, filled rows, values of the state, the
+    record offsets and the records that did not hold together, views whose position is beyond words x 64)."""
+
+    def __init__(self, out, seen, count, nn, status):
+        self.out, self.seen, self.count, self.nn, self.status = out, seen, count, nn, status
+
+
+def lift_masks_stream_finish(st, view_entry, view_pos, view_keep, rec_off, rec_row, rec_seg, total, words, f_seg, logit_seg, fill=True,
+                             buffers=None, workspace=None):
+    """gp_lift_masks_stream_finish, no sync: everything kept since lift_masks_stream_begin -> LiftMasksStreamFinish; nothing kept is
+    changed.  view_entry i64 [V], view_pos i32 [V], view_keep u8 [V], rec_off i64 [V+1] over ALL views added; rec_row / rec_seg i32 [>=
+    total]; total >= 1 records; words >= ceil(most views of one entry / 64); f_seg f32 [>= V, Q, d], logit_seg f32 [>= V, Q, C] in arrival
+    order (segment_tables; d a multiple of 4).  buffers: optional dict of caller-owned out (fp32 rows of a pitch that is a multiple of
+    4) / seen / count / nn / status; workspace: uint8 of at least lift_masks_stream_finish_workspace_bytes(n, V, total, words)."""
+    lib = _lib.load()
+    who = "lift_masks_stream_finish"
+    _chk(view_entry, torch.int64, "view_entry"), _chk(view_pos, torch.int32, "view_pos"), _chk(view_keep, torch.uint8, "view_keep")
+    _chk(rec_off, torch.int64, "rec_off"), _chk(rec_row, torch.int32, "rec_row"), _chk(rec_seg, torch.int32, "rec_seg")
+    _chk(f_seg, torch.float32, "f_seg"), _chk(logit_seg, torch.float32, "logit_seg")
+    nv, n, dev, total = view_entry.shape[0], st.points.shape[0], st.points.device, int(total)
+    if view_entry.dim() != 1 or view_pos.shape != (nv,) or view_keep.shape != (nv,) or rec_off.shape != (nv + 1,):
+        raise ValueError(f"{who}: expected view_entry, view_pos, view_keep [V] and rec_off [V + 1], got "
+                         f"{[list(t.shape) for t in (view_entry, view_pos, view_keep, rec_off)]}")
+    if total < 1 or rec_row.dim() != 1 or rec_seg.dim() != 1 or rec_row.shape[0] < total or rec_seg.shape[0] < total:
+        raise ValueError(f"{who}: expected rec_row and rec_seg of at least total = {total} >= 1 elements, got {list(rec_row.shape)}, "
+                         f"{list(rec_seg.shape)}")
+    if f_seg.dim() != 3 or logit_seg.dim() != 3 or f_seg.shape[0] < nv or logit_seg.shape[0] < nv or f_seg.shape[1] != logit_seg.shape[1]:
+        raise ValueError(f"{who}: expected f_seg [>= {nv}, Q, d] and logit_seg [>= {nv}, Q, C], got {list(f_seg.shape)}, {list(logit_seg.shape)}")
+    Q, d, C = f_seg.shape[1], f_seg.shape[2], logit_seg.shape[2]
+    want = {"seen": (torch.uint8, (n,)), "count": (torch.int32, (n,)), "status": (torch.int64, (8,))}
+    if fill:
+        want["nn"] = (torch.int64, (n,))
+    got = _outputs(who, want, buffers, dev)
+    out = (buffers or {}).get("out")
+    out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
+    need = lib.gp_lift_masks_stream_finish_workspace_bytes(n, nv, total, int(words))
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_masks_stream_finish(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(view_entry), _ptr(view_pos), _ptr(view_keep),
+                                          _ptr(rec_off), nv, _ptr(rec_row), _ptr(rec_seg), total, int(words), _ptr(f_seg), _ptr(logit_seg), Q, d, C,
+                                          _ptr(st.status), 1 if fill else 0, _ptr(out), out.stride(0), _ptr(got["seen"]), _ptr(got["count"]),
+                                          _ptr(got.get("nn")), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()),
+          "gp_lift_masks_stream_finish")
+    return LiftMasksStreamFinish(out, got["seen"], got["count"], got.get("nn"), got["status"])
 
 
 # ------------------------------------------------------------------------------------------ SURVEY 8f-1: training step

@@ -29,6 +29,14 @@ or, from the X-Decoder form of the VLM's outputs (masks, class logits, mask embe
     lifted = lift_masks(points, MaskViews(pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth,
                                           image_shape=(H, W)), text_embed, logit_scale)   # -> .features, .text_features (normalised)
 
+or, with the X-Decoder producing its outputs a batch of views at a time (the reference's own loop, :495-640), without ever holding
+more than one batch of masks:
+
+    stream = LiftMasksStream(points, text_embed, logit_scale)
+    for pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth in vlm_batches:
+        stream.add(MaskViews(pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth, image_shape=(H, W)))
+    lifted = stream.finish()                                    # the bits of lift_masks on all the views; add / finish may go on
+
 and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
 
     pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
@@ -53,6 +61,10 @@ LiftStream is the same lift resumable over chunks of views: ops.lift_stream_begi
 lift_masks is the reference's lift_xdecoder_features (models/affinity_module.py:455-714: per-view mask-embedding lift, in-view nearest
 fill, consensus top-3 fusion, scene-level fill) with the same mapping and drop rule, for all entries and any number of views per entry:
 ops.lift_masks_batched_lists (ordered visible lists), ops.segment_tables, ops.lift_masks_batched, ops.gather_rows; two read-backs.
+LiftMasksStream is the same lift resumable over chunks of views: ops.lift_masks_stream_begin (the entry tables and the per-entry view
+counters, once), per chunk ops.lift_masks_batched_lists around ops.lift_masks_stream_sizes (the one read-back), ops.segment_tables and
+ops.lift_masks_stream_add (segments and in-view fill over a chunk-sized workspace, one (row, segment) record per visible pair kept),
+ops.lift_masks_stream_finish (slot lists from the records, fusion, fill; a snapshot), ops.gather_rows.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -423,6 +435,80 @@ def _tap_tables(h, w, H, W, device):
     return _TAPS[key][0]
 
 
+def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vis_thres, min_visible, max_visible):
+    """lift_masks' argument checks, in lift_masks' order; views None: those of the points, the text and the options alone
+    (LiftMasksStream's construction).  -> (V, Q, h, w, H, W, C, D), or (C, D) without views"""
+    if views is not None and not isinstance(views, MaskViews):
+        raise ValueError(f"{who}: views must be a MaskViews, got {type(views).__name__}")
+    P = points
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    if views is not None:
+        Pm, Pl, Em = views.pred_masks, views.pred_logits, views.mask_embed
+        E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        if not torch.is_tensor(Pm) or Pm.dim() != 4 or min(Pm.shape) < 1 or Pm.dtype != torch.float32:
+            raise ValueError(f"{who}: views.pred_masks must be fp32 [V, Q, h, w] with V, Q, h, w >= 1, got "
+                             f"{(list(Pm.shape), Pm.dtype) if torch.is_tensor(Pm) else type(Pm).__name__}")
+        V, Q, h, w = Pm.shape
+        if V > 65535:
+            raise ValueError(f"{who}: {V} views, at most 65535")
+        if Q > MAX_QUERIES:
+            raise ValueError(f"{who}: {Q} queries per view, at most {MAX_QUERIES} (a view's scores are sorted in LDS)")
+    if not torch.is_tensor(text_embed) or text_embed.dim() != 2 or min(text_embed.shape) < 1 or not text_embed.dtype.is_floating_point:
+        raise ValueError(f"{who}: text_embed must be floating point [C, D] with C, D >= 1, got "
+                         f"{(list(text_embed.shape), text_embed.dtype) if torch.is_tensor(text_embed) else type(text_embed).__name__}")
+    C, D = text_embed.shape
+    if views is not None:
+        if not torch.is_tensor(Pl) or Pl.shape != (V, Q, C + 1) or not Pl.dtype.is_floating_point:
+            raise ValueError(f"{who}: views.pred_logits must be floating point [{V}, {Q}, {C + 1}] (C + 1 columns, the last \"no object\"), got "
+                             f"{(list(Pl.shape), Pl.dtype) if torch.is_tensor(Pl) else type(Pl).__name__}")
+        if not torch.is_tensor(Em) or Em.shape != (V, Q, D) or not Em.dtype.is_floating_point:
+            raise ValueError(f"{who}: views.mask_embed must be floating point [{V}, {Q}, {D}], got "
+                             f"{(list(Em.shape), Em.dtype) if torch.is_tensor(Em) else type(Em).__name__}")
+        if not _is_int_tensor(E) or E.shape != (V,):
+            raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
+                             f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+        if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
+            raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
+        if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
+            raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
+                             f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+        shape = () if views.image_shape is None else tuple(views.image_shape)
+        if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+            raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers (the size the masks are resized to), got "
+                             f"{views.image_shape!r}")
+        H, W = shape
+        if h > H or w > W:
+            raise ValueError(f"{who}: masks of {h} x {w} are larger than image_shape {H} x {W}: the bicubic-antialias resize is evaluated for "
+                             "up-sampling only")
+        if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
+            raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
+                             f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
+        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
+    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
+        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    if isinstance(logit_scale, bool) or not isinstance(logit_scale, (int, float)) or logit_scale != logit_scale:
+        raise ValueError(f"{who}: logit_scale={logit_scale!r} must be a number")
+    named = ([("views.pred_masks", Pm), ("views.pred_logits", Pl), ("views.mask_embed", Em)] if views is not None else []) + [("text_embed", text_embed)]
+    for name, t in named:
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
+                             "no_grad); detach them")
+    tensors = [P] + ([Pm, Pl, Em] if views is not None else []) + [text_embed] + ([E, M, K] + ([Dp] if Dp is not None else []) if views is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points, text_embed and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    return (V, Q, h, w, H, W, C, D) if views is not None else (C, D)
+
+
 def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
     """The reference's default lift, lift_xdecoder_features (models/affinity_module.py:455-714), for several scenes at once, entries
     never mixing and with no cap on the views of an entry.  points as for lift; views: a MaskViews; text_embed floating [C,D].  Per
@@ -451,70 +537,12 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
     the sizes after the counting pass (entries in all, the most views of an entry) and the status after the last launch (rows whose
     batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates: ValueError)."""
     who = "lift_masks"
-    if not isinstance(views, MaskViews):
-        raise ValueError(f"{who}: views must be a MaskViews, got {type(views).__name__}")
+    if views is None:
+        raise ValueError(f"{who}: views must be a MaskViews, got NoneType")
+    V, Q, h, w, H, W, C, D = _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vis_thres, min_visible, max_visible)
     P, Pm, Pl, Em = points, views.pred_masks, views.pred_logits, views.mask_embed
     E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
-    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
-        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
-    if P.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
     n = P.shape[0]
-    if n == 0 or n >= 2 ** 31:
-        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
-    if not torch.is_tensor(Pm) or Pm.dim() != 4 or min(Pm.shape) < 1 or Pm.dtype != torch.float32:
-        raise ValueError(f"{who}: views.pred_masks must be fp32 [V, Q, h, w] with V, Q, h, w >= 1, got "
-                         f"{(list(Pm.shape), Pm.dtype) if torch.is_tensor(Pm) else type(Pm).__name__}")
-    V, Q, h, w = Pm.shape
-    if V > 65535:
-        raise ValueError(f"{who}: {V} views, at most 65535")
-    if Q > MAX_QUERIES:
-        raise ValueError(f"{who}: {Q} queries per view, at most {MAX_QUERIES} (a view's scores are sorted in LDS)")
-    if not torch.is_tensor(text_embed) or text_embed.dim() != 2 or min(text_embed.shape) < 1 or not text_embed.dtype.is_floating_point:
-        raise ValueError(f"{who}: text_embed must be floating point [C, D] with C, D >= 1, got "
-                         f"{(list(text_embed.shape), text_embed.dtype) if torch.is_tensor(text_embed) else type(text_embed).__name__}")
-    C, D = text_embed.shape
-    if not torch.is_tensor(Pl) or Pl.shape != (V, Q, C + 1) or not Pl.dtype.is_floating_point:
-        raise ValueError(f"{who}: views.pred_logits must be floating point [{V}, {Q}, {C + 1}] (C + 1 columns, the last \"no object\"), got "
-                         f"{(list(Pl.shape), Pl.dtype) if torch.is_tensor(Pl) else type(Pl).__name__}")
-    if not torch.is_tensor(Em) or Em.shape != (V, Q, D) or not Em.dtype.is_floating_point:
-        raise ValueError(f"{who}: views.mask_embed must be floating point [{V}, {Q}, {D}], got "
-                         f"{(list(Em.shape), Em.dtype) if torch.is_tensor(Em) else type(Em).__name__}")
-    if not _is_int_tensor(E) or E.shape != (V,):
-        raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
-                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-    if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
-        raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
-    if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
-        raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
-                         f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
-    shape = () if views.image_shape is None else tuple(views.image_shape)
-    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-        raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers (the size the masks are resized to), got "
-                         f"{views.image_shape!r}")
-    H, W = shape
-    if h > H or w > W:
-        raise ValueError(f"{who}: masks of {h} x {w} are larger than image_shape {H} x {W}: the bicubic-antialias resize is evaluated for "
-                         "up-sampling only")
-    if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
-        raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
-                         f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
-    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
-        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
-    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
-        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
-    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
-        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
-    if isinstance(logit_scale, bool) or not isinstance(logit_scale, (int, float)) or logit_scale != logit_scale:
-        raise ValueError(f"{who}: logit_scale={logit_scale!r} must be a number")
-    for name, t in (("views.pred_masks", Pm), ("views.pred_logits", Pl), ("views.mask_embed", Em), ("text_embed", text_embed)):
-        if t.requires_grad:
-            raise ValueError(f"{who}: {name} require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
-                             "no_grad); detach them")
-    tensors = [P, Pm, Pl, Em, text_embed, E, M, K] + ([Dp] if Dp is not None else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points, text_embed and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
     dev = P.device
     with torch.cuda.device(dev), torch.no_grad():
         pts = P.detach().to(torch.float64).contiguous()
@@ -560,6 +588,206 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
     if lists.total and (st[6] or st[7]):
         raise RuntimeError(f"{who}: the visible lists do not hold together ({st[6]} entries, {st[7]} views): the inputs changed during the call")
     return LiftedMasks(feats, seen, count, lists.view_count, lists.view_keep.bool(), text_norm, logit_scale)
+
+
+MAX_RECORDS = 2 ** 31 - 2                                   # gp_lift_masks_batched's limit on the visible entries of one call
+
+
+def _grown(t, used, need, shape_tail, dtype, device, most=None):
+    """a buffer of at least `need` leading rows that keeps the first `used` of t: t itself while it is large enough, otherwise one of
+    max(need, twice the rows of t) rows (at most `most`) -- geometric, so a stream copies every row O(1) times"""
+    if t is not None and t.shape[0] >= need:
+        return t
+    rows = need if t is None else max(need, 2 * t.shape[0])
+    if most is not None:
+        rows = min(rows, most)
+    new = torch.empty((rows,) + tuple(shape_tail), dtype=dtype, device=device)
+    if t is not None and used:
+        new[:used] = t[:used]
+    return new
+
+
+class LiftMasksStream:
+    """lift_masks with the views arriving in chunks -- the reference's own loop (models/affinity_module.py:495-640: the X-Decoder runs on
+    one view, the view's masks become per-point segments, only the small per-point record survives in point_info and the masks are
+    freed; the fusion :647-686 alone looks across views), for several scenes at once.  Only one chunk's masks need to exist at a time:
+
+        stream = LiftMasksStream(points, text_embed, logit_scale)
+        for chunk in vlm_chunks:                                # a MaskViews: views of any entries, any number of them
+            stream.add(chunk)                                   # one read-back: the chunk's sizes
+        lifted = stream.finish()                                # -> LiftedMasks; the one status read-back
+
+    points, text_embed, logit_scale and the options are lift_masks'; every chunk is a MaskViews as lift_masks takes it.
+      1. After any sequence of add calls, finish(fill=f) returns what lift_masks(points, MaskViews(the chunks concatenated in the order
+         added), text_embed, logit_scale, fill=f, ...) returns, bit for bit in features, seen, count, view_count, view_keep and
+         text_features (the view fields in arrival order).
+      2. An entry's views are taken in their order of arrival; a chunk may hold views of any entries.  The slot order of lift_masks'
+         rule 6 ("ascending view index", the earlier slot among equal logits) is arrival order inside the entry, which is what
+         lift_masks sees on the concatenation.  view_keep follows from a view's own count, so it is final when the chunk is added.
+      3. finish is a snapshot: it writes new tensors and changes nothing the stream keeps, so add and finish may go on alternating.
+      4. After add returns the stream holds nothing of the size of the masks (Q x h x w per view).  It keeps: per point the entry
+         tables, written once at construction; per view its entry, count, keep flag, record offset and position inside its entry, and
+         its rows of the segment tables f_seg [Q, D padded to 4] and logit_seg [Q, C] (ops.segment_tables on the chunk); per visible
+         (point, kept view) pair one record (row i32, segment i32 or -1 after the in-view fill), view-major, rows ascending inside a
+         view; one view counter per entry in the state; and scratch -- add's workspaces, reused and grown to the largest chunk seen.
+         The growing buffers double, so finish concatenates nothing.  A chunk in which no kept view sees anything stores its per-view
+         fields alone (its table rows are reserved and never read).
+      5. add makes exactly ONE read-back, the counterpart of lift_masks' first: the chunk's visible entries (they size add's
+         workspace), those of its kept views (the records it appends) and the most views of one entry so far (the bit set's words in
+         finish).  finish makes exactly ONE, the status.  An add without a read-back would have to reserve records for the worst case,
+         every point in every view; that is out of scope.
+      6. text_embed and logit_scale are fixed at construction; the text is normalised once and returned as text_features.
+    Why the bits are lift_masks': visibility and the drop rule, the score sort and the ordered transpose, the segment decision and the
+    in-view fill are per view and read no other view -- the chunk goes through lift_masks' own kernels, over a workspace sized by the
+    chunk.  The fusion kernel reads a point's slots (view, segment) in ascending position inside the entry with that view's table rows;
+    finish rebuilds exactly those lists from the records (the same bit set and popcount kernels) and runs the same fusion and fill.
+    Inside: ops.lift_masks_stream_begin at construction; per chunk ops.lift_masks_batched_lists (its counting call, then
+    ops.lift_masks_stream_sizes in place of its read-back, then its writing call), ops.segment_tables, ops.lift_masks_stream_add; in
+    finish ops.lift_masks_stream_finish and ops.gather_rows.
+    ValueError before any kernel of the call: lift_masks' refusals, for points, text and options at construction and for the chunk at
+    add; a chunk whose Q, (h, w), image_shape or presence of depth differ from the first chunk's (another C, D or device is lift_masks'
+    own refusal against the text and the points); a chunk that takes the views past 65535 in all; finish before any add.  After the
+    chunk's read-back, before anything is changed: records past 2^31 - 2 in all (lift_masks' limit on the visible entries).  A refused
+    add leaves the stream as it was.  From finish's read-back, with lift_masks' messages and precedence: non-finite rows, rows whose
+    batch index is no integer in 0..65535 (both counted once, at construction), views whose entry is outside 0..65535 (counted over all
+    chunks).  RuntimeError from the same read-back: the state, the per-view arrays or the records hold values outside their range or
+    do not hold together, i.e. somebody wrote into what the stream keeps; the kernels force them into range or leave them out first.
+    No gradients, as for lift_masks."""
+
+    def __init__(self, points, text_embed, logit_scale, *, cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None):
+        who = "LiftMasksStream"
+        C, D = _check_lift_masks(who, points, None, text_embed, logit_scale, cut_bound, vis_thres, min_visible, max_visible)
+        self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = cut_bound, vis_thres, min_visible, max_visible
+        self.logit_scale, self.num_classes, self.feature_dim = logit_scale, C, D
+        self.num_views = self.num_records = self.most_views = 0
+        self._points, self._text, self._device = points, text_embed, points.device
+        self._first = None                                      # (Q, (h, w), (H, W), depth present) of the first chunk
+        self._view_entry = self._view_count = self._view_keep = self._view_pos = self._rec_off = None
+        self._f_seg = self._l_seg = self._rec_row = self._rec_seg = None
+        self._ws = {}                                           # add's and finish's workspaces by name
+        dev = self._device
+        with torch.cuda.device(dev), torch.no_grad():
+            self._st = ops.lift_masks_stream_begin(points.detach().to(torch.float64).contiguous())
+            self.text_features = torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
+            self._d4 = _pad_to(D, 4)
+            self._text4 = torch.zeros((C, self._d4), dtype=torch.float32, device=dev)
+            self._text4[:, :D] = self.text_features
+
+    def _workspace(self, name, need):
+        ws = self._ws.get(name)
+        if ws is None or ws.numel() < need:
+            self._ws[name] = None                               # (freed before the larger one is taken)
+            ws = self._ws[name] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=self._device)
+        return ws
+
+    def add(self, views):
+        """One chunk of views (a MaskViews).  One host synchronisation (the read-back of the chunk's sizes)."""
+        who = "LiftMasksStream.add"
+        if views is None:
+            raise ValueError(f"{who}: views must be a MaskViews, got NoneType")
+        V, Q, h, w, H, W, C, D = _check_lift_masks(who, self._points, views, self._text, self.logit_scale, self.cut_bound, self.vis_thres,
+                                                   self.min_visible, self.max_visible)
+        this = (Q, (h, w), (H, W), views.depth is not None)
+        if self._first is not None:
+            for name, a, b in zip(("Q", "(h, w)", "image_shape", "the presence of depth"), this, self._first):
+                if a != b:
+                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
+        V0, R0 = self.num_views, self.num_records
+        if V0 + V > 65535:
+            raise ValueError(f"{who}: {V} more views after {V0}, at most 65535 in all")
+        Pm, Pl, Em = views.pred_masks, views.pred_logits, views.mask_embed
+        E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        n, dev, st, d4 = self._points.shape[0], self._device, self._st, self._d4
+        with torch.cuda.device(dev), torch.no_grad():
+            ve = E.detach().to(torch.int64).contiguous()
+            found, bufs = {}, {}
+
+            def sizes(got):
+                """in place of lift_masks_batched_lists' read-back: the stream's sizes, and the entry arrays out of the scratch"""
+                s = ops.readback(ops.lift_masks_stream_sizes(st, ve, got["view_count"], got["view_keep"],
+                                                             workspace=self._workspace("sizes", ops.lift_masks_stream_sizes_workspace_bytes(V))))
+                total, kept, most = int(s[0]), int(s[1]), int(s[2])
+                if R0 + kept > MAX_RECORDS:
+                    raise ValueError(f"{who}: {kept} more visible (point, kept view) pairs after {R0}, at most 2^31 - 2 in all")
+                found.update(total=total if kept else 0, kept=kept, most=most)
+                if found["total"]:
+                    pitch = _pad_to(total, 32)                  # (8-byte elements stay 256-byte aligned)
+                    ent = self._workspace("entries", 28 * pitch)
+                    for i, name in enumerate(("pt", "x", "y")):
+                        bufs[name] = ent[8 * pitch * i:8 * pitch * i + 8 * total].view(torch.int64)
+                    bufs["view"] = ent[24 * pitch:24 * pitch + 4 * total].view(torch.int32)
+                return found["total"], most
+
+            lists = ops.lift_masks_batched_lists(st.points, ve, M.detach().contiguous(), K.detach().contiguous(),
+                                                 None if Dp is None else Dp.detach().contiguous(), (H, W), self.cut_bound, float(self.vis_thres),
+                                                 self.min_visible, 2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1),
+                                                 buffers=bufs, workspace=self._workspace("lists", ops.lift_masks_batched_lists_workspace_bytes(n, V)),
+                                                 sizes=sizes)
+            total, kept = found["total"], found["kept"]
+            # nothing of the stream has changed so far; from here on nothing is refused
+            used = V0 + 1 if V0 else 0
+            self._view_entry = _grown(self._view_entry, V0, V0 + V, (), torch.int64, dev)
+            self._view_count = _grown(self._view_count, V0, V0 + V, (), torch.int64, dev)
+            self._view_keep = _grown(self._view_keep, V0, V0 + V, (), torch.uint8, dev)
+            self._view_pos = _grown(self._view_pos, V0, V0 + V, (), torch.int32, dev)
+            self._rec_off = _grown(self._rec_off, used, V0 + V + 1, (), torch.int64, dev)
+            self._f_seg = _grown(self._f_seg, V0, V0 + V, (Q, d4), torch.float32, dev)
+            self._l_seg = _grown(self._l_seg, V0, V0 + V, (Q, C), torch.float32, dev)
+            self._view_entry[V0:V0 + V], self._view_count[V0:V0 + V], self._view_keep[V0:V0 + V] = ve, lists.view_count, lists.view_keep
+            pm = scores = taps = None
+            if total:
+                self._rec_row = _grown(self._rec_row, R0, R0 + kept, (), torch.int32, dev, most=MAX_RECORDS)
+                self._rec_seg = _grown(self._rec_seg, R0, R0 + kept, (), torch.int32, dev, most=MAX_RECORDS)
+                pm = Pm.detach().contiguous()
+                scores = torch.softmax(Pl.detach().float(), dim=-1)[..., :-1].max(-1).values.contiguous()
+                taps = _tap_tables(h, w, H, W, dev)
+                emb = torch.zeros((V * Q, d4), dtype=torch.float32, device=dev)
+                emb[:, :D] = Em.detach().float().reshape(V * Q, D)
+                f_seg, l_seg = self._f_seg[V0:V0 + V].view(V * Q, d4), self._l_seg[V0:V0 + V].view(V * Q, C)
+                for r0 in range(0, V * Q, _TABLE_ROWS):
+                    r1 = min(r0 + _TABLE_ROWS, V * Q)
+                    ops.segment_tables(emb[r0:r1], self._text4, float(self.logit_scale), f_seg[r0:r1], l_seg[r0:r1])
+            need = ops.lift_masks_stream_add_workspace_bytes(n, V, Q if total else 1, (h, w) if total else (1, 1), (H, W), total)
+            ops.lift_masks_stream_add(st, ve, pm, scores, taps, (H, W), (lists.pt, lists.x, lists.y, lists.view), lists.view_off, lists.view_keep,
+                                      total, self._rec_row, self._rec_seg, R0, self._rec_off[V0:V0 + V + 1], self._view_pos[V0:V0 + V],
+                                      workspace=self._workspace("add", need))
+        self._first = this
+        self.num_views, self.num_records, self.most_views = V0 + V, R0 + kept, max(self.most_views, found["most"])
+
+    def finish(self, fill=True):
+        """-> LiftedMasks over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
+        who = "LiftMasksStream.finish"
+        if self._first is None:
+            raise ValueError(f"{who}: no views were added")
+        n, D, d4, dev, V, R = self._points.shape[0], self.feature_dim, self._d4, self._device, self.num_views, self.num_records
+        with torch.cuda.device(dev), torch.no_grad():
+            if R == 0:
+                feats = torch.zeros((n, D), dtype=torch.float32, device=dev)
+                seen, count = torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+                status = self._st.status
+            else:
+                words = max(1, -(-self.most_views // 64))
+                r = ops.lift_masks_stream_finish(self._st, self._view_entry[:V], self._view_pos[:V], self._view_keep[:V], self._rec_off[:V + 1],
+                                                 self._rec_row, self._rec_seg, R, words, self._f_seg, self._l_seg, fill=bool(fill),
+                                                 workspace=self._workspace("finish", ops.lift_masks_stream_finish_workspace_bytes(n, V, R, words)))
+                feats = r.out
+                if fill:
+                    feats = ops.gather_rows(r.out, d4, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
+                feats = feats[:, :D].contiguous() if d4 != D else feats
+                seen, count, status = r.seen.bool(), r.count, r.status
+            view_count, view_keep = self._view_count[:V].clone(), self._view_keep[:V].bool()
+            st = ops.readback(status)
+        bad_batch, bad_view, nonfinite = st[:3]
+        if nonfinite:
+            raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+        if bad_batch:
+            raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+        if bad_view:
+            raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+        if st[6] or st[7]:
+            raise RuntimeError(f"{who}: what the stream keeps does not hold together ({st[6]} values of the state, the offsets or the records, "
+                               f"{st[7]} view positions): it was overwritten, or the inputs changed during an add")
+        return LiftedMasks(feats, seen, count, view_count, view_keep, self.text_features, self.logit_scale)
 
 
 def _voxel_size(quantization_size, like):

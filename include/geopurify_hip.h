@@ -973,6 +973,79 @@ int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_e
                           float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg, int64_t *status,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* gp_lift_masks_batched, RESUMABLE: the views arrive in chunks, every chunk's masks are read once, and   */
+/* after any number of chunks the result is the bits of gp_lift_masks_batched on the concatenation of the */
+/* chunks in the order added.  Only the relative order of an entry's views matters, and that is the order */
+/* of arrival.  The caller owns, between the calls: state (gp_lift_masks_stream_state_bytes(n): the       */
+/* points' entry tables and one view counter per entry), the running status i64 [8], and what grows with  */
+/* the views -- per view its entry i64, position inside its entry i32 (-1: the view has no entry), keep   */
+/* u8 and record offset i64 [views + 1], its rows of f_seg / logit_seg (gp_segment_tables) -- and with    */
+/* the visible (point, kept view) pairs: one record (rec_row i32, rec_seg i32 or -1) each, view-major,    */
+/* rows ascending inside a view.  Nothing of the size of the masks is kept.                                */
+/*                                                                                                        */
+/* gp_lift_masks_stream_begin: before the view loop of models/affinity_module.py:495-640.  The entry      */
+/* tables into state, the counters 0; status [0] rows whose batch index is no integer in 0..65535, [2]    */
+/* rows with a non-finite value, [3] the highest valid batch index, the others 0.                         */
+/*                                                                                                        */
+/* gp_lift_masks_stream_sizes: what the caller's one read-back per chunk carries, after the counting call */
+/* of gp_lift_masks_batched_lists on the chunk (view_count, view_keep): sizes i64 [4] = the chunk's        */
+/* visible entries, those of its kept views (the records the chunk appends), the most views one entry has */
+/* once the chunk is added (= 64 x words of finish, rounded up), 0.  It changes nothing.                   */
+/*                                                                                                        */
+/* gp_lift_masks_stream_add: models/affinity_module.py:495-640 for the nviews views of this chunk, of any */
+/* entries, from the chunk's visible lists (gp_lift_masks_batched_lists: total entries, view_off, keep):   */
+/*   view_pos i32 [nviews]: counter of the view's entry + its rank among the chunk's views of that entry  */
+/*     in ascending chunk index; the counters advance; status[4] = the most views of one entry so far;    */
+/*   the checked entries, score sort, ordered transpose, segment decision and in-view fill of              */
+/*     gp_lift_masks_batched over a workspace sized by the chunk;                                          */
+/*   rec_off i64 [nviews + 1] = rec_base + the records of the chunk's kept views before each view;         */
+/*     rec_row / rec_seg [rec_base ..): the records (an entry the checks replaced: row -1); nothing is    */
+/*     written at or beyond rec_cap;                                                                      */
+/*   status[1] += views whose entry is outside 0..65535, [5] += records, [6] += entries that are not what */
+/*     the lists promise and counters that lay outside 0..65535.                                          */
+/* total = 0 (nothing visible in the chunk; the masks, entry arrays and records may be null) advances the */
+/* counters and writes view_pos and rec_off alone.  It does not synchronise.                               */
+/*                                                                                                        */
+/* gp_lift_masks_stream_finish: the fusion and the fill, models/affinity_module.py:647-714, over all views */
+/* added so far (nviews, total records, words >= ceil(most views of one entry / 64)).  Reads everything   */
+/* kept and changes none of it, so it may be called after every chunk.  out, seen, count, nn: as          */
+/* gp_lift_masks_batched.  status_out i64 [8]: [0]..[3] the running status, [4] seen rows, [5] filled     */
+/* rows, [6] the running [6] + values of state, record offsets and records that lay outside their range   */
+/* or do not hold together (entry tables; offsets that do not ascend from 0 to total; a record of a view  */
+/* that is not kept, with a row outside 0..n-1, of another entry than its view's or not ascending inside  */
+/* the view; a segment outside -1..q-1), [7] views of an entry whose position is outside 0..64 x words-1. */
+/* All of them are forced into range or left out first: nothing is read or written outside the extents    */
+/* whatever the kept arrays hold.                                                                         */
+/* 1 <= n < 2^31, 1 <= nviews <= 65535 (per chunk in add, in all in finish), 1 <= q <= 1024, records in  */
+/* all < 2^31 - 1.  No output may overlap an input or another output (GP_EINVAL).                         */
+size_t gp_lift_masks_stream_state_bytes(int64_t n);
+size_t gp_lift_masks_stream_begin_workspace_bytes(int64_t n);
+int gp_lift_masks_stream_begin(const double *points, int64_t n, void *state, size_t state_bytes, int64_t *status,
+                               void *workspace, size_t workspace_bytes, void *stream);
+size_t gp_lift_masks_stream_sizes_workspace_bytes(int32_t nviews);
+int gp_lift_masks_stream_sizes(int64_t n, const void *state, size_t state_bytes, const int64_t *status,
+                               const int64_t *view_entry, const int64_t *view_count, const uint8_t *view_keep, int32_t nviews,
+                               int64_t *sizes, void *workspace, size_t workspace_bytes, void *stream);
+size_t gp_lift_masks_stream_add_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
+                                                int32_t out_w, int64_t total, int64_t fill_cap);
+int gp_lift_masks_stream_add(const double *points, int64_t n, void *state, size_t state_bytes, const int64_t *view_entry,
+                             int32_t nviews, const float *pred_masks, int32_t q, int32_t h, int32_t w, const float *scores,
+                             const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0, const float *tap_wy,
+                             int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y,
+                             const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep, int64_t total,
+                             int64_t fill_cap, int32_t *rec_row, int32_t *rec_seg, int64_t rec_base, int64_t rec_cap,
+                             int64_t *rec_off, int32_t *view_pos, int64_t *status, void *workspace, size_t workspace_bytes,
+                             void *stream);
+size_t gp_lift_masks_stream_finish_workspace_bytes(int64_t n, int32_t nviews, int64_t total, int32_t words);
+int gp_lift_masks_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes,
+                                const int64_t *view_entry, const int32_t *view_pos, const uint8_t *view_keep,
+                                const int64_t *rec_off, int32_t nviews, const int32_t *rec_row, const int32_t *rec_seg,
+                                int64_t total, int32_t words, const float *f_seg, const float *logit_seg, int32_t q, int32_t d,
+                                int32_t c, const int64_t *status, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
+                                int32_t *count, int64_t *nn, int64_t *status_out, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
 #ifdef __cplusplus
 }
 #endif
