@@ -205,6 +205,11 @@ SIGNATURES = {
     "gp_lift_masks_stream_finish_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64, c_int32]),
     "gp_lift_masks_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, _P, _P, c_int32, _P, _P, c_int64, c_int32, _P, _P, c_int32,
                                               c_int32, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_render_depth_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_render_depth_batched": (c_int32, [_P, c_int64, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
+    "gp_render_depth_batched_state_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_render_depth_batched_state": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                                c_size_t, _P]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 // Device functions shared by the per-scene kernels (voxelize.hip, lift.hip) and the batched lift (lift_batched.hip): the point ->
-// pixel mapping with its visibility decision and the bilinear tap of the LSeg resize.  One definition, so both paths take the same
-// decision and the same bits.
+// pixel mapping with its visibility decision, the z-buffer's decision (voxelize.hip, render_depth_batched.hip) and the bilinear tap
+// of the LSeg resize.  One definition, so both paths take the same decision and the same bits.
 #pragma once
 #include "gp_common.h"
 
@@ -35,6 +35,24 @@ __device__ __forceinline__ bool project_point(double x, double y, double z, cons
         inside = inside && (p2 > 0.0);
     }
     return inside;
+}
+
+
+// one point into the z-buffer of one view (fusion_util.py:126-130, depth given as a str): the pixel it lands in and its camera depth
+// p2, true when it projects inside the cut bound with p2 > 0.2 -- the points whose minimum p2 is the pixel's rendered depth
+__device__ __forceinline__ bool render_point(double x, double y, double z, const double *m0, const double *m1, const double *m2,
+                                             double fx, double fy, double cx, double cy, int W, int H, int cut, long long &ui,
+                                             long long &vi, double &p2) {
+    double p0 = dot4_blas(m0, x, y, z), p1 = dot4_blas(m1, x, y, z);
+    p2 = dot4_blas(m2, x, y, z);
+    double u = (p0 * fx) / p2 + cx;
+    double v = (p1 * fy) / p2 + cy;
+    double ur = rint(u), vr = rint(v);
+    bool finite = (fabs(ur) < 9.0e15) && (fabs(vr) < 9.0e15);      // also false for NaN
+    ui = finite ? (long long)ur : -1;
+    vi = finite ? (long long)vr : -1;
+    bool inside = finite && ui >= cut && vi >= cut && ui < (long long)W - cut && vi < (long long)H - cut;
+    return inside && p2 > 0.2;
 }
 
 

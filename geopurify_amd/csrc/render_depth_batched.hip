@@ -1,0 +1,207 @@
+// Rendered depth over BATCHED point clouds (geopurify_amd/sparse.py: render_depth, and depth="render" in lift, LiftStream, lift_masks and
+// LiftMasksStream): the z-buffer of models/utils/fusion_util.py:126-130 -- the ScanNet mapper with depth given as a str -- for every
+// view of every batch entry in one sequence of launches,
+//     depth[v, r, c] = min p_z over the points of view v's entry that project to pixel (r, c) inside the cut bound with p_z > 0.2,
+//                      999999 where no such point lands
+// with the arithmetic of render_depth_kernel (voxelize.hip: gp_render_depth_f64, one scene and one view per call); the decision is
+// render_point of gp_project.h, the one definition both kernels run.  Entries never mix: a view renders the rows of its own entry only.
+//
+// Structure: (1) the entry tables -- gp_render_depth_batched sorts the rows stably by entry with the kernels of gp_lift_entries.h
+// (lb_row_keys_kernel, the rocPRIM radix sort on 17-bit keys, lb_offsets_kernel), the same notion of "an entry's rows" as the lifts;
+// gp_render_depth_batched_state takes them from a stream's state (gp_lift_stream_begin / gp_lift_masks_stream_begin) through
+// ls_tables_kernel, every value forced into its range, and sorts nothing; (2) the whole [V, H, W] buffer filled with 999999 by 16-byte
+// stores (a scalar head and tail where the buffer starts or ends off a 16-byte boundary); (3) the z-buffer: blockIdx.y = view, a view's
+// blocks stride the sorted rows of its entry (lb_counts_kernel's launch shape), one 64-bit unsigned atomicMin on the fp64 bit pattern
+// per rendered point.  Positive doubles order like their bit patterns and a minimum does not depend on the order of its operands, so
+// two calls give the same bits and the bits are the sequential loop's.
+//
+// Bounds: a view's entry is range-checked before the offset table is read (0..65535; the table holds 65538 words) -- a view outside
+// touches nothing, its image stays 999999, and it is counted in status[1]; sorted positions come from the offset table (inside 0..n
+// by construction of the lower bounds, or forced there by ls_tables_kernel together with the row numbers); a row is rendered only when
+// its own batch column names the view's entry, so rows with a bad batch index are never rendered and a state that was overwritten
+// cannot mix entries; a pixel is written only after render_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0.  All
+// offsets are 64-bit.
+#include "gp_lift_stream_state.h"
+
+namespace {
+
+constexpr double RD_FAR = 999999.0;                              // fusion_util.py:127: the depth of a pixel nothing lands in
+constexpr unsigned RD_VIEW_BLOCKS = 64;                          // blocks of 256 threads per view: lb_counts_kernel's launch shape
+constexpr int64_t RD_FILL_BLOCKS = 16384;
+
+struct RdWork {                                                  // gp_render_depth_batched: the entry tables and the sort's scratch
+    uint32_t *k0, *k1;
+    int32_t *r0, *entry_rows, *entry_off;
+    char *tmp;
+    size_t tmp_bytes;
+    RdWork(GpCarver &cv, int64_t n) {
+        tmp_bytes = lb_sort_bytes(n);
+        k0 = cv.take<uint32_t>(n);
+        k1 = cv.take<uint32_t>(n);
+        r0 = cv.take<int32_t>(n);
+        entry_rows = cv.take<int32_t>(n);
+        entry_off = cv.take<int32_t>(LB_TABLE);
+        tmp = cv.take<char>(tmp_bytes);
+    }
+};
+
+struct RdStateWork {                                             // gp_render_depth_batched_state: the checked copies of the state's tables
+    uint32_t *keys;
+    int32_t *rows, *off;
+    RdStateWork(GpCarver &cv, int64_t n) {
+        keys = cv.take<uint32_t>(n);
+        rows = cv.take<int32_t>(n);
+        off = cv.take<int32_t>(LB_TABLE);
+    }
+};
+
+// depth f64 [total], 8-byte aligned: 999999 everywhere, two values per store from the first 16-byte boundary on
+__global__ void __launch_bounds__(256) rd_fill_kernel(double *__restrict__ depth, int64_t total) {
+    const int64_t head = (reinterpret_cast<uintptr_t>(depth) & 15) ? 1 : 0;
+    const int64_t pairs = (total - head) >> 1;
+    double2 *d2 = reinterpret_cast<double2 *>(depth + head);
+    const double2 far2 = make_double2(RD_FAR, RD_FAR);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < pairs; i += (int64_t)gridDim.x * blockDim.x) d2[i] = far2;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (head) depth[0] = RD_FAR;
+        if ((total - head) & 1) depth[total - 1] = RD_FAR;
+    }
+}
+
+// blockIdx.y = view; the blocks of a view stride the sorted rows of its entry.  entry_rows / entry_off hold values inside 0..n-1 /
+// 0..n (the sort's, or ls_tables_kernel's copies).
+__global__ void __launch_bounds__(256) rd_zbuffer_kernel(const double *__restrict__ points, const int32_t *__restrict__ entry_rows,
+                                                         const int32_t *__restrict__ entry_off, const int64_t *__restrict__ view_entry,
+                                                         const double *__restrict__ w2c, const double *__restrict__ intr, int W, int H, int cut,
+                                                         double *__restrict__ depth, unsigned long long *__restrict__ status) {
+    const int v = blockIdx.y;
+    const int64_t e = view_entry[v];
+    if ((uint64_t)e >= (uint64_t)LB_MAX_ENTRIES) {                   // (block-uniform) no entry: nothing is touched
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(status + ST_BAD_VIEW, 1ull);
+        return;
+    }
+    const int64_t r0 = entry_off[e], r1 = entry_off[e + 1];
+    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
+    unsigned long long *dv = reinterpret_cast<unsigned long long *>(depth + (int64_t)v * W * H);
+    for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r1; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *P = points + (int64_t)entry_rows[i] * 4;
+        if (lb_entry_of(P[0]) != (int)e) continue;
+        long long ui, vi;
+        double p2;
+        if (!render_point(P[1], P[2], P[3], M, M + 4, M + 8, fx, fy, cx, cy, W, H, cut, ui, vi, p2)) continue;
+        // p2 > 0.2: ordered like the doubles.  (A plain load of the pixel that skips the atomic when p2 is not smaller measured 9 %
+        // slower at 4 x 150 000 points and 100 views of 240 x 320, DESIGN.md 5.15: every point goes to the atomic.)
+        atomicMin(dv + (vi * W + ui), (unsigned long long)__double_as_longlong(p2));
+    }
+}
+
+int rd_check(const char *who, const double *points, int64_t n, const int64_t *view_entry, const double *w2c, const double *intrinsics,
+             int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, const double *depth, const int64_t *status,
+             const void *workspace) {
+    GP_CHECK_ARG(points && view_entry && w2c && intrinsics && depth && status && workspace, "%s: null argument", who);
+    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
+    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "%s: %d views outside 1..65535", who, nviews);
+    GP_CHECK_ARG(height >= 1 && width >= 1, "%s: image %d x %d", who, height, width);
+    GP_CHECK_ARG(cut_bound >= 0, "%s: cut_bound=%d must not be negative", who, cut_bound);
+    GP_CHECK_ARG((reinterpret_cast<uintptr_t>(depth) & 7) == 0, "%s: depth is not 8-byte aligned", who);
+    return GP_OK;
+}
+
+// the fill and the z-buffer over tables that are ready (or being made earlier on the stream)
+int rd_render(const double *points, int64_t n, const int32_t *entry_rows, const int32_t *entry_off, const int64_t *view_entry,
+              const double *w2c, const double *intrinsics, int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, double *depth,
+              unsigned long long *status, hipStream_t s) {
+    const int64_t total = (int64_t)nviews * height * width, fb = (total / 2 + 255) / 256;
+    rd_fill_kernel<<<(unsigned)(fb < 1 ? 1 : (fb > RD_FILL_BLOCKS ? RD_FILL_BLOCKS : fb)), 256, 0, s>>>(depth, total);
+    const int64_t nb = (n + 255) / 256;
+    rd_zbuffer_kernel<<<dim3(nb < RD_VIEW_BLOCKS ? (unsigned)nb : RD_VIEW_BLOCKS, (unsigned)nviews), 256, 0, s>>>(
+        points, entry_rows, entry_off, view_entry, w2c, intrinsics, width, height, cut_bound, depth, status);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gp_render_depth_batched_workspace_bytes(int64_t n, int32_t nviews) {
+    if (!ls_n_ok(n) || nviews < 1 || nviews > 65535) return 0;
+    GpCarver cv(nullptr, 0);
+    RdWork k(cv, n);
+    return cv.off;
+}
+
+extern "C" int gp_render_depth_batched(const double *points, int64_t n, const int64_t *view_entry, const double *w2c, const double *intrinsics,
+                                       int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, double *depth, int64_t *status,
+                                       void *workspace, size_t workspace_bytes, void *stream_) {
+    const char *who = "gp_render_depth_batched";
+    const int rc = rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace);
+    if (rc != GP_OK) return rc;
+    {
+        // every output against every input and every other output, over their whole extents
+        const void *in[] = {points, view_entry, w2c, intrinsics};
+        const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32};
+        const void *o[] = {depth, status, workspace};
+        const size_t o_bytes[] = {(size_t)nviews * height * width * 8, (size_t)ST_WORDS * 8, workspace_bytes};
+        for (int a = 0; a < 3; ++a) {
+            for (int i = 0; i < 4; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
+            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
+        }
+    }
+    GpCarver cv(workspace, workspace_bytes);
+    RdWork k(cv, n);
+    if (!cv.ok()) {
+        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
+    GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
+    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, st);
+    GP_CHECK_LAUNCH();
+    size_t io = k.tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, k.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));          // (stable)
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.k1, n, k.entry_off);
+    return rd_render(points, n, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, st, s);
+}
+
+extern "C" size_t gp_render_depth_batched_state_workspace_bytes(int64_t n, int32_t nviews) {
+    if (!ls_n_ok(n) || nviews < 1 || nviews > 65535) return 0;
+    GpCarver cv(nullptr, 0);
+    RdStateWork k(cv, n);
+    return cv.off;
+}
+
+extern "C" int gp_render_depth_batched_state(const double *points, int64_t n, const void *state, size_t state_bytes, const int64_t *view_entry,
+                                             const double *w2c, const double *intrinsics, int32_t nviews, int32_t height, int32_t width,
+                                             int32_t cut_bound, double *depth, int64_t *status, void *workspace, size_t workspace_bytes,
+                                             void *stream_) {
+    const char *who = "gp_render_depth_batched_state";
+    const int rc = rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace);
+    if (rc != GP_OK) return rc;
+    GP_CHECK_ARG(state, "%s: null argument", who);
+    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "%s: state too small (%zu < %zu)", who, state_bytes, ls_state_bytes(n));
+    {
+        const void *in[] = {points, state, view_entry, w2c, intrinsics};
+        const size_t in_bytes[] = {(size_t)n * 32, state_bytes, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32};
+        const void *o[] = {depth, status, workspace};
+        const size_t o_bytes[] = {(size_t)nviews * height * width * 8, (size_t)ST_WORDS * 8, workspace_bytes};
+        for (int a = 0; a < 3; ++a) {
+            for (int i = 0; i < 5; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
+            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
+        }
+    }
+    GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
+    const LsState tb(sv, n);
+    RdStateWork k(cv, n);
+    if (!cv.ok()) {
+        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
+        return GP_ENOMEM;
+    }
+    hipStream_t s = gp_stream(stream_);
+    unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
+    GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
+    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
+    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(tb.keys, tb.rows, tb.off, n, k.keys, k.rows, k.off, st);
+    GP_CHECK_LAUNCH();
+    return rd_render(points, n, k.rows, k.off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, st, s);
+}

@@ -173,15 +173,9 @@ __global__ void render_depth_kernel(const double *__restrict__ c, int64_t n, Mat
                                     double cy, int W, int H, int cut, double *__restrict__ depth) {
     int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double x = c[i * 3], y = c[i * 3 + 1], z = c[i * 3 + 2];
-    double p0 = dot4_blas(M.m[0], x, y, z), p1 = dot4_blas(M.m[1], x, y, z), p2 = dot4_blas(M.m[2], x, y, z);
-    double u = (p0 * fx) / p2 + cx;
-    double v = (p1 * fy) / p2 + cy;
-    double ur = rint(u), vr = rint(v);
-    bool finite = (fabs(ur) < 9.0e15) && (fabs(vr) < 9.0e15);
-    long long ui = finite ? (long long)ur : -1, vi = finite ? (long long)vr : -1;
-    bool inside = finite && ui >= cut && vi >= cut && ui < (long long)W - cut && vi < (long long)H - cut;
-    if (inside && p2 > 0.2)
+    long long ui, vi;
+    double p2;
+    if (render_point(c[i * 3], c[i * 3 + 1], c[i * 3 + 2], M.m[0], M.m[1], M.m[2], fx, fy, cx, cy, W, H, cut, ui, vi, p2))
         atomicMin(reinterpret_cast<unsigned long long *>(depth + vi * W + ui), (unsigned long long)__double_as_longlong(p2));
 }
 

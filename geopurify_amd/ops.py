@@ -1658,6 +1658,71 @@ def lift_stream_finish(st, fill=True, buffers=None, workspace=None):
     return LiftStreamFinish(out, got["seen"], got.get("nn"), got["status"])
 
 
+# ------------------------------------------------------------------------------------------ rendered depth over batched point clouds
+def _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev):
+    """the views' arrays of a rendered-depth call, checked -> (V, H, W, depth f64 [V,H,W])"""
+    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
+    H, W = (int(v) for v in image_hw)
+    if view_entry.dim() != 1 or view_entry.shape[0] < 1 or w2c.shape != (view_entry.shape[0], 4, 4) or intrinsics.shape != (view_entry.shape[0], 4):
+        raise ValueError(f"{who}: expected view_entry [V >= 1], w2c [V, 4, 4], intrinsics [V, 4], got {list(view_entry.shape)}, "
+                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    nv = view_entry.shape[0]
+    if H < 1 or W < 1 or int(cut_bound) < 0:
+        raise ValueError(f"{who}: expected image_hw = (H, W) >= 1 and cut_bound >= 0, got {tuple(image_hw)}, {cut_bound}")
+    if depth is None:
+        depth = torch.empty((nv, H, W), dtype=torch.float64, device=dev)
+    elif _chk(depth, torch.float64, "depth").shape != (nv, H, W):
+        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    return nv, H, W, depth
+
+
+def render_depth_batched_workspace_bytes(n, num_views):
+    return int(_lib.load().gp_render_depth_batched_workspace_bytes(int(n), int(num_views)))
+
+
+def render_depth_batched(points, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=None, workspace=None, status=None):
+    """gp_render_depth_batched, no sync: the z-buffer of every view over the points of its entry (the ScanNet mapper with depth given as
+    a str, fusion_util.py:126-130).  points f64 [n,4]; view_entry i64 [V]; w2c f64 [V,4,4]; intrinsics f64 [V,4]; image_hw = (H, W).
+    -> (depth f64 [V,H,W], status i64 [8] = (bad batch rows, bad view entries, non-finite rows, top batch, 0, 0, 0, 0)).  depth / status:
+    optional caller-owned outputs; workspace: uint8 of at least gp_render_depth_batched_workspace_bytes(n, V)."""
+    lib = _lib.load()
+    who = "render_depth_batched"
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    n, dev = points.shape[0], points.device
+    nv, H, W, depth = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev)
+    status = _outputs(who, {"status": (torch.int64, (8,))}, {"status": status}, dev)["status"]
+    ws = _ws(lib.gp_render_depth_batched_workspace_bytes(n, nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_render_depth_batched(_ptr(points), n, _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), nv, H, W, int(cut_bound), _ptr(depth),
+                                      _ptr(status), _ptr(ws), ws.numel(), _stream()), "gp_render_depth_batched")
+    return depth, status
+
+
+def render_depth_stream_workspace_bytes(n, num_views):
+    return int(_lib.load().gp_render_depth_batched_state_workspace_bytes(int(n), int(num_views)))
+
+
+def render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=None, workspace=None, status=None):
+    """gp_render_depth_batched_state, no sync: render_depth_batched with the entry tables taken from a stream's state -- st a
+    LiftStreamState or a LiftMasksStreamState (its points and state; nothing of st is changed) -- so nothing is sorted.  -> (depth f64
+    [V,H,W], status i64 [8] = (0, bad view entries, 0, 0, 0, 0, values of the state outside their range, 0)).  workspace: uint8 of at
+    least gp_render_depth_batched_state_workspace_bytes(n, V)."""
+    lib = _lib.load()
+    who = "render_depth_stream"
+    points, state = _chk(st.points, torch.float64, "points"), _chk(st.state, torch.uint8, "state")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    n, dev = points.shape[0], points.device
+    nv, H, W, depth = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev)
+    status = _outputs(who, {"status": (torch.int64, (8,))}, {"status": status}, dev)["status"]
+    ws = _ws(lib.gp_render_depth_batched_state_workspace_bytes(n, nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_render_depth_batched_state(_ptr(points), n, _ptr(state), state.numel(), _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), nv, H, W,
+                                            int(cut_bound), _ptr(depth), _ptr(status), _ptr(ws), ws.numel(), _stream()),
+          "gp_render_depth_batched_state")
+    return depth, status
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

@@ -53,6 +53,14 @@ differentiable=True) -- puts y.F into the autograd graph, so a loss on the purif
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
 l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene; segment (labels and counts) never does.
 
+All four lifts decide visibility against the caller's depth maps, by p_z > 0 alone (depth=None), or -- depth="render" -- against depth
+maps rendered from the points themselves, the reference's way when it has poses and a reconstructed cloud but no sensor depth
+(models/utils/fusion_util.py:126-130):
+
+    depth = render_depth(points, view_entry, world_to_camera, intrinsics, (H, W))         # fp64 [V,H,W]; or Views(..., depth="render")
+
+render_depth is ops.render_depth_batched: the z-buffer of every view over the points of its entry, one call for all entries; the
+streams render a chunk's views from their own entry tables (ops.render_depth_stream) into a chunk-sized scratch buffer.
 lift is the reference's lift_lseg_features (models/affinity_module.py:404-452) with the point -> pixel mapping of
 models/utils/fusion_util.py:45-147 and the loader's view-drop rule (dataset/data_loader_ablation.py:254-288), for all entries and all
 views in one call of ops.lift_batched, then ops.gather_rows for the fill.
@@ -147,8 +155,9 @@ LIFT_MODES = ("nearest", "bilinear")
 class Views:
     """The views of a batch of scenes: features fp32 [V,D,h,w] (the frozen VLM's maps, NCHW contiguous or torch.channels_last; other
     floating dtypes are upcast), view_entry integer [V] (the batch entry a view looks at), world_to_camera fp64 [V,4,4], intrinsics fp64
-    [V,4] = fx, fy, cx, cy at the image size, depth fp64 [V,H,W] or None (None: a point is visible where it projects inside the image
-    with p_z > 0), image_shape = (H, W) shared by all views (default: the maps' (h, w)).
+    [V,4] = fx, fy, cx, cy at the image size, depth fp64 [V,H,W], None (a point is visible where it projects inside the image with
+    p_z > 0: no occlusion) or the string "render" (the depth maps are rendered from the points themselves, see render_depth: occlusion
+    without sensor depth), image_shape = (H, W) shared by all views (default: the maps' (h, w)).
     world_to_camera is the row-major world->camera matrix: the transpose of the reference's world_view_transform, or the inverse of a
     camera-to-world matrix.  lift checks the fields."""
 
@@ -169,6 +178,46 @@ def _shape_of(t):
     return list(t.shape) if torch.is_tensor(t) else type(t).__name__
 
 
+RENDER = "render"                                           # Views.depth / MaskViews.depth: render the depth maps from the points
+
+
+def _depth_kind(depth):
+    """none / tensor / render: the three ways a lift decides visibility"""
+    return "none" if depth is None else (RENDER if isinstance(depth, str) else "tensor")
+
+
+def _check_depth(who, Dp, V, H, W):
+    """views.depth: fp64 [V,H,W], None, or the string "render" and no other"""
+    if isinstance(Dp, str):
+        if Dp != RENDER:
+            raise ValueError(f"{who}: views.depth={Dp!r}: expected fp64 [{V}, {H}, {W}] (image_shape), None or the string {RENDER!r}")
+    elif Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
+        raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
+                         f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+
+
+def _check_points(who, P):
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+
+
+def _check_poses(who, name, V, E, M, K):
+    """view_entry, world_to_camera and intrinsics of V views; name: how the message calls their owner ("views." or "")"""
+    if not _is_int_tensor(E) or E.shape != (V,):
+        raise ValueError(f"{who}: {name}view_entry must be an integer tensor [{V}], got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
+        raise ValueError(f"{who}: {name}world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
+    if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
+        raise ValueError(f"{who}: {name}intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
+                         f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+
+
 def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible):
     """lift's argument checks, in lift's order; views None: those of the points and the options alone (LiftStream's construction).
     -> (V, D, h, w, H, W), or None without views"""
@@ -177,13 +226,7 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
     if views is not None and not isinstance(views, Views):
         raise ValueError(f"{who}: views must be a Views, got {type(views).__name__}")
     P = points
-    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
-        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
-    if P.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
-    n = P.shape[0]
-    if n == 0 or n >= 2 ** 31:
-        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    _check_points(who, P)
     if views is not None:
         Fm, E, M, K, Dp = views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         if not torch.is_tensor(Fm) or Fm.dim() != 4 or min(Fm.shape) < 1:
@@ -193,21 +236,12 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
         V, D, h, w = Fm.shape
         if V > 65535:
             raise ValueError(f"{who}: {V} views, at most 65535")
-        if not _is_int_tensor(E) or E.shape != (V,):
-            raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
-                             f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-        if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
-            raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
-        if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
-            raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
-                             f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
+        _check_poses(who, "views.", V, E, M, K)
         shape = (h, w) if views.image_shape is None else tuple(views.image_shape)
         if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
             raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers, got {views.image_shape!r}")
         H, W = shape
-        if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
-            raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
-                             f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+        _check_depth(who, Dp, V, H, W)
         if mode == "nearest" and (h, w) != (H, W):
             raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
     if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
@@ -219,11 +253,68 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
     if views is not None and Fm.requires_grad:
         raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
                          "no_grad); detach them")
-    tensors = [P] + ([Fm, E, M, K] + ([Dp] if Dp is not None else []) if views is not None else [])
+    tensors = [P] + ([Fm, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
     if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
         raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
                          f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
     return (V, D, h, w, H, W) if views is not None else None
+
+
+def render_depth(points, view_entry, world_to_camera, intrinsics, image_shape, *, cut_bound=0):
+    """The depth maps the reference renders from the cloud itself when it is given no sensor depth (models/utils/fusion_util.py:126-130,
+    the ScanNet mapper with depth passed as a str), for all views of all entries in one call, entries never mixing.  points,
+    view_entry, world_to_camera and intrinsics as lift takes them (points fp64 or fp32 [N,4], upcast to fp64 first; V views);
+    image_shape = (H, W).  -> fp64 [V,H,W]: a pixel holds the smallest p_z > 0.2 among the points of the view's entry that project
+    into it (rounded half to even) inside [cut_bound, W - cut_bound) x [cut_bound, H - cut_bound), and 999999 where none does.  A view
+    whose entry has no points is 999999 everywhere.  The same bits as ops.render_depth per view on the entry's points, in any row
+    order: the minimum is an integer atomic on the fp64 bit pattern, which no arrival order changes.
+    This is what depth="render" hands to lift, LiftStream, lift_masks and LiftMasksStream; it holds V * H * W * 8 bytes.
+    Inside: ops.render_depth_batched (the entry tables, the fill, the z-buffer kernel).  ValueError before any kernel: lift's refusals
+    for these fields; from the ONE status read-back, with lift's messages and precedence: non-finite rows, rows whose batch index is no
+    integer in 0..65535, views whose entry is outside 0..65535."""
+    who = "render_depth"
+    P, E, M, K = points, view_entry, world_to_camera, intrinsics
+    _check_points(who, P)
+    if not _is_int_tensor(E) or E.dim() != 1 or E.shape[0] < 1:
+        raise ValueError(f"{who}: view_entry must be an integer tensor [V] with V >= 1, got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    V = E.shape[0]
+    if V > 65535:
+        raise ValueError(f"{who}: {V} views, at most 65535")
+    _check_poses(who, "", V, E, M, K)
+    shape = tuple(image_shape) if isinstance(image_shape, (tuple, list)) else ()
+    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+        raise ValueError(f"{who}: image_shape must be (H, W), two positive integers, got {image_shape!r}")
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    tensors = [P, E, M, K]
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    with torch.cuda.device(P.device), torch.no_grad():
+        depth, status = ops.render_depth_batched(P.detach().to(torch.float64).contiguous(), E.detach().to(torch.int64).contiguous(),
+                                                 M.detach().contiguous(), K.detach().contiguous(), shape, cut_bound)
+        bad_batch, bad_view, nonfinite = ops.readback(status)[:3]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    return depth
+
+
+def _render_chunk(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, workspace):
+    """depth="render" in a stream: the z-buffers of a chunk's views from the stream's entry tables (nothing is sorted, nothing read
+    back), into scratch that grows to the largest chunk seen.  -> (fp64 [V,H,W], the depth scratch, the workspace)"""
+    V, (H, W), n, dev = view_entry.shape[0], image_hw, st.points.shape[0], st.points.device
+    if depth is None or depth.numel() < V * H * W:
+        depth = torch.empty(V * H * W, dtype=torch.float64, device=dev)
+    need = ops.render_depth_stream_workspace_bytes(n, V)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    d, _ = ops.render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=depth[:V * H * W].view(V, H, W), workspace=workspace)
+    return d, depth, workspace
 
 
 def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
@@ -232,7 +323,9 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     batch index (integral, 0..65535), world x, y, z, on the GPU, in any row order; views: a Views.  Per entry b -- its points the rows
     with batch b in ascending row order, its views those with view_entry == b in ascending view index:
       1. a point is visible in a view when it projects inside [cut_bound, W - cut_bound) x [cut_bound, H - cut_bound) (pixels rounded
-         half to even) and |depth - p_z| <= vis_thres * depth there (without depths: p_z > 0);
+         half to even) and |depth - p_z| <= vis_thres * depth there (without depths: p_z > 0; with views.depth == "render" the depth
+         maps are render_depth(points, view_entry, world_to_camera, intrinsics, image_shape, cut_bound=cut_bound), and the result is
+         what the call returns when given that tensor; the rendered maps take V * H * W * 8 bytes for the duration of the call);
       2. view_keep[v] = n_v != 0 and n_v >= min_visible and n_v <= max_visible (None: no upper bound), n_v = view_count[v];
       3. the sampled feature columns of the kept views that see a point are summed in fp32 in ascending v;
       4. features = sum / (count == 0 ? 1e-6 : count), seen = count > 0;
@@ -245,8 +338,9 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     require grad are refused and the points are detached.
     Inside: ops.lift_batched (the entry tables, the per-view counts, the fused lift kernel over pixel-major maps -- a channels_last
     tensor is read in place, an NCHW one goes through ops.lift_batched_transpose once --, the per-entry masked 1-NN) and
-    ops.gather_rows.  ValueError before any kernel: shape / dtype / device mismatches, CPU tensors, an unknown mode, maps that require
-    grad, more than 65535 views, N >= 2^31; from the ONE status read-back, taken after the last launch (no buffer is sized by what it
+    ops.gather_rows; with "render", ops.render_depth_batched first (no read-back of its own: the lift's status says the same).
+    ValueError before any kernel: shape / dtype / device mismatches, CPU tensors, an unknown mode, a depth string other than "render",
+    maps that require grad, more than 65535 views, N >= 2^31; from the ONE status read-back, taken after the last launch (no buffer is sized by what it
     carries): rows whose batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates."""
     who = "lift"
     V, D, h, w, H, W = _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible)
@@ -260,7 +354,10 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
             maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)          # (a view: channels_last is pixel-major already)
         else:
             maps_pm = ops.lift_batched_transpose(maps.contiguous())
-        r = ops.lift_batched(pts, maps_pm, (h, w), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous(),
+        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
+            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
+        r = ops.lift_batched(pts, maps_pm, (h, w), ve, w2c, intr,
                              None if Dp is None else Dp.detach().contiguous(), (H, W), mode == "bilinear", cut_bound, float(vis_thres),
                              min_visible, 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1), fill=bool(fill))
         feats = r.out
@@ -298,6 +395,8 @@ class LiftStream:
          one scratch buffer of the stream's that grows only when a chunk is larger than every chunk before it.  Apart from the
          per-view count and keep vectors the stream holds nothing that grows with the views added: the state is the entry tables
          (8 bytes per point), the fp32 sums [N, D] and the counts [N].
+      5. With depth="render" a chunk's depth maps are rendered from the stream's entry tables (ops.render_depth_stream: no sort, no
+         read-back) into a scratch buffer of the largest chunk's V * H * W * 8 bytes; the maps of all views never exist at once.
     Why the bits are lift's: a point's sum starts from +0 and takes the kept views that see it in ascending order, one fp32 add each;
     between two chunks the partial sum is stored and reloaded as fp32, which changes no bit.  A point that no kept view of a chunk
     sees is neither read nor written by that chunk.
@@ -305,7 +404,8 @@ class LiftStream:
     ops.lift_stream_add (the chunk's view table, the per-view counts and drop rule, the accumulating lift kernel), in finish
     ops.lift_stream_finish (divide, seen, the per-entry masked 1-NN) and ops.gather_rows.
     ValueError before any kernel of the call: lift's refusals, for points and options at construction and for the chunk at add; a
-    chunk whose D is not feature_dim, or whose (h, w), image_shape, presence of depth or device differ from the first chunk's; a chunk
+    chunk whose D is not feature_dim, or whose (h, w), image_shape, presence of depth (none, a tensor or "render": three kinds that do
+    not mix) or device differ from the first chunk's; a chunk
     that takes the views past 65535 in all (lift's limit); finish before any add.  A refused add leaves the stream as it was.  From
     finish's ONE status read-back, with lift's messages and precedence: non-finite rows, rows whose batch index is no integer in
     0..65535 (both counted once, at construction), views whose entry is outside 0..65535 (counted over all chunks).  Such rows and
@@ -322,7 +422,7 @@ class LiftStream:
         self._points, self._device = points, points.device
         self._first = None                                      # ((h, w), (H, W), depth present) of the first chunk
         self._view_count, self._view_keep = [], []
-        self._scratch = self._ws_add = self._ws_finish = None
+        self._scratch = self._ws_add = self._ws_finish = self._depth = self._ws_render = None
         with torch.cuda.device(self._device), torch.no_grad():
             self._st = ops.lift_stream_begin(points.detach().to(torch.float64).contiguous(), self.feature_dim)
 
@@ -335,9 +435,9 @@ class LiftStream:
         V, D, h, w, H, W = _check_lift(who, self._points, views, *self._options())
         if D != self.feature_dim:
             raise ValueError(f"{who}: the chunk's maps have {D} channels, the stream was built with feature_dim={self.feature_dim}")
-        this = ((h, w), (H, W), views.depth is not None)
+        this = ((h, w), (H, W), _depth_kind(views.depth))
         if self._first is not None:
-            for name, a, b in zip(("(h, w)", "image_shape", "the presence of depth"), this, self._first):
+            for name, a, b in zip(("(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')"), this, self._first):
                 if a != b:
                     raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
         if self.num_views + V > 65535:
@@ -356,8 +456,10 @@ class LiftStream:
             if self._ws_add is None or self._ws_add.numel() < need:
                 self._ws_add = None
                 self._ws_add = torch.empty(need, dtype=torch.uint8, device=self._device)
-            vc, vk = ops.lift_stream_add(self._st, maps_pm, (h, w), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(),
-                                         K.detach().contiguous(), None if Dp is None else Dp.detach().contiguous(), (H, W),
+            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
+                Dp, self._depth, self._ws_render = _render_chunk(self._st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
+            vc, vk = ops.lift_stream_add(self._st, maps_pm, (h, w), ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(), (H, W),
                                          self.mode == "bilinear", self.cut_bound, float(self.vis_thres), self.min_visible,
                                          2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1), workspace=self._ws_add)
         self._first = this
@@ -401,7 +503,7 @@ _TABLE_ROWS = 2 ** 24                                       # rows of one ops.se
 class MaskViews:
     """The views of a batch of scenes with the X-Decoder form of the VLM's outputs: pred_masks fp32 [V,Q,h,w] (mask logits), pred_logits
     floating [V,Q,C+1] (class logits, the last column "no object"), mask_embed floating [V,Q,D]; view_entry, world_to_camera,
-    intrinsics, depth exactly as in Views; image_shape = (H, W), required: the reference's cfg.mask_shape, the size the masks are
+    intrinsics, depth exactly as in Views (a tensor, None or "render"); image_shape = (H, W), required: the reference's cfg.mask_shape, the size the masks are
     resized to and the depths and intrinsics refer to (h <= H and w <= W).  Every view has the same number of queries Q.  lift_masks
     checks the fields."""
 
@@ -486,9 +588,7 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
         if h > H or w > W:
             raise ValueError(f"{who}: masks of {h} x {w} are larger than image_shape {H} x {W}: the bicubic-antialias resize is evaluated for "
                              "up-sampling only")
-        if Dp is not None and (not torch.is_tensor(Dp) or Dp.shape != (V, H, W) or Dp.dtype != torch.float64):
-            raise ValueError(f"{who}: views.depth must be fp64 [{V}, {H}, {W}] (image_shape) or None, got "
-                             f"{(list(Dp.shape), Dp.dtype) if torch.is_tensor(Dp) else type(Dp).__name__}")
+        _check_depth(who, Dp, V, H, W)
     if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
         raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
     if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
@@ -502,7 +602,7 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
         if t.requires_grad:
             raise ValueError(f"{who}: {name} require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
                              "no_grad); detach them")
-    tensors = [P] + ([Pm, Pl, Em] if views is not None else []) + [text_embed] + ([E, M, K] + ([Dp] if Dp is not None else []) if views is not None else [])
+    tensors = [P] + ([Pm, Pl, Em] if views is not None else []) + [text_embed] + ([E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
     if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
         raise ValueError(f"{who}: points, text_embed and the views' tensors must be CUDA tensors on one device (got "
                          f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
@@ -513,7 +613,8 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
     """The reference's default lift, lift_xdecoder_features (models/affinity_module.py:455-714), for several scenes at once, entries
     never mixing and with no cap on the views of an entry.  points as for lift; views: a MaskViews; text_embed floating [C,D].  Per
     entry b -- its points the rows with batch b in ascending row order, its views those with view_entry == b in ascending view index:
-      1. visibility, view_count and view_keep exactly as lift's steps 1-2;
+      1. visibility, view_count and view_keep exactly as lift's steps 1-2 (views.depth == "render" included: the rendered maps take
+         V * H * W * 8 bytes for the duration of the call and cost no read-back);
       2. score[v,q] = softmax(pred_logits[v,q])[:-1].max() (torch on the device);
       3. the segment of a visible pixel of a kept view: the bicubic-antialias resize of pred_masks[v] to image_shape evaluated at that
          pixel; over the queries with score > 0 the arg-max of score_q * sigmoid(logit_q), the smallest q among equal products; that q
@@ -546,8 +647,10 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
     dev = P.device
     with torch.cuda.device(dev), torch.no_grad():
         pts = P.detach().to(torch.float64).contiguous()
-        ve = E.detach().to(torch.int64).contiguous()
-        lists = ops.lift_masks_batched_lists(pts, ve, M.detach().contiguous(), K.detach().contiguous(),
+        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
+            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
+        lists = ops.lift_masks_batched_lists(pts, ve, w2c, intr,
                                              None if Dp is None else Dp.detach().contiguous(), (H, W), cut_bound, float(vis_thres), min_visible,
                                              2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1))    # (the first read-back)
         text_norm = torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
@@ -645,7 +748,9 @@ class LiftMasksStream:
     ops.lift_masks_stream_sizes in place of its read-back, then its writing call), ops.segment_tables, ops.lift_masks_stream_add; in
     finish ops.lift_masks_stream_finish and ops.gather_rows.
     ValueError before any kernel of the call: lift_masks' refusals, for points, text and options at construction and for the chunk at
-    add; a chunk whose Q, (h, w), image_shape or presence of depth differ from the first chunk's (another C, D or device is lift_masks'
+    add; a chunk whose Q, (h, w), image_shape or presence of depth (none, a tensor or "render": three kinds that do not mix) differ from
+    the first chunk's (with "render" a chunk's maps are rendered from the stream's entry tables by ops.render_depth_stream into scratch of
+    the largest chunk's V * H * W * 8 bytes, with no further read-back; another C, D or device is lift_masks'
     own refusal against the text and the points); a chunk that takes the views past 65535 in all; finish before any add.  After the
     chunk's read-back, before anything is changed: records past 2^31 - 2 in all (lift_masks' limit on the visible entries).  A refused
     add leaves the stream as it was.  From finish's read-back, with lift_masks' messages and precedence: non-finite rows, rows whose
@@ -665,6 +770,7 @@ class LiftMasksStream:
         self._view_entry = self._view_count = self._view_keep = self._view_pos = self._rec_off = None
         self._f_seg = self._l_seg = self._rec_row = self._rec_seg = None
         self._ws = {}                                           # add's and finish's workspaces by name
+        self._depth = self._ws_render = None                    # depth="render": a chunk's rendered depth and its workspace
         dev = self._device
         with torch.cuda.device(dev), torch.no_grad():
             self._st = ops.lift_masks_stream_begin(points.detach().to(torch.float64).contiguous())
@@ -687,9 +793,9 @@ class LiftMasksStream:
             raise ValueError(f"{who}: views must be a MaskViews, got NoneType")
         V, Q, h, w, H, W, C, D = _check_lift_masks(who, self._points, views, self._text, self.logit_scale, self.cut_bound, self.vis_thres,
                                                    self.min_visible, self.max_visible)
-        this = (Q, (h, w), (H, W), views.depth is not None)
+        this = (Q, (h, w), (H, W), _depth_kind(views.depth))
         if self._first is not None:
-            for name, a, b in zip(("Q", "(h, w)", "image_shape", "the presence of depth"), this, self._first):
+            for name, a, b in zip(("Q", "(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')"), this, self._first):
                 if a != b:
                     raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
         V0, R0 = self.num_views, self.num_records
@@ -699,7 +805,9 @@ class LiftMasksStream:
         E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         n, dev, st, d4 = self._points.shape[0], self._device, self._st, self._d4
         with torch.cuda.device(dev), torch.no_grad():
-            ve = E.detach().to(torch.int64).contiguous()
+            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
+                Dp, self._depth, self._ws_render = _render_chunk(st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
             found, bufs = {}, {}
 
             def sizes(got):
@@ -718,7 +826,7 @@ class LiftMasksStream:
                     bufs["view"] = ent[24 * pitch:24 * pitch + 4 * total].view(torch.int32)
                 return found["total"], most
 
-            lists = ops.lift_masks_batched_lists(st.points, ve, M.detach().contiguous(), K.detach().contiguous(),
+            lists = ops.lift_masks_batched_lists(st.points, ve, w2c, intr,
                                                  None if Dp is None else Dp.detach().contiguous(), (H, W), self.cut_bound, float(self.vis_thres),
                                                  self.min_visible, 2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1),
                                                  buffers=bufs, workspace=self._workspace("lists", ops.lift_masks_batched_lists_workspace_bytes(n, V)),

@@ -1046,6 +1046,42 @@ int gp_lift_masks_stream_finish(const double *points, int64_t n, const void *sta
                                 int32_t *count, int64_t *nn, int64_t *status_out, void *workspace, size_t workspace_bytes,
                                 void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Rendered depth over BATCHED point clouds: the depth "render" mode of the ScanNet mapper,             */
+/* models/utils/fusion_util.py:126-130 (compute_mapping(depth=<str>): the z-buffer of the cloud itself),  */
+/* for every view of every batch entry in one sequence of launches; entries never mix.  It replaces, per  */
+/* scene and per view, one gp_render_depth_f64 call on the entry's slice of the points (a launch and a    */
+/* host-side matrix upload each), and gives the same bits.  Points, entries, views and poses are worded   */
+/* as in gp_lift_batched: points f64 [n,4], view_entry i64 [nviews], w2c f64 [nviews,16], intrinsics f64  */
+/* [nviews,4].                                                                                            */
+/*   depth f64 [nviews,height,width] (8-byte aligned): 999999 everywhere, then per view the minimum        */
+/*     camera-space z over the points OF THE VIEW'S ENTRY with z > 0.2 that project inside [cut_bound,     */
+/*     width - cut_bound) x [cut_bound, height - cut_bound), pixels rounded half to even -- the depth      */
+/*     argument of gp_lift_batched, gp_lift_stream_add and gp_lift_masks_batched_lists;                    */
+/*   status i64 [8]: gp_render_depth_batched: [0] rows whose batch index is no integer in 0..65535, [1]    */
+/*     views whose entry is outside 0..65535, [2] rows with a non-finite value, [3] the highest valid      */
+/*     batch index; gp_render_depth_batched_state: [1] as above, [6] values of state that lay outside      */
+/*     their range; the others 0.  Rows counted in [0] are never rendered, the image of a view counted in  */
+/*     [1] stays 999999; nothing is read or written outside the extents whatever they hold.                */
+/* The minimum is a 64-bit unsigned atomic on the fp64 bit pattern (positive doubles order like their      */
+/* bits): it does not depend on arrival order, two calls give the same bits.                               */
+/* gp_render_depth_batched sorts the rows by entry itself (the tables of gp_lift_batched, in its           */
+/* workspace).  gp_render_depth_batched_state takes the tables from the state that gp_lift_stream_begin    */
+/* or gp_lift_masks_stream_begin wrote for these points (state_bytes of at least                           */
+/* gp_lift_stream_state_bytes(n); the mask stream's state begins with the same tables), forced into range  */
+/* first as gp_lift_stream_finish does, and sorts nothing; it changes no byte of state.                    */
+/* 1 <= n < 2^31, 1 <= nviews <= 65535, height, width >= 1, cut_bound >= 0.  No output may overlap an      */
+/* input or another output (GP_EINVAL).                                                                    */
+size_t gp_render_depth_batched_workspace_bytes(int64_t n, int32_t nviews);
+int gp_render_depth_batched(const double *points, int64_t n, const int64_t *view_entry, const double *w2c,
+                            const double *intrinsics, int32_t nviews, int32_t height, int32_t width, int32_t cut_bound,
+                            double *depth, int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t gp_render_depth_batched_state_workspace_bytes(int64_t n, int32_t nviews);
+int gp_render_depth_batched_state(const double *points, int64_t n, const void *state, size_t state_bytes,
+                                  const int64_t *view_entry, const double *w2c, const double *intrinsics, int32_t nviews,
+                                  int32_t height, int32_t width, int32_t cut_bound, double *depth, int64_t *status,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
