@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("GP_LIB") or os.path.join(_HERE, "libgeopurify_hip.so"
 
 _P = c_void_p  # every device pointer travels as void*
 GP_KNN_MAX_K = 127  # include/geopurify_hip.h: K+1 <= 128
+GP_ELEM_F32, GP_ELEM_F16, GP_ELEM_BF16 = 0, 1, 2  # include/geopurify_hip.h: the element-type tags of the batched lifts' *_t entry points
 
 # name -> (restype, [argtypes])  -- mirrors include/geopurify_hip.h one to one
 SIGNATURES = {
@@ -173,15 +174,20 @@ SIGNATURES = {
     "gp_fused_decode": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "gp_lift_batched_col_chunk": (c_int32, []),
     "gp_lift_batched_transpose": (c_int32, [_P, c_int32, c_int32, c_int64, _P, _P]),
+    "gp_lift_batched_transpose_t": (c_int32, [_P, c_int32, c_int32, c_int32, c_int64, _P, _P]),
     "gp_lift_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_lift_batched": (c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_double, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_batched_t": (c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32,
+                                    c_int32, c_double, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gp_lift_stream_state_bytes": (c_size_t, [c_int64]),
     "gp_lift_stream_begin_workspace_bytes": (c_size_t, [c_int64]),
     "gp_lift_stream_begin": (c_int32, [_P, c_int64, c_int32, _P, c_size_t, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "gp_lift_stream_add_workspace_bytes": (c_size_t, [c_int32]),
     "gp_lift_stream_add": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32,
                                      c_int32, c_int32, c_double, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_stream_add_t": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32,
+                                       c_int32, c_int32, c_int32, c_double, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gp_lift_stream_finish_workspace_bytes": (c_size_t, [c_int64]),
     "gp_lift_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int64, _P, _P, c_int32, _P, c_int64, _P, _P, _P, _P,
                                         c_size_t, _P]),
@@ -193,6 +199,11 @@ SIGNATURES = {
     "gp_lift_masks_batched": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32,
                                         _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
                                         _P, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_masks_batched_workspace_bytes_t": (c_size_t, [c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64,
+                                                           c_int32, c_int64]),
+    "gp_lift_masks_batched_t": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32,
+                                          _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
+                                          _P, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gp_lift_masks_stream_state_bytes": (c_size_t, [c_int64]),
     "gp_lift_masks_stream_begin_workspace_bytes": (c_size_t, [c_int64]),
     "gp_lift_masks_stream_begin": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, c_size_t, _P]),
@@ -202,6 +213,11 @@ SIGNATURES = {
     "gp_lift_masks_stream_add": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32,
                                            c_int32, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P,
                                            c_size_t, _P]),
+    "gp_lift_masks_stream_add_workspace_bytes_t": (c_size_t, [c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64,
+                                                              c_int64]),
+    "gp_lift_masks_stream_add_t": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                             c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P,
+                                             c_size_t, _P]),
     "gp_lift_masks_stream_finish_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64, c_int32]),
     "gp_lift_masks_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, _P, _P, c_int32, _P, _P, c_int64, c_int32, _P, _P, c_int32,
                                               c_int32, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),

@@ -1,18 +1,23 @@
 // Device code of the mask-embedding lift shared by the per-scene path (lift.hip: gp_lift_masks_views) and the batched one
 // (lift_masks_batched.hip: gp_lift_masks_batched): the score sort, the ordered transpose, the segment decision of a visible pixel on
 // the score-ordered copy, and the in-view fill over view-major entries.  One definition, so both paths take the same decisions and
-// give the same bits.
+// give the same bits.  The transpose and the segment decision are templates over the masks' element type (gp_map_elem.h): the batched
+// paths read fp32, fp16 or bf16 logits, keep the ordered copy in that type and convert the 16 taps of a pixel to fp32 as they are
+// loaded; the per-scene path instantiates float alone.
 #pragma once
 #include "gp_common.h"
+#include "gp_map_elem.h"
 
 namespace {
 
 // ---- the same for ALL views of a scene: entries e = (view, point, pixel) in view-major order (gp_views_visible_lists); the masks
 // of view v are mt + v * h*w*Q, its scores scores + v * Q.  Entries of dropped views get -1.
 // (order: the queries of view blockIdx.z by descending score, lv_sort_scores_kernel -- row r of the transposed copy is query order[r])
-__global__ void transpose_views_kernel(const float *__restrict__ src, int rows, int cols, float *__restrict__ dst,
+// T: float, or uint16_t for both half types of the masks (gp_map_elem.h): the copy keeps the input's type, the elements are moved
+template <typename T>
+__global__ void transpose_views_kernel(const T *__restrict__ src, int rows, int cols, T *__restrict__ dst,
                                        const int32_t *__restrict__ order) {
-    __shared__ float tile[64][65];
+    __shared__ T tile[64][65];
     const int64_t vo = (int64_t)blockIdx.z * rows * cols;
     const int32_t *ord = order + (int64_t)blockIdx.z * rows;
     int bx = blockIdx.x * 64, by = blockIdx.y * 64;
@@ -22,7 +27,7 @@ __global__ void transpose_views_kernel(const float *__restrict__ src, int rows, 
     __syncthreads();
     for (int r = ty; r < 64; r += 4) {
         int row = by + r, col = bx + tx;
-        tile[r][tx] = (row < rows && col < cols) ? src[vo + (int64_t)s_ord[r] * cols + col] : 0.f;
+        tile[r][tx] = (row < rows && col < cols) ? src[vo + (int64_t)s_ord[r] * cols + col] : T(0);
     }
     __syncthreads();
     for (int r = ty; r < 64; r += 4) {
@@ -70,7 +75,9 @@ __global__ void __launch_bounds__(256) lv_sort_scores_kernel(const float *__rest
 // score is strictly below the best product found so far (nothing in it can win or tie).  The decision is the one of
 // lift_masks_point (largest product, then smallest query index; the same arithmetic per candidate), reached after 1.1 passes
 // instead of 4 on the S scene's synthetic masks (92 % of the pixels stop after the first 64 queries).
-__device__ __forceinline__ void lift_masks_point_sorted(const float *__restrict__ mt /*[h*w, Q] in rank order*/, int Q, int h, int w,
+// T: the masks' element type (float, gp_f16, gp_bf16); the 16 taps are converted to fp32 as they are loaded, the chain is the same.
+template <typename T>
+__device__ __forceinline__ void lift_masks_point_sorted(const T *__restrict__ mt /*[h*w, Q] in rank order*/, int Q, int h, int w,
                                                         const float *__restrict__ sscore, const int32_t *__restrict__ order,
                                                         const int32_t *__restrict__ tx0, const float *__restrict__ twx,
                                                         const int32_t *__restrict__ ty0, const float *__restrict__ twy, int out_h, int out_w,
@@ -97,10 +104,10 @@ __device__ __forceinline__ void lift_masks_point_sorted(const float *__restrict_
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int yy = min(y0 + j, h - 1);
-                    const float *r = mt + ((int64_t)yy * w) * Q + q;
-                    float t = __fmul_rn(r[(int64_t)min(x0, w - 1) * Q], wx[0]);
+                    const T *r = mt + ((int64_t)yy * w) * Q + q;
+                    float t = __fmul_rn(gp_to_f32(r[(int64_t)min(x0, w - 1) * Q]), wx[0]);
 #pragma unroll
-                    for (int a = 1; a < 4; ++a) t = fmaf(r[(int64_t)min(x0 + a, w - 1) * Q], wx[a], t);
+                    for (int a = 1; a < 4; ++a) t = fmaf(gp_to_f32(r[(int64_t)min(x0 + a, w - 1) * Q]), wx[a], t);
                     hr[j] = t;
                 }
                 float v = __fmul_rn(hr[0], wy[0]);
@@ -134,7 +141,8 @@ __device__ __forceinline__ void lift_masks_point_sorted(const float *__restrict_
 // four passes of 16 dword loads, the last with 8 live lanes; same bits) is SLOWER: 733 us -- the four passes keep four times as many
 // loads in flight.  Round 5: a tile-major form (bins of 16 low-resolution cells staged in LDS from the [Q, h, w] layout): 1.9 ms
 // (profiles/r05_lift_tile_major.log); what pays is doing less of the work: the score order above.
-__global__ void lift_masks_views_kernel(const float *__restrict__ mt /*[V, h*w, Q] in rank order*/, int Q, int h, int w,
+template <typename T>
+__global__ void lift_masks_views_kernel(const T *__restrict__ mt /*[V, h*w, Q] in rank order*/, int Q, int h, int w,
                                         const float *__restrict__ sscore /*[V,Q]*/, const int32_t *__restrict__ order /*[V,Q]*/,
                                         const int32_t *__restrict__ tx0, const float *__restrict__ twx, const int32_t *__restrict__ ty0,
                                         const float *__restrict__ twy, int out_h, int out_w,

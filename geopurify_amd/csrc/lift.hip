@@ -477,8 +477,8 @@ extern "C" int gp_lift_masks_views(const float *pred_masks, int32_t nsrc, int32_
     hipStream_t s = gp_stream(stream_);
     const int hw = h * w;
     lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    transpose_views_kernel<<<dim3((hw + 63) / 64, (q + 63) / 64, nviews), 256, 0, s>>>(pred_masks, q, hw, k.mt, k.order);
-    lift_masks_views_kernel<<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(k.mt, q, h, w, k.sscore, k.order, tap_x0, tap_wx, tap_y0,
+    transpose_views_kernel<float><<<dim3((hw + 63) / 64, (q + 63) / 64, nviews), 256, 0, s>>>(pred_masks, q, hw, k.mt, k.order);
+    lift_masks_views_kernel<float><<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(k.mt, q, h, w, k.sscore, k.order, tap_x0, tap_wx, tap_y0,
                                                                                tap_wy, out_h, out_w, ent_x, ent_y, ent_view, keep, total, seg);
     // in-view fill
     const unsigned eb = (unsigned)((total + 1 + 255) / 256);

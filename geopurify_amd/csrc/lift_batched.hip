@@ -15,7 +15,10 @@
 // lane l projects the point through the l-th view of a group of 64 of its entry, a 64-bit ballot is the visible-and-kept mask, its
 // set bits are walked in ascending view order with all lanes striding the channels and accumulating in registers; the row is divided
 // and stored once.  No float atomics and no read-modify-write of the sums: the fp32 add order is the sequential index_add_'s.  The
-// maps are read PIXEL-MAJOR ([V, h*w, D]: one contiguous row of 4 D bytes per sample); (4) the fill: references (seen rows) and
+// maps are read PIXEL-MAJOR ([V, h*w, D]: one contiguous row of 4 D bytes per sample -- or of 2 D bytes: the maps may be fp16 or bf16
+// (gp_map_elem.h, the *_t entry points), every loaded element is converted to fp32, which is exact, and then takes the same adds and
+// fmas in the same order, so half maps give the bits of their fp32 copy; aligned half rows are read 8 or 16 bytes per lane); (4) the
+// fill: references (seen rows) and
 // queries (unseen rows of entries that have seen ones) compacted in the entry-sorted order, so an entry's references are one
 // contiguous run; a block of 256 queries streams the runs of its queries' entries through LDS tiles, each query comparing only inside
 // its own run.
@@ -27,6 +30,7 @@
 // (The entry tables, the per-view counts with the drop rule and the fill kernels live in gp_lift_entries.h: lift_masks_batched.hip runs
 // them too.)
 #include "gp_lift_entries.h"
+#include "gp_map_elem.h"
 
 namespace {
 
@@ -35,8 +39,10 @@ constexpr int LB_COL_CHUNK = GP_WAVE * LB_COLS_PER_LANE;         // channels one
 
 
 // ------------------------------------------------------------------------------------------------ [V, D, hw] -> [V, hw, D]
-__global__ void __launch_bounds__(256) lb_transpose_kernel(const float *__restrict__ src, int rows, int64_t cols, float *__restrict__ dst) {
-    __shared__ float tile[64][65];
+// (T: float, or uint16_t for both half types -- the elements are moved, never read as numbers)
+template <typename T>
+__global__ void __launch_bounds__(256) lb_transpose_kernel(const T *__restrict__ src, int rows, int64_t cols, T *__restrict__ dst) {
+    __shared__ T tile[64][65];
     const int64_t vo = (int64_t)blockIdx.z * rows * cols;
     const int64_t bx = (int64_t)blockIdx.x * 64;
     const int by = blockIdx.y * 64;
@@ -44,7 +50,7 @@ __global__ void __launch_bounds__(256) lb_transpose_kernel(const float *__restri
     for (int r = ty; r < 64; r += 4) {
         const int row = by + r;
         const int64_t col = bx + tx;
-        tile[r][tx] = (row < rows && col < cols) ? src[vo + (int64_t)row * cols + col] : 0.f;
+        tile[r][tx] = (row < rows && col < cols) ? src[vo + (int64_t)row * cols + col] : T(0);
     }
     __syncthreads();
     for (int r = ty; r < 64; r += 4) {
@@ -58,8 +64,13 @@ __global__ void __launch_bounds__(256) lb_transpose_kernel(const float *__restri
 // One wave per point.  BILINEAR: the map is [h, w] and the pixel indexes the [H, W] image the reference resizes the map to
 // (F.interpolate(bilinear, align_corners=True)); the resize is evaluated at the sampled pixel with the arithmetic of
 // lift_dense_bilinear_accum_kernel.  Otherwise (h, w) == (H, W) and the pixel's row is added as it is.
-template <bool BILINEAR>
-__global__ void __launch_bounds__(256) lb_lift_kernel(const double *__restrict__ points, int64_t n, const float *__restrict__ feat, int d, int h,
+// T: the maps' element type (gp_map_elem.h), converted to fp32 as it is loaded.  VEC: the consecutive columns a lane takes with one
+// load.  VEC = 1 is the mapping the kernel was written with (accumulator k of lane l holds column c0 + l + 64 k); with VEC = 4 or 8
+// (half maps whose rows are aligned to 8 / 16 bytes) accumulator k holds column c0 + (64 (k / VEC) + l) VEC + k % VEC, one 8- or
+// 16-byte load per lane and tap instead of VEC 2-byte ones.  A column is summed by one lane in view order under either mapping: the
+// same bits.  The vector forms store their rows as float4 where out and ld_out allow it (a wave-uniform test).
+template <typename T, int VEC, bool BILINEAR>
+__global__ void __launch_bounds__(256) lb_lift_kernel(const double *__restrict__ points, int64_t n, const T *__restrict__ feat, int d, int h,
                                                       int w, float scale_h, float scale_w, const int32_t *__restrict__ entry_views,
                                                       const int32_t *__restrict__ view_off, const double *__restrict__ w2c,
                                                       const double *__restrict__ intr, const double *__restrict__ depth, int W, int H, int cut,
@@ -101,39 +112,92 @@ __global__ void __launch_bounds__(256) lb_lift_kernel(const double *__restrict__
                 const int j = __ffsll((long long)m) - 1;
                 m &= m - 1;
                 const int vj = __shfl(v, j, 64), col = __shfl(px, j, 64), row = __shfl(py, j, 64);
-                const float *f = feat + (int64_t)vj * map;
+                const T *f = feat + (int64_t)vj * map;
                 if (BILINEAR) {
                     int r0, r1, q0, q1;
                     float wr0, wr1, wc0, wc1;
                     bilinear_tap(scale_h, row, h, r0, r1, wr0, wr1);
                     bilinear_tap(scale_w, col, w, q0, q1, wc0, wc1);
-                    const float *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
-                    const float *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+                    const T *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
+                    const T *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+                    if constexpr (VEC == 1) {
 #pragma unroll
-                    for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
-                        const int c = c0 + lane + k * GP_WAVE;
-                        if (c < d) {
-                            const float top = __builtin_fmaf(wc0, f00[c], wc1 * f01[c]);
-                            const float bot = __builtin_fmaf(wc0, f10[c], wc1 * f11[c]);
-                            acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                        for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                            const int c = c0 + lane + k * GP_WAVE;
+                            if (c < d) {
+                                const float top = __builtin_fmaf(wc0, gp_to_f32(f00[c]), wc1 * gp_to_f32(f01[c]));
+                                const float bot = __builtin_fmaf(wc0, gp_to_f32(f10[c]), wc1 * gp_to_f32(f11[c]));
+                                acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < LB_COLS_PER_LANE / VEC; ++j) {
+                            const int c = c0 + (j * GP_WAVE + lane) * VEC;   // (d is a multiple of VEC: the group is inside or outside)
+                            if (c < d) {
+                                float a00[VEC], a01[VEC], a10[VEC], a11[VEC];
+                                gp_load_f32<VEC>(f00 + c, a00);
+                                gp_load_f32<VEC>(f01 + c, a01);
+                                gp_load_f32<VEC>(f10 + c, a10);
+                                gp_load_f32<VEC>(f11 + c, a11);
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) {
+                                    const float top = __builtin_fmaf(wc0, a00[i], wc1 * a01[i]);
+                                    const float bot = __builtin_fmaf(wc0, a10[i], wc1 * a11[i]);
+                                    acc[j * VEC + i] += __builtin_fmaf(wr0, top, wr1 * bot);
+                                }
+                            }
                         }
                     }
                 } else {
-                    const float *fr = f + ((int64_t)row * w + col) * d;
+                    const T *fr = f + ((int64_t)row * w + col) * d;
+                    if constexpr (VEC == 1) {
 #pragma unroll
-                    for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
-                        const int c = c0 + lane + k * GP_WAVE;
-                        if (c < d) acc[k] += fr[c];
+                        for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                            const int c = c0 + lane + k * GP_WAVE;
+                            if (c < d) acc[k] += gp_to_f32(fr[c]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < LB_COLS_PER_LANE / VEC; ++j) {
+                            const int c = c0 + (j * GP_WAVE + lane) * VEC;
+                            if (c < d) {
+                                float a[VEC];
+                                gp_load_f32<VEC>(fr + c, a);
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) acc[j * VEC + i] += a[i];
+                            }
+                        }
                     }
                 }
             }
         }
         cnt = seen_by;                                               // (every column chunk sees the same views)
         const float den = cnt == 0 ? 1e-6f : (float)cnt;
+        if constexpr (VEC == 1) {
 #pragma unroll
-        for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
-            const int c = c0 + lane + k * GP_WAVE;
-            if (c < d) orow[c] = acc[k] / den;
+            for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                const int c = c0 + lane + k * GP_WAVE;
+                if (c < d) orow[c] = acc[k] / den;
+            }
+        } else {
+            const bool wide = (((uintptr_t)out | (uintptr_t)(ld_out * 4)) & 15) == 0;   // (wave-uniform) c is a multiple of 4
+#pragma unroll
+            for (int j = 0; j < LB_COLS_PER_LANE / VEC; ++j) {
+                const int c = c0 + (j * GP_WAVE + lane) * VEC;
+                if (c < d) {
+#pragma unroll
+                    for (int i = 0; i < VEC; i += 4) {
+                        const float4 q = make_float4(acc[j * VEC + i] / den, acc[j * VEC + i + 1] / den, acc[j * VEC + i + 2] / den,
+                                                     acc[j * VEC + i + 3] / den);
+                        if (wide) {
+                            *reinterpret_cast<float4 *>(orow + c + i) = q;
+                        } else {
+                            orow[c + i] = q.x; orow[c + i + 1] = q.y; orow[c + i + 2] = q.z; orow[c + i + 3] = q.w;
+                        }
+                    }
+                }
+            }
         }
     }
     if (lane == 0) {
@@ -178,19 +242,27 @@ struct LbWork {
 
 extern "C" int32_t gp_lift_batched_col_chunk(void) { return LB_COL_CHUNK; }
 
-extern "C" int gp_lift_batched_transpose(const float *src, int32_t nviews, int32_t d, int64_t hw, float *dst, void *stream_) {
+extern "C" int gp_lift_batched_transpose_t(const void *src, int32_t elem, int32_t nviews, int32_t d, int64_t hw, void *dst, void *stream_) {
     GP_CHECK_ARG(src && dst, "gp_lift_batched_transpose: null argument");
+    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_batched_transpose: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
     GP_CHECK_ARG(nviews >= 1 && nviews <= 65535 && d >= 1 && hw >= 1 && hw < (1ll << 31), "gp_lift_batched_transpose: %d views of %d x %lld",
                  nviews, d, (long long)hw);
     GP_CHECK_ARG((hw + 63) / 64 < (1ll << 31) && (d + 63) / 64 <= 65535, "gp_lift_batched_transpose: %d channels exceed the grid", d);
     {
-        const size_t bytes = (size_t)nviews * (size_t)d * (size_t)hw * 4;
+        const size_t bytes = (size_t)nviews * (size_t)d * (size_t)hw * gp_elem_size(elem);
         GP_CHECK_ARG(!lb_overlap(dst, bytes, src, bytes), "gp_lift_batched_transpose: dst overlaps src");
     }
-    lb_transpose_kernel<<<dim3((unsigned)((hw + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)nviews), 256, 0, gp_stream(stream_)>>>(src, d, hw,
-                                                                                                                                       dst);
+    const dim3 grid((unsigned)((hw + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)nviews);
+    if (elem == GP_ELEM_F32)
+        lb_transpose_kernel<float><<<grid, 256, 0, gp_stream(stream_)>>>(static_cast<const float *>(src), d, hw, static_cast<float *>(dst));
+    else
+        lb_transpose_kernel<uint16_t><<<grid, 256, 0, gp_stream(stream_)>>>(static_cast<const uint16_t *>(src), d, hw, static_cast<uint16_t *>(dst));
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_lift_batched_transpose(const float *src, int32_t nviews, int32_t d, int64_t hw, float *dst, void *stream_) {
+    return gp_lift_batched_transpose_t(src, GP_ELEM_F32, nviews, d, hw, dst, stream_);
 }
 
 extern "C" size_t gp_lift_batched_workspace_bytes(int64_t n, int32_t nviews) {
@@ -200,13 +272,15 @@ extern "C" size_t gp_lift_batched_workspace_bytes(int64_t n, int32_t nviews) {
     return cv.off;
 }
 
-extern "C" int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t d, int32_t h, int32_t w, const int64_t *view_entry,
-                               const double *w2c, const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
-                               int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible, int32_t fill,
-                               float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn,
-                               int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+extern "C" int gp_lift_batched_t(const double *points, int64_t n, const void *feat, int32_t elem, int32_t d, int32_t h, int32_t w,
+                                 const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth, int32_t nviews,
+                                 int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible,
+                                 int64_t max_visible, int32_t fill, float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *view_count,
+                                 uint8_t *view_keep, int64_t *nn, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
     GP_CHECK_ARG(points && feat && view_entry && w2c && intrinsics && out && seen && count && view_count && view_keep && status && workspace,
                  "gp_lift_batched: null argument");
+    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_batched: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
+    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)feat % 2 == 0, "gp_lift_batched: half maps at an odd address");
     GP_CHECK_ARG(n > 0 && n < (1ll << 31), "gp_lift_batched: n=%lld outside 1..2^31-1", (long long)n);
     GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_batched: %d views outside 1..65535", nviews);
     GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_out >= d, "gp_lift_batched: d=%d, map %d x %d, image %d x %d, ld_out=%lld",
@@ -218,7 +292,7 @@ extern "C" int gp_lift_batched(const double *points, int64_t n, const float *fea
     GP_CHECK_ARG(fill == 0 || nn, "gp_lift_batched: the fill writes nn");
     {
         // every output against every input and every other output, over their whole extents
-        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * 4;
+        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * gp_elem_size(elem);
         const void *in[] = {points, feat, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32, maps, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32, (size_t)nviews * px * 8};
         const void *o[] = {out, seen, count, view_count, view_keep, nn, status, workspace};
@@ -262,12 +336,26 @@ extern "C" int gp_lift_batched(const double *points, int64_t n, const float *fea
     const float sh = height > 1 ? (float)(h - 1) / (float)(height - 1) : 0.f;
     const float sw = width > 1 ? (float)(w - 1) / (float)(width - 1) : 0.f;
     const unsigned lb = (unsigned)((n * 64 + 255) / 256);
-    if (bilinear)
-        lb_lift_kernel<true><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
-                                                cut_bound, vis_thres, view_keep, out, ld_out, seen, count, nn);
-    else
-        lb_lift_kernel<false><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
-                                                 cut_bound, vis_thres, view_keep, out, ld_out, seen, count, nn);
+    const int vec = gp_elem_vec(feat, d, gp_elem_size(elem));    // (launch-uniform: every sampled row is aligned to the load it names)
+#define LB_LIFT(T, VEC)                                                                                                                      \
+    do {                                                                                                                                     \
+        if (bilinear)                                                                                                                        \
+            lb_lift_kernel<T, VEC, true><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views, k.view_off,  \
+                                                            w2c, intrinsics, depth, width, height, cut_bound, vis_thres, view_keep, out, ld_out, \
+                                                            seen, count, nn);                                                                \
+        else                                                                                                                                 \
+            lb_lift_kernel<T, VEC, false><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views, k.view_off, \
+                                                             w2c, intrinsics, depth, width, height, cut_bound, vis_thres, view_keep, out,     \
+                                                             ld_out, seen, count, nn);                                                       \
+    } while (0)
+    if (elem == GP_ELEM_F32) LB_LIFT(float, 1);
+    else if (elem == GP_ELEM_F16 && vec == 8) LB_LIFT(gp_f16, 8);
+    else if (elem == GP_ELEM_F16 && vec == 4) LB_LIFT(gp_f16, 4);
+    else if (elem == GP_ELEM_F16) LB_LIFT(gp_f16, 1);
+    else if (vec == 8) LB_LIFT(gp_bf16, 8);
+    else if (vec == 4) LB_LIFT(gp_bf16, 4);
+    else LB_LIFT(gp_bf16, 1);
+#undef LB_LIFT
     GP_CHECK_LAUNCH();
     // (4) the fill
     const unsigned nb1 = (unsigned)((n + 1 + 255) / 256);
@@ -281,4 +369,14 @@ extern "C" int gp_lift_batched(const double *points, int64_t n, const float *fea
     if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.k1, k.entry_rows, k.entry_off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, st);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t d, int32_t h, int32_t w, const int64_t *view_entry,
+                               const double *w2c, const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                               int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible, int32_t fill,
+                               float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn,
+                               int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    return gp_lift_batched_t(points, n, feat, GP_ELEM_F32, d, h, w, view_entry, w2c, intrinsics, depth, nviews, height, width, bilinear, cut_bound,
+                             vis_thres, min_visible, max_visible, fill, out, ld_out, seen, count, view_count, view_keep, nn, status, workspace,
+                             workspace_bytes, stream_);
 }

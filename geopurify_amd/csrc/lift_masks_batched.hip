@@ -161,7 +161,8 @@ struct LmbWork {
     uint8_t *c_live, *c_keep;
     float *xyz;
     // the segment decision and the in-view fill (as LvWork)
-    float *mt, *sscore, *f_rxyz;
+    void *mt;                                                    // (the rank-ordered transposed masks, in the masks' own element type)
+    float *sscore, *f_rxyz;
     int32_t *order, *cov, *f_rs, *rent, *qent, *part_i;
     double *part_d;
     int4 *tab;
@@ -173,7 +174,7 @@ struct LmbWork {
     size_t tmp_bytes;
     static size_t scan64_bytes(int64_t n) { return LmlWork::scan64_bytes(n); }
     LmbWork(GpCarver &cv, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int64_t total, int32_t words,
-            int64_t fill_cap) {
+            int64_t fill_cap, size_t esize) {
         size_t t[5] = {lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1), lb_scan_bytes(total + 1), scan64_bytes(n + 1)};
         tmp_bytes = 0;
         for (size_t b : t) tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
@@ -205,7 +206,7 @@ struct LmbWork {
         cx0 = cv.take<int32_t>(out_w);
         cy0 = cv.take<int32_t>(out_h);
         xyz = cv.take<float>(3 * n);
-        mt = cv.take<float>((size_t)nviews * q * h * w);
+        mt = cv.take<char>((size_t)nviews * q * h * w * esize);
         order = cv.take<int32_t>((size_t)nviews * q);
         sscore = cv.take<float>((size_t)nviews * q);
         cov = cv.take<int32_t>(total + 1);
@@ -297,26 +298,35 @@ extern "C" int gp_lift_masks_batched_lists(const double *points, int64_t n, cons
     return GP_OK;
 }
 
-extern "C" size_t gp_lift_masks_batched_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
-                                                        int64_t total, int32_t words, int64_t fill_cap) {
+extern "C" size_t gp_lift_masks_batched_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
+                                                          int32_t out_w, int64_t total, int32_t words, int64_t fill_cap) {
+    if (!gp_elem_ok(elem)) return 0;
     if (n <= 0 || n >= (1ll << 31) || nviews < 1 || nviews > 65535 || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 1 ||
         total >= (int64_t)INT32_MAX || words < 1 || words > 1024 || fill_cap < 0 || fill_cap > total)
         return 0;
     GpCarver cv(nullptr, 0);
-    LmbWork k(cv, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap ? fill_cap : total);
+    LmbWork k(cv, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap ? fill_cap : total, gp_elem_size(elem));
     return cv.off;
 }
 
-extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, const float *pred_masks, int32_t q,
-                                     int32_t h, int32_t w, const float *scores, const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0,
-                                     const float *tap_wy, int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x,
-                                     const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep, int64_t total,
-                                     int32_t words, int64_t fill_cap, const float *f_seg, const float *logit_seg, int32_t d, int32_t c, int32_t fill,
-                                     float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg, int64_t *status,
-                                     void *workspace, size_t workspace_bytes, void *stream_) {
+extern "C" size_t gp_lift_masks_batched_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
+                                                        int64_t total, int32_t words, int64_t fill_cap) {
+    return gp_lift_masks_batched_workspace_bytes_t(GP_ELEM_F32, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap);
+}
+
+extern "C" int gp_lift_masks_batched_t(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, const void *pred_masks,
+                                       int32_t elem, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0, const float *tap_wx,
+                                       const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w, const int64_t *ent_pt,
+                                       const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off,
+                                       const uint8_t *keep, int64_t total, int32_t words, int64_t fill_cap, const float *f_seg,
+                                       const float *logit_seg, int32_t d, int32_t c, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
+                                       int32_t *count, int64_t *nn, int32_t *seg, int64_t *status, void *workspace, size_t workspace_bytes,
+                                       void *stream_) {
     GP_CHECK_ARG(points && view_entry && pred_masks && scores && tap_x0 && tap_wx && tap_y0 && tap_wy && ent_pt && ent_x && ent_y && ent_view &&
                      view_off && keep && f_seg && logit_seg && out && seen && count && seg && status && workspace,
                  "gp_lift_masks_batched: null argument");
+    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_masks_batched: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
+    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)pred_masks % 2 == 0, "gp_lift_masks_batched: half masks at an odd address");
     GP_CHECK_ARG(n > 0 && n < (1ll << 31), "gp_lift_masks_batched: n=%lld outside 1..2^31-1", (long long)n);
     GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_masks_batched: %d views outside 1..65535", nviews);
     GP_CHECK_ARG(q >= 1 && q <= 1024, "gp_lift_masks_batched: %d queries outside 1..1024 (the score sort holds 1024)", q);
@@ -335,7 +345,7 @@ extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int6
         const size_t vq = (size_t)nviews * q;
         const void *in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off, keep,
                             f_seg, logit_seg};
-        const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * 4, vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
+        const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * gp_elem_size(elem), vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
                                    (size_t)out_h * 16, (size_t)total * 8, (size_t)total * 8, (size_t)total * 8, (size_t)total * 4,
                                    ((size_t)nviews + 1) * 8, (size_t)nviews, vq * d * 4, vq * c * 4};
         const void *o[] = {out, seen, count, nn, seg, status, workspace};
@@ -348,7 +358,7 @@ extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int6
         }
     }
     GpCarver cv(workspace, workspace_bytes);
-    LmbWork k(cv, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap);
+    LmbWork k(cv, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap, gp_elem_size(elem));
     if (!cv.ok()) {
         gp_set_error("gp_lift_masks_batched: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return GP_ENOMEM;
@@ -374,10 +384,18 @@ extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int6
     // the segment of every entry (gp_lift_masks.h: the kernels of gp_lift_masks_views)
     const int64_t hw = (int64_t)h * w;
     lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    transpose_views_kernel<<<dim3((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews), 256, 0, s>>>(pred_masks, q, (int)hw, k.mt,
-                                                                                                                        k.order);
-    lift_masks_views_kernel<<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(k.mt, q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy, out_h,
-                                                                                out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, seg);
+    const dim3 tg((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews);
+    const unsigned sb = (unsigned)((total * 64 + 255) / 256);
+#define LMB_SEGMENTS(T, BITS)                                                                                                                  \
+    do {                                                                                                                                       \
+        transpose_views_kernel<BITS><<<tg, 256, 0, s>>>(static_cast<const BITS *>(pred_masks), q, (int)hw, static_cast<BITS *>(k.mt), k.order);   \
+        lift_masks_views_kernel<T><<<sb, 256, 0, s>>>(static_cast<const T *>(k.mt), q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy,    \
+                                                      out_h, out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, seg);                             \
+    } while (0)
+    if (elem == GP_ELEM_F32) LMB_SEGMENTS(float, float);
+    else if (elem == GP_ELEM_F16) LMB_SEGMENTS(gp_f16, uint16_t);
+    else LMB_SEGMENTS(gp_bf16, uint16_t);
+#undef LMB_SEGMENTS
     GP_CHECK_LAUNCH();
     // the in-view fill
     fill_flags_kernel<<<eb, 256, 0, s>>>(seg, total, k.cov);
@@ -413,4 +431,16 @@ extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int6
     if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.k1, k.entry_rows, k.entry_off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, st);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, const float *pred_masks, int32_t q,
+                                     int32_t h, int32_t w, const float *scores, const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0,
+                                     const float *tap_wy, int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x,
+                                     const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep, int64_t total,
+                                     int32_t words, int64_t fill_cap, const float *f_seg, const float *logit_seg, int32_t d, int32_t c, int32_t fill,
+                                     float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg, int64_t *status,
+                                     void *workspace, size_t workspace_bytes, void *stream_) {
+    return gp_lift_masks_batched_t(points, n, view_entry, nviews, pred_masks, GP_ELEM_F32, q, h, w, scores, tap_x0, tap_wx, tap_y0, tap_wy, out_h,
+                                   out_w, ent_pt, ent_x, ent_y, ent_view, view_off, keep, total, words, fill_cap, f_seg, logit_seg, d, c, fill, out,
+                                   ld_out, seen, count, nn, seg, status, workspace, workspace_bytes, stream_);
 }

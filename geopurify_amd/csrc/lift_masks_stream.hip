@@ -92,14 +92,15 @@ struct LmsAddWork {
     uint8_t *c_live = nullptr, *c_keep;
     float *xyz = nullptr;
     // the segment decision and the in-view fill (as LmbWork)
-    float *mt = nullptr, *sscore = nullptr, *f_rxyz = nullptr;
+    void *mt = nullptr;                                          // (the rank-ordered transposed masks, in the masks' own element type)
+    float *sscore = nullptr, *f_rxyz = nullptr;
     int32_t *order = nullptr, *seg = nullptr, *cov = nullptr, *f_rs = nullptr, *rent = nullptr, *qent = nullptr, *part_i = nullptr;
     double *part_d = nullptr;
     int4 *tab = nullptr;
     char *tmp;
     size_t tmp_bytes;
     LmsAddWork(GpCarver &cv, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int64_t total,
-               int64_t fill_cap)
+               int64_t fill_cap, size_t esize)
         : t(cv, nviews) {
         const size_t a = lb_sort_bytes(nviews), b = lb_scan_bytes(total + 1);
         tmp_bytes = a > b ? a : b;
@@ -115,7 +116,7 @@ struct LmsAddWork {
             cx0 = cv.take<int32_t>(out_w);
             cy0 = cv.take<int32_t>(out_h);
             xyz = cv.take<float>(3 * n);
-            mt = cv.take<float>((size_t)nviews * q * h * w);
+            mt = cv.take<char>((size_t)nviews * q * h * w * esize);
             order = cv.take<int32_t>((size_t)nviews * q);
             sscore = cv.take<float>((size_t)nviews * q);
             seg = cv.take<int32_t>(total);
@@ -437,25 +438,33 @@ extern "C" int gp_lift_masks_stream_sizes(int64_t n, const void *state, size_t s
     return GP_OK;
 }
 
-extern "C" size_t gp_lift_masks_stream_add_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
-                                                           int64_t total, int64_t fill_cap) {
+extern "C" size_t gp_lift_masks_stream_add_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
+                                                             int32_t out_w, int64_t total, int64_t fill_cap) {
+    if (!gp_elem_ok(elem)) return 0;
     if (!ls_n_ok(n) || !lms_chunk_ok(nviews) || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 0 ||
         total >= (int64_t)INT32_MAX || fill_cap < 0 || fill_cap > total)
         return 0;
     GpCarver cv(nullptr, 0);
-    LmsAddWork k(cv, n, nviews, q, h, w, out_h, out_w, total, fill_cap ? fill_cap : total);
+    LmsAddWork k(cv, n, nviews, q, h, w, out_h, out_w, total, fill_cap ? fill_cap : total, gp_elem_size(elem));
     return cv.off;
 }
 
-extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *state, size_t state_bytes, const int64_t *view_entry, int32_t nviews,
-                                        const float *pred_masks, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0,
-                                        const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w,
-                                        const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view,
-                                        const int64_t *view_off, const uint8_t *keep, int64_t total, int64_t fill_cap, int32_t *rec_row,
-                                        int32_t *rec_seg, int64_t rec_base, int64_t rec_cap, int64_t *rec_off, int32_t *view_pos, int64_t *status,
-                                        void *workspace, size_t workspace_bytes, void *stream_) {
+extern "C" size_t gp_lift_masks_stream_add_workspace_bytes(int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
+                                                           int64_t total, int64_t fill_cap) {
+    return gp_lift_masks_stream_add_workspace_bytes_t(GP_ELEM_F32, n, nviews, q, h, w, out_h, out_w, total, fill_cap);
+}
+
+extern "C" int gp_lift_masks_stream_add_t(const double *points, int64_t n, void *state, size_t state_bytes, const int64_t *view_entry,
+                                          int32_t nviews, const void *pred_masks, int32_t elem, int32_t q, int32_t h, int32_t w, const float *scores,
+                                          const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h,
+                                          int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view,
+                                          const int64_t *view_off, const uint8_t *keep, int64_t total, int64_t fill_cap, int32_t *rec_row,
+                                          int32_t *rec_seg, int64_t rec_base, int64_t rec_cap, int64_t *rec_off, int32_t *view_pos, int64_t *status,
+                                          void *workspace, size_t workspace_bytes, void *stream_) {
     GP_CHECK_ARG(points && state && view_entry && view_off && keep && rec_off && view_pos && status && workspace,
                  "gp_lift_masks_stream_add: null argument");
+    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_masks_stream_add: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
+    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)pred_masks % 2 == 0, "gp_lift_masks_stream_add: half masks at an odd address");
     GP_CHECK_ARG(ls_n_ok(n), "gp_lift_masks_stream_add: n=%lld outside 1..2^31-1", (long long)n);
     GP_CHECK_ARG(lms_chunk_ok(nviews), "gp_lift_masks_stream_add: %d views outside 1..65535", nviews);
     GP_CHECK_ARG(total >= 0 && total < (int64_t)INT32_MAX, "gp_lift_masks_stream_add: %lld entries outside 0..2^31-2", (long long)total);
@@ -472,7 +481,7 @@ extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *s
     {
         const size_t vq = (size_t)nviews * q;
         const void *in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off, keep};
-        const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * 4, vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
+        const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * gp_elem_size(elem), vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
                                    (size_t)out_h * 16, (size_t)total * 8, (size_t)total * 8, (size_t)total * 8, (size_t)total * 4,
                                    ((size_t)nviews + 1) * 8, (size_t)nviews};
         const void *o[] = {state, rec_row, rec_seg, rec_off, view_pos, status, workspace};
@@ -486,7 +495,7 @@ extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *s
     }
     GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
     LmsState st(sv, n);
-    LmsAddWork k(cv, n, nviews, q, h, w, out_h, out_w, total, fill_cap);
+    LmsAddWork k(cv, n, nviews, q, h, w, out_h, out_w, total, fill_cap, gp_elem_size(elem));
     if (!cv.ok()) {
         gp_set_error("gp_lift_masks_stream_add: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return GP_ENOMEM;
@@ -516,10 +525,18 @@ extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *s
     // the segment of every entry
     const int64_t hw = (int64_t)h * w;
     lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    transpose_views_kernel<<<dim3((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews), 256, 0, s>>>(pred_masks, q, (int)hw, k.mt,
-                                                                                                                        k.order);
-    lift_masks_views_kernel<<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(k.mt, q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy, out_h,
-                                                                                out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, k.seg);
+    const dim3 tg((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews);
+    const unsigned sb = (unsigned)((total * 64 + 255) / 256);
+#define LMS_SEGMENTS(T, BITS)                                                                                                                  \
+    do {                                                                                                                                       \
+        transpose_views_kernel<BITS><<<tg, 256, 0, s>>>(static_cast<const BITS *>(pred_masks), q, (int)hw, static_cast<BITS *>(k.mt), k.order);   \
+        lift_masks_views_kernel<T><<<sb, 256, 0, s>>>(static_cast<const T *>(k.mt), q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy,    \
+                                                      out_h, out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, k.seg);                           \
+    } while (0)
+    if (elem == GP_ELEM_F32) LMS_SEGMENTS(float, float);
+    else if (elem == GP_ELEM_F16) LMS_SEGMENTS(gp_f16, uint16_t);
+    else LMS_SEGMENTS(gp_bf16, uint16_t);
+#undef LMS_SEGMENTS
     GP_CHECK_LAUNCH();
     // the in-view fill
     fill_flags_kernel<<<eb, 256, 0, s>>>(k.seg, total, k.cov);
@@ -537,6 +554,18 @@ extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *s
     lms_append_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.c_keep, k.voff, k.loc, k.seg, total, rec_base, rec_cap, rec_row, rec_seg);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *state, size_t state_bytes, const int64_t *view_entry, int32_t nviews,
+                                        const float *pred_masks, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0,
+                                        const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w,
+                                        const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view,
+                                        const int64_t *view_off, const uint8_t *keep, int64_t total, int64_t fill_cap, int32_t *rec_row,
+                                        int32_t *rec_seg, int64_t rec_base, int64_t rec_cap, int64_t *rec_off, int32_t *view_pos, int64_t *status,
+                                        void *workspace, size_t workspace_bytes, void *stream_) {
+    return gp_lift_masks_stream_add_t(points, n, state, state_bytes, view_entry, nviews, pred_masks, GP_ELEM_F32, q, h, w, scores, tap_x0, tap_wx,
+                                      tap_y0, tap_wy, out_h, out_w, ent_pt, ent_x, ent_y, ent_view, view_off, keep, total, fill_cap, rec_row, rec_seg,
+                                      rec_base, rec_cap, rec_off, view_pos, status, workspace, workspace_bytes, stream_);
 }
 
 extern "C" size_t gp_lift_masks_stream_finish_workspace_bytes(int64_t n, int32_t nviews, int64_t total, int32_t words) {

@@ -27,6 +27,7 @@
 // A pixel is read only after project_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0; bilinear taps are clamped to
 // the map; channel indices are guarded by c < d.  All offsets are 64-bit.
 #include "gp_lift_stream_state.h"
+#include "gp_map_elem.h"
 
 namespace {
 
@@ -101,10 +102,20 @@ __global__ void __launch_bounds__(256) ls_counts_kernel(const double *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------ the accumulating lift
+// the column accumulator k of a lane holds in the chunk at c0 (VEC = 1: the mapping the kernel was written with)
+template <int VEC>
+__device__ __forceinline__ int ls_col(int c0, int lane, int k) {
+    if constexpr (VEC == 1) return c0 + lane + k * GP_WAVE;
+    else return c0 + ((k / VEC) * GP_WAVE + lane) * VEC + k % VEC;
+}
+
 // One wave per point, over the views of the point's entry in this chunk.  BILINEAR as in lb_lift_kernel: the map is [h, w], the pixel
 // indexes the [H, W] image, and the resize is evaluated at the pixel with the arithmetic of lift_dense_bilinear_accum_kernel.
-template <bool BILINEAR>
-__global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict__ points, int64_t n, const float *__restrict__ feat, int d, int h,
+// T and VEC as in lb_lift_kernel: the maps' element type, converted to fp32 as it is loaded, and the consecutive columns a lane takes
+// with one load (1: the mapping the kernel was written with; 4 / 8: aligned half maps).  The sums stay fp32 whatever T is, so the
+// chunks of one stream may differ in type.
+template <typename T, int VEC, bool BILINEAR>
+__global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict__ points, int64_t n, const T *__restrict__ feat, int d, int h,
                                                        int w, float scale_h, float scale_w, const int32_t *__restrict__ entry_views,
                                                        const int32_t *__restrict__ view_off, const double *__restrict__ w2c,
                                                        const double *__restrict__ intr, const double *__restrict__ depth, int W, int H, int cut,
@@ -121,6 +132,9 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
     const double x = P[1], y = P[2], z = P[3];
     const int64_t map = (int64_t)h * w * d;
     float *srow = sums + p * ld_sum;
+    // (wave-uniform; the vector forms only) a lane's groups of four columns start at multiples of 4: float4 row traffic where the
+    // sums' base and pitch allow it
+    const bool wide = VEC > 1 && (((uintptr_t)sums | (uintptr_t)(ld_sum * 4)) & 15) == 0;
     int cnt = 0;
     for (int c0 = 0; c0 < d; c0 += LS_COL_CHUNK) {
         float acc[LS_COLS_PER_LANE];
@@ -143,10 +157,21 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
             }
             unsigned long long m = __ballot(vis);
             if (m && !seen_by) {                                     // (wave-uniform) the first view that sees the point: continue its sum
+                if (VEC > 1 && wide) {
 #pragma unroll
-                for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                    const int c = c0 + lane + k * GP_WAVE;
-                    if (c < d) acc[k] = srow[c];
+                    for (int k = 0; k < LS_COLS_PER_LANE; k += 4) {
+                        const int c = ls_col<VEC>(c0, lane, k);
+                        if (c < d) {
+                            const float4 q = *reinterpret_cast<const float4 *>(srow + c);
+                            acc[k] = q.x; acc[k + 1] = q.y; acc[k + 2] = q.z; acc[k + 3] = q.w;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                        const int c = ls_col<VEC>(c0, lane, k);
+                        if (c < d) acc[k] = srow[c];
+                    }
                 }
             }
             seen_by += __popcll(m);
@@ -154,39 +179,80 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
                 const int j = __ffsll((long long)m) - 1;
                 m &= m - 1;
                 const int vj = __shfl(v, j, 64), col = __shfl(px, j, 64), row = __shfl(py, j, 64);
-                const float *f = feat + (int64_t)vj * map;
+                const T *f = feat + (int64_t)vj * map;
                 if (BILINEAR) {
                     int r0, r1, q0, q1;
                     float wr0, wr1, wc0, wc1;
                     bilinear_tap(scale_h, row, h, r0, r1, wr0, wr1);
                     bilinear_tap(scale_w, col, w, q0, q1, wc0, wc1);
-                    const float *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
-                    const float *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+                    const T *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
+                    const T *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
+                    if constexpr (VEC == 1) {
 #pragma unroll
-                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                        const int c = c0 + lane + k * GP_WAVE;
-                        if (c < d) {
-                            const float top = __builtin_fmaf(wc0, f00[c], wc1 * f01[c]);
-                            const float bot = __builtin_fmaf(wc0, f10[c], wc1 * f11[c]);
-                            acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                            const int c = c0 + lane + k * GP_WAVE;
+                            if (c < d) {
+                                const float top = __builtin_fmaf(wc0, gp_to_f32(f00[c]), wc1 * gp_to_f32(f01[c]));
+                                const float bot = __builtin_fmaf(wc0, gp_to_f32(f10[c]), wc1 * gp_to_f32(f11[c]));
+                                acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < LS_COLS_PER_LANE / VEC; ++j) {
+                            const int c = c0 + (j * GP_WAVE + lane) * VEC;   // (d is a multiple of VEC: the group is inside or outside)
+                            if (c < d) {
+                                float a00[VEC], a01[VEC], a10[VEC], a11[VEC];
+                                gp_load_f32<VEC>(f00 + c, a00);
+                                gp_load_f32<VEC>(f01 + c, a01);
+                                gp_load_f32<VEC>(f10 + c, a10);
+                                gp_load_f32<VEC>(f11 + c, a11);
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) {
+                                    const float top = __builtin_fmaf(wc0, a00[i], wc1 * a01[i]);
+                                    const float bot = __builtin_fmaf(wc0, a10[i], wc1 * a11[i]);
+                                    acc[j * VEC + i] += __builtin_fmaf(wr0, top, wr1 * bot);
+                                }
+                            }
                         }
                     }
                 } else {
-                    const float *fr = f + ((int64_t)row * w + col) * d;
+                    const T *fr = f + ((int64_t)row * w + col) * d;
+                    if constexpr (VEC == 1) {
 #pragma unroll
-                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                        const int c = c0 + lane + k * GP_WAVE;
-                        if (c < d) acc[k] += fr[c];
+                        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                            const int c = c0 + lane + k * GP_WAVE;
+                            if (c < d) acc[k] += gp_to_f32(fr[c]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < LS_COLS_PER_LANE / VEC; ++j) {
+                            const int c = c0 + (j * GP_WAVE + lane) * VEC;
+                            if (c < d) {
+                                float a[VEC];
+                                gp_load_f32<VEC>(fr + c, a);
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) acc[j * VEC + i] += a[i];
+                            }
+                        }
                     }
                 }
             }
         }
         cnt = seen_by;                                               // (every column chunk sees the same views)
         if (!cnt) return;                                            // unseen by this chunk: the row is neither loaded nor stored
+        if (VEC > 1 && wide) {
 #pragma unroll
-        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-            const int c = c0 + lane + k * GP_WAVE;
-            if (c < d) srow[c] = acc[k];
+            for (int k = 0; k < LS_COLS_PER_LANE; k += 4) {
+                const int c = ls_col<VEC>(c0, lane, k);
+                if (c < d) *reinterpret_cast<float4 *>(srow + c) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
+                const int c = ls_col<VEC>(c0, lane, k);
+                if (c < d) srow[c] = acc[k];
+            }
         }
     }
     if (lane == 0) count[p] += cnt;
@@ -268,13 +334,16 @@ extern "C" size_t gp_lift_stream_add_workspace_bytes(int32_t nviews) {
     return cv.off;
 }
 
-extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const float *feat, int32_t d, int32_t h,
-                                  int32_t w, const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
-                                  int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres,
-                                  int64_t min_visible, int64_t max_visible, float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count,
-                                  uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+extern "C" int gp_lift_stream_add_t(const double *points, int64_t n, const void *state, size_t state_bytes, const void *feat, int32_t elem,
+                                    int32_t d, int32_t h, int32_t w, const int64_t *view_entry, const double *w2c, const double *intrinsics,
+                                    const double *depth, int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound,
+                                    double vis_thres, int64_t min_visible, int64_t max_visible, float *sums, int64_t ld_sum, int32_t *count,
+                                    int64_t *view_count, uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes,
+                                    void *stream_) {
     GP_CHECK_ARG(points && state && feat && view_entry && w2c && intrinsics && sums && count && view_count && view_keep && status && workspace,
                  "gp_lift_stream_add: null argument");
+    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_stream_add: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
+    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)feat % 2 == 0, "gp_lift_stream_add: half maps at an odd address");
     GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_add: n=%lld outside 1..2^31-1", (long long)n);
     GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_stream_add: %d views outside 1..65535", nviews);
     GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_sum >= d,
@@ -286,7 +355,7 @@ extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *s
     GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_add: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
     {
         // every output against every input and every other output, over their whole extents
-        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * 4;
+        const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * gp_elem_size(elem);
         const void *in[] = {points, state, feat, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32,      state_bytes,          maps, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32,
                                    (size_t)nviews * px * 8};
@@ -326,14 +395,38 @@ extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *s
     const float sh = height > 1 ? (float)(h - 1) / (float)(height - 1) : 0.f;
     const float sw = width > 1 ? (float)(w - 1) / (float)(width - 1) : 0.f;
     const unsigned lb = (unsigned)((n * 64 + 255) / 256);
-    if (bilinear)
-        ls_accum_kernel<true><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
-                                                 cut_bound, vis_thres, view_keep, sums, ld_sum, count);
-    else
-        ls_accum_kernel<false><<<lb, 256, 0, s>>>(points, n, feat, d, h, w, sh, sw, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height,
-                                                  cut_bound, vis_thres, view_keep, sums, ld_sum, count);
+    const int vec = gp_elem_vec(feat, d, gp_elem_size(elem));    // (launch-uniform: every sampled row is aligned to the load it names)
+#define LS_ACCUM(T, VEC)                                                                                                                      \
+    do {                                                                                                                                      \
+        if (bilinear)                                                                                                                         \
+            ls_accum_kernel<T, VEC, true><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views, k.view_off, \
+                                                             w2c, intrinsics, depth, width, height, cut_bound, vis_thres, view_keep, sums,     \
+                                                             ld_sum, count);                                                                  \
+        else                                                                                                                                  \
+            ls_accum_kernel<T, VEC, false><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views,          \
+                                                              k.view_off, w2c, intrinsics, depth, width, height, cut_bound, vis_thres,        \
+                                                              view_keep, sums, ld_sum, count);                                                \
+    } while (0)
+    if (elem == GP_ELEM_F32) LS_ACCUM(float, 1);
+    else if (elem == GP_ELEM_F16 && vec == 8) LS_ACCUM(gp_f16, 8);
+    else if (elem == GP_ELEM_F16 && vec == 4) LS_ACCUM(gp_f16, 4);
+    else if (elem == GP_ELEM_F16) LS_ACCUM(gp_f16, 1);
+    else if (vec == 8) LS_ACCUM(gp_bf16, 8);
+    else if (vec == 4) LS_ACCUM(gp_bf16, 4);
+    else LS_ACCUM(gp_bf16, 1);
+#undef LS_ACCUM
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const float *feat, int32_t d, int32_t h,
+                                  int32_t w, const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
+                                  int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres,
+                                  int64_t min_visible, int64_t max_visible, float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count,
+                                  uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    return gp_lift_stream_add_t(points, n, state, state_bytes, feat, GP_ELEM_F32, d, h, w, view_entry, w2c, intrinsics, depth, nviews, height, width,
+                                bilinear, cut_bound, vis_thres, min_visible, max_visible, sums, ld_sum, count, view_count, view_keep, status,
+                                workspace, workspace_bytes, stream_);
 }
 
 extern "C" size_t gp_lift_stream_finish_workspace_bytes(int64_t n) {

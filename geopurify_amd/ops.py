@@ -1492,23 +1492,36 @@ def segment_loss_reduce(term, coords, entry_cnt, num_entries, reduction, loss=No
 
 
 # ------------------------------------------------------------------------------------------ the lift over batched point clouds
+# the element types the batched lifts read maps and mask logits in, by the tag of the *_t entry points
+ELEM_TAG = {torch.float32: _lib.GP_ELEM_F32, torch.float16: _lib.GP_ELEM_F16, torch.bfloat16: _lib.GP_ELEM_BF16}
+
+
+def _chk_elem(t, name):
+    """a contiguous CUDA tensor of fp32, fp16 or bf16 -> its element-type tag"""
+    if t.dtype not in ELEM_TAG or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous CUDA torch.float32, torch.float16 or torch.bfloat16, got {t.dtype} cuda={t.is_cuda} "
+                         f"contig={t.is_contiguous()}")
+    return ELEM_TAG[t.dtype]
+
+
 def lift_batched_col_chunk():
     """channels one pass of gp_lift_batched's lift kernel holds in registers (asked of the library)"""
     return int(_lib.load().gp_lift_batched_col_chunk())
 
 
 def lift_batched_transpose(maps, out=None):
-    """maps fp32 [V, D, h, w] contiguous (NCHW) -> the pixel-major copy fp32 [V, h*w, D] that gp_lift_batched reads"""
+    """maps fp32, fp16 or bf16 [V, D, h, w] contiguous (NCHW) -> the pixel-major copy [V, h*w, D] of the same dtype that gp_lift_batched
+    reads (gp_lift_batched_transpose_t: the elements are moved, not converted)"""
     lib = _lib.load()
-    _chk(maps, torch.float32, "maps")
+    elem = _chk_elem(maps, "maps")
     if maps.dim() != 4:
         raise ValueError(f"lift_batched_transpose: expected maps [V, D, h, w], got {list(maps.shape)}")
     v, d, h, w = maps.shape
     if out is None:
-        out = torch.empty((v, h * w, d), dtype=torch.float32, device=maps.device)
-    elif _chk(out, torch.float32, "out").shape != (v, h * w, d):
+        out = torch.empty((v, h * w, d), dtype=maps.dtype, device=maps.device)
+    elif _chk(out, maps.dtype, "out").shape != (v, h * w, d):
         raise ValueError(f"lift_batched_transpose: expected out [{v}, {h * w}, {d}], got {list(out.shape)}")
-    check(lib.gp_lift_batched_transpose(_ptr(maps), v, d, h * w, _ptr(out), _stream()), "gp_lift_batched_transpose")
+    check(lib.gp_lift_batched_transpose_t(_ptr(maps), elem, v, d, h * w, _ptr(out), _stream()), "gp_lift_batched_transpose")
     return out
 
 
@@ -1523,12 +1536,14 @@ class LiftBatched:
 
 def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, image_hw, bilinear, cut_bound, vis_thres, min_visible,
                  max_visible, fill=True, buffers=None, workspace=None):
-    """gp_lift_batched, no sync: points f64 [n,4]; maps_pm fp32 [V, h*w, D] pixel-major with map_hw = (h, w); view_entry i64 [V]; w2c f64
+    """gp_lift_batched_t, no sync: points f64 [n,4]; maps_pm fp32, fp16 or bf16 [V, h*w, D] pixel-major (read in place, the sums and the
+    rows are fp32 whatever the maps' dtype) with map_hw = (h, w); view_entry i64 [V]; w2c f64
     [V,4,4]; intrinsics f64 [V,4]; depth f64 [V,H,W] or None; image_hw = (H, W).  -> LiftBatched.  buffers: optional dict of
     caller-owned outputs by attribute name (out: fp32 rows of any pitch); workspace: uint8 of at least
     gp_lift_batched_workspace_bytes(n, V)."""
     lib = _lib.load()
-    _chk(points, torch.float64, "points"), _chk(maps_pm, torch.float32, "maps_pm"), _chk(view_entry, torch.int64, "view_entry")
+    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry")
+    elem = _chk_elem(maps_pm, "maps_pm")
     _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     (h, w), (H, W) = map_hw, image_hw
     n, dev = points.shape[0], points.device
@@ -1556,11 +1571,11 @@ def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, im
     out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
     need = lib.gp_lift_batched_workspace_bytes(n, nv)
     ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
-    check(lib.gp_lift_batched(_ptr(points), n, _ptr(maps_pm), d, int(h), int(w), _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv,
-                              int(H), int(W), 1 if bilinear else 0, int(cut_bound), float(vis_thres), int(min_visible), int(max_visible),
-                              1 if fill else 0, _ptr(out), out.stride(0), _ptr(got["seen"]), _ptr(got["count"]), _ptr(got["view_count"]),
-                              _ptr(got["view_keep"]), _ptr(got.get("nn")), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()),
-          "gp_lift_batched")
+    check(lib.gp_lift_batched_t(_ptr(points), n, _ptr(maps_pm), elem, d, int(h), int(w), _ptr(view_entry), _ptr(w2c), _ptr(intrinsics),
+                                _ptr(depth), nv, int(H), int(W), 1 if bilinear else 0, int(cut_bound), float(vis_thres), int(min_visible),
+                                int(max_visible), 1 if fill else 0, _ptr(out), out.stride(0), _ptr(got["seen"]), _ptr(got["count"]),
+                                _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(got.get("nn")), _ptr(got["status"]), _ptr(ws), ws.numel(),
+                                _stream()), "gp_lift_batched")
     return LiftBatched(out, got["seen"], got["count"], got["view_count"], got["view_keep"], got.get("nn"), got["status"])
 
 
@@ -1604,13 +1619,13 @@ def lift_stream_finish_workspace_bytes(n):
 
 def lift_stream_add(st, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, image_hw, bilinear, cut_bound, vis_thres, min_visible, max_visible,
                     buffers=None, workspace=None):
-    """gp_lift_stream_add, no sync: one chunk of views onto the LiftStreamState st; the chunk's arrays as ops.lift_batched takes them
-    (maps_pm fp32 [V, h*w, D] pixel-major).  -> (view_count i64 [V], view_keep u8 [V]) of the chunk.  buffers: optional dict of
+    """gp_lift_stream_add_t, no sync: one chunk of views onto the LiftStreamState st; the chunk's arrays as ops.lift_batched takes them
+    (maps_pm fp32, fp16 or bf16 [V, h*w, D] pixel-major; the chunks of one stream may differ in dtype).  -> (view_count i64 [V], view_keep u8 [V]) of the chunk.  buffers: optional dict of
     caller-owned view_count / view_keep; workspace: uint8 of at least gp_lift_stream_add_workspace_bytes(V)."""
     lib = _lib.load()
     who = "lift_stream_add"
-    _chk(maps_pm, torch.float32, "maps_pm"), _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c")
-    _chk(intrinsics, torch.float64, "intrinsics")
+    elem = _chk_elem(maps_pm, "maps_pm")
+    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     (h, w), (H, W) = map_hw, image_hw
     n, d, dev = st.points.shape[0], st.sums.shape[1], st.points.device
     if maps_pm.dim() != 3 or maps_pm.shape[1] != h * w or maps_pm.shape[2] != d:
@@ -1623,10 +1638,10 @@ def lift_stream_add(st, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, ima
         raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
     got = _outputs(who, {"view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,))}, buffers, dev)
     ws = _ws(lib.gp_lift_stream_add_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
-    check(lib.gp_lift_stream_add(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(maps_pm), d, int(h), int(w), _ptr(view_entry),
-                                 _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv, int(H), int(W), 1 if bilinear else 0, int(cut_bound),
-                                 float(vis_thres), int(min_visible), int(max_visible), _ptr(st.sums), st.sums.stride(0), _ptr(st.count),
-                                 _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(st.status), _ptr(ws), ws.numel(), _stream()),
+    check(lib.gp_lift_stream_add_t(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(maps_pm), elem, d, int(h), int(w), _ptr(view_entry),
+                                   _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv, int(H), int(W), 1 if bilinear else 0, int(cut_bound),
+                                   float(vis_thres), int(min_visible), int(max_visible), _ptr(st.sums), st.sums.stride(0), _ptr(st.count),
+                                   _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(st.status), _ptr(ws), ws.numel(), _stream()),
           "gp_lift_stream_add")
     return got["view_count"], got["view_keep"]
 
@@ -1808,15 +1823,16 @@ class LiftMasksBatched:
 
 def lift_masks_batched(points, view_entry, pred_masks, scores, taps, out_hw, ent, view_off, view_keep, total, words, f_seg, logit_seg, fill=True,
                        fill_cap=None, buffers=None, workspace=None):
-    """gp_lift_masks_batched, no sync: from view-major entries to the fused rows.  points f64 [n,4]; view_entry i64 [V]; pred_masks f32
-    [V,Q,h,w]; scores f32 [V,Q]; taps = (x0 i32 [W], wx f32 [W,4], y0 i32 [H], wy f32 [H,4]); out_hw = (H, W); ent = (pt, x, y i64
+    """gp_lift_masks_batched_t, no sync: from view-major entries to the fused rows.  points f64 [n,4]; view_entry i64 [V]; pred_masks f32,
+    f16 or bf16 [V,Q,h,w] (read in place; the workspace's transposed copy keeps their dtype); scores f32 [V,Q]; taps = (x0 i32 [W], wx f32 [W,4], y0 i32 [H], wy f32 [H,4]); out_hw = (H, W); ent = (pt, x, y i64
     [>= total], view i32 [>= total]) -- lift_masks_batched_lists' or the caller's own: entries of a view contiguous, rows ascending inside
     it --; view_off i64 [V+1]; view_keep u8 [V]; words >= ceil(most views of one entry / 64); f_seg f32 [V,Q,d], logit_seg f32 [V,Q,C]
     (segment_tables; d a multiple of 4).  -> LiftMasksBatched.  buffers: optional dict of caller-owned outputs by attribute name (out:
     fp32 rows of a pitch that is a multiple of 4); workspace: uint8 of at least gp_lift_masks_batched_workspace_bytes(...)."""
     lib = _lib.load()
     who = "lift_masks_batched"
-    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry"), _chk(pred_masks, torch.float32, "pred_masks")
+    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry")
+    elem = _chk_elem(pred_masks, "pred_masks")
     _chk(scores, torch.float32, "scores"), _chk(view_off, torch.int64, "view_off"), _chk(view_keep, torch.uint8, "view_keep")
     _chk(f_seg, torch.float32, "f_seg"), _chk(logit_seg, torch.float32, "logit_seg")
     tx0, twx, ty0, twy = taps
@@ -1847,13 +1863,13 @@ def lift_masks_batched(points, view_entry, pred_masks, scores, taps, out_hw, ent
     out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
     if fill_cap is None:
         fill_cap = min(total, max(total // 4, 65536))
-    need = lib.gp_lift_masks_batched_workspace_bytes(n, nv, Q, h, w, int(H), int(W), total, int(words), int(fill_cap))
+    need = lib.gp_lift_masks_batched_workspace_bytes_t(elem, n, nv, Q, h, w, int(H), int(W), total, int(words), int(fill_cap))
     ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
-    check(lib.gp_lift_masks_batched(_ptr(points), n, _ptr(view_entry), nv, _ptr(pred_masks), Q, h, w, _ptr(scores), _ptr(tx0), _ptr(twx), _ptr(ty0),
-                                    _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y), _ptr(view), _ptr(view_off), _ptr(view_keep), total,
-                                    int(words), int(fill_cap), _ptr(f_seg), _ptr(logit_seg), d, C, 1 if fill else 0, _ptr(out), out.stride(0),
-                                    _ptr(got["seen"]), _ptr(got["count"]), _ptr(got.get("nn")), _ptr(got["seg"]), _ptr(got["status"]), _ptr(ws),
-                                    ws.numel(), _stream()), "gp_lift_masks_batched")
+    check(lib.gp_lift_masks_batched_t(_ptr(points), n, _ptr(view_entry), nv, _ptr(pred_masks), elem, Q, h, w, _ptr(scores), _ptr(tx0), _ptr(twx),
+                                      _ptr(ty0), _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y), _ptr(view), _ptr(view_off), _ptr(view_keep),
+                                      total, int(words), int(fill_cap), _ptr(f_seg), _ptr(logit_seg), d, C, 1 if fill else 0, _ptr(out),
+                                      out.stride(0), _ptr(got["seen"]), _ptr(got["count"]), _ptr(got.get("nn")), _ptr(got["seg"]),
+                                      _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_lift_masks_batched")
     return LiftMasksBatched(out, got["seen"], got["count"], got.get("nn"), got["seg"], got["status"])
 
 
@@ -1898,11 +1914,27 @@ def lift_masks_stream_sizes_workspace_bytes(num_views):
     return int(_lib.load().gp_lift_masks_stream_sizes_workspace_bytes(int(num_views)))
 
 
-def lift_masks_stream_add_workspace_bytes(n, num_views, Q, mask_hw, image_hw, total, fill_cap=None):
+def _elem_of(dtype, who):
+    if dtype not in ELEM_TAG:
+        raise ValueError(f"{who}: the masks are torch.float32, torch.float16 or torch.bfloat16, got {dtype}")
+    return ELEM_TAG[dtype]
+
+
+def lift_masks_batched_workspace_bytes(n, num_views, Q, mask_hw, image_hw, total, words, fill_cap=None, dtype=torch.float32):
+    """bytes of gp_lift_masks_batched_t's workspace for pred_masks of `dtype`: the transposed copy in it keeps the masks' element size"""
     if fill_cap is None:
         fill_cap = min(total, max(total // 4, 65536))
-    return int(_lib.load().gp_lift_masks_stream_add_workspace_bytes(int(n), int(num_views), int(Q), int(mask_hw[0]), int(mask_hw[1]),
-                                                                    int(image_hw[0]), int(image_hw[1]), int(total), int(fill_cap)))
+    return int(_lib.load().gp_lift_masks_batched_workspace_bytes_t(_elem_of(dtype, "lift_masks_batched_workspace_bytes"), int(n), int(num_views),
+                                                                   int(Q), int(mask_hw[0]), int(mask_hw[1]), int(image_hw[0]), int(image_hw[1]),
+                                                                   int(total), int(words), int(fill_cap)))
+
+
+def lift_masks_stream_add_workspace_bytes(n, num_views, Q, mask_hw, image_hw, total, fill_cap=None, dtype=torch.float32):
+    if fill_cap is None:
+        fill_cap = min(total, max(total // 4, 65536))
+    return int(_lib.load().gp_lift_masks_stream_add_workspace_bytes_t(_elem_of(dtype, "lift_masks_stream_add_workspace_bytes"), int(n),
+                                                                      int(num_views), int(Q), int(mask_hw[0]), int(mask_hw[1]), int(image_hw[0]),
+                                                                      int(image_hw[1]), int(total), int(fill_cap)))
 
 
 def lift_masks_stream_finish_workspace_bytes(n, num_views, total, words):
@@ -1931,7 +1963,7 @@ def lift_masks_stream_sizes(st, view_entry, view_count, view_keep, buffers=None,
 def lift_masks_stream_add(st, view_entry, pred_masks, scores, taps, out_hw, ent, view_off, view_keep, total, rec_row, rec_seg, rec_base, rec_off,
                           view_pos, fill_cap=None, workspace=None):
     """gp_lift_masks_stream_add, no sync: one chunk of views onto the LiftMasksStreamState st.  The chunk's arrays as
-    ops.lift_masks_batched takes them (view_entry i64 [V]; pred_masks f32 [V,Q,h,w]; scores f32 [V,Q]; taps; out_hw; ent = (pt, x, y,
+    ops.lift_masks_batched takes them (view_entry i64 [V]; pred_masks f32, f16 or bf16 [V,Q,h,w]; scores f32 [V,Q]; taps; out_hw; ent = (pt, x, y,
     view) and view_off i64 [V+1], view_keep u8 [V], total from lift_masks_batched_lists ON THE CHUNK).  What the caller keeps: rec_row /
     rec_seg i32 [capacity] (the chunk's records go to rec_base ..), rec_off i64 [V+1] and view_pos i32 [V] (the chunk's slices of the
     per-view arrays; rec_off[V] is the next chunk's rec_off[0]).  total = 0: nothing is visible in a kept view of the chunk -- pred_masks,
@@ -1949,9 +1981,10 @@ def lift_masks_stream_add(st, view_entry, pred_masks, scores, taps, out_hw, ent,
     Q = h = w = 1
     tx0 = twx = ty0 = twy = None
     pt = x = y = view = None
-    cap = 0
+    cap, elem = 0, _lib.GP_ELEM_F32
     if total:
-        _chk(pred_masks, torch.float32, "pred_masks"), _chk(scores, torch.float32, "scores")
+        elem = _chk_elem(pred_masks, "pred_masks")
+        _chk(scores, torch.float32, "scores")
         _chk(rec_row, torch.int32, "rec_row"), _chk(rec_seg, torch.int32, "rec_seg")
         tx0, twx, ty0, twy = taps
         _chk(tx0, torch.int32, "tap_x0"), _chk(twx, torch.float32, "tap_wx"), _chk(ty0, torch.int32, "tap_y0"), _chk(twy, torch.float32, "tap_wy")
@@ -1969,13 +2002,13 @@ def lift_masks_stream_add(st, view_entry, pred_masks, scores, taps, out_hw, ent,
         cap = rec_row.shape[0]
     if fill_cap is None:
         fill_cap = min(total, max(total // 4, 65536))
-    need = lib.gp_lift_masks_stream_add_workspace_bytes(n, nv, Q, h, w, int(H), int(W), total, int(fill_cap))
+    need = lib.gp_lift_masks_stream_add_workspace_bytes_t(elem, n, nv, Q, h, w, int(H), int(W), total, int(fill_cap))
     ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
-    check(lib.gp_lift_masks_stream_add(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(view_entry), nv, _ptr(pred_masks), Q, h, w,
-                                       _ptr(scores), _ptr(tx0), _ptr(twx), _ptr(ty0), _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y),
-                                       _ptr(view), _ptr(view_off), _ptr(view_keep), total, int(fill_cap), _ptr(rec_row), _ptr(rec_seg),
-                                       int(rec_base), max(cap, int(rec_base)), _ptr(rec_off), _ptr(view_pos), _ptr(st.status), _ptr(ws), ws.numel(),
-                                       _stream()), "gp_lift_masks_stream_add")
+    check(lib.gp_lift_masks_stream_add_t(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(view_entry), nv, _ptr(pred_masks), elem, Q, h, w,
+                                         _ptr(scores), _ptr(tx0), _ptr(twx), _ptr(ty0), _ptr(twy), int(H), int(W), _ptr(pt), _ptr(x), _ptr(y),
+                                         _ptr(view), _ptr(view_off), _ptr(view_keep), total, int(fill_cap), _ptr(rec_row), _ptr(rec_seg),
+                                         int(rec_base), max(cap, int(rec_base)), _ptr(rec_off), _ptr(view_pos), _ptr(st.status), _ptr(ws),
+                                         ws.numel(), _stream()), "gp_lift_masks_stream_add")
 
 
 class LiftMasksStreamFinish:

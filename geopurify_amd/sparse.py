@@ -53,6 +53,9 @@ differentiable=True) -- puts y.F into the autograd graph, so a loss on the purif
 through the quantiser the points' features (ops.pool_transpose_build, pool_ell_transpose, pool_ell_wgrad, affinity_softmax_backward,
 l2norm_rows_backward).  The default takes no gradients, like the reference's evaluate_scene; segment (labels and counts) never does.
 
+All four lifts read the VLM's large outputs -- the feature maps [V,D,h,w], the mask logits [V,Q,h,w] -- in fp32, fp16 or bf16 as they are:
+a VLM run under autocast hands over half tensors, and no fp32 copy of them is made.  The kernels convert every loaded element to fp32
+(exact for both half types) and sum in fp32, so the result is, bit for bit, that of the same call on the caller's own upcast copy.
 All four lifts decide visibility against the caller's depth maps, by p_z > 0 alone (depth=None), or -- depth="render" -- against depth
 maps rendered from the points themselves, the reference's way when it has poses and a reconstructed cloud but no sensor depth
 (models/utils/fusion_util.py:126-130):
@@ -63,7 +66,7 @@ render_depth is ops.render_depth_batched: the z-buffer of every view over the po
 streams render a chunk's views from their own entry tables (ops.render_depth_stream) into a chunk-sized scratch buffer.
 lift is the reference's lift_lseg_features (models/affinity_module.py:404-452) with the point -> pixel mapping of
 models/utils/fusion_util.py:45-147 and the loader's view-drop rule (dataset/data_loader_ablation.py:254-288), for all entries and all
-views in one call of ops.lift_batched, then ops.gather_rows for the fill.
+views in one call of ops.lift_batched (the maps pixel-major in their own dtype), then ops.gather_rows for the fill.
 LiftStream is the same lift resumable over chunks of views: ops.lift_stream_begin (the entry tables, once), ops.lift_stream_add per chunk
 (fp32 sums continued in view order), ops.lift_stream_finish (divide and fill; a snapshot), ops.gather_rows.
 lift_masks is the reference's lift_xdecoder_features (models/affinity_module.py:455-714: per-view mask-embedding lift, in-view nearest
@@ -153,8 +156,9 @@ LIFT_MODES = ("nearest", "bilinear")
 
 
 class Views:
-    """The views of a batch of scenes: features fp32 [V,D,h,w] (the frozen VLM's maps, NCHW contiguous or torch.channels_last; other
-    floating dtypes are upcast), view_entry integer [V] (the batch entry a view looks at), world_to_camera fp64 [V,4,4], intrinsics fp64
+    """The views of a batch of scenes: features fp32, fp16 or bf16 [V,D,h,w] (the frozen VLM's maps, NCHW contiguous or
+    torch.channels_last; half maps are read as they are, with no fp32 copy, and give the bits of their fp32 copy; fp64 and other
+    floating dtypes are upcast to fp32), view_entry integer [V] (the batch entry a view looks at), world_to_camera fp64 [V,4,4], intrinsics fp64
     [V,4] = fx, fy, cx, cy at the image size, depth fp64 [V,H,W], None (a point is visible where it projects inside the image with
     p_z > 0: no occlusion) or the string "render" (the depth maps are rendered from the points themselves, see render_depth: occlusion
     without sensor depth), image_shape = (H, W) shared by all views (default: the maps' (h, w)).
@@ -260,6 +264,14 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
     return (V, D, h, w, H, W) if views is not None else None
 
 
+def _lift_maps(Fm):
+    """the maps as the lift kernels read them: fp32, fp16 and bf16 stay what they are (the kernels convert every loaded element to
+    fp32, which is exact, so a half map gives the bits of its fp32 copy without that copy existing); fp64 and any other floating
+    dtype are upcast to fp32"""
+    maps = Fm.detach()
+    return maps if maps.dtype in ops.ELEM_TAG else maps.to(torch.float32)
+
+
 def render_depth(points, view_entry, world_to_camera, intrinsics, image_shape, *, cut_bound=0):
     """The depth maps the reference renders from the cloud itself when it is given no sensor depth (models/utils/fusion_util.py:126-130,
     the ScanNet mapper with depth passed as a str), for all views of all entries in one call, entries never mixing.  points,
@@ -336,8 +348,13 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     seen, keeps zero rows; a view whose entry has no points has view_count 0.  The result is the same bits as HotPath.lift_dense /
     lift_lseg on each scene by itself.  -> Lifted.  No gradients: the VLM is frozen and the reference lifts under no_grad, so maps that
     require grad are refused and the points are detached.
+    fp16 / bf16 maps: every sampled element is converted to fp32 as it is loaded (exact) and takes the fp32 arithmetic, so the result
+    is bit for bit lift(points, Views(features.float(), ...)) -- without that copy: beside the maps the call holds nothing of their
+    size (channels_last) or one transposed buffer of their own dtype (NCHW).  Half rows whose length and base address allow it
+    (D % 8 == 0 and 16-byte aligned, or D % 4 == 0 and 8-byte aligned) are read 16 or 8 bytes per lane; any other half tensor 2 bytes.
     Inside: ops.lift_batched (the entry tables, the per-view counts, the fused lift kernel over pixel-major maps -- a channels_last
-    tensor is read in place, an NCHW one goes through ops.lift_batched_transpose once --, the per-entry masked 1-NN) and
+    tensor is read in place, an NCHW one goes through ops.lift_batched_transpose once, into a buffer of the maps' dtype --, the
+    per-entry masked 1-NN) and
     ops.gather_rows; with "render", ops.render_depth_batched first (no read-back of its own: the lift's status says the same).
     ValueError before any kernel: shape / dtype / device mismatches, CPU tensors, an unknown mode, a depth string other than "render",
     maps that require grad, more than 65535 views, N >= 2^31; from the ONE status read-back, taken after the last launch (no buffer is sized by what it
@@ -349,11 +366,11 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     dev = P.device
     with torch.cuda.device(dev), torch.no_grad():
         pts = P.detach().to(torch.float64).contiguous()
-        maps = Fm.detach().to(torch.float32)
+        maps = _lift_maps(Fm)                                                # (fp32, fp16 and bf16 as they are: no fp32 copy of half maps)
         if maps.is_contiguous(memory_format=torch.channels_last):
             maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)          # (a view: channels_last is pixel-major already)
         else:
-            maps_pm = ops.lift_batched_transpose(maps.contiguous())
+            maps_pm = ops.lift_batched_transpose(maps.contiguous())          # (of the maps' own dtype)
         ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
         if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
             Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
@@ -391,8 +408,10 @@ class LiftStream:
          when the chunk is added.
       3. finish is a snapshot: it writes new tensors from the sums and counts and changes neither, so add and finish may go on
          alternating (the online use: a result after every chunk for one divide pass over [N, D] and the fill).
-      4. Maps of other floating dtypes are upcast per chunk; a channels_last chunk is read in place, an NCHW chunk is transposed into
-         one scratch buffer of the stream's that grows only when a chunk is larger than every chunk before it.  Apart from the
+      4. fp32, fp16 and bf16 chunks are read as they are and may alternate inside one stream (the sums are fp32 whatever the chunk's
+         dtype; a half chunk gives the bits of its fp32 copy); maps of other floating dtypes are upcast to fp32 per chunk.  A
+         channels_last chunk is read in place, an NCHW chunk is transposed, in its own dtype, into one scratch buffer of the stream's
+         that is sized in bytes, shared by all dtypes, and grows only when a chunk needs more bytes than every chunk before it.  Apart from the
          per-view count and keep vectors the stream holds nothing that grows with the views added: the state is the entry tables
          (8 bytes per point), the fp32 sums [N, D] and the counts [N].
       5. With depth="render" a chunk's depth maps are rendered from the stream's entry tables (ops.render_depth_stream: no sort, no
@@ -444,14 +463,17 @@ class LiftStream:
             raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
         Fm, E, M, K, Dp = views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         with torch.cuda.device(self._device), torch.no_grad():
-            maps = Fm.detach().to(torch.float32)
+            maps = _lift_maps(Fm)                                            # (fp32, fp16 and bf16 as they are; the sums are fp32)
             if maps.is_contiguous(memory_format=torch.channels_last):
                 maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)      # (a view: channels_last is pixel-major already)
             else:
-                if self._scratch is None or self._scratch.numel() < maps.numel():
+                nbytes = maps.numel() * maps.element_size()                 # (the scratch is sized in bytes: chunks of any dtype share it)
+                words = -(-nbytes // 4)                                      # (kept as fp32 words: an fp32 chunk's element count)
+                if self._scratch is None or self._scratch.numel() < words:
                     self._scratch = None                                    # (freed before the larger one is taken)
-                    self._scratch = torch.empty(maps.numel(), dtype=torch.float32, device=self._device)
-                maps_pm = ops.lift_batched_transpose(maps.contiguous(), out=self._scratch[:maps.numel()].view(V, h * w, D))
+                    self._scratch = torch.empty(words, dtype=torch.float32, device=self._device)
+                maps_pm = ops.lift_batched_transpose(maps.contiguous(),
+                                                     out=self._scratch.view(torch.uint8)[:nbytes].view(maps.dtype).view(V, h * w, D))
             need = ops.lift_stream_add_workspace_bytes(V)
             if self._ws_add is None or self._ws_add.numel() < need:
                 self._ws_add = None
@@ -501,7 +523,8 @@ _TABLE_ROWS = 2 ** 24                                       # rows of one ops.se
 
 
 class MaskViews:
-    """The views of a batch of scenes with the X-Decoder form of the VLM's outputs: pred_masks fp32 [V,Q,h,w] (mask logits), pred_logits
+    """The views of a batch of scenes with the X-Decoder form of the VLM's outputs: pred_masks fp32, fp16 or bf16 [V,Q,h,w] (mask logits;
+    half logits are read as they are and give the bits of their fp32 copy), pred_logits
     floating [V,Q,C+1] (class logits, the last column "no object"), mask_embed floating [V,Q,D]; view_entry, world_to_camera,
     intrinsics, depth exactly as in Views (a tensor, None or "render"); image_shape = (H, W), required: the reference's cfg.mask_shape, the size the masks are
     resized to and the depths and intrinsics refer to (h <= H and w <= W).  Every view has the same number of queries Q.  lift_masks
@@ -553,8 +576,8 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
     if views is not None:
         Pm, Pl, Em = views.pred_masks, views.pred_logits, views.mask_embed
         E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
-        if not torch.is_tensor(Pm) or Pm.dim() != 4 or min(Pm.shape) < 1 or Pm.dtype != torch.float32:
-            raise ValueError(f"{who}: views.pred_masks must be fp32 [V, Q, h, w] with V, Q, h, w >= 1, got "
+        if not torch.is_tensor(Pm) or Pm.dim() != 4 or min(Pm.shape) < 1 or Pm.dtype not in ops.ELEM_TAG:
+            raise ValueError(f"{who}: views.pred_masks must be fp32, fp16 or bf16 [V, Q, h, w] with V, Q, h, w >= 1, got "
                              f"{(list(Pm.shape), Pm.dtype) if torch.is_tensor(Pm) else type(Pm).__name__}")
         V, Q, h, w = Pm.shape
         if V > 65535:
@@ -629,12 +652,16 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
       7. count = the slots, seen = count > 0, unseen rows are zero; with fill an unseen point of an entry that has seen points takes
          the row of the seen point of its entry minimising (d^2, row) -- lift's step 5;
       8. text_features = normalize(text_embed): the reference returns those (:628 rebinds the name).
-    The rows are the same bits as HotPath.lift_masks' kernels on each scene by itself.  -> LiftedMasks.  No gradients: inputs that
+    The rows are the same bits as HotPath.lift_masks' kernels on each scene by itself.  -> LiftedMasks.  fp16 / bf16 pred_masks are read
+    in place: the 16 taps of a pixel are converted to fp32 as they are loaded (exact), the resize, the products and the decision are
+    the fp32 call's, so the result is bit for bit lift_masks on pred_masks.float() -- without that copy, and with the call's own
+    rank-ordered transposed copy (V * h * w * Q elements of the workspace) in the masks' dtype too: half the bytes.  pred_logits and
+    mask_embed are small and upcast by torch.  No gradients: inputs that
     require grad are refused and the points are detached.  Deterministic: no float atomics, no order that depends on arrival.
     Inside: ops.lift_masks_batched_lists (entry tables, ordered visible lists), ops.segment_tables, ops.lift_masks_batched (segments,
     in-view fill, point -> view lists over a bit set of ceil(most views of an entry / 64) words, fusion, per-entry 1-NN), ops.gather_rows.
-    D is padded to a multiple of 4 inside (the fusion kernel's rows).  ValueError before any kernel: shape / dtype / device mismatches,
-    CPU tensors, inputs that require grad, Q > 1024, more than 65535 views, masks larger than image_shape, N >= 2^31.  TWO read-backs:
+    D is padded to a multiple of 4 inside (the fusion kernel's rows).  ValueError before any kernel: shape / dtype / device mismatches
+    (pred_masks of any dtype but fp32, fp16 and bf16 among them), CPU tensors, inputs that require grad, Q > 1024, more than 65535 views, masks larger than image_shape, N >= 2^31.  TWO read-backs:
     the sizes after the counting pass (entries in all, the most views of an entry) and the status after the last launch (rows whose
     batch index is no integer in 0..65535, views whose entry is outside 0..65535, non-finite coordinates: ValueError)."""
     who = "lift_masks"
@@ -740,6 +767,9 @@ class LiftMasksStream:
          finish).  finish makes exactly ONE, the status.  An add without a read-back would have to reserve records for the worst case,
          every point in every view; that is out of scope.
       6. text_embed and logit_scale are fixed at construction; the text is normalised once and returned as text_features.
+      7. A chunk's pred_masks may be fp32, fp16 or bf16, chunk by chunk: a chunk leaves (row, segment) records behind, which are the
+         same whatever the dtype its logits were read in, and a half chunk's records are those of its fp32 copy.  add's workspace
+         holds the chunk's transposed copy in the chunk's dtype.
     Why the bits are lift_masks': visibility and the drop rule, the score sort and the ordered transpose, the segment decision and the
     in-view fill are per view and read no other view -- the chunk goes through lift_masks' own kernels, over a workspace sized by the
     chunk.  The fusion kernel reads a point's slots (view, segment) in ascending position inside the entry with that view's table rows;
@@ -855,7 +885,7 @@ class LiftMasksStream:
                 for r0 in range(0, V * Q, _TABLE_ROWS):
                     r1 = min(r0 + _TABLE_ROWS, V * Q)
                     ops.segment_tables(emb[r0:r1], self._text4, float(self.logit_scale), f_seg[r0:r1], l_seg[r0:r1])
-            need = ops.lift_masks_stream_add_workspace_bytes(n, V, Q if total else 1, (h, w) if total else (1, 1), (H, W), total)
+            need = ops.lift_masks_stream_add_workspace_bytes(n, V, Q if total else 1, (h, w) if total else (1, 1), (H, W), total, dtype=Pm.dtype)
             ops.lift_masks_stream_add(st, ve, pm, scores, taps, (H, W), (lists.pt, lists.x, lists.y, lists.view), lists.view_off, lists.view_keep,
                                       total, self._rec_row, self._rec_seg, R0, self._rec_off[V0:V0 + V + 1], self._view_pos[V0:V0 + V],
                                       workspace=self._workspace("add", need))

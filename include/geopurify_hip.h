@@ -33,6 +33,11 @@ extern "C" {
 
 #define GP_KNN_MAX_K 127  /* K+1 <= 128 */
 
+/* element-type tags of the batched lifts' *_t entry points (feature maps, mask logits) */
+#define GP_ELEM_F32 0
+#define GP_ELEM_F16 1     /* IEEE binary16 */
+#define GP_ELEM_BF16 2    /* bfloat16 */
+
 int gp_version(void);
 /* Tuning knobs for experiments (table in csrc/error.hip).  No knob reaches a PRODUCT kernel: the pooling / convolution  */
 /* tuning bits (knobs 4 / 3) are honoured only by the *_tuning_kernel twins, the others select a launch shape or a slower, */
@@ -863,6 +868,22 @@ int gp_lift_batched(const double *points, int64_t n, const float *feat, int32_t 
                     int64_t min_visible, int64_t max_visible, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
                     int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn, int64_t *status,
                     void *workspace, size_t workspace_bytes, void *stream);
+/* The same calls on maps of another element type, read in place: `elem` names the type of src / dst /   */
+/* feat -- GP_ELEM_F32, GP_ELEM_F16 (IEEE binary16) or GP_ELEM_BF16; any other tag is GP_EINVAL.  Every   */
+/* loaded element is converted to fp32 (exact for both half types) and then takes the arithmetic of the  */
+/* fp32 call, so the outputs are the bits of the fp32 call on the caller's own upcast copy; sums and     */
+/* outputs stay fp32.  The transpose keeps the element type (it moves bits).  Half maps need 2-byte      */
+/* alignment only; when d is a multiple of 8 (4) and feat is 16 (8) byte aligned a lane reads 8 (4)      */
+/* consecutive channels with one load.  Extents and overlap checks count elements of the tag's size.     */
+/* The untagged entry points above are these with GP_ELEM_F32.                                           */
+int gp_lift_batched_transpose_t(const void *src, int32_t elem, int32_t nviews, int32_t d, int64_t hw, void *dst,
+                                void *stream);
+int gp_lift_batched_t(const double *points, int64_t n, const void *feat, int32_t elem, int32_t d, int32_t h, int32_t w,
+                      const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
+                      int32_t nviews, int32_t height, int32_t width, int32_t bilinear, int32_t cut_bound, double vis_thres,
+                      int64_t min_visible, int64_t max_visible, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
+                      int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *nn, int64_t *status,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* gp_lift_batched, RESUMABLE: the views arrive in chunks (the VLM's batches), every chunk's maps are  */
@@ -909,6 +930,14 @@ int gp_lift_stream_add(const double *points, int64_t n, const void *state, size_
                        int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible,
                        float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count, uint8_t *view_keep,
                        int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+/* gp_lift_stream_add on maps of element type `elem` (see gp_lift_batched_t); the sums stay fp32, so the */
+/* chunks of one stream may differ in type.                                                             */
+int gp_lift_stream_add_t(const double *points, int64_t n, const void *state, size_t state_bytes, const void *feat,
+                         int32_t elem, int32_t d, int32_t h, int32_t w, const int64_t *view_entry, const double *w2c,
+                         const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                         int32_t bilinear, int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible,
+                         float *sums, int64_t ld_sum, int32_t *count, int64_t *view_count, uint8_t *view_keep,
+                         int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
 size_t gp_lift_stream_finish_workspace_bytes(int64_t n);
 int gp_lift_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes, const float *sums,
                           int32_t d, int64_t ld_sum, const int32_t *count, const int64_t *status, int32_t fill, float *out,
@@ -972,6 +1001,22 @@ int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_e
                           int64_t fill_cap, const float *f_seg, const float *logit_seg, int32_t d, int32_t c, int32_t fill,
                           float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg, int64_t *status,
                           void *workspace, size_t workspace_bytes, void *stream);
+/* The same on pred_masks of element type `elem` (GP_ELEM_F32 / GP_ELEM_F16 / GP_ELEM_BF16, any other    */
+/* tag: GP_EINVAL, 0 bytes), read in place: the rank-ordered transposed copy in the workspace keeps the   */
+/* masks' type (nviews * h * w * q elements of the tag's size), the 16 taps of a pixel are converted to   */
+/* fp32 as they are loaded and the resize, the products and the decision are the fp32 call's: the same    */
+/* bits as the fp32 call on the caller's own upcast copy.  The untagged entry points are these with      */
+/* GP_ELEM_F32.                                                                                           */
+size_t gp_lift_masks_batched_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w,
+                                               int32_t out_h, int32_t out_w, int64_t total, int32_t words, int64_t fill_cap);
+int gp_lift_masks_batched_t(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews,
+                            const void *pred_masks, int32_t elem, int32_t q, int32_t h, int32_t w, const float *scores,
+                            const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0, const float *tap_wy,
+                            int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y,
+                            const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep, int64_t total,
+                            int32_t words, int64_t fill_cap, const float *f_seg, const float *logit_seg, int32_t d, int32_t c,
+                            int32_t fill, float *out, int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int32_t *seg,
+                            int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* gp_lift_masks_batched, RESUMABLE: the views arrive in chunks, every chunk's masks are read once, and   */
@@ -1037,6 +1082,18 @@ int gp_lift_masks_stream_add(const double *points, int64_t n, void *state, size_
                              int64_t fill_cap, int32_t *rec_row, int32_t *rec_seg, int64_t rec_base, int64_t rec_cap,
                              int64_t *rec_off, int32_t *view_pos, int64_t *status, void *workspace, size_t workspace_bytes,
                              void *stream);
+/* gp_lift_masks_stream_add on pred_masks of element type `elem` (see gp_lift_masks_batched_t); the       */
+/* records are the same whatever the type, so the chunks of one stream may differ in type.               */
+size_t gp_lift_masks_stream_add_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w,
+                                                  int32_t out_h, int32_t out_w, int64_t total, int64_t fill_cap);
+int gp_lift_masks_stream_add_t(const double *points, int64_t n, void *state, size_t state_bytes, const int64_t *view_entry,
+                               int32_t nviews, const void *pred_masks, int32_t elem, int32_t q, int32_t h, int32_t w,
+                               const float *scores, const int32_t *tap_x0, const float *tap_wx, const int32_t *tap_y0,
+                               const float *tap_wy, int32_t out_h, int32_t out_w, const int64_t *ent_pt, const int64_t *ent_x,
+                               const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off, const uint8_t *keep,
+                               int64_t total, int64_t fill_cap, int32_t *rec_row, int32_t *rec_seg, int64_t rec_base,
+                               int64_t rec_cap, int64_t *rec_off, int32_t *view_pos, int64_t *status, void *workspace,
+                               size_t workspace_bytes, void *stream);
 size_t gp_lift_masks_stream_finish_workspace_bytes(int64_t n, int32_t nviews, int64_t total, int32_t words);
 int gp_lift_masks_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes,
                                 const int64_t *view_entry, const int32_t *view_pos, const uint8_t *view_keep,
