@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GP_LIB") or os.path.join(_HERE, "libgeopurify_hip.so"
 _P = c_void_p  # every device pointer travels as void*
 GP_KNN_MAX_K = 127  # include/geopurify_hip.h: K+1 <= 128
 GP_ELEM_F32, GP_ELEM_F16, GP_ELEM_BF16 = 0, 1, 2  # include/geopurify_hip.h: the element-type tags of the batched lifts' *_t entry points
+GP_LABEL_U8, GP_LABEL_I16, GP_LABEL_I32, GP_LABEL_I64 = 0, 1, 2, 3  # include/geopurify_hip.h: the element-type tags of the label maps
 
 # name -> (restype, [argtypes])  -- mirrors include/geopurify_hip.h one to one
 SIGNATURES = {
@@ -226,6 +227,19 @@ SIGNATURES = {
     "gp_render_depth_batched_state_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gp_render_depth_batched_state": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                                 c_size_t, _P]),
+    "gp_lift_labels_batched_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_lift_labels_batched": (c_int32, [_P, c_int64, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_double,
+                                         c_int64, c_int64, POINTER(c_int64), c_int32, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P,
+                                         _P, c_size_t, _P]),
+    "gp_lift_labels_stream_state_bytes": (c_size_t, [c_int64]),
+    "gp_lift_labels_stream_begin_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_lift_labels_stream_begin": (c_int32, [_P, c_int64, c_int32, _P, c_size_t, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_labels_stream_add_workspace_bytes": (c_size_t, [c_int32]),
+    "gp_lift_labels_stream_add": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32,
+                                            c_double, c_int64, c_int64, POINTER(c_int64), c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_lift_labels_stream_finish_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_lift_labels_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int64, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P,
+                                               c_size_t, _P]),
 }
 
 _lib = None

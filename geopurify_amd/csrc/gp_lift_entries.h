@@ -1,4 +1,5 @@
-// Device code shared by the lifts over BATCHED point clouds (lift_batched.hip: gp_lift_batched; lift_masks_batched.hip): the
+// Device code shared by the lifts over BATCHED point clouds (lift_batched.hip: gp_lift_batched; lift_masks_batched.hip; lift_labels.hip,
+// whose fill passes the mask "voted" where the others pass "seen"): the
 // entry tables (rows and views sorted stably by entry, offsets by binary search), the per-view counts with the view-drop rule, and
 // the per-entry scene-level fill (references and queries compacted in the entry-sorted order).  One definition for both.
 #pragma once
@@ -114,7 +115,8 @@ __global__ void lb_keep_kernel(const unsigned long long *__restrict__ view_count
 }
 
 // ------------------------------------------------------------------------------------------------ the fill
-// sorted position s: ref[s] = the row is seen; qry[s] = unseen, in a valid entry (decided later whether that entry has references)
+// sorted position s: ref[s] = the row is seen (any byte mask: lift_labels.hip passes "voted"); qry[s] = unseen, in a valid entry
+// (decided later whether that entry has references)
 __global__ void __launch_bounds__(256) lb_fill_flags_kernel(const uint32_t *__restrict__ keys_sorted, const int32_t *__restrict__ entry_rows,
                                                             const uint8_t *__restrict__ seen, int64_t n, int32_t *__restrict__ ref,
                                                             int32_t *__restrict__ qry) {

@@ -34,73 +34,6 @@ namespace {
 constexpr int LS_COLS_PER_LANE = 8;
 constexpr int LS_COL_CHUNK = GP_WAVE * LS_COLS_PER_LANE;         // channels one pass holds in registers (gp_lift_batched's)
 
-struct LsAddWork {
-    uint32_t *vk0, *vk1;
-    int32_t *w0, *entry_views, *view_off;
-    char *tmp;
-    size_t tmp_bytes;
-    LsAddWork(GpCarver &cv, int32_t nviews) {
-        tmp_bytes = lb_sort_bytes(nviews);
-        vk0 = cv.take<uint32_t>(nviews);
-        vk1 = cv.take<uint32_t>(nviews);
-        w0 = cv.take<int32_t>(nviews);
-        entry_views = cv.take<int32_t>(nviews);
-        view_off = cv.take<int32_t>(LB_TABLE);
-        tmp = cv.take<char>(tmp_bytes);
-    }
-};
-
-struct LsFinishWork {
-    uint32_t *keys;
-    int32_t *rows, *off, *ref, *qry, *rs, *qs, *rrow, *qpos;
-    float *rxyz;
-    char *tmp;
-    size_t tmp_bytes;
-    LsFinishWork(GpCarver &cv, int64_t n) {
-        tmp_bytes = lb_scan_bytes(n + 1);
-        keys = cv.take<uint32_t>(n);
-        rows = cv.take<int32_t>(n);
-        off = cv.take<int32_t>(LB_TABLE);
-        ref = cv.take<int32_t>(n + 1);
-        qry = cv.take<int32_t>(n + 1);
-        rs = cv.take<int32_t>(n + 1);
-        qs = cv.take<int32_t>(n + 1);
-        rrow = cv.take<int32_t>(n);
-        qpos = cv.take<int32_t>(n);
-        rxyz = cv.take<float>(3 * n);
-        tmp = cv.take<char>(tmp_bytes);
-    }
-};
-
-// ------------------------------------------------------------------------------------------------ per-view counts over the state
-// lb_counts_kernel with every index of the state checked before use: blockIdx.y = view; the blocks of a view stride the sorted rows
-// of its entry.  Integer atomics: the counts do not depend on arrival order.
-__global__ void __launch_bounds__(256) ls_counts_kernel(const double *__restrict__ points, int64_t n, const int32_t *__restrict__ entry_rows,
-                                                        const int32_t *__restrict__ entry_off, const int64_t *__restrict__ view_entry,
-                                                        const double *__restrict__ w2c, const double *__restrict__ intr,
-                                                        const double *__restrict__ depth, int W, int H, int cut, double tau,
-                                                        unsigned long long *__restrict__ view_count) {
-    const int v = blockIdx.y;
-    const int64_t e = view_entry[v];
-    if ((uint64_t)e >= (uint64_t)LB_MAX_ENTRIES) return;             // (block-uniform)
-    int64_t r0 = entry_off[e], r1 = entry_off[e + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > n ? n : r1;
-    const double *M = w2c + (int64_t)v * 16, *K = intr + (int64_t)v * 4;
-    const double *dv = depth ? depth + (int64_t)v * W * H : nullptr;
-    int local = 0;
-    for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r1; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = entry_rows[i];
-        if ((uint64_t)row >= (uint64_t)n) continue;
-        const double *P = points + row * 4;
-        if (lb_entry_of(P[0]) != (int)e) continue;
-        long long ui, vi;
-        local += project_point(P[1], P[2], P[3], M, M + 4, M + 8, K[0], K[1], K[2], K[3], dv, W, H, cut, tau, ui, vi) ? 1 : 0;
-    }
-    local = gp_wave_sum_i(local);
-    if (gp_lane() == 0 && local) atomicAdd(view_count + v, (unsigned long long)local);
-}
-
 // ------------------------------------------------------------------------------------------------ the accumulating lift
 // the column accumulator k of a lane holds in the chunk at c0 (VEC = 1: the mapping the kernel was written with)
 template <int VEC>

@@ -1673,6 +1673,188 @@ def lift_stream_finish(st, fill=True, buffers=None, workspace=None):
     return LiftStreamFinish(out, got["seen"], got.get("nn"), got["status"])
 
 
+# ------------------------------------------------------------------------------------------ the label vote over batched point clouds
+# the element types the label votes read label maps in, by the tag of gp_lift_labels_batched
+LABEL_TAG = {torch.uint8: _lib.GP_LABEL_U8, torch.int16: _lib.GP_LABEL_I16, torch.int32: _lib.GP_LABEL_I32, torch.int64: _lib.GP_LABEL_I64}
+LIFT_LABELS_MAX_CLASSES = 1024                              # gp_lift_labels_batched: the histogram is a wave's LDS slice
+LIFT_LABELS_MAX_IGNORE = 16
+
+
+def _chk_labels(t, name):
+    """a contiguous CUDA tensor of uint8, int16, int32 or int64 -> its element-type tag"""
+    if t.dtype not in LABEL_TAG or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous CUDA torch.uint8, torch.int16, torch.int32 or torch.int64, got {t.dtype} cuda={t.is_cuda} "
+                         f"contig={t.is_contiguous()}")
+    return LABEL_TAG[t.dtype]
+
+
+def _ignore_ids(who, ignore_ids):
+    ids = [int(v) for v in ignore_ids]
+    if len(ids) > LIFT_LABELS_MAX_IGNORE or any(not -2 ** 63 <= v < 2 ** 63 for v in ids):
+        raise ValueError(f"{who}: at most {LIFT_LABELS_MAX_IGNORE} ignore labels, each a 64-bit integer, got {ids}")
+    return (ctypes.c_int64 * max(len(ids), 1))(*ids), len(ids)
+
+
+def _label_views(who, labels2d, view_entry, w2c, intrinsics, depth):
+    """the views' arrays of a label vote, checked -> (elem, V, H, W)"""
+    elem = _chk_labels(labels2d, "labels2d")
+    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
+    if labels2d.dim() != 3 or min(labels2d.shape) < 1:
+        raise ValueError(f"{who}: expected labels2d [V, H, W], got {list(labels2d.shape)}")
+    nv, H, W = labels2d.shape
+    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
+        raise ValueError(f"{who}: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
+                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
+        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    return elem, nv, H, W
+
+
+def lift_labels_batched_workspace_bytes(n, num_views):
+    return int(_lib.load().gp_lift_labels_batched_workspace_bytes(int(n), int(num_views)))
+
+
+class LiftLabelsBatched:
+    """What gp_lift_labels_batched writes: labels i64 [n] (after the fill), votes i32 [n, C], voted i32 [n], seen u8 [n], count i32 [n],
+    view_count i64 [V], view_keep u8 [V], status i64 [8] = (bad batch rows, bad view entries, non-finite rows, top batch, voted rows,
+    filled rows, 0, sampled labels out of range)."""
+
+    def __init__(self, labels, votes, voted, seen, count, view_count, view_keep, status):
+        self.labels, self.votes, self.voted, self.seen, self.count = labels, votes, voted, seen, count
+        self.view_count, self.view_keep, self.status = view_count, view_keep, status
+
+
+def lift_labels_batched(points, labels2d, num_classes, view_entry, w2c, intrinsics, depth, cut_bound, vis_thres, min_visible, max_visible,
+                        ignore_ids=(255,), unlabeled=255, fill=True, buffers=None, workspace=None):
+    """gp_lift_labels_batched, no sync: points f64 [n,4]; labels2d uint8, int16, int32 or int64 [V,H,W] (read in place); view_entry i64 [V];
+    w2c f64 [V,4,4]; intrinsics f64 [V,4]; depth f64 [V,H,W] or None.  -> LiftLabelsBatched.  buffers: optional dict of caller-owned
+    outputs by attribute name (votes: int32 rows of any pitch); workspace: uint8 of at least gp_lift_labels_batched_workspace_bytes(n, V)."""
+    lib = _lib.load()
+    who = "lift_labels_batched"
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    n, dev, C = points.shape[0], points.device, int(num_classes)
+    elem, nv, H, W = _label_views(who, labels2d, view_entry, w2c, intrinsics, depth)
+    if not 1 <= C <= LIFT_LABELS_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes={num_classes} outside 1..{LIFT_LABELS_MAX_CLASSES}")
+    ids, n_ids = _ignore_ids(who, ignore_ids)
+    got = _outputs(who, {"labels": (torch.int64, (n,)), "voted": (torch.int32, (n,)), "seen": (torch.uint8, (n,)), "count": (torch.int32, (n,)),
+                         "view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,)), "status": (torch.int64, (8,))}, buffers, dev)
+    votes = (buffers or {}).get("votes")
+    votes = torch.empty((n, C), dtype=torch.int32, device=dev) if votes is None else _rows_i32(votes, "votes", n, C)
+    ws = _ws(lib.gp_lift_labels_batched_workspace_bytes(n, nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_labels_batched(_ptr(points), n, _ptr(labels2d), elem, C, _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), _ptr(depth), nv, H, W,
+                                     int(cut_bound), float(vis_thres), int(min_visible), int(max_visible), ids, n_ids, int(unlabeled),
+                                     1 if fill else 0, _ptr(got["labels"]), _ptr(votes), votes.stride(0), _ptr(got["voted"]), _ptr(got["seen"]),
+                                     _ptr(got["count"]), _ptr(got["view_count"]), _ptr(got["view_keep"]), _ptr(got["status"]), _ptr(ws), ws.numel(),
+                                     _stream()), "gp_lift_labels_batched")
+    return LiftLabelsBatched(got["labels"], votes, got["voted"], got["seen"], got["count"], got["view_count"], got["view_keep"], got["status"])
+
+
+def _rows_i32(t, name, n, d):
+    """caller-owned int32 rows [n, d] of any pitch (unit column stride)"""
+    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 2 or t.shape != (n, d) or t.stride(1) != 1 or (n > 1 and t.stride(0) < d):
+        raise ValueError(f"{name}: expected CUDA int32 rows [{n}, {d}] with unit column stride, got {t.dtype} {list(t.shape)} strides {t.stride()}")
+    return t
+
+
+class LiftLabelsStreamState:
+    """What a resumable label vote keeps between its calls, all of it the caller's: points f64 [n,4], state u8 (the entry tables, written
+    by gp_lift_labels_stream_begin alone; ops.render_depth_stream reads them too), votes i32 [n, C] rows of any pitch, count i32 [n],
+    status i64 [8] (the running words: bad batch rows, bad view entries so far, non-finite rows, top batch, ..., labels out of range so
+    far)."""
+
+    def __init__(self, points, state, votes, count, status):
+        self.points, self.state, self.votes, self.count, self.status = points, state, votes, count, status
+
+
+def lift_labels_stream_state_bytes(n):
+    return int(_lib.load().gp_lift_labels_stream_state_bytes(int(n)))
+
+
+def lift_labels_stream_begin_workspace_bytes(n):
+    return int(_lib.load().gp_lift_labels_stream_begin_workspace_bytes(int(n)))
+
+
+def lift_labels_stream_add_workspace_bytes(num_views):
+    return int(_lib.load().gp_lift_labels_stream_add_workspace_bytes(int(num_views)))
+
+
+def lift_labels_stream_finish_workspace_bytes(n):
+    return int(_lib.load().gp_lift_labels_stream_finish_workspace_bytes(int(n)))
+
+
+def lift_labels_stream_begin(points, num_classes, buffers=None, workspace=None):
+    """gp_lift_labels_stream_begin, no sync: points f64 [n,4] -> LiftLabelsStreamState for num_classes classes (votes 0, counts 0).
+    buffers: optional dict of caller-owned state / votes / count / status (state: uint8 of at least
+    gp_lift_labels_stream_state_bytes(n); votes: int32 rows of any pitch); workspace: uint8 of at least
+    gp_lift_labels_stream_begin_workspace_bytes(n)."""
+    lib = _lib.load()
+    who = "lift_labels_stream_begin"
+    _chk(points, torch.float64, "points")
+    C = int(num_classes)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1 or not 1 <= C <= LIFT_LABELS_MAX_CLASSES:
+        raise ValueError(f"{who}: expected points [n >= 1, 4] and num_classes in 1..{LIFT_LABELS_MAX_CLASSES}, got {list(points.shape)}, "
+                         f"num_classes={num_classes}")
+    n, dev = points.shape[0], points.device
+    got = _outputs(who, {"count": (torch.int32, (n,)), "status": (torch.int64, (8,))}, buffers, dev)
+    state = (buffers or {}).get("state")
+    state = _ws(lib.gp_lift_labels_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")
+    votes = (buffers or {}).get("votes")
+    votes = torch.empty((n, C), dtype=torch.int32, device=dev) if votes is None else _rows_i32(votes, "votes", n, C)
+    ws = _ws(lib.gp_lift_labels_stream_begin_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_labels_stream_begin(_ptr(points), n, C, _ptr(state), state.numel(), _ptr(votes), votes.stride(0), _ptr(got["count"]),
+                                          _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_lift_labels_stream_begin")
+    return LiftLabelsStreamState(points, state, votes, got["count"], got["status"])
+
+
+def lift_labels_stream_add(st, labels2d, view_entry, w2c, intrinsics, depth, cut_bound, vis_thres, min_visible, max_visible, ignore_ids=(255,),
+                           buffers=None, workspace=None):
+    """gp_lift_labels_stream_add, no sync: one chunk of views onto the LiftLabelsStreamState st; the chunk's arrays as
+    ops.lift_labels_batched takes them (the chunks of one stream may differ in dtype).  -> (view_count i64 [V], view_keep u8 [V]) of the
+    chunk.  buffers: optional dict of caller-owned view_count / view_keep; workspace: uint8 of at least
+    gp_lift_labels_stream_add_workspace_bytes(V)."""
+    lib = _lib.load()
+    who = "lift_labels_stream_add"
+    n, C, dev = st.points.shape[0], st.votes.shape[1], st.points.device
+    elem, nv, H, W = _label_views(who, labels2d, view_entry, w2c, intrinsics, depth)
+    ids, n_ids = _ignore_ids(who, ignore_ids)
+    got = _outputs(who, {"view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,))}, buffers, dev)
+    ws = _ws(lib.gp_lift_labels_stream_add_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_labels_stream_add(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(labels2d), elem, C, _ptr(view_entry), _ptr(w2c),
+                                        _ptr(intrinsics), _ptr(depth), nv, H, W, int(cut_bound), float(vis_thres), int(min_visible),
+                                        int(max_visible), ids, n_ids, _ptr(st.votes), st.votes.stride(0), _ptr(st.count), _ptr(got["view_count"]),
+                                        _ptr(got["view_keep"]), _ptr(st.status), _ptr(ws), ws.numel(), _stream()), "gp_lift_labels_stream_add")
+    return got["view_count"], got["view_keep"]
+
+
+class LiftLabelsStreamFinish:
+    """What gp_lift_labels_stream_finish writes: labels i64 [n] (after the fill), voted i32 [n], seen u8 [n], status i64 [8] = (bad batch
+    rows, bad view entries, non-finite rows, top batch, voted rows, filled rows, values of the state outside their range, sampled labels
+    out of range)."""
+
+    def __init__(self, labels, voted, seen, status):
+        self.labels, self.voted, self.seen, self.status = labels, voted, seen, status
+
+
+def lift_labels_stream_finish(st, unlabeled=255, fill=True, buffers=None, workspace=None):
+    """gp_lift_labels_stream_finish, no sync: the LiftLabelsStreamState st as it stands -> LiftLabelsStreamFinish; st is not changed.
+    buffers: optional dict of caller-owned labels / voted / seen / status; workspace: uint8 of at least
+    gp_lift_labels_stream_finish_workspace_bytes(n)."""
+    lib = _lib.load()
+    who = "lift_labels_stream_finish"
+    n, C, dev = st.points.shape[0], st.votes.shape[1], st.points.device
+    got = _outputs(who, {"labels": (torch.int64, (n,)), "voted": (torch.int32, (n,)), "seen": (torch.uint8, (n,)), "status": (torch.int64, (8,))},
+                   buffers, dev)
+    ws = _ws(lib.gp_lift_labels_stream_finish_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_lift_labels_stream_finish(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(st.votes), C, st.votes.stride(0),
+                                           _ptr(st.count), _ptr(st.status), int(unlabeled), 1 if fill else 0, _ptr(got["labels"]),
+                                           _ptr(got["voted"]), _ptr(got["seen"]), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()),
+          "gp_lift_labels_stream_finish")
+    return LiftLabelsStreamFinish(got["labels"], got["voted"], got["seen"], got["status"])
+
+
 # ------------------------------------------------------------------------------------------ rendered depth over batched point clouds
 def _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev):
     """the views' arrays of a rendered-depth call, checked -> (V, H, W, depth f64 [V,H,W])"""

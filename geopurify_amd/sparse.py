@@ -37,6 +37,12 @@ more than one batch of masks:
         stream.add(MaskViews(pred_masks, pred_logits, mask_embed, view_entry, world_to_camera, intrinsics, depth, image_shape=(H, W)))
     lifted = stream.finish()                                    # the bits of lift_masks on all the views; add / finish may go on
 
+or, the third start of the chain, from integer label maps (a 2D segmenter's per-pixel predictions or 2D ground truth, the loader's
+label_2ds): the majority vote per point, its histogram, and the labels that segment_loss / purified_loss and segment take
+
+    voted = lift_labels(points, LabelViews(label_maps, view_entry, world_to_camera, intrinsics, depth), num_classes=C)
+    # -> .labels i64 [N] (255 where nothing voted), .votes i32 [N,C]; LiftLabelsStream(points, C).add(...) / .finish() in chunks
+
 and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
 
     pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
@@ -76,6 +82,9 @@ LiftMasksStream is the same lift resumable over chunks of views: ops.lift_masks_
 counters, once), per chunk ops.lift_masks_batched_lists around ops.lift_masks_stream_sizes (the one read-back), ops.segment_tables and
 ops.lift_masks_stream_add (segments and in-view fill over a chunk-sized workspace, one (row, segment) record per visible pair kept),
 ops.lift_masks_stream_finish (slot lists from the records, fusion, fill; a snapshot), ops.gather_rows.
+lift_labels has no counterpart in the reference; it votes integer label maps onto the points with lift's geometry (the mapper, the
+drop rule) in one call of ops.lift_labels_batched, one read-back; LiftLabelsStream is the same vote over chunks of views
+(ops.lift_labels_stream_begin / _add / _finish), order-free because the sums are integers.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -222,6 +231,16 @@ def _check_poses(who, name, V, E, M, K):
                          f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
 
 
+def _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visible):
+    """the options every lift decides visibility and the view-drop rule with"""
+    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
+        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
+    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
+        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
+    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
+        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+
+
 def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible):
     """lift's argument checks, in lift's order; views None: those of the points and the options alone (LiftStream's construction).
     -> (V, D, h, w, H, W), or None without views"""
@@ -248,12 +267,7 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
         _check_depth(who, Dp, V, H, W)
         if mode == "nearest" and (h, w) != (H, W):
             raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
-    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
-        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
-    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
-        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
-    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
-        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visible)
     if views is not None and Fm.requires_grad:
         raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
                          "no_grad); detach them")
@@ -515,6 +529,209 @@ class LiftStream:
         if bad_state:
             raise RuntimeError(f"{who}: {bad_state} values of the stream's entry tables are out of range: the state was overwritten")
         return Lifted(feats, r.seen.bool(), count, view_count, view_keep)
+
+
+# ------------------------------------------------------------------------------------------ the label vote
+LABEL_DTYPES = tuple(ops.LABEL_TAG)                         # uint8, int16, int32, int64
+MAX_CLASSES = ops.LIFT_LABELS_MAX_CLASSES
+
+
+class LabelViews:
+    """The views of a batch of scenes with an integer label map each: labels uint8, int16, int32 or int64 [V,H,W] (a 2D segmenter's
+    per-pixel predictions, or 2D ground truth: the loader's label_2ds; read in place, no widened copy; bool and floating maps are
+    refused), view_entry, world_to_camera, intrinsics and depth (fp64 [V,H,W], None or "render") exactly as Views takes them.  The image
+    shape is the maps' (H, W): labels are never resampled.  lift_labels checks the fields."""
+
+    def __init__(self, labels, view_entry, world_to_camera, intrinsics, depth=None):
+        self.labels, self.view_entry, self.world_to_camera, self.intrinsics, self.depth = labels, view_entry, world_to_camera, intrinsics, depth
+
+
+class LiftedLabels:
+    """labels i64 [N] in the points' row order (the voted class, a filled one, or `unlabeled`), votes i32 [N, num_classes] (zero rows for
+    filled and unlabeled points), voted i32 [N] (the votes of a point), seen bool [N] and count i32 [N] (the kept views that see it:
+    lift's), view_count i64 [V] and view_keep bool [V] (lift's)."""
+
+    def __init__(self, labels, votes, voted, seen, count, view_count, view_keep):
+        self.labels, self.votes, self.voted, self.seen, self.count = labels, votes, voted, seen, count
+        self.view_count, self.view_keep = view_count, view_keep
+
+
+def _check_lift_labels(who, points, views, num_classes, ignore_labels, unlabeled, cut_bound, vis_thres, min_visible, max_visible):
+    """lift_labels' argument checks, in lift's order; views None: those of the points and the options alone (LiftLabelsStream's
+    construction).  -> (V, H, W), or None without views"""
+    if views is not None and not isinstance(views, LabelViews):
+        raise ValueError(f"{who}: views must be a LabelViews, got {type(views).__name__}")
+    P = points
+    _check_points(who, P)
+    if views is not None:
+        L, E, M, K, Dp = views.labels, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        if not torch.is_tensor(L) or L.dim() != 3 or min(L.shape) < 1:
+            raise ValueError(f"{who}: views.labels must be [V, H, W] with V, H, W >= 1, got {_shape_of(L)}")
+        if L.dtype not in LABEL_DTYPES:
+            raise ValueError(f"{who}: views.labels must be uint8, int16, int32 or int64 (bool and floating label maps are refused), got {L.dtype}")
+        V, H, W = L.shape
+        if V > 65535:
+            raise ValueError(f"{who}: {V} views, at most 65535")
+        _check_poses(who, "views.", V, E, M, K)
+        _check_depth(who, Dp, V, H, W)
+    _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visible)
+    if not _is_count(num_classes, 1) or num_classes > MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes={num_classes!r} must be an integer in 1..{MAX_CLASSES}")
+    if not isinstance(ignore_labels, (tuple, list)) or len(ignore_labels) > ops.LIFT_LABELS_MAX_IGNORE or \
+            not all(isinstance(v, int) and not isinstance(v, bool) and -2 ** 63 <= v < 2 ** 63 for v in ignore_labels):
+        raise ValueError(f"{who}: ignore_labels={ignore_labels!r} must be a tuple of at most {ops.LIFT_LABELS_MAX_IGNORE} integers")
+    if not isinstance(unlabeled, int) or isinstance(unlabeled, bool) or not -2 ** 63 <= unlabeled < 2 ** 63 or 0 <= unlabeled < num_classes:
+        raise ValueError(f"{who}: unlabeled={unlabeled!r} must be an integer outside 0..{num_classes - 1}, the classes")
+    tensors = [P] + ([L, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    return (V, H, W) if views is not None else None
+
+
+def _raise_label_status(who, status, num_classes):
+    """the status errors of a label vote, lift's three first"""
+    bad_batch, bad_view, nonfinite, bad_state, bad_label = status[0], status[1], status[2], status[6], status[7]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    if bad_label:
+        raise ValueError(f"{who}: {bad_label} sampled labels are neither in 0..{num_classes - 1} nor in ignore_labels")
+    if bad_state:
+        raise RuntimeError(f"{who}: {bad_state} values of the stream's entry tables are out of range: the state was overwritten")
+
+
+def lift_labels(points, views, num_classes, *, ignore_labels=(255,), unlabeled=255, cut_bound=0, vis_thres=0.25, min_visible=0,
+                max_visible=None, fill=True):
+    """Integer 2D label maps voted onto the points of several scenes at once, entries never mixing: the majority vote of a 2D
+    segmenter's per-pixel predictions (the 2D-fusion baseline a purified result is compared with), or of 2D ground truth (pseudo-labels
+    for segment_loss / purified_loss).  The reference has no such function; the geometry is its own (models/utils/fusion_util.py:99-147,
+    dataset/data_loader_ablation.py:254-288).  points as lift takes them; views: a LabelViews.  Per entry b -- its points the rows with
+    batch b, its views those with view_entry == b:
+      1. visible(p, v), view_count, view_keep, count and seen are lift's rules 1 and 2: on the same geometry they equal lift's;
+      2. votes[p, c] = the kept views v that see p with labels[v, py, px] == c, c in 0..num_classes-1; a sampled pixel whose value is in
+         ignore_labels casts no vote;
+      3. any other sampled value outside 0..num_classes-1 casts no vote and is an error (ValueError from the status read-back);
+      4. voted[p] = sum_c votes[p, c]; a seen point may have voted == 0 (every view that sees it shows an ignored pixel);
+      5. labels[p] = the lowest class with the most votes, where voted[p] > 0;
+      6. with fill, in an entry that has both voted and unvoted points every unvoted point takes the label of the voted point OF ITS ENTRY
+         that minimises (d^2, row number), d^2 = (dx*dx + dy*dy) + dz*dz in fp64 over the fp32-rounded xyz (lift's rule 5 with "seen" read
+         as "voted"); its votes row stays zero, so a filled label stays recognisable;
+      7. everywhere else labels[p] = unlabeled (which must lie outside 0..num_classes-1).
+    Everything is integer arithmetic: the result is exact and independent of any order.  -> LiftedLabels.  No gradients; the points are
+    detached.  The vote histogram is a feature matrix too: quantize(points, votes.float()) followed by affinity_pool purifies label
+    distributions with the operator that purifies features.
+    Inside: ops.lift_labels_batched (the entry tables, the per-view counts, the vote kernel -- one wave per point, one label load per
+    (point, view) sample, the histogram in LDS --, the per-entry masked 1-NN over "voted"); with "render", ops.render_depth_batched first.
+    ValueError before any kernel: lift's refusals for the shared fields; label maps that are not uint8 / int16 / int32 / int64;
+    num_classes outside 1..1024; unlabeled inside 0..num_classes-1; more than 16 ignore labels.  From the ONE status read-back, taken after
+    the last launch (no buffer is sized by what it carries), lift's three first: non-finite coordinates, rows whose batch index is no
+    integer in 0..65535, views whose entry is outside 0..65535, then sampled labels out of range."""
+    who = "lift_labels"
+    V, H, W = _check_lift_labels(who, points, views, num_classes, ignore_labels, unlabeled, cut_bound, vis_thres, min_visible, max_visible)
+    P, L, E, M, K, Dp = points, views.labels, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+    with torch.cuda.device(P.device), torch.no_grad():
+        pts = P.detach().to(torch.float64).contiguous()
+        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
+            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
+        r = ops.lift_labels_batched(pts, L.detach().contiguous(), num_classes, ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(),
+                                    cut_bound, float(vis_thres), min_visible, 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1),
+                                    ignore_ids=tuple(ignore_labels), unlabeled=unlabeled, fill=bool(fill))
+        status = ops.readback(r.status)
+    _raise_label_status(who, status, num_classes)
+    return LiftedLabels(r.labels, r.votes, r.voted, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
+
+
+class LiftLabelsStream:
+    """lift_labels with the views arriving in chunks, for several scenes at once.  Only one chunk's label maps need to exist at a time:
+
+        stream = LiftLabelsStream(points, num_classes=C)
+        for chunk in segmenter_chunks:                          # a LabelViews: views of any entries, any number of them
+            stream.add(chunk)                                   # no host synchronisation
+        lifted = stream.finish()                                # -> LiftedLabels; the one status read-back
+
+    points and the options are lift_labels'; every chunk is a LabelViews as lift_labels takes it.
+      1. After any sequence of add calls, finish(fill=f) returns what lift_labels(points, LabelViews(the chunks concatenated in the order
+         added), num_classes, fill=f, ...) returns; view_count and view_keep come in arrival order.
+      2. votes, voted, count, seen and labels do not depend on the order of the chunks: the sums are integers.
+      3. finish is a snapshot: it writes new tensors and changes no state, so add and finish may go on alternating.
+      4. Chunks of different label dtypes may alternate.  Apart from the per-view count and keep vectors the stream holds nothing that
+         grows with the views added: the state is the entry tables (8 bytes per point), votes i32 [N, num_classes] and count [N].
+      5. With depth="render" a chunk's depth maps are rendered from the stream's entry tables (ops.render_depth_stream), as LiftStream
+         does it.
+    Inside: ops.lift_labels_stream_begin at construction (the entry tables, once), per chunk ops.lift_labels_stream_add (the chunk's view
+    table, the per-view counts and drop rule, the accumulating vote kernel), in finish ops.lift_labels_stream_finish (voted, arg-max,
+    seen, the per-entry masked 1-NN over "voted").
+    ValueError before any kernel of the call: lift_labels' refusals, for points and options at construction and for the chunk at add; a
+    chunk whose (H, W), presence of depth (none, a tensor or "render") or device differ from the first chunk's; a chunk that takes the
+    views past 65535 in all; finish before any add.  A refused add leaves the stream as it was.  From finish's ONE status read-back, with
+    lift_labels' messages and precedence; the out-of-range labels are counted over all chunks, kept in the state and reported by every
+    finish.  (RuntimeError from the same read-back: the entry tables hold values outside their range, i.e. somebody wrote into the
+    stream's state.)"""
+
+    def __init__(self, points, num_classes, *, ignore_labels=(255,), unlabeled=255, cut_bound=0, vis_thres=0.25, min_visible=0,
+                 max_visible=None):
+        who = "LiftLabelsStream"
+        _check_lift_labels(who, points, None, num_classes, ignore_labels, unlabeled, cut_bound, vis_thres, min_visible, max_visible)
+        self.num_classes, self.ignore_labels, self.unlabeled = int(num_classes), tuple(ignore_labels), unlabeled
+        self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = cut_bound, vis_thres, min_visible, max_visible
+        self.num_views = 0
+        self._points, self._device = points, points.device
+        self._first = None                                      # ((H, W), depth kind) of the first chunk
+        self._view_count, self._view_keep = [], []
+        self._ws_add = self._ws_finish = self._depth = self._ws_render = None
+        with torch.cuda.device(self._device), torch.no_grad():
+            self._st = ops.lift_labels_stream_begin(points.detach().to(torch.float64).contiguous(), self.num_classes)
+
+    def add(self, views):
+        """One chunk of views (a LabelViews) onto the votes.  No host synchronisation."""
+        who = "LiftLabelsStream.add"
+        V, H, W = _check_lift_labels(who, self._points, views, self.num_classes, self.ignore_labels, self.unlabeled, self.cut_bound,
+                                     self.vis_thres, self.min_visible, self.max_visible)
+        this = ((H, W), _depth_kind(views.depth))
+        if self._first is not None:
+            for name, a, b in zip(("(H, W)", "the presence of depth (none, tensor or 'render')"), this, self._first):
+                if a != b:
+                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
+        if self.num_views + V > 65535:
+            raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
+        L, E, M, K, Dp = views.labels, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
+        with torch.cuda.device(self._device), torch.no_grad():
+            need = ops.lift_labels_stream_add_workspace_bytes(V)
+            if self._ws_add is None or self._ws_add.numel() < need:
+                self._ws_add = None
+                self._ws_add = torch.empty(need, dtype=torch.uint8, device=self._device)
+            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
+                Dp, self._depth, self._ws_render = _render_chunk(self._st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
+            vc, vk = ops.lift_labels_stream_add(self._st, L.detach().contiguous(), ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(),
+                                                self.cut_bound, float(self.vis_thres), self.min_visible,
+                                                2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1),
+                                                ignore_ids=self.ignore_labels, workspace=self._ws_add)
+        self._first = this
+        self.num_views += V
+        self._view_count.append(vc)
+        self._view_keep.append(vk)
+
+    def finish(self, fill=True):
+        """-> LiftedLabels over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
+        who = "LiftLabelsStream.finish"
+        if self._first is None:
+            raise ValueError(f"{who}: no views were added")
+        n, dev = self._points.shape[0], self._device
+        with torch.cuda.device(dev), torch.no_grad():
+            if self._ws_finish is None:
+                self._ws_finish = torch.empty(ops.lift_labels_stream_finish_workspace_bytes(n), dtype=torch.uint8, device=dev)
+            r = ops.lift_labels_stream_finish(self._st, unlabeled=self.unlabeled, fill=bool(fill), workspace=self._ws_finish)
+            votes, count = self._st.votes.clone(), self._st.count.clone()
+            view_count, view_keep = torch.cat(self._view_count), torch.cat(self._view_keep).bool()
+            status = ops.readback(r.status)
+        _raise_label_status(who, status, self.num_classes)
+        return LiftedLabels(r.labels, votes, r.voted, r.seen.bool(), count, view_count, view_keep)
 
 
 # ------------------------------------------------------------------------------------------ the mask-embedding lift

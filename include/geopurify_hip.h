@@ -1139,6 +1139,80 @@ int gp_render_depth_batched_state(const double *points, int64_t n, const void *s
                                   int32_t height, int32_t width, int32_t cut_bound, double *depth, int64_t *status,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The label vote over BATCHED point clouds: integer 2D label maps -- the loader's label_2ds, slot 11 of   */
+/* its 20-tuple (dataset/data_loader_ablation.py:296-346) -- voted onto the points.  The reference has no   */
+/* such function; every geometric decision is its own: the point -> pixel mapping of                       */
+/* models/utils/fusion_util.py:99-147 and the view-drop rule of dataset/data_loader_ablation.py:254-288,   */
+/* for every batch entry and every view in one sequence of launches; entries never mix.  Points, entries,  */
+/* views, poses, depth, view_count, view_keep, count and seen are worded as in gp_lift_batched and hold    */
+/* the same values on the same geometry.                                                                   */
+/* labels2d [nviews, height, width] of element type `elem`: GP_LABEL_U8, GP_LABEL_I16, GP_LABEL_I32 or     */
+/* GP_LABEL_I64 (any other tag is GP_EINVAL), aligned to its element, read in place and widened to 64 bits */
+/* as it is loaded.  ignore_ids: n_ignore <= 16 values in HOST memory.                                      */
+/*   votes i32 [n, ld_votes >= num_classes]: votes[p, c] = the kept views that see p and hold class c at    */
+/*     the sampled pixel.  A sampled value in ignore_ids casts no vote; any other sampled value outside    */
+/*     0..num_classes-1 casts none and is counted in status[7];                                            */
+/*   voted i32 [n] = sum_c votes[p, c] (a seen point may have 0);                                          */
+/*   labels i64 [n]: the lowest class with the most votes where voted > 0; with fill != 0, in an entry      */
+/*     with voted and unvoted points, an unvoted point takes the label of the voted point OF ITS ENTRY     */
+/*     that minimises (d^2, row) -- gp_lift_batched's fill with "seen" read as "voted", its votes row       */
+/*     staying zero; `unlabeled` (outside 0..num_classes-1) everywhere else;                               */
+/*   status i64 [8]: [0]..[3] as gp_lift_batched, [4] voted rows, [5] filled rows, [7] sampled labels out  */
+/*     of range.                                                                                           */
+/* Integer arithmetic throughout: exact, and independent of any order.  1 <= n < 2^31, 1 <= nviews <=      */
+/* 65535, 1 <= num_classes <= 1024, cut_bound >= 0.  No output may overlap an input or another output      */
+/* (GP_EINVAL).                                                                                            */
+/* gp_lift_labels_batched: the mapper, fusion_util.py:99-147, and the loader's drop rule,                  */
+/* data_loader_ablation.py:254-288, over the label_2ds of data_loader_ablation.py:296-346.                 */
+#define GP_LABEL_U8 0
+#define GP_LABEL_I16 1
+#define GP_LABEL_I32 2
+#define GP_LABEL_I64 3
+size_t gp_lift_labels_batched_workspace_bytes(int64_t n, int32_t nviews);
+int gp_lift_labels_batched(const double *points, int64_t n, const void *labels2d, int32_t elem, int32_t num_classes,
+                           const int64_t *view_entry, const double *w2c, const double *intrinsics, const double *depth,
+                           int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, double vis_thres,
+                           int64_t min_visible, int64_t max_visible, const int64_t *ignore_ids, int32_t n_ignore,
+                           int64_t unlabeled, int32_t fill, int64_t *labels, int32_t *votes, int64_t ld_votes, int32_t *voted,
+                           uint8_t *seen, int32_t *count, int64_t *view_count, uint8_t *view_keep, int64_t *status,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* The same vote RESUMABLE, the views in chunks (the loader hands label_2ds out per view,                  */
+/* data_loader_ablation.py:296-346; the chunk loop is the one gp_lift_stream_* follows,                    */
+/* models/affinity_module.py:365-449).  The caller owns, between the calls: state                          */
+/* (gp_lift_labels_stream_state_bytes(n): the entry tables of gp_lift_stream_begin), votes i32 [n, ld_votes */
+/* >= num_classes], count i32 [n] and the running status i64 [8].  The sums are integers, so votes, count  */
+/* and what follows from them do not depend on the order of the chunks.                                    */
+/* gp_lift_labels_stream_begin (before the chunk loop, models/affinity_module.py:365): the tables into     */
+/*   state, votes = 0, count = 0, status [0], [2], [3] as gp_lift_stream_begin.                            */
+/* gp_lift_labels_stream_add (one pass of the loop, models/affinity_module.py:365-436 with                  */
+/*   fusion_util.py:99-147 and data_loader_ablation.py:254-288): view_count / view_keep of this chunk's     */
+/*   views; votes and count of every point that a kept view of the chunk sees grow by the chunk's votes    */
+/*   (other rows are neither read nor written); status[1] += bad view entries, status[7] += sampled labels */
+/*   out of range.  Chunks may differ in elem.  No synchronisation, nothing sized by device data.          */
+/* gp_lift_labels_stream_finish (the end, models/affinity_module.py:435-449): reads state, votes, count and */
+/*   status and changes none: labels, voted, seen as gp_lift_labels_batched writes them; status_out        */
+/*   [0]..[3] and [7] the running words, [4] voted rows, [5] filled rows, [6] values of state outside      */
+/*   their range (forced into range before use, as gp_lift_stream_finish does).                            */
+size_t gp_lift_labels_stream_state_bytes(int64_t n);
+size_t gp_lift_labels_stream_begin_workspace_bytes(int64_t n);
+int gp_lift_labels_stream_begin(const double *points, int64_t n, int32_t num_classes, void *state, size_t state_bytes,
+                                int32_t *votes, int64_t ld_votes, int32_t *count, int64_t *status, void *workspace,
+                                size_t workspace_bytes, void *stream);
+size_t gp_lift_labels_stream_add_workspace_bytes(int32_t nviews);
+int gp_lift_labels_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const void *labels2d,
+                              int32_t elem, int32_t num_classes, const int64_t *view_entry, const double *w2c,
+                              const double *intrinsics, const double *depth, int32_t nviews, int32_t height, int32_t width,
+                              int32_t cut_bound, double vis_thres, int64_t min_visible, int64_t max_visible,
+                              const int64_t *ignore_ids, int32_t n_ignore, int32_t *votes, int64_t ld_votes, int32_t *count,
+                              int64_t *view_count, uint8_t *view_keep, int64_t *status, void *workspace,
+                              size_t workspace_bytes, void *stream);
+size_t gp_lift_labels_stream_finish_workspace_bytes(int64_t n);
+int gp_lift_labels_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes, const int32_t *votes,
+                                 int32_t num_classes, int64_t ld_votes, const int32_t *count, const int64_t *status,
+                                 int64_t unlabeled, int32_t fill, int64_t *labels, int32_t *voted, uint8_t *seen,
+                                 int64_t *status_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
