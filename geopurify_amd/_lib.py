@@ -6,7 +6,7 @@ pointers, sizes and a hipStream_t.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GP_LIB") or os.path.join(_HERE, "libgeopurify_hip.so")      # (GP_LIB: another build of the library, for same-box A/B runs)
@@ -240,6 +240,12 @@ SIGNATURES = {
     "gp_lift_labels_stream_finish_workspace_bytes": (c_size_t, [c_int64]),
     "gp_lift_labels_stream_finish": (c_int32, [_P, c_int64, _P, c_size_t, _P, c_int32, c_int64, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P,
                                                c_size_t, _P]),
+    "gp_fuse_state_bytes": (c_size_t, [c_int64, c_int32]),
+    "gp_fuse_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
+    "gp_fuse_plan": (c_int32, [_P, c_int64, _P, c_int32, c_int64, c_uint64, c_int32, _P, _P, c_size_t, _P, _P, c_size_t, _P]),
+    "gp_fuse_write": (c_int32, [_P, c_int32, c_int64, _P, c_int64, c_int32, _P, c_size_t, c_int64, _P, c_int32, c_int64, _P, _P, _P]),
+    "gp_fuse_dense_workspace_bytes": (c_size_t, [c_int64]),
+    "gp_fuse_dense": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -2600,3 +2600,122 @@ def fused_decode(mask_chunk, feat, vox_ind, mode, row_keep=None):
     if mode == 0:
         out = out[:kept]
     return out, mask_out.bool()
+
+
+# ------------------------------------------------------------------------------------------ fused-feature files from batched clouds
+FUSE_FORMS = {"merged": 0, "chunk": 1}                      # the two-key and the three-key file of dataset/feature_loader.py:113-192
+FUSE_ELEM = {torch.float32: _lib.GP_ELEM_F32, torch.float16: _lib.GP_ELEM_F16}
+FUSE_MAX_FILES = 16
+
+
+def fuse_state_bytes(n, num_files):
+    return int(_lib.load().gp_fuse_state_bytes(int(n), int(num_files)))
+
+
+def fuse_workspace_bytes(n, num_files, n_split_points=None):
+    return int(_lib.load().gp_fuse_workspace_bytes(int(n), int(num_files), int(n_split_points or 0)))
+
+
+def fuse_dense_workspace_bytes(n):
+    return int(_lib.load().gp_fuse_dense_workspace_bytes(int(n)))
+
+
+def _fuse_points(who, points):
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or not 1 <= points.shape[0] < 2 ** 31 - 1:
+        raise ValueError(f"{who}: expected points [1 <= n < 2^31 - 1, 4], got {list(points.shape)}")
+    return points.shape[0]
+
+
+class FusePlan:
+    """What gp_fuse_plan writes: mask_full u8 [num_files, n], state (opaque, for fuse_write), status i64 [8] = (rows whose batch index
+    is no integer in 0..65535, 0, 0, top batch index, rows of feat over all files, 0, 0, 0); and what it was called with."""
+
+    def __init__(self, n, seen, num_files, form, mask_full, state, status):
+        self.n, self.seen, self.num_files, self.form = n, seen, num_files, form
+        self.mask_full, self.state, self.status = mask_full, state, status
+
+
+def fuse_plan(points, seen, n_split_points=None, num_files=1, seed=0, form="merged", buffers=None, workspace=None):
+    """gp_fuse_plan, no sync: points f64 [n,4] (the batch column is read), seen u8 [n].  n_split_points None: every file holds the whole
+    entry.  buffers: optional caller-owned mask_full / state (uint8 of gp_fuse_state_bytes) / status; workspace: uint8 of at least
+    fuse_workspace_bytes(n, num_files, n_split_points).  -> FusePlan."""
+    lib = _lib.load()
+    who = "fuse_plan"
+    n = _fuse_points(who, points)
+    _chk(seen, torch.uint8, "seen")
+    nf, split, seed = int(num_files), int(n_split_points or 0), int(seed)
+    if seen.shape != (n,):
+        raise ValueError(f"{who}: expected seen [{n}], got {list(seen.shape)}")
+    if not 1 <= nf <= FUSE_MAX_FILES or form not in FUSE_FORMS or (n_split_points is not None and split < 1) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: num_files={num_files} outside 1..{FUSE_MAX_FILES}, form={form!r} not in {sorted(FUSE_FORMS)}, "
+                         f"n_split_points={n_split_points} < 1 or seed={seed} outside 0..2^64-1")
+    dev = points.device
+    sb = int(lib.gp_fuse_state_bytes(n, nf))
+    got = _outputs(who, {"mask_full": (torch.uint8, (nf, n)), "status": (torch.int64, (8,))}, buffers, dev)
+    state = (buffers or {}).get("state")
+    state = _ws(sb, dev) if state is None else _chk(state, torch.uint8, "state")
+    ws = _ws(lib.gp_fuse_workspace_bytes(n, nf, split), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_fuse_plan(_ptr(points), n, _ptr(seen), nf, split, seed, FUSE_FORMS[form], _ptr(got["mask_full"]), _ptr(state), state.numel(),
+                           _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_fuse_plan")
+    return FusePlan(n, seen, nf, form, got["mask_full"], state, got["status"])
+
+
+def fuse_write(plan, features, num_entries, total_rows, dtype=torch.float16, buffers=None):
+    """gp_fuse_write, no sync: features fp32 or fp16 [n, D] (contiguous; any element-aligned base) -> (feat dtype [total_rows, D], mask
+    u8 [total_rows] or None (merged form), offsets i64 [num_files, num_entries + 1]).  num_entries / total_rows: status[3] + 1 /
+    status[4] of the plan.  buffers: optional caller-owned feat / mask / offsets."""
+    lib = _lib.load()
+    who = "fuse_write"
+    if features.dtype not in FUSE_ELEM or not features.is_cuda or not features.is_contiguous() or features.dim() != 2 or \
+            features.shape[0] != plan.n or features.shape[1] < 1:
+        raise ValueError(f"{who}: expected contiguous CUDA fp32 or fp16 features [{plan.n}, D >= 1], got {features.dtype} "
+                         f"{list(features.shape)} cuda={features.is_cuda} contig={features.is_contiguous()}")
+    if dtype not in FUSE_ELEM:
+        raise ValueError(f"{who}: dtype={dtype} (torch.float16 or torch.float32)")
+    B, R, D, nf, dev = int(num_entries), int(total_rows), features.shape[1], plan.num_files, features.device
+    want = {"feat": (dtype, (R, D)), "offsets": (torch.int64, (nf, B + 1))}
+    if plan.form == "chunk":
+        want["mask"] = (torch.uint8, (R,))
+    got = _outputs(who, want, buffers, dev)
+    check(lib.gp_fuse_write(_ptr(features), FUSE_ELEM[features.dtype], D, _ptr(plan.seen), plan.n, nf, _ptr(plan.state), plan.state.numel(), B,
+                            _ptr(got["feat"]) if R else None, FUSE_ELEM[dtype], R, _ptr(got["mask"]) if R and "mask" in got else None,
+                            _ptr(got["offsets"]), _stream()), "gp_fuse_write")
+    return got["feat"], got.get("mask"), got["offsets"]
+
+
+class FuseBatched:
+    """mask_full u8 [num_files, n], feat [R, D], offsets i64 [num_files, B + 1], mask u8 [R] or None, status: the plan's words as a list"""
+
+    def __init__(self, mask_full, feat, offsets, mask, status):
+        self.mask_full, self.feat, self.offsets, self.mask, self.status = mask_full, feat, offsets, mask, status
+
+
+def fuse_batched(points, features, seen, n_split_points=None, num_files=1, seed=0, form="merged", dtype=torch.float16):
+    """fuse_plan, ONE read-back (the plan's status: it carries the sizes that allocate feat and offsets), fuse_write.  -> FuseBatched;
+    rows whose batch index is no integer in 0..65535 (status[0] of them) are in no file."""
+    plan = fuse_plan(points, seen, n_split_points, num_files, seed, form)
+    status = readback(plan.status)
+    feat, mask, offsets = fuse_write(plan, features, status[3] + 1, status[4], dtype)
+    return FuseBatched(plan.mask_full, feat, offsets, mask, status)
+
+
+def fuse_dense(points, mask_full, feat, buffers=None, workspace=None):
+    """gp_fuse_dense, no sync: points f64 [n,4], mask_full u8 [n] (one file set), feat fp16 or fp32 [rows, D] -> (out fp32 [n, D]:
+    feat's rows at the points with mask_full, zero rows elsewhere; status i64 [8]: [0] bad batch rows, [3] top batch, [4] the rows
+    mask_full selects, to be compared with feat's)."""
+    lib = _lib.load()
+    who = "fuse_dense"
+    n = _fuse_points(who, points)
+    _chk(mask_full, torch.uint8, "mask_full")
+    if mask_full.shape != (n,):
+        raise ValueError(f"{who}: expected mask_full [{n}], got {list(mask_full.shape)}")
+    if feat.dtype not in FUSE_ELEM or not feat.is_cuda or not feat.is_contiguous() or feat.dim() != 2 or feat.shape[1] < 1:
+        raise ValueError(f"{who}: expected contiguous CUDA fp32 or fp16 feat [rows, D >= 1], got {feat.dtype} {list(feat.shape)} "
+                         f"cuda={feat.is_cuda} contig={feat.is_contiguous()}")
+    R, D, dev = feat.shape[0], feat.shape[1], points.device
+    got = _outputs(who, {"out": (torch.float32, (n, D)), "status": (torch.int64, (8,))}, buffers, dev)
+    ws = _ws(lib.gp_fuse_dense_workspace_bytes(n), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_fuse_dense(_ptr(points), n, _ptr(mask_full), _ptr(feat) if R else None, FUSE_ELEM[feat.dtype], R, D, _ptr(got["out"]),
+                            _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_fuse_dense")
+    return got["out"], got["status"]

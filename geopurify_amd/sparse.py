@@ -43,6 +43,13 @@ label_2ds): the majority vote per point, its histogram, and the labels that segm
     voted = lift_labels(points, LabelViews(label_maps, view_entry, world_to_camera, intrinsics, depth), num_classes=C)
     # -> .labels i64 [N] (255 where nothing voted), .votes i32 [N,C]; LiftLabelsStream(points, C).add(...) / .finish() in chunks
 
+The chain also has an end and a fourth start on disk: the fused-feature files that dataset/feature_loader.py:113-192 reads (lift once,
+then train and evaluate from files many times without the VLM)
+
+    chunks = fuse(points, lifted, n_split_points=80000, num_files=5)   # per scene and file a random chunk of the points, fp16 rows
+    chunks.save(out_dir, scene_names)                           # {scene}_{k}.pt, what FusedFeatureLoader loads; chunks.file(b, k): one dict
+    feats, mask = load_fused(points, files).dense()             # files back in: fp32 [N,D] (zero rows outside the file), ready for quantize
+
 and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
 
     pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
@@ -85,6 +92,9 @@ ops.lift_masks_stream_finish (slot lists from the records, fusion, fill; a snaps
 lift_labels has no counterpart in the reference; it votes integer label maps onto the points with lift's geometry (the mapper, the
 drop rule) in one call of ops.lift_labels_batched, one read-back; LiftLabelsStream is the same vote over chunks of views
 (ops.lift_labels_stream_begin / _add / _finish), order-free because the sums are integers.
+fuse has no counterpart in the reference either (it ships the reader and the writer's settings, config/fusion_scannet.yaml:34-35): ops.fuse_plan
+(entry tables, an exact radix select of each (file, entry)'s threshold key, flags and scans per file), one read-back, ops.fuse_write
+(every row loaded once, converted once, stored to each file that holds it); FusedChunks.dense is ops.fuse_dense.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -1143,6 +1153,213 @@ class LiftMasksStream:
             raise RuntimeError(f"{who}: what the stream keeps does not hold together ({st[6]} values of the state, the offsets or the records, "
                                f"{st[7]} view positions): it was overwritten, or the inputs changed during an add")
         return LiftedMasks(feats, seen, count, view_count, view_keep, self.text_features, self.logit_scale)
+
+
+# ------------------------------------------------------------------------------------------ fused-feature files: the chain's end and a start
+FUSE_FORMS = ("merged", "chunk")
+FUSE_DTYPES = (torch.float16, torch.float32)
+
+
+def _fuse_points(who, points):
+    """the points of fuse / load_fused / dense as contiguous fp64 rows (only the batch column is read)"""
+    _check_points(who, points)
+    if not points.is_cuda:
+        raise ValueError(f"{who}: points must be a CUDA tensor (got {points.device}); there is no CPU path")
+    return points.detach().to(torch.float64).contiguous()
+
+
+class FusedChunks:
+    """The fused-feature files of a batch, on the device.  mask_full bool [num_files, N] in the points' row order; feat fp16 or fp32
+    [R, D], the rows of file k of entry b are feat[offsets[k, b] : offsets[k, b + 1]] (ascending row order of the entry); offsets i64
+    [num_files, B + 1], B = highest batch index + 1; mask bool [R] in feat's row order (the "chunk" form: the row was seen) or None
+    (the "merged" form: mask_full holds seen points only).  points: the fp64 [N,4] rows the chunks were made for."""
+
+    def __init__(self, points, mask_full, feat, offsets, mask, form):
+        self.points, self.mask_full, self.feat, self.offsets, self.mask, self.form = points, mask_full, feat, offsets, mask, form
+        self._offsets = self._rows = None
+
+    @property
+    def num_files(self):
+        return self.mask_full.shape[0]
+
+    @property
+    def num_entries(self):
+        return self.offsets.shape[1] - 1
+
+    def _host_offsets(self):
+        """offsets as nested lists: one read-back, made once"""
+        if self._offsets is None:
+            self._offsets = ops.readback(self.offsets)
+        return self._offsets
+
+    def _tables(self):
+        """(offsets as nested lists, the rows of every entry), made once"""
+        if self._rows is None:
+            batch = self.points[:, 0]
+            self._rows = [torch.nonzero(batch == b).reshape(-1) for b in range(self.num_entries)]
+        return self._host_offsets(), self._rows
+
+    def _pair(self, who, b, k):
+        if not (isinstance(b, int) and isinstance(k, int) and 0 <= b < self.num_entries and 0 <= k < self.num_files):
+            raise ValueError(f"{who}: entry {b!r} / file {k!r} outside 0..{self.num_entries - 1} / 0..{self.num_files - 1}")
+
+    def file(self, b, k=0):
+        """The dict the reader loads for file k of entry b (dataset/feature_loader.py:113-192), CPU tensors: "feat" [rows, D],
+        "mask_full" bool [n_b], and in the chunk form "mask" bool [rows]."""
+        self._pair("FusedChunks.file", b, k)
+        off, rows = self._tables()
+        lo, hi = off[k][b], off[k][b + 1]
+        d = {"feat": self.feat[lo:hi].cpu(), "mask_full": self.mask_full[k].index_select(0, rows[b]).cpu()}
+        if self.mask is not None:
+            d["mask"] = self.mask[lo:hi].cpu()
+        return d
+
+    def save(self, out_dir, scene_names, skip_empty=False):
+        """torch.save(self.file(b, k), out_dir/{scene_names[b]}_{k}.pt) for every entry and file -> the paths written.  A file without
+        rows is refused (ValueError naming it, before anything is written): the reader drops scenes without files and its decoder
+        refuses zero rows; skip_empty=True writes no file for it instead."""
+        import os
+        who = "FusedChunks.save"
+        names = list(scene_names) if isinstance(scene_names, (list, tuple)) else None
+        if names is None or len(names) != self.num_entries or not all(isinstance(s, str) and s for s in names):
+            raise ValueError(f"{who}: scene_names must be {self.num_entries} names, one per entry 0..{self.num_entries - 1}, got {scene_names!r}")
+        off, _ = self._tables()
+        empty = [(b, k) for b in range(self.num_entries) for k in range(self.num_files) if off[k][b + 1] == off[k][b]]
+        if empty and not skip_empty:
+            b, k = empty[0]
+            raise ValueError(f"{who}: file {k} of entry {b} ({names[b]}_{k}.pt) has no rows ({len(empty)} such files); skip_empty=True "
+                             f"writes no file for them")
+        os.makedirs(out_dir, exist_ok=True)
+        paths = []
+        for b in range(self.num_entries):
+            for k in range(self.num_files):
+                if (b, k) in empty:
+                    continue
+                paths.append(os.path.join(out_dir, f"{names[b]}_{k}.pt"))
+                torch.save(self.file(b, k), paths[-1])
+        return paths
+
+    def dense(self, k=0):
+        """(fp32 [N, D], bool [N]) on the device: feat's rows of file k at the points it holds, zero rows elsewhere, and mask_full[k] --
+        the reader's evaluation form (dataset/feature_loader.py:119-126) on the unvoxelized points of all entries, ready for
+        quantize(points, features).  ops.fuse_dense; read-backs: the offsets (once per FusedChunks) and the status."""
+        self._pair("FusedChunks.dense", 0, k)
+        with torch.cuda.device(self.points.device), torch.no_grad():
+            off = self._host_offsets()
+            lo, hi = off[k][0], off[k][-1]
+            out, status = ops.fuse_dense(self.points, self.mask_full[k].to(torch.uint8), self.feat[lo:hi])
+            st = ops.readback(status)
+        if st[0]:
+            raise ValueError(f"FusedChunks.dense: {st[0]} rows have a batch index that is no integer in 0..65535")
+        if st[4] != hi - lo:
+            raise ValueError(f"FusedChunks.dense: mask_full[{k}] selects {st[4]} points but feat holds {hi - lo} rows of file {k}")
+        return out, self.mask_full[k]
+
+
+def fuse(points, lifted, *, n_split_points=None, num_files=1, seed=0, form="merged", dtype=torch.float16):
+    """The fused-feature files of a lifted batch: what dataset/feature_loader.py:113-192 reads, written with the settings of
+    config/fusion_scannet.yaml:34-35 (n_split_points, num_rand_file_per_scene = num_files).  points [N,4] as lift takes them (only
+    the batch column is read); lifted: a Lifted / LiftedMasks, or a (features fp32 | fp16 [N,D], seen bool [N]) pair.  Per entry b --
+    its points the rows with batch b in ascending row order, local index i -- and file k:
+      chunk_k = every point of the entry when n_split_points is None or n_b <= n_split_points, else the n_split_points points with
+      the smallest key h = fmix32(i ^ c), c = fmix32(k ^ fmix32(b ^ fmix32(seed_lo ^ fmix32(seed_hi)))), fmix32 murmur3's 32-bit
+      finaliser (x ^= x>>16; x *= 0x85ebca6b; x ^= x>>13; x *= 0xc2b2ae35; x ^= x>>16) -- a bijection, so the keys of one (entry,
+      file) are distinct and the chunk has no ties; it depends neither on how the entries' rows interleave nor on any arrival order;
+      form "merged" (the two-key file): mask_full = chunk_k & seen, feat = features[mask_full].to(dtype);
+      form "chunk" (the three-key file): mask_full = chunk_k, feat = features[chunk_k].to(dtype), mask = seen[chunk_k].
+    The conversion is torch's .to(dtype) to the bit (nearest even, inf on overflow, half subnormals kept, -0.0 kept, NaN stays NaN).
+    -> FusedChunks (.file, .save, .dense).  No gradients.  Inside: ops.fuse_plan (entry tables, a radix select of the threshold key
+    per selecting (file, entry), flags and scans per file), ONE read-back (the plan's status: the sizes that allocate feat and
+    offsets, and the bad-row count -- at most the two the interface allows), ops.fuse_write (every source row loaded once, converted
+    once, stored to each file that holds it).  Beside the outputs the call holds 4 * num_files * N bytes of scans and about 20 N bytes
+    of tables.
+    ValueError before any kernel: shape / dtype / device mismatches, CPU tensors, num_files outside 1..16, n_split_points < 1, seed
+    outside 0..2^64-1, an unknown form or dtype; from the read-back: rows whose batch index is no integer in 0..65535."""
+    who = "fuse"
+    P = _fuse_points(who, points)
+    n = P.shape[0]
+    if isinstance(lifted, (tuple, list)) and len(lifted) == 2:
+        Fe, seen = lifted
+    elif hasattr(lifted, "features") and hasattr(lifted, "seen"):
+        Fe, seen = lifted.features, lifted.seen
+    else:
+        raise ValueError(f"{who}: lifted must be a Lifted, a LiftedMasks or a (features, seen) pair, got {type(lifted).__name__}")
+    if not torch.is_tensor(Fe) or Fe.dim() != 2 or Fe.shape[0] != n or Fe.shape[1] < 1 or Fe.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{who}: features must be fp32 or fp16 [N, D] with N = {n} point rows, got "
+                         f"{(list(Fe.shape), Fe.dtype) if torch.is_tensor(Fe) else type(Fe).__name__}")
+    if not torch.is_tensor(seen) or seen.shape != (n,) or seen.dtype != torch.bool:
+        raise ValueError(f"{who}: seen must be bool [{n}], got {(list(seen.shape), seen.dtype) if torch.is_tensor(seen) else type(seen).__name__}")
+    if Fe.device != P.device or seen.device != P.device:
+        raise ValueError(f"{who}: points, features and seen must be on one CUDA device (got {P.device} / {Fe.device} / {seen.device})")
+    if isinstance(num_files, bool) or not isinstance(num_files, int) or not 1 <= num_files <= ops.FUSE_MAX_FILES:
+        raise ValueError(f"{who}: num_files={num_files!r} outside 1..{ops.FUSE_MAX_FILES}")
+    if n_split_points is not None and (isinstance(n_split_points, bool) or not isinstance(n_split_points, int) or n_split_points < 1):
+        raise ValueError(f"{who}: n_split_points={n_split_points!r} must be None or an integer >= 1")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: seed={seed!r} outside 0..2^64-1")
+    if form not in FUSE_FORMS:
+        raise ValueError(f"{who}: form={form!r}, expected one of {FUSE_FORMS}")
+    if dtype not in FUSE_DTYPES:
+        raise ValueError(f"{who}: dtype={dtype!r}, expected torch.float16 or torch.float32")
+    with torch.cuda.device(P.device), torch.no_grad():
+        r = ops.fuse_batched(P, Fe.detach().contiguous(), seen.to(torch.uint8).contiguous(), n_split_points, num_files, seed, form, dtype)
+    if r.status[0]:
+        raise ValueError(f"{who}: {r.status[0]} rows have a batch index that is no integer in 0..65535")
+    return FusedChunks(P, r.mask_full.bool(), r.feat, r.offsets, None if r.mask is None else r.mask.bool(), form)
+
+
+def load_fused(points, files):
+    """Fused-feature files back into the batched chain: files holds, per entry 0 .. B-1, a path, a dict as torch.load gives it, or
+    None (an entry without a file: no rows).  Either form of dataset/feature_loader.py:113-192 -- "feat" and "mask_full", with "mask"
+    (a bool mask or a list of row indices, :129-139) the three-key form -- but one form for all entries.  -> FusedChunks with
+    num_files = 1 on the points' device; .dense() then gives what quantize takes.  Host work and copies only (the loader's side of
+    the chain); ValueError where a file does not fit its entry's points."""
+    who = "load_fused"
+    P = _fuse_points(who, points)
+    if not isinstance(files, (list, tuple)) or not files:
+        raise ValueError(f"{who}: files must be a list with one path, dict or None per entry, got {type(files).__name__}")
+    dev, n, B = P.device, P.shape[0], len(files)
+    with torch.cuda.device(dev), torch.no_grad():
+        batch = P[:, 0]
+        mask_full = torch.zeros((1, n), dtype=torch.bool, device=dev)
+        feats, masks, sizes, rows_of = [], [], [0], []
+        for b in range(B):
+            rows_of.append(torch.nonzero(batch == b).reshape(-1))
+        covered = sum(int(r.numel()) for r in rows_of)
+        if covered != n:
+            raise ValueError(f"{who}: {n - covered} rows have a batch index that is no integer in 0..{B - 1} (one file per entry)")
+        for b, f in enumerate(files):
+            if f is None:
+                sizes.append(sizes[-1])
+                continue
+            d = torch.load(f, map_location="cpu") if isinstance(f, (str, bytes)) or hasattr(f, "__fspath__") else f
+            if not isinstance(d, dict) or "feat" not in d or "mask_full" not in d:
+                raise ValueError(f"{who}: file of entry {b} must hold 'feat' and 'mask_full', got {sorted(d) if isinstance(d, dict) else type(d).__name__}")
+            feat, mf = torch.as_tensor(d["feat"]), torch.as_tensor(d["mask_full"]).bool().reshape(-1)
+            nb = int(rows_of[b].numel())
+            if feat.dim() != 2 or feat.dtype not in FUSE_DTYPES or mf.shape[0] != nb or int(mf.sum()) != feat.shape[0]:
+                raise ValueError(f"{who}: file of entry {b}: feat {list(feat.shape)} {feat.dtype}, mask_full [{mf.shape[0]}] with "
+                                 f"{int(mf.sum())} points, for an entry of {nb} points")
+            if "mask" in d:
+                m = torch.as_tensor(d["mask"])
+                if m.dtype != torch.bool:                                        # (a list of row indices, feature_loader.py:129-139)
+                    m = torch.zeros(feat.shape[0], dtype=torch.bool).index_fill_(0, m.reshape(-1).long(), True)
+                if m.shape != (feat.shape[0],):
+                    raise ValueError(f"{who}: file of entry {b}: mask {list(m.shape)} for {feat.shape[0]} rows of feat")
+                masks.append(m)
+            mask_full[0, rows_of[b]] = mf.to(dev)
+            feats.append(feat)
+            sizes.append(sizes[-1] + feat.shape[0])
+        if not feats:
+            raise ValueError(f"{who}: no entry has a file")
+        if masks and len(masks) != len(feats):
+            raise ValueError(f"{who}: {len(masks)} of {len(feats)} files hold 'mask': one form for all entries")
+        if len({(f.dtype, f.shape[1]) for f in feats}) != 1:
+            raise ValueError(f"{who}: the files' feat differ in dtype or width: {sorted({(str(f.dtype), f.shape[1]) for f in feats})}")
+        feat = torch.cat(feats).to(dev)
+        mask = torch.cat(masks).to(dev) if masks else None
+        offsets = torch.tensor([sizes], dtype=torch.int64, device=dev)
+    return FusedChunks(P, mask_full, feat, offsets, mask, "chunk" if masks else "merged")
 
 
 def _voxel_size(quantization_size, like):

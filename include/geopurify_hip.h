@@ -1213,6 +1213,46 @@ int gp_lift_labels_stream_finish(const double *points, int64_t n, const void *st
                                  int64_t unlabeled, int32_t fill, int64_t *labels, int32_t *voted, uint8_t *seen,
                                  int64_t *status_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused-feature files FROM lifted batched clouds, and back.  The reader is                           */
+/* dataset/feature_loader.py:113-192 ({scene}_{k}.pt: feat, mask_full, and mask in the three-key      */
+/* form); the writer's settings are config/fusion_scannet.yaml:34-35 (n_split_points,                 */
+/* num_rand_file_per_scene).  points f64 [n,4]: only the batch column is read.  Per entry b (its rows  */
+/* in ascending row order, local index i) and file k: chunk = all of the entry when n_split_points == 0 */
+/* or n_b <= n_split_points, else the n_split_points points with the smallest key                      */
+/*   h = fmix32(i ^ fmix32(k ^ fmix32(b ^ fmix32(seed_lo ^ fmix32(seed_hi))))),                         */
+/* fmix32 murmur3's finaliser (a bijection: the keys of a pair are distinct, the chunk has no ties).   */
+/* form 0 (merged, two keys): mask_full = chunk & seen; form 1 (chunk, three keys): mask_full = chunk, */
+/* mask = seen at the file's rows.  feat: the rows of features where mask_full, file after file, in a   */
+/* file entry after entry, in an entry by ascending row.                                                */
+/* gp_fuse_plan (the settings, config/fusion_scannet.yaml:34-35): mask_full u8 [num_files, n]; state    */
+/*   (gp_fuse_state_bytes) for gp_fuse_write; status i64 [8]: [0] rows whose batch index is no integer  */
+/*   in 0..65535 (in no file), [3] top batch index, [4] rows of feat over all files.                    */
+/* gp_fuse_write (what the reader loads, dataset/feature_loader.py:113-192): features fp32 or fp16      */
+/*   [n, d] -> feat fp16 or fp32 [total_rows, d] (GP_ELEM_F32 / GP_ELEM_F16; fp32 -> fp16 rounds to     */
+/*   nearest even, overflows to inf, keeps subnormals), mask u8 [total_rows] (form 1; NULL: not         */
+/*   written), offsets i64 [num_files, num_entries + 1]: file (k, b) is feat[offsets[k][b] ..           */
+/*   offsets[k][b+1]).  num_entries = status[3] + 1, total_rows = status[4] of the plan; a state the    */
+/*   plan did not write moves no row outside [0, n) or [0, total_rows).                                 */
+/* gp_fuse_dense (the reader's evaluation form, dataset/feature_loader.py:119-126, on unvoxelized       */
+/*   points): out fp32 [n, d]: out[p] = mask_full[p] ? feat[rank(p)] : 0, rank(p) the position of p     */
+/*   among the rows with mask_full in (entry, row) order; feat [feat_rows, d] the rows of ONE file set  */
+/*   (all entries); status [0], [3] as above, [4] = rows with mask_full in a valid entry: the caller    */
+/*   compares it with feat_rows (ranks beyond feat_rows read nothing and give zero rows).               */
+/* 1 <= n < 2^31 - 1, 1 <= num_files <= 16, d >= 1.  No output may overlap an input or another output.  */
+size_t gp_fuse_state_bytes(int64_t n, int32_t num_files);
+size_t gp_fuse_workspace_bytes(int64_t n, int32_t num_files, int64_t n_split_points);
+int gp_fuse_plan(const double *points, int64_t n, const uint8_t *seen, int32_t num_files, int64_t n_split_points,
+                 uint64_t seed, int32_t form, uint8_t *mask_full, void *state, size_t state_bytes, int64_t *status,
+                 void *workspace, size_t workspace_bytes, void *stream);
+int gp_fuse_write(const void *features, int32_t elem_in, int64_t d, const uint8_t *seen, int64_t n, int32_t num_files,
+                  const void *state, size_t state_bytes, int64_t num_entries, void *feat, int32_t elem_out,
+                  int64_t total_rows, uint8_t *mask, int64_t *offsets, void *stream);
+size_t gp_fuse_dense_workspace_bytes(int64_t n);
+int gp_fuse_dense(const double *points, int64_t n, const uint8_t *mask_full, const void *feat, int32_t elem,
+                  int64_t feat_rows, int64_t d, float *out, int64_t *status, void *workspace, size_t workspace_bytes,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif
