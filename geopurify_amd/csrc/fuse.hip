@@ -309,8 +309,7 @@ struct FuPlanWork {
           rank(cv.take<uint32_t>((size_t)num_files * cap)), hist(cv.take<uint32_t>((size_t)num_files * cap * 256)), r0(cv.take<int32_t>(n)),
           flag(cv.take<int32_t>(n + 1)), sel(cv.take<int32_t>(LB_MAX_ENTRIES + 1)), sel_idx(cv.take<int32_t>(LB_MAX_ENTRIES + 1)),
           sel_list(cv.take<int32_t>(cap)) {
-        const size_t a = lb_sort_bytes(n), b = lb_scan_bytes(n + 1), c = lb_scan_bytes(LB_MAX_ENTRIES + 1);
-        tmp_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_scan_bytes(n + 1), lb_scan_bytes(LB_MAX_ENTRIES + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -323,8 +322,7 @@ struct FuDenseWork {
     FuDenseWork(GpCarver &cv, int64_t n)
         : k0(cv.take<uint32_t>(n)), k1(cv.take<uint32_t>(n)), r0(cv.take<int32_t>(n)), entry_rows(cv.take<int32_t>(n)),
           flag(cv.take<int32_t>(n + 1)), scan(cv.take<int32_t>(n + 1)) {
-        const size_t a = lb_sort_bytes(n), b = lb_scan_bytes(n + 1);
-        tmp_bytes = a > b ? a : b;
+        tmp_bytes = std::max(lb_sort_bytes(n), lb_scan_bytes(n + 1));
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -384,14 +382,11 @@ extern "C" int gp_fuse_plan(const double *points, int64_t n, const uint8_t *seen
     GP_CHECK_ARG(form == FU_MERGED || form == FU_CHUNK, "%s: form=%d (0 merged, 1 chunk)", who, form);
     GP_CHECK_ARG(n_split_points >= 0, "%s: n_split_points=%lld (0: no split)", who, (long long)n_split_points);
     {
-        const void *in[] = {points, seen};
+        const void *const in[] = {points, seen};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)n};
-        const void *o[] = {mask_full, state, status, workspace};
+        const void *const o[] = {mask_full, state, status, workspace};
         const size_t o_bytes[] = {(size_t)num_files * n, state_bytes, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 4; ++a) {
-            for (int i = 0; i < 2; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 4; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     const int64_t cap = fu_sel_cap(n, n_split_points);
     GpCarver cs_(state, state_bytes);
@@ -407,18 +402,16 @@ extern "C" int gp_fuse_plan(const double *points, int64_t n, const uint8_t *seen
     const uint32_t cs = fu_fmix32((uint32_t)seed ^ fu_fmix32((uint32_t)(seed >> 32)));
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
     const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
-    // (1) entry tables
+    // (1) entry tables: the sorted rows and the offsets into the state
     fu_row_keys_kernel<<<nb, 256, 0, s>>>(points, n, k.k0, k.r0, stw);
     GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, st.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));   // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.k1, n, st.entry_off);
-    GP_CHECK_LAUNCH();
+    const LbTable rows = {k.k0, k.k1, k.r0, st.entry_rows, st.entry_off};
+    LB_TRY(lb_table_finish(rows, n, k.tmp, k.tmp_bytes, s));
     // (2) the threshold key of every (file, entry) that selects
     if (cap > 0) {
         const unsigned eb = (LB_MAX_ENTRIES + 1 + 255) / 256;
         fu_sel_flags_kernel<<<eb, 256, 0, s>>>(st.entry_off, n_split_points, k.sel);
-        io = k.tmp_bytes;
+        size_t io = k.tmp_bytes;
         GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.sel, k.sel_idx, (int32_t)0, (size_t)(LB_MAX_ENTRIES + 1), rocprim::plus<int32_t>(), s));
         fu_sel_list_kernel<<<eb, 256, 0, s>>>(k.sel, k.sel_idx, n_split_points, num_files, cap, k.sel_list, k.prefix, k.rank);
         GP_CHECK_HIP(hipMemsetAsync(k.hist, 0, (size_t)num_files * cap * 256 * sizeof(uint32_t), s));
@@ -436,7 +429,7 @@ extern "C" int gp_fuse_plan(const double *points, int64_t n, const uint8_t *seen
     for (int f = 0; f < num_files; ++f) {
         fu_flags_kernel<<<nb1, 256, 0, s>>>(k.k1, st.entry_rows, st.entry_off, k.sel_idx, k.prefix, seen, n, cap > 0 ? n_split_points : 0, cs,
                                             (uint32_t)f, form, cap, k.flag, mask_full + (size_t)f * n);
-        io = k.tmp_bytes;
+        size_t io = k.tmp_bytes;
         GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.flag, st.scan + (size_t)f * (n + 1), (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
     }
     fu_base_kernel<<<1, 64, 0, s>>>(st.scan, n, num_files, st.base, stw);
@@ -463,14 +456,11 @@ extern "C" int gp_fuse_write(const void *features, int32_t elem_in, int64_t d, c
         return GP_ENOMEM;
     }
     {
-        const void *in[] = {features, seen, state};
+        const void *const in[] = {features, seen, state};
         const size_t in_bytes[] = {(size_t)n * d * si, (size_t)n, state_bytes};
-        const void *o[] = {feat, mask, offsets};
+        const void *const o[] = {feat, mask, offsets};
         const size_t o_bytes[] = {(size_t)total_rows * d * so, (size_t)total_rows, (size_t)num_files * (num_entries + 1) * 8};
-        for (int a = 0; a < 3; ++a) {
-            for (int i = 0; i < 3; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     hipStream_t s = gp_stream(stream_);
     const int64_t cells = (int64_t)num_files * (num_entries + 1);
@@ -501,31 +491,25 @@ extern "C" int gp_fuse_dense(const double *points, int64_t n, const uint8_t *mas
     const size_t si = gp_elem_size(elem);
     GP_CHECK_ARG((uintptr_t)feat % si == 0 && (uintptr_t)out % 4 == 0, "%s: rows not aligned to their element", who);
     {
-        const void *in[] = {points, mask_full, feat};
+        const void *const in[] = {points, mask_full, feat};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)n, (size_t)feat_rows * d * si};
-        const void *o[] = {out, status, workspace};
+        const void *const o[] = {out, status, workspace};
         const size_t o_bytes[] = {(size_t)n * d * 4, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 3; ++a) {
-            for (int i = 0; i < 3; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver cv(workspace, workspace_bytes);
     FuDenseWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *stw = reinterpret_cast<unsigned long long *>(status);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
     const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
     fu_row_keys_kernel<<<nb, 256, 0, s>>>(points, n, k.k0, k.r0, stw);
     GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, k.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));    // (stable)
+    const LbTable rows = {k.k0, k.k1, k.r0, k.entry_rows, nullptr};      // (the sorted rows alone: nothing here reads an entry's offset)
+    LB_TRY(lb_table_sort(rows, n, k.tmp, k.tmp_bytes, s));
     fu_dense_flags_kernel<<<nb1, 256, 0, s>>>(k.k1, k.entry_rows, mask_full, n, k.flag);
-    io = k.tmp_bytes;
+    size_t io = k.tmp_bytes;
     GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.flag, k.scan, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
     fu_dense_count_kernel<<<1, 64, 0, s>>>(k.scan, n, stw);
     GP_CHECK_LAUNCH();

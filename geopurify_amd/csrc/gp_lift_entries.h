@@ -1,12 +1,17 @@
-// Device code shared by the lifts over BATCHED point clouds (lift_batched.hip: gp_lift_batched; lift_masks_batched.hip; lift_labels.hip,
-// whose fill passes the mask "voted" where the others pass "seen"): the
-// entry tables (rows and views sorted stably by entry, offsets by binary search), the per-view counts with the view-drop rule, and
-// the per-entry scene-level fill (references and queries compacted in the entry-sorted order).  One definition for both.
+// Shared by every lift over BATCHED point clouds (lift_batched.hip, lift_stream.hip, lift_labels.hip -- whose fill passes the mask
+// "voted" where the others pass "seen" --, lift_masks_batched.hip, lift_masks_stream.hip, render_depth_batched.hip, fuse.hip).
+// Device code: the entry tables (rows and views sorted stably by entry, offsets by binary search), the per-view counts with the
+// view-drop rule, and the per-entry scene-level fill (references and queries compacted in the entry-sorted order).  Host code, at the
+// end of the file: the carve struct and the launch sequence of each of these (LbTable with lb_row_table / lb_view_table,
+// lb_view_counts, LbFill with lb_fill), the overlap check of the entry points (lb_no_overlap) and the argument checks they word alike.
+// One definition for all: the library's only rocprim::radix_sort_pairs call and its only lb_fill_kernel launch are here.
 #pragma once
+#include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_map_elem.h"
 #include "gp_project.h"
 
 namespace {
@@ -218,6 +223,189 @@ size_t lb_scan_bytes(int64_t n) {
     size_t t = 0;
     (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
     return t;
+}
+
+// ================================================================================================ host side
+// ------------------------------------------------------------------------------------------------ argument checks
+// Every output against every input and every later output, over their whole extents: for each output first all inputs, then the later
+// outputs.  A null pointer overlaps nothing (an optional argument, or an array that a zero capacity leaves unused: pass nullptr).
+inline int lb_no_overlap(const char *who, const void *const *in, const size_t *in_bytes, size_t n_in, const void *const *out,
+                         const size_t *out_bytes, size_t n_out) {
+    for (size_t a = 0; a < n_out; ++a) {
+        for (size_t i = 0; i < n_in; ++i)
+            GP_CHECK_ARG(!lb_overlap(out[a], out_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
+        for (size_t q = a + 1; q < n_out; ++q) GP_CHECK_ARG(!lb_overlap(out[a], out_bytes[a], out[q], out_bytes[q]), "%s: two outputs overlap", who);
+    }
+    return GP_OK;
+}
+template <size_t NI, size_t NO>
+int lb_no_overlap(const char *who, const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO],
+                  const size_t (&out_bytes)[NO]) {
+    return lb_no_overlap(who, in, in_bytes, NI, out, out_bytes, NO);
+}
+
+// run a check that sets the message itself; leave the entry point with its code when it fails
+#define LB_TRY(call)                     \
+    do {                                 \
+        const int rc_ = (call);          \
+        if (rc_ != GP_OK) return rc_;    \
+    } while (0)
+
+inline bool lb_n_ok(int64_t n) { return n > 0 && n < (1ll << 31); }
+inline bool lb_nviews_ok(int32_t nviews) { return nviews >= 1 && nviews <= 65535; }
+
+inline int lb_check_n(const char *who, int64_t n) {
+    GP_CHECK_ARG(lb_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
+    return GP_OK;
+}
+inline int lb_check_nviews(const char *who, int32_t nviews) {
+    GP_CHECK_ARG(lb_nviews_ok(nviews), "%s: %d views outside 1..65535", who, nviews);
+    return GP_OK;
+}
+// elem: GP_ELEM_* of gp_map_elem.h (0 fp32, 1 fp16, 2 bf16); what: "maps" or "masks"
+inline int lb_check_elem(const char *who, int32_t elem, const void *p, const char *what) {
+    GP_CHECK_ARG(gp_elem_ok(elem), "%s: element type %d (0 fp32, 1 fp16, 2 bf16)", who, elem);
+    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)p % 2 == 0, "%s: half %s at an odd address", who, what);
+    return GP_OK;
+}
+inline int lb_check_sampling(const char *who, int32_t bilinear, int32_t h, int32_t w, int32_t height, int32_t width) {
+    GP_CHECK_ARG(bilinear == 0 || bilinear == 1, "%s: bilinear=%d (0 nearest, 1 bilinear)", who, bilinear);
+    GP_CHECK_ARG(bilinear || (h == height && w == width), "%s: the nearest mode samples the map itself: map %d x %d, image %d x %d", who, h, w,
+                 height, width);
+    return GP_OK;
+}
+inline int lb_check_cut(const char *who, int32_t cut_bound) {
+    GP_CHECK_ARG(cut_bound >= 0, "%s: cut_bound=%d must not be negative", who, cut_bound);
+    return GP_OK;
+}
+inline int lb_check_image(const char *who, int32_t height, int32_t width) {
+    GP_CHECK_ARG(height >= 1 && width >= 1, "%s: image %d x %d", who, height, width);
+    return GP_OK;
+}
+inline int lb_check_state(const char *who, size_t state_bytes, size_t need) {
+    GP_CHECK_ARG(state_bytes >= need, "%s: state too small (%zu < %zu)", who, state_bytes, need);
+    return GP_OK;
+}
+inline int lb_check_workspace(const char *who, const GpCarver &cv, size_t workspace_bytes) {
+    if (cv.ok()) return GP_OK;
+    gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
+    return GP_ENOMEM;
+}
+
+// ------------------------------------------------------------------------------------------------ entry tables
+// The rows (or views) sorted stably by entry: (k0, idx0) the keys and indices as the keys kernel wrote them, (k1, idx) sorted, off[b] the
+// first sorted position of entry b.  A workspace carves all five; the streams' begin puts k1 / idx / off into the caller's state.
+struct LbTable {
+    uint32_t *k0, *k1;
+    int32_t *idx0, *idx, *off;
+};
+
+inline LbTable lb_table(GpCarver &cv, int64_t n) {
+    LbTable t;
+    t.k0 = cv.take<uint32_t>(n);
+    t.k1 = cv.take<uint32_t>(n);
+    t.idx0 = cv.take<int32_t>(n);
+    t.idx = cv.take<int32_t>(n);
+    t.off = cv.take<int32_t>(LB_TABLE);
+    return t;
+}
+
+// (k0, idx0) -> (k1, idx): stable, so an entry's rows ascend by row and its views by view index
+inline int lb_table_sort(const LbTable &t, int64_t n, char *tmp, size_t tmp_bytes, hipStream_t s) {
+    size_t io = tmp_bytes;
+    GP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, io, t.k0, t.k1, t.idx0, t.idx, (size_t)n, 0, LB_KEY_BITS, s));
+    return GP_OK;
+}
+
+// the sort and the offsets, for keys that are written (lb_row_table, lb_view_table, or a caller with a keys kernel of its own)
+inline int lb_table_finish(const LbTable &t, int64_t n, char *tmp, size_t tmp_bytes, hipStream_t s) {
+    LB_TRY(lb_table_sort(t, n, tmp, tmp_bytes, s));
+    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(t.k1, n, t.off);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+inline int lb_row_table(const double *points, int64_t n, const LbTable &t, char *tmp, size_t tmp_bytes, unsigned long long *st, hipStream_t s) {
+    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, t.k0, t.idx0, st);
+    GP_CHECK_LAUNCH();
+    return lb_table_finish(t, n, tmp, tmp_bytes, s);
+}
+
+inline int lb_view_table(const int64_t *view_entry, int32_t nviews, const LbTable &t, char *tmp, size_t tmp_bytes, unsigned long long *st,
+                         hipStream_t s) {
+    lb_view_keys_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(view_entry, nviews, t.k0, t.idx0, st);
+    GP_CHECK_LAUNCH();
+    return lb_table_finish(t, nviews, tmp, tmp_bytes, s);
+}
+
+// both tables of a call that has all its views at once
+struct LbTables {
+    LbTable rows, views;
+    LbTables(GpCarver &cv, int64_t n, int32_t nviews) : rows(lb_table(cv, n)), views(lb_table(cv, nviews)) {}
+};
+
+inline int lb_entry_tables(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, const LbTables &t, char *tmp,
+                           size_t tmp_bytes, unsigned long long *st, hipStream_t s) {
+    LB_TRY(lb_row_table(points, n, t.rows, tmp, tmp_bytes, st, s));
+    return lb_view_table(view_entry, nviews, t.views, tmp, tmp_bytes, st, s);
+}
+
+// ------------------------------------------------------------------------------------------------ per-view counts and the drop rule
+// view_count = 0, the counts -- launch_counts(grid, view_count) launches the counting kernel --, keep
+template <typename LaunchCounts>
+int lb_counts_and_keep(LaunchCounts launch_counts, int64_t n, int32_t nviews, int64_t min_visible, int64_t max_visible, int64_t *view_count,
+                       uint8_t *view_keep, hipStream_t s) {
+    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
+    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    launch_counts(dim3(nb < 64 ? nb : 64, (unsigned)nviews), vc);
+    lb_keep_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+// over the sort's own tables (the form over a stream's state, every index of it checked: ls_view_counts, gp_lift_stream_state.h)
+inline int lb_view_counts(const double *points, int64_t n, const int32_t *entry_rows, const int32_t *entry_off, const int64_t *view_entry,
+                          const double *w2c, const double *intr, const double *depth, int32_t nviews, int32_t W, int32_t H, int32_t cut,
+                          double tau, int64_t min_visible, int64_t max_visible, int64_t *view_count, uint8_t *view_keep, hipStream_t s) {
+    return lb_counts_and_keep(
+        [&](dim3 grid, unsigned long long *vc) {
+            lb_counts_kernel<<<grid, 256, 0, s>>>(points, entry_rows, entry_off, view_entry, w2c, intr, depth, W, H, cut, tau, vc);
+        },
+        n, nviews, min_visible, max_visible, view_count, view_keep, s);
+}
+
+// ------------------------------------------------------------------------------------------------ the fill
+struct LbFill {                                                  // what the fill needs beside the entry tables
+    int32_t *ref, *qry, *rs, *qs, *rrow, *qpos;
+    float *rxyz;
+    LbFill(GpCarver &cv, int64_t n) {
+        ref = cv.take<int32_t>(n + 1);
+        qry = cv.take<int32_t>(n + 1);
+        rs = cv.take<int32_t>(n + 1);
+        qs = cv.take<int32_t>(n + 1);
+        rrow = cv.take<int32_t>(n);
+        qpos = cv.take<int32_t>(n);
+        rxyz = cv.take<float>(3 * n);
+    }
+};
+
+// keys / rows / off: the entry tables (the sort's, or the checked copies of a stream's state); mask: the rows that are references
+// ("seen", or "voted"); status words ST_SEEN and ST_QUERIES; fill == 0 stops before the search, nn is then not written.
+// tmp holds lb_scan_bytes(n + 1).
+inline int lb_fill(const double *points, int64_t n, const uint32_t *keys, const int32_t *rows, const int32_t *off, const LbFill &f, char *tmp,
+                   size_t tmp_bytes, const uint8_t *mask, int32_t fill, int64_t *nn, unsigned long long *st, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
+    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(keys, rows, mask, n, f.ref, f.qry);
+    GP_CHECK_LAUNCH();
+    size_t io = tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, io, f.ref, f.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    io = tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, io, f.qry, f.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
+    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, rows, f.ref, f.qry, f.rs, f.qs, n, f.rxyz, f.rrow, f.qpos, st);
+    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, keys, rows, off, f.rs, f.qs, n, f.rxyz, f.rrow, f.qpos, nn, st);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
 }
 
 }  // namespace

@@ -1,10 +1,13 @@
-// Device code of the mask-embedding lift shared by the per-scene path (lift.hip: gp_lift_masks_views) and the batched one
-// (lift_masks_batched.hip: gp_lift_masks_batched): the score sort, the ordered transpose, the segment decision of a visible pixel on
-// the score-ordered copy, and the in-view fill over view-major entries.  One definition, so both paths take the same decisions and
-// give the same bits.  The transpose and the segment decision are templates over the masks' element type (gp_map_elem.h): the batched
+// The part of the mask-embedding lift shared by the per-scene path (lift.hip: gp_lift_masks_views) and the batched ones
+// (lift_masks_batched.hip: gp_lift_masks_batched; lift_masks_stream.hip: its chunks): the score sort, the ordered transpose, the
+// segment decision of a visible pixel on the score-ordered copy, and the in-view fill over view-major entries -- the kernels and, at
+// the end of the file, their workspace (LvSegWork) and launch sequence (lv_segments).  One definition, so all paths take the same
+// decisions and give the same bits.  The transpose and the segment decision are templates over the masks' element type (gp_map_elem.h): the batched
 // paths read fp32, fp16 or bf16 logits, keep the ordered copy in that type and convert the 16 taps of a pixel to fp32 as they are
 // loaded; the per-scene path instantiates float alone.
 #pragma once
+#include <rocprim/device/device_scan.hpp>
+
 #include "gp_common.h"
 #include "gp_map_elem.h"
 
@@ -288,6 +291,62 @@ __global__ void fill_reduce_kernel(const int4 *__restrict__ tab, int nviews,
         if (i >= 0 && d < best) { best = d; bi = i; }
     }
     if (bi >= 0) seg[qent[qi]] = seg[rent[bi]];                  // references keep their segment: no read/write overlap
+}
+
+// ================================================================================================ host side
+// the arrays of the segment decision and the in-view fill.  nsets: the mask sets the ordered copy holds ([nsets, h * w, q] elements of
+// esize bytes); fill_cap: the queries the fill's partial results hold; ntab: the rows of the fill's view table (views + 1 at least)
+struct LvSegWork {
+    void *mt = nullptr;                                          // (the rank-ordered transposed masks, in the masks' own element type)
+    float *sscore = nullptr, *rxyz = nullptr;
+    int32_t *order = nullptr, *cov = nullptr, *rs = nullptr, *rent = nullptr, *qent = nullptr, *part_i = nullptr;
+    double *part_d = nullptr;
+    int4 *tab = nullptr;
+    LvSegWork() = default;
+    LvSegWork(GpCarver &cv, int32_t nsets, int32_t q, int32_t h, int32_t w, int64_t total, int64_t fill_cap, size_t esize, size_t ntab) {
+        mt = cv.take<char>((size_t)nsets * q * h * w * esize);
+        order = cv.take<int32_t>((size_t)nsets * q);
+        sscore = cv.take<float>((size_t)nsets * q);
+        cov = cv.take<int32_t>(total + 1);
+        rs = cv.take<int32_t>(total + 1);
+        rent = cv.take<int32_t>(total);
+        qent = cv.take<int32_t>(total);
+        rxyz = cv.take<float>(total * 3);
+        part_d = cv.take<double>((size_t)FV_CHUNKS * fill_cap);
+        part_i = cv.take<int32_t>((size_t)FV_CHUNKS * fill_cap);
+        tab = cv.take<int4>(ntab);
+    }
+};
+
+// seg[e] = the segment of every entry e = (view, point, pixel), view-major with view v's entries at [view_off[v], view_off[v + 1]):
+// the score sort, the ordered copy of the masks, the decision at the entry's pixel, then the in-view fill.  T: the masks' element
+// type, BITS: the integer or float type of its size that the transpose moves.  tmp holds an int32 scan over total + 1 elements.
+template <typename T, typename BITS>
+int lv_segments(const void *pred_masks, int32_t nviews, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0,
+                const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w, const float *xyz,
+                const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off,
+                const uint8_t *keep, int64_t total, int64_t fill_cap, const LvSegWork &k, char *tmp, size_t tmp_bytes, int32_t *seg,
+                hipStream_t s) {
+    const int64_t hw = (int64_t)h * w;
+    lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
+    const dim3 tg((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews);
+    transpose_views_kernel<BITS><<<tg, 256, 0, s>>>(static_cast<const BITS *>(pred_masks), q, (int)hw, static_cast<BITS *>(k.mt), k.order);
+    lift_masks_views_kernel<T><<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(static_cast<const T *>(k.mt), q, h, w, k.sscore, k.order,
+                                                                                     tap_x0, tap_wx, tap_y0, tap_wy, out_h, out_w, ent_x, ent_y,
+                                                                                     ent_view, keep, total, seg);
+    GP_CHECK_LAUNCH();
+    // the in-view fill
+    const unsigned eb = (unsigned)((total + 1 + 255) / 256);
+    fill_flags_kernel<<<eb, 256, 0, s>>>(seg, total, k.cov);
+    size_t tb = tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, tb, k.cov, k.rs, (int32_t)0, (size_t)(total + 1), rocprim::plus<int32_t>(), s));
+    fill_compact_kernel<<<eb, 256, 0, s>>>(xyz, ent_pt, seg, k.rs, total, k.rxyz, k.rent, k.qent);
+    const unsigned qb = (unsigned)(total / 256 + nviews + 1);                            // >= sum over views of ceil(queries / 256)
+    fill_table_kernel<<<1, 64, 0, s>>>(view_off, k.rs, nviews, k.tab);
+    fill_part_kernel<<<dim3(qb, FV_CHUNKS), 256, 0, s>>>(xyz, ent_pt, k.tab, nviews, k.rxyz, k.qent, k.part_d, k.part_i, fill_cap, k.rent, seg);
+    fill_reduce_kernel<<<qb, 256, 0, s>>>(k.tab, nviews, k.part_d, k.part_i, fill_cap, k.rent, k.qent, seg);
+    GP_CHECK_LAUNCH();
+    return GP_OK;
 }
 
 }  // namespace

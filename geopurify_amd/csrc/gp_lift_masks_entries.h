@@ -1,8 +1,12 @@
-// Device code shared by the mask-embedding lifts over BATCHED point clouds (lift_masks_batched.hip: gp_lift_masks_batched, all views in
-// one call; lift_masks_stream.hip: the same lift with the views arriving in chunks): the views' positions inside their entries, the
-// checked copies of the visible entries, and the point -> (view, segment) lists over a bit set per point.  One definition for both.
+// Shared by the mask-embedding lifts over BATCHED point clouds (lift_masks_batched.hip: gp_lift_masks_batched, all views in one call;
+// lift_masks_stream.hip: the same lift with the views arriving in chunks).  Device code: the views' positions inside their entries,
+// the checked copies of the visible entries, and the point -> (view, segment) lists over a bit set per point.  Host code, at the end
+// of the file: the pipeline of a call's or a chunk's entries (LmbEntries, lmb_chunk_segments: checked entries, the segments of
+// gp_lift_masks.h, the in-view fill) and the end both share (LmbLists, lmb_fuse_fill: the lists, the top-3 fusion, the scene-level
+// fill of gp_lift_entries.h), with the argument checks the entry points word alike.  One definition for both.
 #pragma once
 #include "gp_lift_entries.h"
+#include "gp_lift_masks.h"
 
 namespace {
 
@@ -179,21 +183,117 @@ __global__ void __launch_bounds__(256) lmb_pv_fill_kernel(const int64_t *__restr
     pv_seg[s_] = seg[e];
 }
 
-int lmb_entry_tables(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, uint32_t *k0, uint32_t *k1, int32_t *r0,
-                     int32_t *entry_rows, uint32_t *vk0, uint32_t *vk1, int32_t *w0, int32_t *entry_views, int32_t *entry_off, int32_t *view_off,
-                     char *tmp, size_t tmp_bytes, unsigned long long *st, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
-    lb_row_keys_kernel<<<nb, 256, 0, s>>>(points, n, k0, r0, st);
-    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, vk0, w0, st);
+// ================================================================================================ host side
+inline int lmb_check_masks(const char *who, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w) {
+    GP_CHECK_ARG(q >= 1 && q <= 1024, "%s: %d queries outside 1..1024 (the score sort holds 1024)", who, q);
+    GP_CHECK_ARG(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1 && (int64_t)h * w < (1ll << 31), "%s: masks %d x %d, image %d x %d", who, h, w, out_h,
+                 out_w);
+    return GP_OK;
+}
+inline int lmb_check_words(const char *who, int32_t words) {
+    GP_CHECK_ARG(words >= 1 && words <= 1024, "%s: words=%d outside 1..1024", who, words);
+    return GP_OK;
+}
+inline int lmb_check_fill_cap(const char *who, int64_t fill_cap, int64_t total) {
+    GP_CHECK_ARG(fill_cap >= 0 && fill_cap <= total, "%s: fill_cap=%lld outside 0..total", who, (long long)fill_cap);
+    return GP_OK;
+}
+// what the fusion and the scene-level fill ask of the segment tables and the outputs
+inline int lmb_check_fused(const char *who, int32_t d, int32_t c, int64_t ld_out, const float *f_seg, const float *out, int32_t fill,
+                           const int64_t *nn) {
+    GP_CHECK_ARG(d >= 1 && c >= 1 && d % 4 == 0 && ld_out % 4 == 0 && ld_out >= d, "%s: d=%d and ld_out=%lld must be multiples of 4, c=%d", who, d,
+                 (long long)ld_out, c);
+    GP_CHECK_ARG(((uintptr_t)f_seg | (uintptr_t)out) % 16 == 0, "%s: f_seg and out must be 16-byte aligned", who);
+    GP_CHECK_ARG(fill == 0 || nn, "%s: the fill writes nn", who);
+    return GP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ a call's or a chunk's entries
+// the checked copies of the per-view arrays and of the visible entries; total == 0 (a chunk in which nothing is visible): the per-view
+// arrays alone
+struct LmbEntries {
+    int64_t *voff, *c_pt = nullptr, *c_x = nullptr, *c_y = nullptr;
+    int32_t *c_view = nullptr, *cx0 = nullptr, *cy0 = nullptr;
+    uint8_t *c_keep, *c_live = nullptr;
+    float *xyz = nullptr;
+    LmbEntries(GpCarver &cv, int64_t n, int32_t nviews, int32_t out_h, int32_t out_w, int64_t total) {
+        voff = cv.take<int64_t>((size_t)nviews + 1);
+        c_keep = cv.take<uint8_t>(nviews);
+        if (total == 0) return;
+        c_pt = cv.take<int64_t>(total);
+        c_x = cv.take<int64_t>(total);
+        c_y = cv.take<int64_t>(total);
+        c_view = cv.take<int32_t>(total);
+        c_live = cv.take<uint8_t>(total);
+        cx0 = cv.take<int32_t>(out_w);
+        cy0 = cv.take<int32_t>(out_h);
+        xyz = cv.take<float>(3 * n);
+    }
+};
+
+// seg[e] = the segment that entry e shows after the in-view fill, -1 for none.  The entries are checked and copied first -- an entry
+// that is not what the lists promise is counted in the status and replaced by one that decides nothing --, then the kernels of
+// gp_lift_masks.h run on the copies.  view_local: the position of every view inside its entry, -1 for none (lmb_view_local_kernel, or
+// a stream's view_pos).  tmp holds lb_scan_bytes(total + 1).
+inline int lmb_chunk_segments(const double *points, int64_t n, const int64_t *view_entry, const int32_t *view_local, int32_t nviews,
+                              const void *pred_masks, int32_t elem, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0,
+                              const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w,
+                              const int64_t *ent_pt, const int64_t *ent_x, const int64_t *ent_y, const int32_t *ent_view, const int64_t *view_off,
+                              const uint8_t *keep, int64_t total, int64_t fill_cap, const LmbEntries &e, const LvSegWork &k, char *tmp,
+                              size_t tmp_bytes, int32_t *seg, unsigned long long *st, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256), eb = (unsigned)((total + 1 + 255) / 256);
+    lmb_xyz_kernel<<<nb, 256, 0, s>>>(points, n, e.xyz);
+    lmb_view_off_kernel<<<1, 64, 0, s>>>(view_off, nviews, total, e.voff, st);
+    lmb_taps_kernel<<<(unsigned)((out_w + out_h + 255) / 256), 256, 0, s>>>(tap_x0, tap_y0, out_w, out_h, w, h, e.cx0, e.cy0, st);
+    lmb_entries_kernel<<<eb, 256, 0, s>>>(points, n, view_entry, view_local, e.voff, nviews, out_h, out_w, ent_pt, ent_x, ent_y, ent_view, keep,
+                                          total, e.c_pt, e.c_x, e.c_y, e.c_view, e.c_live, st);
+    lmb_keep_kernel<<<vb, 256, 0, s>>>(keep, view_local, nviews, e.c_keep);
     GP_CHECK_LAUNCH();
-    size_t io = tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, io, k0, k1, r0, entry_rows, (size_t)n, 0, LB_KEY_BITS, s));               // (stable)
-    io = tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, io, vk0, vk1, w0, entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));       // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k1, n, entry_off);
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(vk1, nviews, view_off);
+#define LMB_SEGMENTS(T, BITS)                                                                                                                \
+    lv_segments<T, BITS>(pred_masks, nviews, q, h, w, scores, e.cx0, tap_wx, e.cy0, tap_wy, out_h, out_w, e.xyz, e.c_pt, e.c_x, e.c_y, e.c_view, \
+                         e.voff, e.c_keep, total, fill_cap, k, tmp, tmp_bytes, seg, s)
+    if (elem == GP_ELEM_F32) LB_TRY(LMB_SEGMENTS(float, float));
+    else if (elem == GP_ELEM_F16) LB_TRY(LMB_SEGMENTS(gp_f16, uint16_t));
+    else LB_TRY(LMB_SEGMENTS(gp_bf16, uint16_t));
+#undef LMB_SEGMENTS
+    lmb_dead_kernel<<<eb, 256, 0, s>>>(e.c_live, total, seg);
     GP_CHECK_LAUNCH();
     return GP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the end: lists, fusion, fill
+struct LmbLists {                                                // the point -> (view, segment) lists
+    unsigned long long *vmask;
+    int64_t *cnt, *pv_start;
+    int32_t *pv_view, *pv_seg;
+    LmbLists(GpCarver &cv, int64_t n, int64_t total, int32_t words) {
+        vmask = cv.take<unsigned long long>((size_t)n * words);
+        cnt = cv.take<int64_t>(n + 1);
+        pv_start = cv.take<int64_t>(n + 1);
+        pv_view = cv.take<int32_t>(total);
+        pv_seg = cv.take<int32_t>(total);
+    }
+};
+
+// From the checked entries (or records) and their segments: every point's (view, segment) list in ascending position of the view
+// inside its entry, count, the consensus top-3 fusion (the kernel of the per-scene path: out, seen), and the scene-level fill inside
+// every entry over the tables keys / rows / off (nn).  tmp holds lb_scan_bytes(n + 1) and lmb_scan64_bytes(n + 1).
+inline int lmb_fuse_fill(const double *points, int64_t n, const int64_t *c_pt, const int32_t *c_view, const uint8_t *c_live,
+                         const int32_t *view_local, const int32_t *seg, int64_t total, int32_t words, const LmbLists &l, const uint32_t *keys,
+                         const int32_t *rows, const int32_t *off, const LbFill &f, char *tmp, size_t tmp_bytes, const float *f_seg,
+                         const float *logit_seg, int32_t q, int32_t d, int32_t c, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
+                         int32_t *count, int64_t *nn, unsigned long long *st, void *stream_) {
+    hipStream_t s = gp_stream(stream_);
+    const unsigned eb = (unsigned)((total + 255) / 256);
+    GP_CHECK_HIP(hipMemsetAsync(l.vmask, 0, (size_t)n * words * sizeof(unsigned long long), s));
+    lmb_pv_mask_kernel<<<eb, 256, 0, s>>>(c_pt, c_view, c_live, view_local, total, words, l.vmask);
+    lmb_pv_cnt_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(l.vmask, n, words, l.cnt, count, nn);
+    size_t tb = tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, tb, l.cnt, l.pv_start, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), s));
+    lmb_pv_fill_kernel<<<eb, 256, 0, s>>>(c_pt, c_view, c_live, view_local, seg, total, words, l.vmask, l.pv_start, l.pv_view, l.pv_seg);
+    GP_CHECK_LAUNCH();
+    LB_TRY(gp_fuse_views_top3(l.pv_start, l.pv_view, l.pv_seg, n, f_seg, logit_seg, q, d, c, out, ld_out, seen, stream_));
+    return lb_fill(points, n, keys, rows, off, f, tmp, tmp_bytes, seen, fill, nn, st, s);
 }
 
 }  // namespace

@@ -416,39 +416,29 @@ static size_t lv_scan64_tmp(int64_t n) {
     return t;
 }
 struct LvWork {
-    float *mt; int32_t *cov, *rs, *rent, *qent; float *rxyz; double *part_d; int32_t *part_i; unsigned long long *vmask; int4 *tab;
-    int64_t *cnt; char *tmp; size_t tmp_bytes;
-    int32_t *order; float *sscore;                       // the queries of every view by descending score
+    LvSegWork seg;                                       // the segment decision and the in-view fill (gp_lift_masks.h); 130: 128 views + 2
+    unsigned long long *vmask;
+    int64_t *cnt;
+    char *tmp;
+    size_t tmp_bytes;
+    LvWork(GpCarver &cv, int32_t nsrc, int32_t q, int32_t h, int32_t w, int64_t total, int64_t n, int64_t fill_cap)
+        : seg(cv, nsrc, q, h, w, total, fill_cap, sizeof(float), 130) {
+        vmask = cv.take<unsigned long long>(n * 2);
+        cnt = cv.take<int64_t>(n + 1);
+        size_t a = lv_scan32_tmp(total + 1), b = lv_scan64_tmp(n + 1);
+        tmp_bytes = a > b ? a : b;
+        tmp = cv.take<char>(tmp_bytes);
+    }
 };
-static size_t lv_carve(void *ws, size_t bytes, int32_t nsrc, int32_t q, int32_t h, int32_t w, int64_t total, int64_t n, int64_t fill_cap,
-                       LvWork &k) {
-    GpCarver cv(ws, bytes);
-    k.mt = cv.take<float>((size_t)nsrc * q * h * w);
-    k.order = cv.take<int32_t>((size_t)nsrc * q);
-    k.sscore = cv.take<float>((size_t)nsrc * q);
-    k.cov = cv.take<int32_t>(total + 1);
-    k.rs = cv.take<int32_t>(total + 1);
-    k.rent = cv.take<int32_t>(total);
-    k.qent = cv.take<int32_t>(total);
-    k.rxyz = cv.take<float>(total * 3);
-    k.part_d = cv.take<double>((size_t)FV_CHUNKS * fill_cap);
-    k.part_i = cv.take<int32_t>((size_t)FV_CHUNKS * fill_cap);
-    k.vmask = cv.take<unsigned long long>(n * 2);
-    k.cnt = cv.take<int64_t>(n + 1);
-    k.tab = cv.take<int4>(130);
-    size_t a = lv_scan32_tmp(total + 1), b = lv_scan64_tmp(n + 1);
-    k.tmp_bytes = a > b ? a : b;
-    k.tmp = cv.take<char>(k.tmp_bytes);
-    return cv.off;
-}
 // fill_cap: capacity (in fill queries = uncovered entries) of the partial-result arrays of the in-view fill, 1 .. total; 0 = total
 // (every entry could be a query).  Queries beyond the capacity are still answered (one block per 256 of them sweeps the whole
 // reference range), so any value is CORRECT; a capacity of the expected query count keeps the fill fully parallel.
 extern "C" size_t gp_lift_masks_views_workspace_bytes(int32_t nsrc, int32_t q, int32_t h, int32_t w, int64_t total, int64_t n,
                                                       int64_t fill_cap) {
     if (nsrc <= 0 || q <= 0 || h <= 0 || w <= 0 || total <= 0 || n <= 0 || fill_cap < 0 || fill_cap > total) return 0;
-    LvWork k;
-    return lv_carve(nullptr, 0, nsrc, q, h, w, total, n, fill_cap ? fill_cap : total, k);
+    GpCarver cv(nullptr, 0);
+    LvWork k(cv, nsrc, q, h, w, total, n, fill_cap ? fill_cap : total);
+    return cv.off;
 }
 // seg i32 [total] (out: segment of every entry after the in-view fill, -1 = none); pv_start i64 [n+1], pv_view / pv_seg i32 [total]
 // (out: the point -> (view, segment) CSR that gp_fuse_views_top3 reads).  Replaces, for all views together, the per-view
@@ -469,33 +459,23 @@ extern "C" int gp_lift_masks_views(const float *pred_masks, int32_t nsrc, int32_
     GP_CHECK_ARG(total < (int64_t)INT32_MAX, "gp_lift_masks_views: too many entries");
     GP_CHECK_ARG(fill_cap >= 0 && fill_cap <= total, "gp_lift_masks_views: fill_cap=%lld outside 0..total", (long long)fill_cap);
     if (fill_cap == 0) fill_cap = total;
-    LvWork k;
-    if (lv_carve(workspace, workspace_bytes, nsrc, q, h, w, total, n, fill_cap, k) > workspace_bytes) {
+    GpCarver cv(workspace, workspace_bytes);
+    LvWork k(cv, nsrc, q, h, w, total, n, fill_cap);
+    if (!cv.ok()) {
         gp_set_error("gp_lift_masks_views: workspace too small");
         return GP_ENOMEM;
     }
     hipStream_t s = gp_stream(stream_);
-    const int hw = h * w;
-    lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    transpose_views_kernel<float><<<dim3((hw + 63) / 64, (q + 63) / 64, nviews), 256, 0, s>>>(pred_masks, q, hw, k.mt, k.order);
-    lift_masks_views_kernel<float><<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(k.mt, q, h, w, k.sscore, k.order, tap_x0, tap_wx, tap_y0,
-                                                                               tap_wy, out_h, out_w, ent_x, ent_y, ent_view, keep, total, seg);
-    // in-view fill
+    // the segment of every entry, then the in-view fill
+    int rc = lv_segments<float, float>(pred_masks, nviews, q, h, w, scores, tap_x0, tap_wx, tap_y0, tap_wy, out_h, out_w, xyz, ent_pt, ent_x, ent_y,
+                                       ent_view, view_off, keep, total, fill_cap, k.seg, k.tmp, k.tmp_bytes, seg, s);
+    if (rc != GP_OK) return rc;
     const unsigned eb = (unsigned)((total + 1 + 255) / 256);
-    fill_flags_kernel<<<eb, 256, 0, s>>>(seg, total, k.cov);
-    size_t tb = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cov, k.rs, (int32_t)0, (size_t)(total + 1), rocprim::plus<int32_t>(), s));
-    fill_compact_kernel<<<eb, 256, 0, s>>>(xyz, ent_pt, seg, k.rs, total, k.rxyz, k.rent, k.qent);
-    const unsigned qb = (unsigned)(total / 256 + nviews + 1);                           // >= sum over views of ceil(queries / 256)
-    fill_table_kernel<<<1, 64, 0, s>>>(view_off, k.rs, nviews, k.tab);
-    fill_part_kernel<<<dim3(qb, FV_CHUNKS), 256, 0, s>>>(xyz, ent_pt, k.tab, nviews, k.rxyz, k.qent, k.part_d, k.part_i, fill_cap,
-                                                         k.rent, seg);
-    fill_reduce_kernel<<<qb, 256, 0, s>>>(k.tab, nviews, k.part_d, k.part_i, fill_cap, k.rent, k.qent, seg);
     // point -> (view, segment) lists
     GP_CHECK_HIP(hipMemsetAsync(k.vmask, 0, (size_t)n * 2 * sizeof(unsigned long long), s));
     pv_mask_kernel<<<eb, 256, 0, s>>>(ent_pt, ent_view, keep, total, k.vmask);
     pv_cnt_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(k.vmask, n, k.cnt);
-    tb = k.tmp_bytes;
+    size_t tb = k.tmp_bytes;
     GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cnt, pv_start, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), s));
     pv_fill_views_kernel<<<eb, 256, 0, s>>>(ent_pt, ent_view, keep, seg, total, k.vmask, pv_start, pv_view, pv_seg);
     GP_CHECK_LAUNCH();

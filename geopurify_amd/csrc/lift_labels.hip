@@ -173,56 +173,34 @@ __global__ void __launch_bounds__(256) ll_fill_apply_kernel(const int64_t *__res
     if ((uint64_t)j < (uint64_t)n) labels[p] = labels[j];
 }
 
-// the running words into finish's status: bad batch rows, bad view entries, non-finite rows, top batch and the out-of-range labels
-__global__ void ll_status_kernel(const int64_t *__restrict__ running, int64_t *__restrict__ status_out) {
-    const int i = threadIdx.x;
-    if (i < ST_WORDS) status_out[i] = (i <= ST_TOP_BATCH || i == ST_BAD_LABEL) ? running[i] : 0;
-}
-
-struct LlFill {                                                  // what the fill needs beside the entry tables
-    int32_t *ref, *qry, *rs, *qs, *rrow, *qpos;
-    float *rxyz;
+struct LlFill {                                                  // the fill over "voted" and what the label move needs beside it
+    LbFill f;
     uint8_t *has_vote;
     int64_t *nn;
-    LlFill(GpCarver &cv, int64_t n) {
-        ref = cv.take<int32_t>(n + 1);
-        qry = cv.take<int32_t>(n + 1);
-        rs = cv.take<int32_t>(n + 1);
-        qs = cv.take<int32_t>(n + 1);
-        rrow = cv.take<int32_t>(n);
-        qpos = cv.take<int32_t>(n);
-        rxyz = cv.take<float>(3 * n);
+    LlFill(GpCarver &cv, int64_t n) : f(cv, n) {
         has_vote = cv.take<uint8_t>(n);
         nn = cv.take<int64_t>(n);
     }
 };
 
 struct LlWork {
-    uint32_t *k0, *k1, *vk0, *vk1;
-    int32_t *r0, *entry_rows, *w0, *entry_views, *entry_off, *view_off;
+    LbTables t;
+    LlFill f;
     char *tmp;
     size_t tmp_bytes;
-    LlFill f;
-    static size_t tmp_need(int64_t n, int32_t nviews) {
-        const size_t a = lb_sort_bytes(n), b = lb_sort_bytes(nviews), c = lb_scan_bytes(n + 1);
-        return a > b ? (a > c ? a : c) : (b > c ? b : c);
-    }
-    LlWork(GpCarver &cv, int64_t n, int32_t nviews)
-        : k0(cv.take<uint32_t>(n)), k1(cv.take<uint32_t>(n)), vk0(cv.take<uint32_t>(nviews)), vk1(cv.take<uint32_t>(nviews)),
-          r0(cv.take<int32_t>(n)), entry_rows(cv.take<int32_t>(n)), w0(cv.take<int32_t>(nviews)), entry_views(cv.take<int32_t>(nviews)),
-          entry_off(cv.take<int32_t>(LB_TABLE)), view_off(cv.take<int32_t>(LB_TABLE)), tmp_bytes(tmp_need(n, nviews)), f(cv, n) {
+    LlWork(GpCarver &cv, int64_t n, int32_t nviews) : t(cv, n, nviews), f(cv, n) {
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };
 
 struct LlFinishWork {                                            // the checked copies of the state's tables, the fill
-    uint32_t *keys;
-    int32_t *rows, *off;
+    LsState tables;
+    LlFill f;
     char *tmp;
     size_t tmp_bytes;
-    LlFill f;
-    LlFinishWork(GpCarver &cv, int64_t n)
-        : keys(cv.take<uint32_t>(n)), rows(cv.take<int32_t>(n)), off(cv.take<int32_t>(LB_TABLE)), tmp_bytes(lb_scan_bytes(n + 1)), f(cv, n) {
+    LlFinishWork(GpCarver &cv, int64_t n) : tables(cv, n), f(cv, n) {
+        tmp_bytes = lb_scan_bytes(n + 1);
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -238,19 +216,35 @@ int ll_ignore(const char *who, const int64_t *ignore_ids, int32_t n_ignore, LlIg
 // the fill over the mask f.has_vote and the labels it moves; keys / rows / off: the entry tables (the sort's, or the checked copies)
 int ll_fill(const double *points, int64_t n, const uint32_t *keys, const int32_t *rows, const int32_t *off, const LlFill &f, char *tmp,
             size_t tmp_bytes, int32_t fill, int64_t *labels, unsigned long long *st, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
-    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(keys, rows, f.has_vote, n, f.ref, f.qry);
+    LB_TRY(lb_fill(points, n, keys, rows, off, f.f, tmp, tmp_bytes, f.has_vote, fill, f.nn, st, s));
+    if (fill) ll_fill_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(f.nn, n, labels);
     GP_CHECK_LAUNCH();
-    size_t io = tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, io, f.ref, f.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    io = tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(tmp, io, f.qry, f.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, rows, f.ref, f.qry, f.rs, f.qs, n, f.rxyz, f.rrow, f.qpos, st);
-    if (fill) {
-        lb_fill_kernel<<<nb, 256, 0, s>>>(points, keys, rows, off, f.rs, f.qs, n, f.rxyz, f.rrow, f.qpos, f.nn, st);
-        ll_fill_apply_kernel<<<nb, 256, 0, s>>>(f.nn, n, labels);
-    }
-    GP_CHECK_LAUNCH();
+    return GP_OK;
+}
+
+// the checks the entry points word alike: the votes' shape
+int ll_check_classes(const char *who, int32_t num_classes, int64_t ld_votes) {
+    GP_CHECK_ARG(num_classes >= 1 && num_classes <= LL_MAX_CLASSES && ld_votes >= num_classes, "%s: num_classes=%d outside 1..%d, ld_votes=%lld", who,
+                 num_classes, LL_MAX_CLASSES, (long long)ld_votes);
+    return GP_OK;
+}
+
+// the two calls that read label maps: element type and alignment, n, the views, the votes' shape, the image, the cut bound
+int ll_check_maps(const char *who, const void *labels2d, int32_t elem, int64_t n, int32_t nviews, int32_t num_classes, int64_t ld_votes,
+                  int32_t height, int32_t width, int32_t cut_bound) {
+    GP_CHECK_ARG(ll_elem_ok(elem), "%s: label type %d (0 u8, 1 i16, 2 i32, 3 i64)", who, elem);
+    GP_CHECK_ARG((uintptr_t)labels2d % ll_elem_size(elem) == 0, "%s: label maps not aligned to their element", who);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    LB_TRY(ll_check_classes(who, num_classes, ld_votes));
+    LB_TRY(lb_check_image(who, height, width));
+    return lb_check_cut(who, cut_bound);
+}
+
+// fill is a flag, and `unlabeled` no class
+int ll_check_fill(const char *who, int32_t fill, int64_t unlabeled, int32_t num_classes) {
+    GP_CHECK_ARG(fill == 0 || fill == 1, "%s: fill=%d (0 or 1)", who, fill);
+    GP_CHECK_ARG((uint64_t)unlabeled >= (uint64_t)num_classes, "%s: unlabeled=%lld is a class of 0..%d", who, (long long)unlabeled, num_classes - 1);
     return GP_OK;
 }
 
@@ -276,7 +270,7 @@ int ll_vote(const double *points, int64_t n, const void *labels2d, int32_t elem,
 }  // namespace
 
 extern "C" size_t gp_lift_labels_batched_workspace_bytes(int64_t n, int32_t nviews) {
-    if (!ls_n_ok(n) || nviews < 1 || nviews > 65535) return 0;
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews)) return 0;
     GpCarver cv(nullptr, 0);
     LlWork k(cv, n, nviews);
     return cv.off;
@@ -292,120 +286,69 @@ extern "C" int gp_lift_labels_batched(const double *points, int64_t n, const voi
     GP_CHECK_ARG(points && labels2d && view_entry && w2c && intrinsics && labels && votes && voted && seen && count && view_count && view_keep &&
                      status && workspace,
                  "%s: null argument", who);
-    GP_CHECK_ARG(ll_elem_ok(elem), "%s: label type %d (0 u8, 1 i16, 2 i32, 3 i64)", who, elem);
-    GP_CHECK_ARG((uintptr_t)labels2d % ll_elem_size(elem) == 0, "%s: label maps not aligned to their element", who);
-    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "%s: %d views outside 1..65535", who, nviews);
-    GP_CHECK_ARG(num_classes >= 1 && num_classes <= LL_MAX_CLASSES && ld_votes >= num_classes, "%s: num_classes=%d outside 1..%d, ld_votes=%lld", who,
-                 num_classes, LL_MAX_CLASSES, (long long)ld_votes);
-    GP_CHECK_ARG(height >= 1 && width >= 1, "%s: image %d x %d", who, height, width);
-    GP_CHECK_ARG(cut_bound >= 0, "%s: cut_bound=%d must not be negative", who, cut_bound);
-    GP_CHECK_ARG(fill == 0 || fill == 1, "%s: fill=%d (0 or 1)", who, fill);
-    GP_CHECK_ARG((uint64_t)unlabeled >= (uint64_t)num_classes, "%s: unlabeled=%lld is a class of 0..%d", who, (long long)unlabeled, num_classes - 1);
+    LB_TRY(ll_check_maps(who, labels2d, elem, n, nviews, num_classes, ld_votes, height, width, cut_bound));
+    LB_TRY(ll_check_fill(who, fill, unlabeled, num_classes));
     LlIgnore ign;
-    if (int rc = ll_ignore(who, ignore_ids, n_ignore, ign)) return rc;
+    LB_TRY(ll_ignore(who, ignore_ids, n_ignore, ign));
     {
-        // every output against every input and every other output, over their whole extents
         const size_t px = (size_t)height * width;
-        const void *in[] = {points, labels2d, view_entry, w2c, intrinsics, depth};
+        const void *const in[] = {points, labels2d, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32,       (size_t)nviews * px * ll_elem_size(elem), (size_t)nviews * 8, (size_t)nviews * 128,
                                    (size_t)nviews * 32, (size_t)nviews * px * 8};
-        const void *o[] = {labels, votes, voted, seen, count, view_count, view_keep, status, workspace};
+        const void *const o[] = {labels, votes, voted, seen, count, view_count, view_keep, status, workspace};
         const size_t o_bytes[] = {(size_t)n * 8, (size_t)((n - 1) * ld_votes + num_classes) * 4, (size_t)n * 4, (size_t)n, (size_t)n * 4,
                                   (size_t)nviews * 8, (size_t)nviews, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 9; ++a) {
-            for (int i = 0; i < 6; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 9; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver cv(workspace, workspace_bytes);
     LlWork k(cv, n, nviews);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
-    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
-    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
-    // (1) entry tables
-    lb_row_keys_kernel<<<nb, 256, 0, s>>>(points, n, k.k0, k.r0, st);
-    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, k.vk0, k.w0, st);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, k.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));          // (stable)
-    io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.vk0, k.vk1, k.w0, k.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));  // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.k1, n, k.entry_off);
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.vk1, nviews, k.view_off);
-    // (2) per-view counts and the drop rule
-    lb_counts_kernel<<<dim3(nb < 64 ? nb : 64, (unsigned)nviews), 256, 0, s>>>(points, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, depth,
-                                                                                width, height, cut_bound, vis_thres, vc);
-    lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
-    GP_CHECK_LAUNCH();
+    // (1) entry tables, (2) per-view counts and the drop rule
+    LB_TRY(lb_entry_tables(points, n, view_entry, nviews, k.t, k.tmp, k.tmp_bytes, st, s));
+    LB_TRY(lb_view_counts(points, n, k.t.rows.idx, k.t.rows.off, view_entry, w2c, intrinsics, depth, nviews, width, height, cut_bound, vis_thres,
+                          min_visible, max_visible, view_count, view_keep, s));
     // (3) the vote
-    if (int rc = ll_vote<false>(points, n, labels2d, elem, num_classes, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height, cut_bound,
-                                vis_thres, view_keep, ign, votes, ld_votes, count, seen, voted, k.f.has_vote, labels, unlabeled, k.f.nn, st, s))
-        return rc;
+    LB_TRY(ll_vote<false>(points, n, labels2d, elem, num_classes, k.t.views.idx, k.t.views.off, w2c, intrinsics, depth, width, height, cut_bound,
+                          vis_thres, view_keep, ign, votes, ld_votes, count, seen, voted, k.f.has_vote, labels, unlabeled, k.f.nn, st, s));
     // (4) the fill over "voted"
-    return ll_fill(points, n, k.k1, k.entry_rows, k.entry_off, k.f, k.tmp, k.tmp_bytes, fill, labels, st, s);
+    return ll_fill(points, n, k.t.rows.k1, k.t.rows.idx, k.t.rows.off, k.f, k.tmp, k.tmp_bytes, fill, labels, st, s);
 }
 
 // ------------------------------------------------------------------------------------------------ the same vote, the views in chunks
-extern "C" size_t gp_lift_labels_stream_state_bytes(int64_t n) { return ls_n_ok(n) ? ls_state_bytes(n) : 0; }
+extern "C" size_t gp_lift_labels_stream_state_bytes(int64_t n) { return lb_n_ok(n) ? ls_state_bytes(n) : 0; }
 
-extern "C" size_t gp_lift_labels_stream_begin_workspace_bytes(int64_t n) {
-    if (!ls_n_ok(n)) return 0;
-    GpCarver cv(nullptr, 0);
-    LsBeginWork k(cv, n);
-    return cv.off;
-}
+extern "C" size_t gp_lift_labels_stream_begin_workspace_bytes(int64_t n) { return lb_n_ok(n) ? ls_begin_workspace_bytes(n) : 0; }
 
 extern "C" int gp_lift_labels_stream_begin(const double *points, int64_t n, int32_t num_classes, void *state, size_t state_bytes, int32_t *votes,
                                            int64_t ld_votes, int32_t *count, int64_t *status, void *workspace, size_t workspace_bytes,
                                            void *stream_) {
     const char *who = "gp_lift_labels_stream_begin";
     GP_CHECK_ARG(points && state && votes && count && status && workspace, "%s: null argument", who);
-    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
-    GP_CHECK_ARG(num_classes >= 1 && num_classes <= LL_MAX_CLASSES && ld_votes >= num_classes, "%s: num_classes=%d outside 1..%d, ld_votes=%lld", who,
-                 num_classes, LL_MAX_CLASSES, (long long)ld_votes);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "%s: state too small (%zu < %zu)", who, state_bytes, ls_state_bytes(n));
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(ll_check_classes(who, num_classes, ld_votes));
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        const void *o[] = {state, votes, count, status, workspace};
+        const void *const in[] = {points};
+        const size_t in_bytes[] = {(size_t)n * 32};
+        const void *const o[] = {state, votes, count, status, workspace};
         const size_t o_bytes[] = {state_bytes, (size_t)((n - 1) * ld_votes + num_classes) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 5; ++a) {
-            GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], points, (size_t)n * 32), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
     LsState st(sv, n);
     LsBeginWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
     GP_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int32_t), s));
     GP_CHECK_HIP(hipMemset2DAsync(votes, (size_t)ld_votes * 4, 0, (size_t)num_classes * 4, (size_t)n, s));   // the pitch columns untouched
-    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, reinterpret_cast<unsigned long long *>(status));
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, st.keys, k.r0, st.rows, (size_t)n, 0, LB_KEY_BITS, s));             // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(st.keys, n, st.off);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    return ls_begin_tables(points, n, st, k, status, s);
 }
 
-extern "C" size_t gp_lift_labels_stream_add_workspace_bytes(int32_t nviews) {
-    if (nviews < 1 || nviews > 65535) return 0;
-    GpCarver cv(nullptr, 0);
-    LsAddWork k(cv, nviews);
-    return cv.off;
-}
+extern "C" size_t gp_lift_labels_stream_add_workspace_bytes(int32_t nviews) { return lb_nviews_ok(nviews) ? ls_add_workspace_bytes(nviews) : 0; }
 
 extern "C" int gp_lift_labels_stream_add(const double *points, int64_t n, const void *state, size_t state_bytes, const void *labels2d, int32_t elem,
                                          int32_t num_classes, const int64_t *view_entry, const double *w2c, const double *intrinsics,
@@ -416,61 +359,37 @@ extern "C" int gp_lift_labels_stream_add(const double *points, int64_t n, const 
     const char *who = "gp_lift_labels_stream_add";
     GP_CHECK_ARG(points && state && labels2d && view_entry && w2c && intrinsics && votes && count && view_count && view_keep && status && workspace,
                  "%s: null argument", who);
-    GP_CHECK_ARG(ll_elem_ok(elem), "%s: label type %d (0 u8, 1 i16, 2 i32, 3 i64)", who, elem);
-    GP_CHECK_ARG((uintptr_t)labels2d % ll_elem_size(elem) == 0, "%s: label maps not aligned to their element", who);
-    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "%s: %d views outside 1..65535", who, nviews);
-    GP_CHECK_ARG(num_classes >= 1 && num_classes <= LL_MAX_CLASSES && ld_votes >= num_classes, "%s: num_classes=%d outside 1..%d, ld_votes=%lld", who,
-                 num_classes, LL_MAX_CLASSES, (long long)ld_votes);
-    GP_CHECK_ARG(height >= 1 && width >= 1, "%s: image %d x %d", who, height, width);
-    GP_CHECK_ARG(cut_bound >= 0, "%s: cut_bound=%d must not be negative", who, cut_bound);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "%s: state too small (%zu < %zu)", who, state_bytes, ls_state_bytes(n));
+    LB_TRY(ll_check_maps(who, labels2d, elem, n, nviews, num_classes, ld_votes, height, width, cut_bound));
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     LlIgnore ign;
-    if (int rc = ll_ignore(who, ignore_ids, n_ignore, ign)) return rc;
+    LB_TRY(ll_ignore(who, ignore_ids, n_ignore, ign));
     {
-        // every output against every input and every other output, over their whole extents
         const size_t px = (size_t)height * width;
-        const void *in[] = {points, state, labels2d, view_entry, w2c, intrinsics, depth};
+        const void *const in[] = {points, state, labels2d, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32,       state_bytes,          (size_t)nviews * px * ll_elem_size(elem), (size_t)nviews * 8,
                                    (size_t)nviews * 128, (size_t)nviews * 32, (size_t)nviews * px * 8};
-        const void *o[] = {votes, count, view_count, view_keep, status, workspace};
+        const void *const o[] = {votes, count, view_count, view_keep, status, workspace};
         const size_t o_bytes[] = {(size_t)((n - 1) * ld_votes + num_classes) * 4, (size_t)n * 4, (size_t)nviews * 8, (size_t)nviews,
                                   (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 6; ++a) {
-            for (int i = 0; i < 7; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 6; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LsState st(sv, n);
     LsAddWork k(cv, nviews);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
-    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
     unsigned long long *sw = reinterpret_cast<unsigned long long *>(status);
-    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
-    // (1) the chunk's view table; its bad entries join the running count
-    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, k.vk0, k.w0, sw);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.vk0, k.vk1, k.w0, k.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));  // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.vk1, nviews, k.view_off);
-    // (2) the chunk's per-view counts and the drop rule
-    ls_counts_kernel<<<dim3(nb < 64 ? nb : 64, (unsigned)nviews), 256, 0, s>>>(points, n, st.rows, st.off, view_entry, w2c, intrinsics, depth, width,
-                                                                                height, cut_bound, vis_thres, vc);
-    lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
-    GP_CHECK_LAUNCH();
+    // (1) the chunk's view table; its bad entries join the running count.  (2) the chunk's per-view counts and the drop rule
+    LB_TRY(lb_view_table(view_entry, nviews, k.views, k.tmp, k.tmp_bytes, sw, s));
+    LB_TRY(ls_view_counts(points, n, st, view_entry, w2c, intrinsics, depth, nviews, width, height, cut_bound, vis_thres, min_visible, max_visible,
+                          view_count, view_keep, s));
     // (3) the accumulating vote; the chunk's out-of-range labels join the running count
-    return ll_vote<true>(points, n, labels2d, elem, num_classes, k.entry_views, k.view_off, w2c, intrinsics, depth, width, height, cut_bound, vis_thres,
+    return ll_vote<true>(points, n, labels2d, elem, num_classes, k.views.idx, k.views.off, w2c, intrinsics, depth, width, height, cut_bound, vis_thres,
                          view_keep, ign, votes, ld_votes, count, nullptr, nullptr, nullptr, nullptr, 0, nullptr, sw, s);
 }
 
 extern "C" size_t gp_lift_labels_stream_finish_workspace_bytes(int64_t n) {
-    if (!ls_n_ok(n)) return 0;
+    if (!lb_n_ok(n)) return 0;
     GpCarver cv(nullptr, 0);
     LlFinishWork k(cv, n);
     return cv.off;
@@ -482,37 +401,28 @@ extern "C" int gp_lift_labels_stream_finish(const double *points, int64_t n, con
                                             size_t workspace_bytes, void *stream_) {
     const char *who = "gp_lift_labels_stream_finish";
     GP_CHECK_ARG(points && state && votes && count && status && labels && voted && seen && status_out && workspace, "%s: null argument", who);
-    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
-    GP_CHECK_ARG(num_classes >= 1 && num_classes <= LL_MAX_CLASSES && ld_votes >= num_classes, "%s: num_classes=%d outside 1..%d, ld_votes=%lld", who,
-                 num_classes, LL_MAX_CLASSES, (long long)ld_votes);
-    GP_CHECK_ARG(fill == 0 || fill == 1, "%s: fill=%d (0 or 1)", who, fill);
-    GP_CHECK_ARG((uint64_t)unlabeled >= (uint64_t)num_classes, "%s: unlabeled=%lld is a class of 0..%d", who, (long long)unlabeled, num_classes - 1);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "%s: state too small (%zu < %zu)", who, state_bytes, ls_state_bytes(n));
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(ll_check_classes(who, num_classes, ld_votes));
+    LB_TRY(ll_check_fill(who, fill, unlabeled, num_classes));
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        const void *in[] = {points, state, votes, count, status};
+        const void *const in[] = {points, state, votes, count, status};
         const size_t in_bytes[] = {(size_t)n * 32, state_bytes, (size_t)((n - 1) * ld_votes + num_classes) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8};
-        const void *o[] = {labels, voted, seen, status_out, workspace};
+        const void *const o[] = {labels, voted, seen, status_out, workspace};
         const size_t o_bytes[] = {(size_t)n * 8, (size_t)n * 4, (size_t)n, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 5; ++a) {
-            for (int i = 0; i < 5; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LsState st(sv, n);
     LlFinishWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
-    unsigned long long *so = reinterpret_cast<unsigned long long *>(status_out);
-    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
-    ll_status_kernel<<<1, 64, 0, s>>>(status, status_out);
-    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(st.keys, st.rows, st.off, n, k.keys, k.rows, k.off, so);
+    // the running words into finish's status: those of every stream and the out-of-range labels
+    LB_TRY(ls_checked_tables(st, n, k.tables, status, LS_CARRY | (1u << ST_BAD_LABEL), status_out, s));
     ll_labels_kernel<<<(unsigned)((n * 64 + 255) / 256), 256, 0, s>>>(votes, ld_votes, count, n, num_classes, unlabeled, voted, k.f.has_vote, seen,
                                                                        labels, k.f.nn);
     GP_CHECK_LAUNCH();
     // the fill of gp_lift_labels_batched, over the checked copies of the tables
-    return ll_fill(points, n, k.keys, k.rows, k.off, k.f, k.tmp, k.tmp_bytes, fill, labels, so, s);
+    return ll_fill(points, n, k.tables.keys, k.tables.rows, k.tables.off, k.f, k.tmp, k.tmp_bytes, fill, labels,
+                   reinterpret_cast<unsigned long long *>(status_out), s);
 }

@@ -21,10 +21,9 @@
 // image, view_off clamped to ascend inside 0..total, tap origins inside the mask); a bit-set word index is < words by the check of the
 // view's position; a slot index is start[p] + rank < start[p+1] because rank counts set bits below a set bit; every write of an entry
 // is guarded by the capacity.  All offsets are 64-bit.
-// The kernels of (2) and (3) and the entry tables' launch sequence live in gp_lift_masks_entries.h: lift_masks_stream.hip, the same
-// lift with the views arriving in chunks, runs them too.
+// (2) to (4) -- kernels, workspace structs and launch sequences -- live in gp_lift_masks_entries.h, on top of gp_lift_masks.h and
+// gp_lift_entries.h: lift_masks_stream.hip, the same lift with the views arriving in chunks, runs them too.
 #include "gp_lift_masks_entries.h"
-#include "gp_lift_masks.h"
 
 namespace {
 
@@ -121,29 +120,16 @@ __global__ void __launch_bounds__(256) lml_max_views_kernel(const int32_t *__res
 }
 
 struct LmlWork {
-    uint32_t *k0, *k1, *vk0, *vk1;
-    int32_t *r0, *entry_rows, *w0, *entry_views, *entry_off, *view_off;
+    LbTables t;
     int64_t *blkcnt, *scan;
     char *tmp;
     size_t tmp_bytes;
     int parts;
-    static size_t scan64_bytes(int64_t n) { return lmb_scan64_bytes(n); }
-    LmlWork(GpCarver &cv, int64_t n, int32_t nviews) {
+    LmlWork(GpCarver &cv, int64_t n, int32_t nviews) : t(cv, n, nviews) {
         const int64_t nb = (n + 255) / 256;
         parts = (int)(nb < LML_PARTS ? nb : LML_PARTS);
         const size_t slots = (size_t)nviews * parts + 1;
-        const size_t a = lb_sort_bytes(n), b = lb_sort_bytes(nviews), c = scan64_bytes((int64_t)slots);
-        tmp_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
-        k0 = cv.take<uint32_t>(n);
-        k1 = cv.take<uint32_t>(n);
-        r0 = cv.take<int32_t>(n);
-        entry_rows = cv.take<int32_t>(n);
-        vk0 = cv.take<uint32_t>(nviews);
-        vk1 = cv.take<uint32_t>(nviews);
-        w0 = cv.take<int32_t>(nviews);
-        entry_views = cv.take<int32_t>(nviews);
-        entry_off = cv.take<int32_t>(LB_TABLE);
-        view_off = cv.take<int32_t>(LB_TABLE);
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lmb_scan64_bytes((int64_t)slots)});
         blkcnt = cv.take<int64_t>(slots);
         scan = cv.take<int64_t>(slots);
         tmp = cv.take<char>(tmp_bytes);
@@ -151,77 +137,19 @@ struct LmlWork {
 };
 
 struct LmbWork {
-    // entry tables and the scene-level fill (as LbWork)
-    uint32_t *k0, *k1, *vk0, *vk1;
-    int32_t *r0, *entry_rows, *w0, *entry_views, *entry_off, *view_off, *ref, *qry, *rs, *qs, *rrow, *qpos;
-    float *rxyz;
-    // the checked entries
-    int32_t *view_local, *c_view, *cx0, *cy0;
-    int64_t *voff, *c_pt, *c_x, *c_y;
-    uint8_t *c_live, *c_keep;
-    float *xyz;
-    // the segment decision and the in-view fill (as LvWork)
-    void *mt;                                                    // (the rank-ordered transposed masks, in the masks' own element type)
-    float *sscore, *f_rxyz;
-    int32_t *order, *cov, *f_rs, *rent, *qent, *part_i;
-    double *part_d;
-    int4 *tab;
-    // the point -> (view, segment) lists
-    unsigned long long *vmask;
-    int64_t *cnt, *pv_start;
-    int32_t *pv_view, *pv_seg;
+    LbTables t;                                                  // the entry tables
+    LbFill f;                                                    // the scene-level fill
+    int32_t *view_local;                                         // the views' positions inside their entries
+    LmbEntries e;                                                // the checked entries
+    LvSegWork k;                                                 // the segment decision and the in-view fill
+    LmbLists l;                                                  // the point -> (view, segment) lists
     char *tmp;
     size_t tmp_bytes;
-    static size_t scan64_bytes(int64_t n) { return LmlWork::scan64_bytes(n); }
     LmbWork(GpCarver &cv, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int64_t total, int32_t words,
-            int64_t fill_cap, size_t esize) {
-        size_t t[5] = {lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1), lb_scan_bytes(total + 1), scan64_bytes(n + 1)};
-        tmp_bytes = 0;
-        for (size_t b : t) tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-        k0 = cv.take<uint32_t>(n);
-        k1 = cv.take<uint32_t>(n);
-        r0 = cv.take<int32_t>(n);
-        entry_rows = cv.take<int32_t>(n);
-        vk0 = cv.take<uint32_t>(nviews);
-        vk1 = cv.take<uint32_t>(nviews);
-        w0 = cv.take<int32_t>(nviews);
-        entry_views = cv.take<int32_t>(nviews);
-        entry_off = cv.take<int32_t>(LB_TABLE);
-        view_off = cv.take<int32_t>(LB_TABLE);
-        ref = cv.take<int32_t>(n + 1);
-        qry = cv.take<int32_t>(n + 1);
-        rs = cv.take<int32_t>(n + 1);
-        qs = cv.take<int32_t>(n + 1);
-        rrow = cv.take<int32_t>(n);
-        qpos = cv.take<int32_t>(n);
-        rxyz = cv.take<float>(3 * n);
-        view_local = cv.take<int32_t>(nviews);
-        voff = cv.take<int64_t>((size_t)nviews + 1);
-        c_pt = cv.take<int64_t>(total);
-        c_x = cv.take<int64_t>(total);
-        c_y = cv.take<int64_t>(total);
-        c_view = cv.take<int32_t>(total);
-        c_live = cv.take<uint8_t>(total);
-        c_keep = cv.take<uint8_t>(nviews);
-        cx0 = cv.take<int32_t>(out_w);
-        cy0 = cv.take<int32_t>(out_h);
-        xyz = cv.take<float>(3 * n);
-        mt = cv.take<char>((size_t)nviews * q * h * w * esize);
-        order = cv.take<int32_t>((size_t)nviews * q);
-        sscore = cv.take<float>((size_t)nviews * q);
-        cov = cv.take<int32_t>(total + 1);
-        f_rs = cv.take<int32_t>(total + 1);
-        rent = cv.take<int32_t>(total);
-        qent = cv.take<int32_t>(total);
-        f_rxyz = cv.take<float>(total * 3);
-        part_d = cv.take<double>((size_t)FV_CHUNKS * fill_cap);
-        part_i = cv.take<int32_t>((size_t)FV_CHUNKS * fill_cap);
-        tab = cv.take<int4>((size_t)nviews + 1);
-        vmask = cv.take<unsigned long long>((size_t)n * words);
-        cnt = cv.take<int64_t>(n + 1);
-        pv_start = cv.take<int64_t>(n + 1);
-        pv_view = cv.take<int32_t>(total);
-        pv_seg = cv.take<int32_t>(total);
+            int64_t fill_cap, size_t esize)
+        : t(cv, n, nviews), f(cv, n), view_local(cv.take<int32_t>(nviews)), e(cv, n, nviews, out_h, out_w, total),
+          k(cv, nviews, q, h, w, total, fill_cap, esize, (size_t)nviews + 1), l(cv, n, total, words) {
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1), lb_scan_bytes(total + 1), lmb_scan64_bytes(n + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -229,7 +157,7 @@ struct LmbWork {
 }  // namespace
 
 extern "C" size_t gp_lift_masks_batched_lists_workspace_bytes(int64_t n, int32_t nviews) {
-    if (n <= 0 || n >= (1ll << 31) || nviews < 1 || nviews > 65535) return 0;
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews)) return 0;
     GpCarver cv(nullptr, 0);
     LmlWork k(cv, n, nviews);
     return cv.off;
@@ -241,57 +169,47 @@ extern "C" int gp_lift_masks_batched_lists(const double *points, int64_t n, cons
                                            int64_t *ent_pt, int64_t *ent_x, int64_t *ent_y, int32_t *ent_view, int64_t *view_off,
                                            int64_t *view_count, uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes,
                                            void *stream_) {
-    GP_CHECK_ARG(points && view_entry && w2c && intrinsics && view_off && view_count && view_keep && status && workspace,
-                 "gp_lift_masks_batched_lists: null argument");
-    GP_CHECK_ARG(n > 0 && n < (1ll << 31), "gp_lift_masks_batched_lists: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_masks_batched_lists: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(height >= 1 && width >= 1 && cut_bound >= 0, "gp_lift_masks_batched_lists: image %d x %d, cut_bound=%d", height, width, cut_bound);
-    GP_CHECK_ARG(cap >= 0, "gp_lift_masks_batched_lists: cap=%lld must not be negative", (long long)cap);
-    GP_CHECK_ARG(cap == 0 || (ent_pt && ent_x && ent_y && ent_view), "gp_lift_masks_batched_lists: cap=%lld entries need the entry arrays",
-                 (long long)cap);
+    const char *who = "gp_lift_masks_batched_lists";
+    GP_CHECK_ARG(points && view_entry && w2c && intrinsics && view_off && view_count && view_keep && status && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    GP_CHECK_ARG(height >= 1 && width >= 1 && cut_bound >= 0, "%s: image %d x %d, cut_bound=%d", who, height, width, cut_bound);
+    GP_CHECK_ARG(cap >= 0, "%s: cap=%lld must not be negative", who, (long long)cap);
+    GP_CHECK_ARG(cap == 0 || (ent_pt && ent_x && ent_y && ent_view), "%s: cap=%lld entries need the entry arrays", who, (long long)cap);
     {
+        // (cap == 0: the entry arrays are not written, whatever they point at)
         const size_t px = (size_t)height * width;
-        const void *in[] = {points, view_entry, w2c, intrinsics, depth};
+        const void *const in[] = {points, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32, (size_t)nviews * px * 8};
-        const void *o[] = {ent_pt, ent_x, ent_y, ent_view, view_off, view_count, view_keep, status, workspace};
+        const void *const o[] = {cap ? ent_pt : nullptr, cap ? ent_x : nullptr, cap ? ent_y : nullptr, cap ? ent_view : nullptr, view_off, view_count,
+                                 view_keep, status, workspace};
         const size_t o_bytes[] = {(size_t)cap * 8, (size_t)cap * 8, (size_t)cap * 8, (size_t)cap * 4, ((size_t)nviews + 1) * 8, (size_t)nviews * 8,
                                   (size_t)nviews, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 9; ++a) {
-            if (a < 4 && cap == 0) continue;
-            for (int i = 0; i < 5; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_masks_batched_lists: an output overlaps an input");
-            for (int q = a + 1; q < 9; ++q)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_masks_batched_lists: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver cv(workspace, workspace_bytes);
     LmlWork k(cv, n, nviews);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_batched_lists: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
     unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
-    int rc = lmb_entry_tables(points, n, view_entry, nviews, k.k0, k.k1, k.r0, k.entry_rows, k.vk0, k.vk1, k.w0, k.entry_views, k.entry_off,
-                              k.view_off, k.tmp, k.tmp_bytes, st, s);
-    if (rc != GP_OK) return rc;
+    LB_TRY(lb_entry_tables(points, n, view_entry, nviews, k.t, k.tmp, k.tmp_bytes, st, s));
     const unsigned vb = (unsigned)((nviews + 255) / 256);
     const size_t slots = (size_t)nviews * k.parts + 1;
     const dim3 grid((unsigned)k.parts, (unsigned)nviews);
     GP_CHECK_HIP(hipMemsetAsync(k.blkcnt + (slots - 1), 0, sizeof(int64_t), s));
-    lml_walk_kernel<false><<<grid, 256, 0, s>>>(points, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, depth, width, height, cut_bound,
+    lml_walk_kernel<false><<<grid, 256, 0, s>>>(points, k.t.rows.idx, k.t.rows.off, view_entry, w2c, intrinsics, depth, width, height, cut_bound,
                                                 vis_thres, k.parts, k.blkcnt, nullptr, 0, nullptr, nullptr, nullptr, nullptr, st);
     GP_CHECK_LAUNCH();
     size_t io = k.tmp_bytes;
     GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.blkcnt, k.scan, (int64_t)0, slots, rocprim::plus<int64_t>(), s));
     lml_view_off_kernel<<<(unsigned)((nviews + 1 + 255) / 256), 256, 0, s>>>(k.scan, nviews, k.parts, view_off, vc, st);
     lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
-    lml_max_views_kernel<<<LB_MAX_ENTRIES / 256, 256, 0, s>>>(k.view_off, st);
+    lml_max_views_kernel<<<LB_MAX_ENTRIES / 256, 256, 0, s>>>(k.t.views.off, st);
     GP_CHECK_LAUNCH();
     if (cap > 0) {
-        lml_walk_kernel<true><<<grid, 256, 0, s>>>(points, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, depth, width, height, cut_bound,
+        lml_walk_kernel<true><<<grid, 256, 0, s>>>(points, k.t.rows.idx, k.t.rows.off, view_entry, w2c, intrinsics, depth, width, height, cut_bound,
                                                    vis_thres, k.parts, nullptr, k.scan, cap, ent_pt, ent_x, ent_y, ent_view, st);
         GP_CHECK_LAUNCH();
     }
@@ -301,7 +219,7 @@ extern "C" int gp_lift_masks_batched_lists(const double *points, int64_t n, cons
 extern "C" size_t gp_lift_masks_batched_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
                                                           int32_t out_w, int64_t total, int32_t words, int64_t fill_cap) {
     if (!gp_elem_ok(elem)) return 0;
-    if (n <= 0 || n >= (1ll << 31) || nviews < 1 || nviews > 65535 || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 1 ||
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews) || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 1 ||
         total >= (int64_t)INT32_MAX || words < 1 || words > 1024 || fill_cap < 0 || fill_cap > total)
         return 0;
     GpCarver cv(nullptr, 0);
@@ -322,115 +240,48 @@ extern "C" int gp_lift_masks_batched_t(const double *points, int64_t n, const in
                                        const float *logit_seg, int32_t d, int32_t c, int32_t fill, float *out, int64_t ld_out, uint8_t *seen,
                                        int32_t *count, int64_t *nn, int32_t *seg, int64_t *status, void *workspace, size_t workspace_bytes,
                                        void *stream_) {
+    const char *who = "gp_lift_masks_batched";
     GP_CHECK_ARG(points && view_entry && pred_masks && scores && tap_x0 && tap_wx && tap_y0 && tap_wy && ent_pt && ent_x && ent_y && ent_view &&
                      view_off && keep && f_seg && logit_seg && out && seen && count && seg && status && workspace,
-                 "gp_lift_masks_batched: null argument");
-    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_masks_batched: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
-    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)pred_masks % 2 == 0, "gp_lift_masks_batched: half masks at an odd address");
-    GP_CHECK_ARG(n > 0 && n < (1ll << 31), "gp_lift_masks_batched: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_masks_batched: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(q >= 1 && q <= 1024, "gp_lift_masks_batched: %d queries outside 1..1024 (the score sort holds 1024)", q);
-    GP_CHECK_ARG(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1 && (int64_t)h * w < (1ll << 31), "gp_lift_masks_batched: masks %d x %d, image %d x %d", h,
-                 w, out_h, out_w);
-    GP_CHECK_ARG(((int64_t)h * w + 63) / 64 < (1ll << 31), "gp_lift_masks_batched: masks of %d x %d exceed the grid", h, w);
-    GP_CHECK_ARG(total >= 1 && total < (int64_t)INT32_MAX, "gp_lift_masks_batched: %lld entries outside 1..2^31-2", (long long)total);
-    GP_CHECK_ARG(words >= 1 && words <= 1024, "gp_lift_masks_batched: words=%d outside 1..1024", words);
-    GP_CHECK_ARG(fill_cap >= 0 && fill_cap <= total, "gp_lift_masks_batched: fill_cap=%lld outside 0..total", (long long)fill_cap);
-    GP_CHECK_ARG(d >= 1 && c >= 1 && d % 4 == 0 && ld_out % 4 == 0 && ld_out >= d, "gp_lift_masks_batched: d=%d and ld_out=%lld must be multiples of 4, c=%d",
-                 d, (long long)ld_out, c);
-    GP_CHECK_ARG(((uintptr_t)f_seg | (uintptr_t)out) % 16 == 0, "gp_lift_masks_batched: f_seg and out must be 16-byte aligned");
-    GP_CHECK_ARG(fill == 0 || nn, "gp_lift_masks_batched: the fill writes nn");
+                 "%s: null argument", who);
+    LB_TRY(lb_check_elem(who, elem, pred_masks, "masks"));
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    LB_TRY(lmb_check_masks(who, q, h, w, out_h, out_w));
+    GP_CHECK_ARG(((int64_t)h * w + 63) / 64 < (1ll << 31), "%s: masks of %d x %d exceed the grid", who, h, w);
+    GP_CHECK_ARG(total >= 1 && total < (int64_t)INT32_MAX, "%s: %lld entries outside 1..2^31-2", who, (long long)total);
+    LB_TRY(lmb_check_words(who, words));
+    LB_TRY(lmb_check_fill_cap(who, fill_cap, total));
+    LB_TRY(lmb_check_fused(who, d, c, ld_out, f_seg, out, fill, nn));
     if (fill_cap == 0) fill_cap = total;
     {
         const size_t vq = (size_t)nviews * q;
-        const void *in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off, keep,
-                            f_seg, logit_seg};
+        const void *const in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off,
+                                  keep, f_seg, logit_seg};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * gp_elem_size(elem), vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
                                    (size_t)out_h * 16, (size_t)total * 8, (size_t)total * 8, (size_t)total * 8, (size_t)total * 4,
                                    ((size_t)nviews + 1) * 8, (size_t)nviews, vq * d * 4, vq * c * 4};
-        const void *o[] = {out, seen, count, nn, seg, status, workspace};
+        const void *const o[] = {out, seen, count, nn, seg, status, workspace};
         const size_t o_bytes[] = {(size_t)((n - 1) * ld_out + d) * 4, (size_t)n, (size_t)n * 4, (size_t)n * 8, (size_t)total * 4, (size_t)ST_WORDS * 8,
                                   workspace_bytes};
-        for (int a = 0; a < 7; ++a) {
-            for (int i = 0; i < 16; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_masks_batched: an output overlaps an input");
-            for (int b = a + 1; b < 7; ++b) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[b], o_bytes[b]), "gp_lift_masks_batched: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver cv(workspace, workspace_bytes);
     LmbWork k(cv, n, nviews, q, h, w, out_h, out_w, total, words, fill_cap, gp_elem_size(elem));
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_batched: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
-    // the entry tables, the views' positions inside their entries, the fp32 xyz
-    int rc = lmb_entry_tables(points, n, view_entry, nviews, k.k0, k.k1, k.r0, k.entry_rows, k.vk0, k.vk1, k.w0, k.entry_views, k.entry_off,
-                              k.view_off, k.tmp, k.tmp_bytes, st, s);
-    if (rc != GP_OK) return rc;
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256), eb = (unsigned)((total + 1 + 255) / 256);
+    // the entry tables, the views' positions inside their entries
+    LB_TRY(lb_entry_tables(points, n, view_entry, nviews, k.t, k.tmp, k.tmp_bytes, st, s));
     GP_CHECK_HIP(hipMemsetAsync(k.view_local, 0xff, (size_t)nviews * sizeof(int32_t), s));
-    lmb_view_local_kernel<<<vb, 256, 0, s>>>(k.vk1, k.entry_views, k.view_off, nviews, words, k.view_local, st);
-    lmb_xyz_kernel<<<nb, 256, 0, s>>>(points, n, k.xyz);
-    // the entries, checked
-    lmb_view_off_kernel<<<1, 64, 0, s>>>(view_off, nviews, total, k.voff, st);
-    lmb_taps_kernel<<<(unsigned)((out_w + out_h + 255) / 256), 256, 0, s>>>(tap_x0, tap_y0, out_w, out_h, w, h, k.cx0, k.cy0, st);
-    lmb_entries_kernel<<<eb, 256, 0, s>>>(points, n, view_entry, k.view_local, k.voff, nviews, out_h, out_w, ent_pt, ent_x, ent_y, ent_view, keep,
-                                          total, k.c_pt, k.c_x, k.c_y, k.c_view, k.c_live, st);
-    lmb_keep_kernel<<<vb, 256, 0, s>>>(keep, k.view_local, nviews, k.c_keep);
-    GP_CHECK_LAUNCH();
-    // the segment of every entry (gp_lift_masks.h: the kernels of gp_lift_masks_views)
-    const int64_t hw = (int64_t)h * w;
-    lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    const dim3 tg((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews);
-    const unsigned sb = (unsigned)((total * 64 + 255) / 256);
-#define LMB_SEGMENTS(T, BITS)                                                                                                                  \
-    do {                                                                                                                                       \
-        transpose_views_kernel<BITS><<<tg, 256, 0, s>>>(static_cast<const BITS *>(pred_masks), q, (int)hw, static_cast<BITS *>(k.mt), k.order);   \
-        lift_masks_views_kernel<T><<<sb, 256, 0, s>>>(static_cast<const T *>(k.mt), q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy,    \
-                                                      out_h, out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, seg);                             \
-    } while (0)
-    if (elem == GP_ELEM_F32) LMB_SEGMENTS(float, float);
-    else if (elem == GP_ELEM_F16) LMB_SEGMENTS(gp_f16, uint16_t);
-    else LMB_SEGMENTS(gp_bf16, uint16_t);
-#undef LMB_SEGMENTS
-    GP_CHECK_LAUNCH();
-    // the in-view fill
-    fill_flags_kernel<<<eb, 256, 0, s>>>(seg, total, k.cov);
-    size_t tb = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cov, k.f_rs, (int32_t)0, (size_t)(total + 1), rocprim::plus<int32_t>(), s));
-    fill_compact_kernel<<<eb, 256, 0, s>>>(k.xyz, k.c_pt, seg, k.f_rs, total, k.f_rxyz, k.rent, k.qent);
-    const unsigned qb = (unsigned)(total / 256 + nviews + 1);                            // >= sum over views of ceil(queries / 256)
-    fill_table_kernel<<<1, 64, 0, s>>>(k.voff, k.f_rs, nviews, k.tab);
-    fill_part_kernel<<<dim3(qb, FV_CHUNKS), 256, 0, s>>>(k.xyz, k.c_pt, k.tab, nviews, k.f_rxyz, k.qent, k.part_d, k.part_i, fill_cap, k.rent, seg);
-    fill_reduce_kernel<<<qb, 256, 0, s>>>(k.tab, nviews, k.part_d, k.part_i, fill_cap, k.rent, k.qent, seg);
-    lmb_dead_kernel<<<eb, 256, 0, s>>>(k.c_live, total, seg);
-    GP_CHECK_LAUNCH();
-    // point -> (view, segment) lists in ascending view index
-    GP_CHECK_HIP(hipMemsetAsync(k.vmask, 0, (size_t)n * words * sizeof(unsigned long long), s));
-    lmb_pv_mask_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.view_local, total, words, k.vmask);
-    lmb_pv_cnt_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(k.vmask, n, words, k.cnt, count, nn);
-    tb = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cnt, k.pv_start, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), s));
-    lmb_pv_fill_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.view_local, seg, total, words, k.vmask, k.pv_start, k.pv_view, k.pv_seg);
-    GP_CHECK_LAUNCH();
-    // consensus top-3 fusion: the kernel of the per-scene path
-    rc = gp_fuse_views_top3(k.pv_start, k.pv_view, k.pv_seg, n, f_seg, logit_seg, q, d, c, out, ld_out, seen, stream_);
-    if (rc != GP_OK) return rc;
-    // the scene-level fill inside every entry
-    const unsigned nb1 = (unsigned)((n + 1 + 255) / 256);
-    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(k.k1, k.entry_rows, seen, n, k.ref, k.qry);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.ref, k.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.qry, k.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, k.entry_rows, k.ref, k.qry, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, st);
-    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.k1, k.entry_rows, k.entry_off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, st);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    lmb_view_local_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(k.t.views.k1, k.t.views.idx, k.t.views.off, nviews, words, k.view_local, st);
+    // the entries, checked; the segment of every entry; the in-view fill
+    LB_TRY(lmb_chunk_segments(points, n, view_entry, k.view_local, nviews, pred_masks, elem, q, h, w, scores, tap_x0, tap_wx, tap_y0, tap_wy, out_h,
+                              out_w, ent_pt, ent_x, ent_y, ent_view, view_off, keep, total, fill_cap, k.e, k.k, k.tmp, k.tmp_bytes, seg, st, s));
+    // point -> (view, segment) lists in ascending view index, consensus top-3 fusion, the scene-level fill inside every entry
+    return lmb_fuse_fill(points, n, k.e.c_pt, k.e.c_view, k.e.c_live, k.view_local, seg, total, words, k.l, k.t.rows.k1, k.t.rows.idx, k.t.rows.off,
+                         k.f, k.tmp, k.tmp_bytes, f_seg, logit_seg, q, d, c, fill, out, ld_out, seen, count, nn, st, stream_);
 }
 
 extern "C" int gp_lift_masks_batched(const double *points, int64_t n, const int64_t *view_entry, int32_t nviews, const float *pred_masks, int32_t q,

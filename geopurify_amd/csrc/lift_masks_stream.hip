@@ -28,9 +28,10 @@
 // is counted in status words 6 and 7.  A bit-set word index is < words by the position check; a slot index is start[p] + rank <
 // start[p+1] because rank counts set bits below a set bit; an appended record is guarded by the records' capacity.  The chunk's
 // entries go through the checked copies of gp_lift_masks_batched.  All offsets are 64-bit.  No float atomics (integer atomicOr / Add / Max).
+// (The state's tables and their checked copy are gp_lift_stream_state.h's; the chunk's pipeline and the end shared with
+// gp_lift_masks_batched are gp_lift_masks_entries.h's.)
 #include "gp_lift_stream_state.h"
 #include "gp_lift_masks_entries.h"
-#include "gp_lift_masks.h"
 
 namespace {
 
@@ -49,35 +50,12 @@ size_t lms_state_bytes(int64_t n) {
     return cv.off;
 }
 
-struct LmsViewTable {                                            // a chunk's views sorted stably by entry
-    uint32_t *vk0, *vk1;
-    int32_t *w0, *entry_views, *view_off;
-    LmsViewTable(GpCarver &cv, int32_t nviews) {
-        vk0 = cv.take<uint32_t>(nviews);
-        vk1 = cv.take<uint32_t>(nviews);
-        w0 = cv.take<int32_t>(nviews);
-        entry_views = cv.take<int32_t>(nviews);
-        view_off = cv.take<int32_t>(LB_TABLE);
-    }
-};
-
-int lms_view_table(const int64_t *view_entry, int32_t nviews, const LmsViewTable &t, char *tmp, size_t tmp_bytes, unsigned long long *st,
-                   hipStream_t s) {
-    lb_view_keys_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(view_entry, nviews, t.vk0, t.w0, st);
-    GP_CHECK_LAUNCH();
-    size_t io = tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, io, t.vk0, t.vk1, t.w0, t.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));    // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(t.vk1, nviews, t.view_off);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
-}
-
 struct LmsSizesWork {
-    LmsViewTable t;
+    LbTable t;                                                   // the chunk's views sorted stably by entry
     unsigned long long *scratch;                                 // the status words of the table's keys kernel: counted by add, not here
     char *tmp;
     size_t tmp_bytes;
-    LmsSizesWork(GpCarver &cv, int32_t nviews) : t(cv, nviews) {
+    LmsSizesWork(GpCarver &cv, int32_t nviews) : t(lb_table(cv, nviews)) {
         tmp_bytes = lb_sort_bytes(nviews);
         scratch = cv.take<unsigned long long>(ST_WORDS);
         tmp = cv.take<char>(tmp_bytes);
@@ -85,96 +63,36 @@ struct LmsSizesWork {
 };
 
 struct LmsAddWork {
-    LmsViewTable t;
-    // the checked entries
-    int32_t *c_view = nullptr, *cx0 = nullptr, *cy0 = nullptr;
-    int64_t *voff, *loc, *c_pt = nullptr, *c_x = nullptr, *c_y = nullptr;
-    uint8_t *c_live = nullptr, *c_keep;
-    float *xyz = nullptr;
-    // the segment decision and the in-view fill (as LmbWork)
-    void *mt = nullptr;                                          // (the rank-ordered transposed masks, in the masks' own element type)
-    float *sscore = nullptr, *f_rxyz = nullptr;
-    int32_t *order = nullptr, *seg = nullptr, *cov = nullptr, *f_rs = nullptr, *rent = nullptr, *qent = nullptr, *part_i = nullptr;
-    double *part_d = nullptr;
-    int4 *tab = nullptr;
+    LbTable t;                                                   // the chunk's views sorted stably by entry
+    int64_t *loc;
+    LmbEntries e;                                                // the checked entries
+    LvSegWork k;                                                 // the segment decision and the in-view fill
+    int32_t *seg = nullptr;
     char *tmp;
     size_t tmp_bytes;
     LmsAddWork(GpCarver &cv, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int64_t total,
                int64_t fill_cap, size_t esize)
-        : t(cv, nviews) {
-        const size_t a = lb_sort_bytes(nviews), b = lb_scan_bytes(total + 1);
-        tmp_bytes = a > b ? a : b;
-        voff = cv.take<int64_t>((size_t)nviews + 1);
-        loc = cv.take<int64_t>((size_t)nviews + 1);
-        c_keep = cv.take<uint8_t>(nviews);
+        : t(lb_table(cv, nviews)), loc(cv.take<int64_t>((size_t)nviews + 1)), e(cv, n, nviews, out_h, out_w, total) {
         if (total > 0) {                                         // (a chunk in which nothing is visible needs the view table alone)
-            c_pt = cv.take<int64_t>(total);
-            c_x = cv.take<int64_t>(total);
-            c_y = cv.take<int64_t>(total);
-            c_view = cv.take<int32_t>(total);
-            c_live = cv.take<uint8_t>(total);
-            cx0 = cv.take<int32_t>(out_w);
-            cy0 = cv.take<int32_t>(out_h);
-            xyz = cv.take<float>(3 * n);
-            mt = cv.take<char>((size_t)nviews * q * h * w * esize);
-            order = cv.take<int32_t>((size_t)nviews * q);
-            sscore = cv.take<float>((size_t)nviews * q);
+            k = LvSegWork(cv, nviews, q, h, w, total, fill_cap, esize, (size_t)nviews + 1);
             seg = cv.take<int32_t>(total);
-            cov = cv.take<int32_t>(total + 1);
-            f_rs = cv.take<int32_t>(total + 1);
-            rent = cv.take<int32_t>(total);
-            qent = cv.take<int32_t>(total);
-            f_rxyz = cv.take<float>(total * 3);
-            part_d = cv.take<double>((size_t)FV_CHUNKS * fill_cap);
-            part_i = cv.take<int32_t>((size_t)FV_CHUNKS * fill_cap);
-            tab = cv.take<int4>((size_t)nviews + 1);
         }
+        tmp_bytes = std::max(lb_sort_bytes(nviews), lb_scan_bytes(total + 1));
         tmp = cv.take<char>(tmp_bytes);
     }
 };
 
 struct LmsFinishWork {
-    // the checked entry tables and the scene-level fill (as LsFinishWork)
-    uint32_t *keys;
-    int32_t *rows, *off, *ref, *qry, *rs, *qs, *rrow, *qpos;
-    float *rxyz;
+    LsFinishWork base;                                           // the checked entry tables, the scene-level fill, the scans' scratch
     // the checked per-view arrays and records
     int32_t *view_local, *c_view, *c_seg;
     int64_t *voff, *c_pt;
     uint8_t *c_live, *c_keep;
-    // the point -> (view, segment) lists
-    unsigned long long *vmask;
-    int64_t *cnt, *pv_start;
-    int32_t *pv_view, *pv_seg;
-    char *tmp;
-    size_t tmp_bytes;
-    LmsFinishWork(GpCarver &cv, int64_t n, int32_t nviews, int64_t total, int32_t words) {
-        const size_t a = lb_scan_bytes(n + 1), b = lmb_scan64_bytes(n + 1);
-        tmp_bytes = a > b ? a : b;
-        keys = cv.take<uint32_t>(n);
-        rows = cv.take<int32_t>(n);
-        off = cv.take<int32_t>(LB_TABLE);
-        ref = cv.take<int32_t>(n + 1);
-        qry = cv.take<int32_t>(n + 1);
-        rs = cv.take<int32_t>(n + 1);
-        qs = cv.take<int32_t>(n + 1);
-        rrow = cv.take<int32_t>(n);
-        qpos = cv.take<int32_t>(n);
-        rxyz = cv.take<float>(3 * n);
-        view_local = cv.take<int32_t>(nviews);
-        c_keep = cv.take<uint8_t>(nviews);
-        voff = cv.take<int64_t>((size_t)nviews + 1);
-        c_pt = cv.take<int64_t>(total);
-        c_view = cv.take<int32_t>(total);
-        c_seg = cv.take<int32_t>(total);
-        c_live = cv.take<uint8_t>(total);
-        vmask = cv.take<unsigned long long>((size_t)n * words);
-        cnt = cv.take<int64_t>(n + 1);
-        pv_start = cv.take<int64_t>(n + 1);
-        pv_view = cv.take<int32_t>(total);
-        pv_seg = cv.take<int32_t>(total);
-        tmp = cv.take<char>(tmp_bytes);
-    }
+    LmbLists l;                                                  // the point -> (view, segment) lists
+    LmsFinishWork(GpCarver &cv, int64_t n, int32_t nviews, int64_t total, int32_t words)
+        : base(cv, n, lmb_scan64_bytes(n + 1)), view_local(cv.take<int32_t>(nviews)), c_view(cv.take<int32_t>(total)),
+          c_seg(cv.take<int32_t>(total)), voff(cv.take<int64_t>((size_t)nviews + 1)), c_pt(cv.take<int64_t>(total)),
+          c_live(cv.take<uint8_t>(total)), c_keep(cv.take<uint8_t>(nviews)), l(cv, n, total, words) {}
 };
 
 // a counter of the state, forced into 0..65535
@@ -287,11 +205,6 @@ __global__ void __launch_bounds__(256) lms_append_kernel(const int64_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ finish: the checked copies
-__global__ void lms_status_kernel(const int64_t *__restrict__ running, int64_t *__restrict__ status_out) {
-    const int i = threadIdx.x;
-    if (i < ST_WORDS) status_out[i] = (i <= ST_TOP_BATCH || i == LMS_BAD || i == LMS_BEYOND) ? running[i] : 0;
-}
-
 // view_local[v] = the view's position inside its entry when the entry is one and the bit set holds the position, else -1; c_keep[v] =
 // the keep flag of a view that has a position
 __global__ void __launch_bounds__(256) lms_views_kernel(const int64_t *__restrict__ view_entry, const int32_t *__restrict__ view_pos,
@@ -349,54 +262,37 @@ __global__ void __launch_bounds__(256) lms_records_kernel(const double *__restri
     if (gp_lane() == 0 && nbad) atomicAdd(status + LMS_BAD, (unsigned long long)nbad);
 }
 
-bool lms_chunk_ok(int32_t nviews) { return nviews >= 1 && nviews <= 65535; }
-
 }  // namespace
 
-extern "C" size_t gp_lift_masks_stream_state_bytes(int64_t n) { return ls_n_ok(n) ? lms_state_bytes(n) : 0; }
+extern "C" size_t gp_lift_masks_stream_state_bytes(int64_t n) { return lb_n_ok(n) ? lms_state_bytes(n) : 0; }
 
-extern "C" size_t gp_lift_masks_stream_begin_workspace_bytes(int64_t n) {
-    if (!ls_n_ok(n)) return 0;
-    GpCarver cv(nullptr, 0);
-    LsBeginWork k(cv, n);
-    return cv.off;
-}
+extern "C" size_t gp_lift_masks_stream_begin_workspace_bytes(int64_t n) { return lb_n_ok(n) ? ls_begin_workspace_bytes(n) : 0; }
 
 extern "C" int gp_lift_masks_stream_begin(const double *points, int64_t n, void *state, size_t state_bytes, int64_t *status, void *workspace,
                                           size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(points && state && status && workspace, "gp_lift_masks_stream_begin: null argument");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_masks_stream_begin: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(state_bytes >= lms_state_bytes(n), "gp_lift_masks_stream_begin: state too small (%zu < %zu)", state_bytes, lms_state_bytes(n));
+    const char *who = "gp_lift_masks_stream_begin";
+    GP_CHECK_ARG(points && state && status && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_state(who, state_bytes, lms_state_bytes(n)));
     {
-        const void *o[] = {state, status, workspace};
+        const void *const in[] = {points};
+        const size_t in_bytes[] = {(size_t)n * 32};
+        const void *const o[] = {state, status, workspace};
         const size_t o_bytes[] = {state_bytes, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 3; ++a) {
-            GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], points, (size_t)n * 32), "gp_lift_masks_stream_begin: an output overlaps an input");
-            for (int b = a + 1; b < 3; ++b)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[b], o_bytes[b]), "gp_lift_masks_stream_begin: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
     LmsState st(sv, n);
     LsBeginWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_stream_begin: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
     GP_CHECK_HIP(hipMemsetAsync(st.views, 0, (size_t)LB_MAX_ENTRIES * sizeof(int32_t), s));
-    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, reinterpret_cast<unsigned long long *>(status));
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, st.tables.keys, k.r0, st.tables.rows, (size_t)n, 0, LB_KEY_BITS, s));   // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(st.tables.keys, n, st.tables.off);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    return ls_begin_tables(points, n, st.tables, k, status, s);
 }
 
 extern "C" size_t gp_lift_masks_stream_sizes_workspace_bytes(int32_t nviews) {
-    if (!lms_chunk_ok(nviews)) return 0;
+    if (!lb_nviews_ok(nviews)) return 0;
     GpCarver cv(nullptr, 0);
     LmsSizesWork k(cv, nviews);
     return cv.off;
@@ -405,35 +301,32 @@ extern "C" size_t gp_lift_masks_stream_sizes_workspace_bytes(int32_t nviews) {
 extern "C" int gp_lift_masks_stream_sizes(int64_t n, const void *state, size_t state_bytes, const int64_t *status, const int64_t *view_entry,
                                           const int64_t *view_count, const uint8_t *view_keep, int32_t nviews, int64_t *sizes, void *workspace,
                                           size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(state && status && view_entry && view_count && view_keep && sizes && workspace, "gp_lift_masks_stream_sizes: null argument");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_masks_stream_sizes: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(lms_chunk_ok(nviews), "gp_lift_masks_stream_sizes: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(state_bytes >= lms_state_bytes(n), "gp_lift_masks_stream_sizes: state too small (%zu < %zu)", state_bytes, lms_state_bytes(n));
+    const char *who = "gp_lift_masks_stream_sizes";
+    GP_CHECK_ARG(state && status && view_entry && view_count && view_keep && sizes && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    LB_TRY(lb_check_state(who, state_bytes, lms_state_bytes(n)));
     {
-        const void *in[] = {state, status, view_entry, view_count, view_keep};
+        // (this entry point holds both outputs against the inputs before it holds them against each other)
+        const void *const in[] = {state, status, view_entry, view_count, view_keep};
         const size_t in_bytes[] = {state_bytes, (size_t)ST_WORDS * 8, (size_t)nviews * 8, (size_t)nviews * 8, (size_t)nviews};
-        const void *o[] = {sizes, workspace};
+        const void *const o[] = {sizes, workspace};
         const size_t o_bytes[] = {4 * 8, workspace_bytes};
-        for (int a = 0; a < 2; ++a)
-            for (int i = 0; i < 5; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_masks_stream_sizes: an output overlaps an input");
-        GP_CHECK_ARG(!lb_overlap(o[0], o_bytes[0], o[1], o_bytes[1]), "gp_lift_masks_stream_sizes: two outputs overlap");
+        LB_TRY(lb_no_overlap(who, in, in_bytes, 5, o, o_bytes, 1));
+        LB_TRY(lb_no_overlap(who, in, in_bytes, 5, o + 1, o_bytes + 1, 1));
+        LB_TRY(lb_no_overlap(who, in, in_bytes, 0, o, o_bytes, 2));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LmsState st(sv, n);
     LmsSizesWork k(cv, nviews);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_stream_sizes: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *sz = reinterpret_cast<unsigned long long *>(sizes);
     GP_CHECK_HIP(hipMemsetAsync(sizes, 0, 4 * sizeof(int64_t), s));
     GP_CHECK_HIP(hipMemsetAsync(k.scratch, 0, ST_WORDS * sizeof(int64_t), s));
-    int rc = lms_view_table(view_entry, nviews, k.t, k.tmp, k.tmp_bytes, k.scratch, s);
-    if (rc != GP_OK) return rc;
+    LB_TRY(lb_view_table(view_entry, nviews, k.t, k.tmp, k.tmp_bytes, k.scratch, s));
     lms_totals_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(view_count, view_keep, nviews, sz);
-    lms_most_kernel<<<LB_MAX_ENTRIES / 256, 256, 0, s>>>(k.t.view_off, st.views, status, sz);
+    lms_most_kernel<<<LB_MAX_ENTRIES / 256, 256, 0, s>>>(k.t.off, st.views, status, sz);
     GP_CHECK_LAUNCH();
     return GP_OK;
 }
@@ -441,7 +334,7 @@ extern "C" int gp_lift_masks_stream_sizes(int64_t n, const void *state, size_t s
 extern "C" size_t gp_lift_masks_stream_add_workspace_bytes_t(int32_t elem, int64_t n, int32_t nviews, int32_t q, int32_t h, int32_t w, int32_t out_h,
                                                              int32_t out_w, int64_t total, int64_t fill_cap) {
     if (!gp_elem_ok(elem)) return 0;
-    if (!ls_n_ok(n) || !lms_chunk_ok(nviews) || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 0 ||
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews) || q < 1 || q > 1024 || h < 1 || w < 1 || out_h < 1 || out_w < 1 || total < 0 ||
         total >= (int64_t)INT32_MAX || fill_cap < 0 || fill_cap > total)
         return 0;
     GpCarver cv(nullptr, 0);
@@ -461,97 +354,56 @@ extern "C" int gp_lift_masks_stream_add_t(const double *points, int64_t n, void 
                                           const int64_t *view_off, const uint8_t *keep, int64_t total, int64_t fill_cap, int32_t *rec_row,
                                           int32_t *rec_seg, int64_t rec_base, int64_t rec_cap, int64_t *rec_off, int32_t *view_pos, int64_t *status,
                                           void *workspace, size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(points && state && view_entry && view_off && keep && rec_off && view_pos && status && workspace,
-                 "gp_lift_masks_stream_add: null argument");
-    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_masks_stream_add: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
-    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)pred_masks % 2 == 0, "gp_lift_masks_stream_add: half masks at an odd address");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_masks_stream_add: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(lms_chunk_ok(nviews), "gp_lift_masks_stream_add: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(total >= 0 && total < (int64_t)INT32_MAX, "gp_lift_masks_stream_add: %lld entries outside 0..2^31-2", (long long)total);
+    const char *who = "gp_lift_masks_stream_add";
+    GP_CHECK_ARG(points && state && view_entry && view_off && keep && rec_off && view_pos && status && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_elem(who, elem, pred_masks, "masks"));
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    GP_CHECK_ARG(total >= 0 && total < (int64_t)INT32_MAX, "%s: %lld entries outside 0..2^31-2", who, (long long)total);
     GP_CHECK_ARG(total == 0 || (pred_masks && scores && tap_x0 && tap_wx && tap_y0 && tap_wy && ent_pt && ent_x && ent_y && ent_view && rec_row && rec_seg),
-                 "gp_lift_masks_stream_add: %lld entries need the masks, the scores, the taps, the entry arrays and the records", (long long)total);
-    GP_CHECK_ARG(q >= 1 && q <= 1024, "gp_lift_masks_stream_add: %d queries outside 1..1024 (the score sort holds 1024)", q);
-    GP_CHECK_ARG(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1 && (int64_t)h * w < (1ll << 31), "gp_lift_masks_stream_add: masks %d x %d, image %d x %d",
-                 h, w, out_h, out_w);
-    GP_CHECK_ARG(fill_cap >= 0 && fill_cap <= total, "gp_lift_masks_stream_add: fill_cap=%lld outside 0..total", (long long)fill_cap);
-    GP_CHECK_ARG(rec_base >= 0 && rec_cap >= rec_base && rec_cap < (int64_t)INT32_MAX,
-                 "gp_lift_masks_stream_add: records %lld of a capacity of %lld (at most 2^31-2)", (long long)rec_base, (long long)rec_cap);
-    GP_CHECK_ARG(state_bytes >= lms_state_bytes(n), "gp_lift_masks_stream_add: state too small (%zu < %zu)", state_bytes, lms_state_bytes(n));
+                 "%s: %lld entries need the masks, the scores, the taps, the entry arrays and the records", who, (long long)total);
+    LB_TRY(lmb_check_masks(who, q, h, w, out_h, out_w));
+    LB_TRY(lmb_check_fill_cap(who, fill_cap, total));
+    GP_CHECK_ARG(rec_base >= 0 && rec_cap >= rec_base && rec_cap < (int64_t)INT32_MAX, "%s: records %lld of a capacity of %lld (at most 2^31-2)", who,
+                 (long long)rec_base, (long long)rec_cap);
+    LB_TRY(lb_check_state(who, state_bytes, lms_state_bytes(n)));
     if (fill_cap == 0) fill_cap = total;
     {
         const size_t vq = (size_t)nviews * q;
-        const void *in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off, keep};
+        const void *const in[] = {points, view_entry, pred_masks, scores, tap_x0, tap_wx, tap_y0, tap_wy, ent_pt, ent_x, ent_y, ent_view, view_off,
+                                  keep};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, vq * h * w * gp_elem_size(elem), vq * 4, (size_t)out_w * 4, (size_t)out_w * 16, (size_t)out_h * 4,
                                    (size_t)out_h * 16, (size_t)total * 8, (size_t)total * 8, (size_t)total * 8, (size_t)total * 4,
                                    ((size_t)nviews + 1) * 8, (size_t)nviews};
-        const void *o[] = {state, rec_row, rec_seg, rec_off, view_pos, status, workspace};
+        const void *const o[] = {state, rec_row, rec_seg, rec_off, view_pos, status, workspace};
         const size_t o_bytes[] = {state_bytes, (size_t)rec_cap * 4, (size_t)rec_cap * 4, ((size_t)nviews + 1) * 8, (size_t)nviews * 4,
                                   (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 7; ++a) {
-            for (int i = 0; i < 14; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_masks_stream_add: an output overlaps an input");
-            for (int b = a + 1; b < 7; ++b) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[b], o_bytes[b]), "gp_lift_masks_stream_add: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
     LmsState st(sv, n);
     LmsAddWork k(cv, n, nviews, q, h, w, out_h, out_w, total, fill_cap, gp_elem_size(elem));
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_stream_add: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *su = reinterpret_cast<unsigned long long *>(status);
     // the chunk's view table (its bad entries join the running count), the views' positions inside their entries, the counters
-    int rc = lms_view_table(view_entry, nviews, k.t, k.tmp, k.tmp_bytes, su, s);
-    if (rc != GP_OK) return rc;
+    LB_TRY(lb_view_table(view_entry, nviews, k.t, k.tmp, k.tmp_bytes, su, s));
     GP_CHECK_HIP(hipMemsetAsync(view_pos, 0xff, (size_t)nviews * sizeof(int32_t), s));
-    lms_positions_kernel<<<LB_MAX_ENTRIES * 64 / 256, 256, 0, s>>>(k.t.entry_views, k.t.view_off, nviews, st.views, view_pos, su);
+    lms_positions_kernel<<<LB_MAX_ENTRIES * 64 / 256, 256, 0, s>>>(k.t.idx, k.t.off, nviews, st.views, view_pos, su);
     GP_CHECK_LAUNCH();
     if (total == 0) {
-        lms_rec_off_kernel<<<1, 64, 0, s>>>(k.voff, k.c_keep, nviews, 1, rec_base, k.loc, rec_off, su);
+        lms_rec_off_kernel<<<1, 64, 0, s>>>(k.e.voff, k.e.c_keep, nviews, 1, rec_base, k.loc, rec_off, su);
         GP_CHECK_LAUNCH();
         return GP_OK;
     }
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256), eb = (unsigned)((total + 1 + 255) / 256);
-    // the entries, checked (the kernels and the order of gp_lift_masks_batched; a view's position is its view_local)
-    lmb_xyz_kernel<<<nb, 256, 0, s>>>(points, n, k.xyz);
-    lmb_view_off_kernel<<<1, 64, 0, s>>>(view_off, nviews, total, k.voff, su);
-    lmb_taps_kernel<<<(unsigned)((out_w + out_h + 255) / 256), 256, 0, s>>>(tap_x0, tap_y0, out_w, out_h, w, h, k.cx0, k.cy0, su);
-    lmb_entries_kernel<<<eb, 256, 0, s>>>(points, n, view_entry, view_pos, k.voff, nviews, out_h, out_w, ent_pt, ent_x, ent_y, ent_view, keep, total,
-                                          k.c_pt, k.c_x, k.c_y, k.c_view, k.c_live, su);
-    lmb_keep_kernel<<<vb, 256, 0, s>>>(keep, view_pos, nviews, k.c_keep);
-    GP_CHECK_LAUNCH();
-    // the segment of every entry
-    const int64_t hw = (int64_t)h * w;
-    lv_sort_scores_kernel<<<nviews, 256, 0, s>>>(scores, q, k.order, k.sscore);
-    const dim3 tg((unsigned)((hw + 63) / 64), (unsigned)((q + 63) / 64), (unsigned)nviews);
-    const unsigned sb = (unsigned)((total * 64 + 255) / 256);
-#define LMS_SEGMENTS(T, BITS)                                                                                                                  \
-    do {                                                                                                                                       \
-        transpose_views_kernel<BITS><<<tg, 256, 0, s>>>(static_cast<const BITS *>(pred_masks), q, (int)hw, static_cast<BITS *>(k.mt), k.order);   \
-        lift_masks_views_kernel<T><<<sb, 256, 0, s>>>(static_cast<const T *>(k.mt), q, h, w, k.sscore, k.order, k.cx0, tap_wx, k.cy0, tap_wy,    \
-                                                      out_h, out_w, k.c_x, k.c_y, k.c_view, k.c_keep, total, k.seg);                           \
-    } while (0)
-    if (elem == GP_ELEM_F32) LMS_SEGMENTS(float, float);
-    else if (elem == GP_ELEM_F16) LMS_SEGMENTS(gp_f16, uint16_t);
-    else LMS_SEGMENTS(gp_bf16, uint16_t);
-#undef LMS_SEGMENTS
-    GP_CHECK_LAUNCH();
-    // the in-view fill
-    fill_flags_kernel<<<eb, 256, 0, s>>>(k.seg, total, k.cov);
-    size_t tb = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cov, k.f_rs, (int32_t)0, (size_t)(total + 1), rocprim::plus<int32_t>(), s));
-    fill_compact_kernel<<<eb, 256, 0, s>>>(k.xyz, k.c_pt, k.seg, k.f_rs, total, k.f_rxyz, k.rent, k.qent);
-    const unsigned qb = (unsigned)(total / 256 + nviews + 1);                            // >= sum over views of ceil(queries / 256)
-    fill_table_kernel<<<1, 64, 0, s>>>(k.voff, k.f_rs, nviews, k.tab);
-    fill_part_kernel<<<dim3(qb, FV_CHUNKS), 256, 0, s>>>(k.xyz, k.c_pt, k.tab, nviews, k.f_rxyz, k.qent, k.part_d, k.part_i, fill_cap, k.rent, k.seg);
-    fill_reduce_kernel<<<qb, 256, 0, s>>>(k.tab, nviews, k.part_d, k.part_i, fill_cap, k.rent, k.qent, k.seg);
-    lmb_dead_kernel<<<eb, 256, 0, s>>>(k.c_live, total, k.seg);
-    GP_CHECK_LAUNCH();
+    // the pipeline of gp_lift_masks_batched over the chunk (a view's position is its view_local): the entries, checked; the segment
+    // of every entry; the in-view fill
+    LB_TRY(lmb_chunk_segments(points, n, view_entry, view_pos, nviews, pred_masks, elem, q, h, w, scores, tap_x0, tap_wx, tap_y0, tap_wy, out_h, out_w,
+                              ent_pt, ent_x, ent_y, ent_view, view_off, keep, total, fill_cap, k.e, k.k, k.tmp, k.tmp_bytes, k.seg, su, s));
     // the records of the kept views
-    lms_rec_off_kernel<<<1, 64, 0, s>>>(k.voff, k.c_keep, nviews, 0, rec_base, k.loc, rec_off, su);
-    lms_append_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.c_keep, k.voff, k.loc, k.seg, total, rec_base, rec_cap, rec_row, rec_seg);
+    lms_rec_off_kernel<<<1, 64, 0, s>>>(k.e.voff, k.e.c_keep, nviews, 0, rec_base, k.loc, rec_off, su);
+    lms_append_kernel<<<(unsigned)((total + 1 + 255) / 256), 256, 0, s>>>(k.e.c_pt, k.e.c_view, k.e.c_live, k.e.c_keep, k.e.voff, k.loc, k.seg, total,
+                                                                         rec_base, rec_cap, rec_row, rec_seg);
     GP_CHECK_LAUNCH();
     return GP_OK;
 }
@@ -569,7 +421,7 @@ extern "C" int gp_lift_masks_stream_add(const double *points, int64_t n, void *s
 }
 
 extern "C" size_t gp_lift_masks_stream_finish_workspace_bytes(int64_t n, int32_t nviews, int64_t total, int32_t words) {
-    if (!ls_n_ok(n) || !lms_chunk_ok(nviews) || total < 1 || total >= (int64_t)INT32_MAX || words < 1 || words > 1024) return 0;
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews) || total < 1 || total >= (int64_t)INT32_MAX || words < 1 || words > 1024) return 0;
     GpCarver cv(nullptr, 0);
     LmsFinishWork k(cv, n, nviews, total, words);
     return cv.off;
@@ -581,73 +433,42 @@ extern "C" int gp_lift_masks_stream_finish(const double *points, int64_t n, cons
                                            const float *logit_seg, int32_t q, int32_t d, int32_t c, const int64_t *status, int32_t fill, float *out,
                                            int64_t ld_out, uint8_t *seen, int32_t *count, int64_t *nn, int64_t *status_out, void *workspace,
                                            size_t workspace_bytes, void *stream_) {
+    const char *who = "gp_lift_masks_stream_finish";
     GP_CHECK_ARG(points && state && view_entry && view_pos && view_keep && rec_off && rec_row && rec_seg && f_seg && logit_seg && status && out &&
                      seen && count && status_out && workspace,
-                 "gp_lift_masks_stream_finish: null argument");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_masks_stream_finish: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(lms_chunk_ok(nviews), "gp_lift_masks_stream_finish: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(q >= 1 && q <= 1024, "gp_lift_masks_stream_finish: %d queries outside 1..1024", q);
-    GP_CHECK_ARG(total >= 1 && total < (int64_t)INT32_MAX, "gp_lift_masks_stream_finish: %lld records outside 1..2^31-2", (long long)total);
-    GP_CHECK_ARG(words >= 1 && words <= 1024, "gp_lift_masks_stream_finish: words=%d outside 1..1024", words);
-    GP_CHECK_ARG(d >= 1 && c >= 1 && d % 4 == 0 && ld_out % 4 == 0 && ld_out >= d,
-                 "gp_lift_masks_stream_finish: d=%d and ld_out=%lld must be multiples of 4, c=%d", d, (long long)ld_out, c);
-    GP_CHECK_ARG(((uintptr_t)f_seg | (uintptr_t)out) % 16 == 0, "gp_lift_masks_stream_finish: f_seg and out must be 16-byte aligned");
-    GP_CHECK_ARG(fill == 0 || nn, "gp_lift_masks_stream_finish: the fill writes nn");
-    GP_CHECK_ARG(state_bytes >= lms_state_bytes(n), "gp_lift_masks_stream_finish: state too small (%zu < %zu)", state_bytes, lms_state_bytes(n));
+                 "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    GP_CHECK_ARG(q >= 1 && q <= 1024, "%s: %d queries outside 1..1024", who, q);
+    GP_CHECK_ARG(total >= 1 && total < (int64_t)INT32_MAX, "%s: %lld records outside 1..2^31-2", who, (long long)total);
+    LB_TRY(lmb_check_words(who, words));
+    LB_TRY(lmb_check_fused(who, d, c, ld_out, f_seg, out, fill, nn));
+    LB_TRY(lb_check_state(who, state_bytes, lms_state_bytes(n)));
     {
         const size_t vq = (size_t)nviews * q;
-        const void *in[] = {points, state, view_entry, view_pos, view_keep, rec_off, rec_row, rec_seg, f_seg, logit_seg, status};
+        const void *const in[] = {points, state, view_entry, view_pos, view_keep, rec_off, rec_row, rec_seg, f_seg, logit_seg, status};
         const size_t in_bytes[] = {(size_t)n * 32,     state_bytes,        (size_t)nviews * 8, (size_t)nviews * 4, (size_t)nviews, ((size_t)nviews + 1) * 8,
                                    (size_t)total * 4, (size_t)total * 4, vq * d * 4,         vq * c * 4,         (size_t)ST_WORDS * 8};
-        const void *o[] = {out, seen, count, nn, status_out, workspace};
+        const void *const o[] = {out, seen, count, nn, status_out, workspace};
         const size_t o_bytes[] = {(size_t)((n - 1) * ld_out + d) * 4, (size_t)n, (size_t)n * 4, (size_t)n * 8, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 6; ++a) {
-            for (int i = 0; i < 11; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_masks_stream_finish: an output overlaps an input");
-            for (int b = a + 1; b < 6; ++b)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[b], o_bytes[b]), "gp_lift_masks_stream_finish: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LmsState st(sv, n);
     LmsFinishWork k(cv, n, nviews, total, words);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_masks_stream_finish: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *so = reinterpret_cast<unsigned long long *>(status_out);
-    const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
-    const unsigned eb = (unsigned)((total + 255) / 256);
-    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
-    // everything kept between the calls, checked
-    lms_status_kernel<<<1, 64, 0, s>>>(status, status_out);
-    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(st.tables.keys, st.tables.rows, st.tables.off, n, k.keys, k.rows, k.off, so);
+    // everything kept between the calls, checked; beside the words of every stream, this one carries what add had to change or leave out
+    LB_TRY(ls_checked_tables(st.tables, n, k.base.tables, status, LS_CARRY | (1u << LMS_BAD) | (1u << LMS_BEYOND), status_out, s));
     lmb_view_off_kernel<<<1, 64, 0, s>>>(rec_off, nviews, total, k.voff, so);
-    lms_views_kernel<<<vb, 256, 0, s>>>(view_entry, view_pos, view_keep, nviews, words, k.view_local, k.c_keep, so);
-    lms_records_kernel<<<eb, 256, 0, s>>>(points, n, view_entry, k.c_keep, k.voff, nviews, q, rec_row, rec_seg, total, k.c_pt, k.c_view, k.c_seg,
-                                          k.c_live, so);
+    lms_views_kernel<<<(unsigned)((nviews + 255) / 256), 256, 0, s>>>(view_entry, view_pos, view_keep, nviews, words, k.view_local, k.c_keep, so);
+    lms_records_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(points, n, view_entry, k.c_keep, k.voff, nviews, q, rec_row, rec_seg, total,
+                                                                      k.c_pt, k.c_view, k.c_seg, k.c_live, so);
     GP_CHECK_LAUNCH();
-    // point -> (view, segment) lists in ascending position inside the entry (the kernels of gp_lift_masks_batched)
-    GP_CHECK_HIP(hipMemsetAsync(k.vmask, 0, (size_t)n * words * sizeof(unsigned long long), s));
-    lmb_pv_mask_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.view_local, total, words, k.vmask);
-    lmb_pv_cnt_kernel<<<nb1, 256, 0, s>>>(k.vmask, n, words, k.cnt, count, nn);
-    size_t tb = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, tb, k.cnt, k.pv_start, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), s));
-    lmb_pv_fill_kernel<<<eb, 256, 0, s>>>(k.c_pt, k.c_view, k.c_live, k.view_local, k.c_seg, total, words, k.vmask, k.pv_start, k.pv_view, k.pv_seg);
-    GP_CHECK_LAUNCH();
-    // consensus top-3 fusion: the kernel of the per-scene path
-    int rc = gp_fuse_views_top3(k.pv_start, k.pv_view, k.pv_seg, n, f_seg, logit_seg, q, d, c, out, ld_out, seen, stream_);
-    if (rc != GP_OK) return rc;
-    // the scene-level fill inside every entry, over the checked copies of the tables
-    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(k.keys, k.rows, seen, n, k.ref, k.qry);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.ref, k.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.qry, k.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, k.rows, k.ref, k.qry, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, so);
-    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.keys, k.rows, k.off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, so);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    // the end of gp_lift_masks_batched over the records and the checked copies of the tables: point -> (view, segment) lists in ascending
+    // position inside the entry, consensus top-3 fusion, the scene-level fill inside every entry
+    return lmb_fuse_fill(points, n, k.c_pt, k.c_view, k.c_live, k.view_local, k.c_seg, total, words, k.l, k.base.tables.keys, k.base.tables.rows,
+                         k.base.tables.off, k.base.fill, k.base.tmp, k.base.tmp_bytes, f_seg, logit_seg, q, d, c, fill, out, ld_out, seen, count, nn,
+                         so, stream_);
 }

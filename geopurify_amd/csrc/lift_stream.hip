@@ -12,10 +12,11 @@
 // view index, one add each; here the same adds happen in the same order, with a store and a reload of the fp32 partial sum between two
 // chunks, which changes no bit; the integer counts add up; keep_v depends on view v's own count alone; division and fill run once.
 //
-// The accumulating kernel is lb_lift_kernel's walk (lift_batched.hip): one wave per point, lane l projects the point through the l-th
-// view of a group of 64 of its entry's views IN THIS CHUNK, a 64-bit ballot is the visible-and-kept mask, its set bits are walked in
-// ascending order with all lanes striding the channels (pixel-major maps: 256 contiguous bytes per wave load).  The sum row is loaded
-// at the first set bit and stored only if there was one: a point that no kept view of the chunk sees costs its projection and no
+// The accumulating kernel is lb_lift_kernel's walk (lift_batched.hip; both run the sampling body of gp_lift_sample.h): one wave per
+// point, lane l projects the point through the l-th view of a group of 64 of its entry's views IN THIS CHUNK, a 64-bit ballot is the
+// visible-and-kept mask, its set bits are walked in ascending order with all lanes striding the channels (pixel-major maps: 256
+// contiguous bytes per wave load).  The sum row is loaded at the first set bit and stored only if there was one: a point that no
+// kept view of the chunk sees costs its projection and no
 // row traffic.  One wave owns one point: the row's read-modify-write is its own, there are no float atomics.
 //
 // Bounds: a batch or view entry index is range-checked before every table access (0..65535; the tables hold 65538 words).  The state
@@ -27,26 +28,14 @@
 // A pixel is read only after project_point found it inside [cut, W-cut) x [cut, H-cut) with cut >= 0; bilinear taps are clamped to
 // the map; channel indices are guarded by c < d.  All offsets are 64-bit.
 #include "gp_lift_stream_state.h"
-#include "gp_map_elem.h"
+#include "gp_lift_sample.h"
 
 namespace {
 
-constexpr int LS_COLS_PER_LANE = 8;
-constexpr int LS_COL_CHUNK = GP_WAVE * LS_COLS_PER_LANE;         // channels one pass holds in registers (gp_lift_batched's)
-
 // ------------------------------------------------------------------------------------------------ the accumulating lift
-// the column accumulator k of a lane holds in the chunk at c0 (VEC = 1: the mapping the kernel was written with)
-template <int VEC>
-__device__ __forceinline__ int ls_col(int c0, int lane, int k) {
-    if constexpr (VEC == 1) return c0 + lane + k * GP_WAVE;
-    else return c0 + ((k / VEC) * GP_WAVE + lane) * VEC + k % VEC;
-}
-
-// One wave per point, over the views of the point's entry in this chunk.  BILINEAR as in lb_lift_kernel: the map is [h, w], the pixel
-// indexes the [H, W] image, and the resize is evaluated at the pixel with the arithmetic of lift_dense_bilinear_accum_kernel.
-// T and VEC as in lb_lift_kernel: the maps' element type, converted to fp32 as it is loaded, and the consecutive columns a lane takes
-// with one load (1: the mapping the kernel was written with; 4 / 8: aligned half maps).  The sums stay fp32 whatever T is, so the
-// chunks of one stream may differ in type.
+// One wave per point, over the views of the point's entry in this chunk.  T, VEC, BILINEAR as in lb_lift_kernel: the maps' element
+// type, the consecutive columns a lane takes with one load and the sampling mode, as lb_add_sample and lb_col (gp_lift_sample.h)
+// define them.  The sums stay fp32 whatever T is, so the chunks of one stream may differ in type.
 template <typename T, int VEC, bool BILINEAR>
 __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict__ points, int64_t n, const T *__restrict__ feat, int d, int h,
                                                        int w, float scale_h, float scale_w, const int32_t *__restrict__ entry_views,
@@ -69,10 +58,10 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
     // sums' base and pitch allow it
     const bool wide = VEC > 1 && (((uintptr_t)sums | (uintptr_t)(ld_sum * 4)) & 15) == 0;
     int cnt = 0;
-    for (int c0 = 0; c0 < d; c0 += LS_COL_CHUNK) {
-        float acc[LS_COLS_PER_LANE];
+    for (int c0 = 0; c0 < d; c0 += LB_COL_CHUNK) {
+        float acc[LB_COLS_PER_LANE];
 #pragma unroll
-        for (int k = 0; k < LS_COLS_PER_LANE; ++k) acc[k] = 0.f;
+        for (int k = 0; k < LB_COLS_PER_LANE; ++k) acc[k] = 0.f;
         int seen_by = 0;
         for (int g = v0; g < v1; g += GP_WAVE) {
             int v = 0, px = 0, py = 0;
@@ -92,8 +81,8 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
             if (m && !seen_by) {                                     // (wave-uniform) the first view that sees the point: continue its sum
                 if (VEC > 1 && wide) {
 #pragma unroll
-                    for (int k = 0; k < LS_COLS_PER_LANE; k += 4) {
-                        const int c = ls_col<VEC>(c0, lane, k);
+                    for (int k = 0; k < LB_COLS_PER_LANE; k += 4) {
+                        const int c = lb_col<VEC>(c0, lane, k);
                         if (c < d) {
                             const float4 q = *reinterpret_cast<const float4 *>(srow + c);
                             acc[k] = q.x; acc[k + 1] = q.y; acc[k + 2] = q.z; acc[k + 3] = q.w;
@@ -101,8 +90,8 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
                     }
                 } else {
 #pragma unroll
-                    for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                        const int c = ls_col<VEC>(c0, lane, k);
+                    for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                        const int c = lb_col<VEC>(c0, lane, k);
                         if (c < d) acc[k] = srow[c];
                     }
                 }
@@ -113,77 +102,21 @@ __global__ void __launch_bounds__(256) ls_accum_kernel(const double *__restrict_
                 m &= m - 1;
                 const int vj = __shfl(v, j, 64), col = __shfl(px, j, 64), row = __shfl(py, j, 64);
                 const T *f = feat + (int64_t)vj * map;
-                if (BILINEAR) {
-                    int r0, r1, q0, q1;
-                    float wr0, wr1, wc0, wc1;
-                    bilinear_tap(scale_h, row, h, r0, r1, wr0, wr1);
-                    bilinear_tap(scale_w, col, w, q0, q1, wc0, wc1);
-                    const T *f00 = f + ((int64_t)r0 * w + q0) * d, *f01 = f + ((int64_t)r0 * w + q1) * d;
-                    const T *f10 = f + ((int64_t)r1 * w + q0) * d, *f11 = f + ((int64_t)r1 * w + q1) * d;
-                    if constexpr (VEC == 1) {
-#pragma unroll
-                        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                            const int c = c0 + lane + k * GP_WAVE;
-                            if (c < d) {
-                                const float top = __builtin_fmaf(wc0, gp_to_f32(f00[c]), wc1 * gp_to_f32(f01[c]));
-                                const float bot = __builtin_fmaf(wc0, gp_to_f32(f10[c]), wc1 * gp_to_f32(f11[c]));
-                                acc[k] += __builtin_fmaf(wr0, top, wr1 * bot);
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < LS_COLS_PER_LANE / VEC; ++j) {
-                            const int c = c0 + (j * GP_WAVE + lane) * VEC;   // (d is a multiple of VEC: the group is inside or outside)
-                            if (c < d) {
-                                float a00[VEC], a01[VEC], a10[VEC], a11[VEC];
-                                gp_load_f32<VEC>(f00 + c, a00);
-                                gp_load_f32<VEC>(f01 + c, a01);
-                                gp_load_f32<VEC>(f10 + c, a10);
-                                gp_load_f32<VEC>(f11 + c, a11);
-#pragma unroll
-                                for (int i = 0; i < VEC; ++i) {
-                                    const float top = __builtin_fmaf(wc0, a00[i], wc1 * a01[i]);
-                                    const float bot = __builtin_fmaf(wc0, a10[i], wc1 * a11[i]);
-                                    acc[j * VEC + i] += __builtin_fmaf(wr0, top, wr1 * bot);
-                                }
-                            }
-                        }
-                    }
-                } else {
-                    const T *fr = f + ((int64_t)row * w + col) * d;
-                    if constexpr (VEC == 1) {
-#pragma unroll
-                        for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                            const int c = c0 + lane + k * GP_WAVE;
-                            if (c < d) acc[k] += gp_to_f32(fr[c]);
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < LS_COLS_PER_LANE / VEC; ++j) {
-                            const int c = c0 + (j * GP_WAVE + lane) * VEC;
-                            if (c < d) {
-                                float a[VEC];
-                                gp_load_f32<VEC>(fr + c, a);
-#pragma unroll
-                                for (int i = 0; i < VEC; ++i) acc[j * VEC + i] += a[i];
-                            }
-                        }
-                    }
-                }
+                lb_add_sample<T, VEC, BILINEAR>(f, row, col, d, h, w, scale_h, scale_w, c0, lane, acc);
             }
         }
         cnt = seen_by;                                               // (every column chunk sees the same views)
         if (!cnt) return;                                            // unseen by this chunk: the row is neither loaded nor stored
         if (VEC > 1 && wide) {
 #pragma unroll
-            for (int k = 0; k < LS_COLS_PER_LANE; k += 4) {
-                const int c = ls_col<VEC>(c0, lane, k);
+            for (int k = 0; k < LB_COLS_PER_LANE; k += 4) {
+                const int c = lb_col<VEC>(c0, lane, k);
                 if (c < d) *reinterpret_cast<float4 *>(srow + c) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < LS_COLS_PER_LANE; ++k) {
-                const int c = ls_col<VEC>(c0, lane, k);
+            for (int k = 0; k < LB_COLS_PER_LANE; ++k) {
+                const int c = lb_col<VEC>(c0, lane, k);
                 if (c < d) srow[c] = acc[k];
             }
         }
@@ -210,62 +143,38 @@ __global__ void __launch_bounds__(256) ls_divide_kernel(const float *__restrict_
     }
 }
 
-__global__ void ls_status_kernel(const int64_t *__restrict__ running, int64_t *__restrict__ status_out) {
-    const int i = threadIdx.x;
-    if (i < ST_WORDS) status_out[i] = i <= ST_TOP_BATCH ? running[i] : 0;
-}
-
 }  // namespace
 
-extern "C" size_t gp_lift_stream_state_bytes(int64_t n) { return ls_n_ok(n) ? ls_state_bytes(n) : 0; }
+extern "C" size_t gp_lift_stream_state_bytes(int64_t n) { return lb_n_ok(n) ? ls_state_bytes(n) : 0; }
 
-extern "C" size_t gp_lift_stream_begin_workspace_bytes(int64_t n) {
-    if (!ls_n_ok(n)) return 0;
-    GpCarver cv(nullptr, 0);
-    LsBeginWork k(cv, n);
-    return cv.off;
-}
+extern "C" size_t gp_lift_stream_begin_workspace_bytes(int64_t n) { return lb_n_ok(n) ? ls_begin_workspace_bytes(n) : 0; }
 
 extern "C" int gp_lift_stream_begin(const double *points, int64_t n, int32_t d, void *state, size_t state_bytes, float *sums, int64_t ld_sum,
                                     int32_t *count, int64_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(points && state && sums && count && status && workspace, "gp_lift_stream_begin: null argument");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_begin: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(d >= 1 && ld_sum >= d, "gp_lift_stream_begin: d=%d, ld_sum=%lld", d, (long long)ld_sum);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_begin: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+    const char *who = "gp_lift_stream_begin";
+    GP_CHECK_ARG(points && state && sums && count && status && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    GP_CHECK_ARG(d >= 1 && ld_sum >= d, "%s: d=%d, ld_sum=%lld", who, d, (long long)ld_sum);
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        const void *o[] = {state, sums, count, status, workspace};
+        const void *const in[] = {points};
+        const size_t in_bytes[] = {(size_t)n * 32};
+        const void *const o[] = {state, sums, count, status, workspace};
         const size_t o_bytes[] = {state_bytes, (size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 5; ++a) {
-            GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], points, (size_t)n * 32), "gp_lift_stream_begin: an output overlaps an input");
-            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_begin: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(state, state_bytes), cv(workspace, workspace_bytes);
     LsState st(sv, n);
     LsBeginWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_stream_begin: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
     GP_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int32_t), s));
     GP_CHECK_HIP(hipMemset2DAsync(sums, (size_t)ld_sum * 4, 0, (size_t)d * 4, (size_t)n, s));       // +0 in every sum, the pitch columns untouched
-    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, reinterpret_cast<unsigned long long *>(status));
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, st.keys, k.r0, st.rows, (size_t)n, 0, LB_KEY_BITS, s));             // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(st.keys, n, st.off);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    return ls_begin_tables(points, n, st, k, status, s);
 }
 
-extern "C" size_t gp_lift_stream_add_workspace_bytes(int32_t nviews) {
-    if (nviews < 1 || nviews > 65535) return 0;
-    GpCarver cv(nullptr, 0);
-    LsAddWork k(cv, nviews);
-    return cv.off;
-}
+extern "C" size_t gp_lift_stream_add_workspace_bytes(int32_t nviews) { return lb_nviews_ok(nviews) ? ls_add_workspace_bytes(nviews) : 0; }
 
 extern "C" int gp_lift_stream_add_t(const double *points, int64_t n, const void *state, size_t state_bytes, const void *feat, int32_t elem,
                                     int32_t d, int32_t h, int32_t w, const int64_t *view_entry, const double *w2c, const double *intrinsics,
@@ -273,81 +182,48 @@ extern "C" int gp_lift_stream_add_t(const double *points, int64_t n, const void 
                                     double vis_thres, int64_t min_visible, int64_t max_visible, float *sums, int64_t ld_sum, int32_t *count,
                                     int64_t *view_count, uint8_t *view_keep, int64_t *status, void *workspace, size_t workspace_bytes,
                                     void *stream_) {
+    const char *who = "gp_lift_stream_add";
     GP_CHECK_ARG(points && state && feat && view_entry && w2c && intrinsics && sums && count && view_count && view_keep && status && workspace,
-                 "gp_lift_stream_add: null argument");
-    GP_CHECK_ARG(gp_elem_ok(elem), "gp_lift_stream_add: element type %d (0 fp32, 1 fp16, 2 bf16)", elem);
-    GP_CHECK_ARG(elem == GP_ELEM_F32 || (uintptr_t)feat % 2 == 0, "gp_lift_stream_add: half maps at an odd address");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_add: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "gp_lift_stream_add: %d views outside 1..65535", nviews);
-    GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_sum >= d,
-                 "gp_lift_stream_add: d=%d, map %d x %d, image %d x %d, ld_sum=%lld", d, h, w, height, width, (long long)ld_sum);
-    GP_CHECK_ARG(bilinear == 0 || bilinear == 1, "gp_lift_stream_add: bilinear=%d (0 nearest, 1 bilinear)", bilinear);
-    GP_CHECK_ARG(bilinear || (h == height && w == width), "gp_lift_stream_add: the nearest mode samples the map itself: map %d x %d, image %d x %d",
-                 h, w, height, width);
-    GP_CHECK_ARG(cut_bound >= 0, "gp_lift_stream_add: cut_bound=%d must not be negative", cut_bound);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_add: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+                 "%s: null argument", who);
+    LB_TRY(lb_check_elem(who, elem, feat, "maps"));
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    GP_CHECK_ARG(d >= 1 && h >= 1 && w >= 1 && height >= 1 && width >= 1 && ld_sum >= d, "%s: d=%d, map %d x %d, image %d x %d, ld_sum=%lld", who, d, h,
+                 w, height, width, (long long)ld_sum);
+    LB_TRY(lb_check_sampling(who, bilinear, h, w, height, width));
+    LB_TRY(lb_check_cut(who, cut_bound));
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        // every output against every input and every other output, over their whole extents
         const size_t px = (size_t)height * width, maps = (size_t)nviews * h * w * d * gp_elem_size(elem);
-        const void *in[] = {points, state, feat, view_entry, w2c, intrinsics, depth};
+        const void *const in[] = {points, state, feat, view_entry, w2c, intrinsics, depth};
         const size_t in_bytes[] = {(size_t)n * 32,      state_bytes,          maps, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32,
                                    (size_t)nviews * px * 8};
-        const void *o[] = {sums, count, view_count, view_keep, status, workspace};
+        const void *const o[] = {sums, count, view_count, view_keep, status, workspace};
         const size_t o_bytes[] = {(size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)nviews * 8, (size_t)nviews, (size_t)ST_WORDS * 8,
                                   workspace_bytes};
-        for (int a = 0; a < 6; ++a) {
-            for (int i = 0; i < 7; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_stream_add: an output overlaps an input");
-            for (int q = a + 1; q < 6; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_add: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LsState st(sv, n);
     LsAddWork k(cv, nviews);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_stream_add: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
-    unsigned long long *vc = reinterpret_cast<unsigned long long *>(view_count);
-    GP_CHECK_HIP(hipMemsetAsync(view_count, 0, (size_t)nviews * sizeof(int64_t), s));
-    const unsigned nb = (unsigned)((n + 255) / 256), vb = (unsigned)((nviews + 255) / 256);
-    // (1) the chunk's view table; its bad entries join the running count
-    lb_view_keys_kernel<<<vb, 256, 0, s>>>(view_entry, nviews, k.vk0, k.w0, reinterpret_cast<unsigned long long *>(status));
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.vk0, k.vk1, k.w0, k.entry_views, (size_t)nviews, 0, LB_KEY_BITS, s));  // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.vk1, nviews, k.view_off);
-    // (2) the chunk's per-view counts and the drop rule
-    ls_counts_kernel<<<dim3(nb < 64 ? nb : 64, (unsigned)nviews), 256, 0, s>>>(points, n, st.rows, st.off, view_entry, w2c, intrinsics, depth, width,
-                                                                                height, cut_bound, vis_thres, vc);
-    lb_keep_kernel<<<vb, 256, 0, s>>>(vc, nviews, min_visible, max_visible, view_keep);
-    GP_CHECK_LAUNCH();
+    // (1) the chunk's view table; its bad entries join the running count.  (2) the chunk's per-view counts and the drop rule
+    LB_TRY(lb_view_table(view_entry, nviews, k.views, k.tmp, k.tmp_bytes, reinterpret_cast<unsigned long long *>(status), s));
+    LB_TRY(ls_view_counts(points, n, st, view_entry, w2c, intrinsics, depth, nviews, width, height, cut_bound, vis_thres, min_visible, max_visible,
+                          view_count, view_keep, s));
     // (3) the accumulating lift
     // area_pixel_compute_scale<float>(in, out, align_corners=true): (in-1)/(out-1) in fp32, 0 for a single output pixel
     const float sh = height > 1 ? (float)(h - 1) / (float)(height - 1) : 0.f;
     const float sw = width > 1 ? (float)(w - 1) / (float)(width - 1) : 0.f;
     const unsigned lb = (unsigned)((n * 64 + 255) / 256);
-    const int vec = gp_elem_vec(feat, d, gp_elem_size(elem));    // (launch-uniform: every sampled row is aligned to the load it names)
-#define LS_ACCUM(T, VEC)                                                                                                                      \
-    do {                                                                                                                                      \
-        if (bilinear)                                                                                                                         \
-            ls_accum_kernel<T, VEC, true><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views, k.view_off, \
-                                                             w2c, intrinsics, depth, width, height, cut_bound, vis_thres, view_keep, sums,     \
-                                                             ld_sum, count);                                                                  \
-        else                                                                                                                                  \
-            ls_accum_kernel<T, VEC, false><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.entry_views,          \
-                                                              k.view_off, w2c, intrinsics, depth, width, height, cut_bound, vis_thres,        \
-                                                              view_keep, sums, ld_sum, count);                                                \
-    } while (0)
-    if (elem == GP_ELEM_F32) LS_ACCUM(float, 1);
-    else if (elem == GP_ELEM_F16 && vec == 8) LS_ACCUM(gp_f16, 8);
-    else if (elem == GP_ELEM_F16 && vec == 4) LS_ACCUM(gp_f16, 4);
-    else if (elem == GP_ELEM_F16) LS_ACCUM(gp_f16, 1);
-    else if (vec == 8) LS_ACCUM(gp_bf16, 8);
-    else if (vec == 4) LS_ACCUM(gp_bf16, 4);
-    else LS_ACCUM(gp_bf16, 1);
-#undef LS_ACCUM
+    lb_sample_dispatch(feat, elem, d, bilinear, [&](auto form) {
+        using F = decltype(form);
+        using T = typename F::type;
+        ls_accum_kernel<T, F::vec, F::bilinear><<<lb, 256, 0, s>>>(points, n, static_cast<const T *>(feat), d, h, w, sh, sw, k.views.idx, k.views.off,
+                                                                   w2c, intrinsics, depth, width, height, cut_bound, vis_thres, view_keep, sums,
+                                                                   ld_sum, count);
+    });
     GP_CHECK_LAUNCH();
     return GP_OK;
 }
@@ -363,7 +239,7 @@ extern "C" int gp_lift_stream_add(const double *points, int64_t n, const void *s
 }
 
 extern "C" size_t gp_lift_stream_finish_workspace_bytes(int64_t n) {
-    if (!ls_n_ok(n)) return 0;
+    if (!lb_n_ok(n)) return 0;
     GpCarver cv(nullptr, 0);
     LsFinishWork k(cv, n);
     return cv.off;
@@ -372,47 +248,28 @@ extern "C" size_t gp_lift_stream_finish_workspace_bytes(int64_t n) {
 extern "C" int gp_lift_stream_finish(const double *points, int64_t n, const void *state, size_t state_bytes, const float *sums, int32_t d,
                                      int64_t ld_sum, const int32_t *count, const int64_t *status, int32_t fill, float *out, int64_t ld_out,
                                      uint8_t *seen, int64_t *nn, int64_t *status_out, void *workspace, size_t workspace_bytes, void *stream_) {
-    GP_CHECK_ARG(points && state && sums && count && status && out && seen && status_out && workspace, "gp_lift_stream_finish: null argument");
-    GP_CHECK_ARG(ls_n_ok(n), "gp_lift_stream_finish: n=%lld outside 1..2^31-1", (long long)n);
-    GP_CHECK_ARG(d >= 1 && ld_sum >= d && ld_out >= d, "gp_lift_stream_finish: d=%d, ld_sum=%lld, ld_out=%lld", d, (long long)ld_sum,
-                 (long long)ld_out);
-    GP_CHECK_ARG(fill == 0 || nn, "gp_lift_stream_finish: the fill writes nn");
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "gp_lift_stream_finish: state too small (%zu < %zu)", state_bytes, ls_state_bytes(n));
+    const char *who = "gp_lift_stream_finish";
+    GP_CHECK_ARG(points && state && sums && count && status && out && seen && status_out && workspace, "%s: null argument", who);
+    LB_TRY(lb_check_n(who, n));
+    GP_CHECK_ARG(d >= 1 && ld_sum >= d && ld_out >= d, "%s: d=%d, ld_sum=%lld, ld_out=%lld", who, d, (long long)ld_sum, (long long)ld_out);
+    GP_CHECK_ARG(fill == 0 || nn, "%s: the fill writes nn", who);
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        const void *in[] = {points, state, sums, count, status};
+        const void *const in[] = {points, state, sums, count, status};
         const size_t in_bytes[] = {(size_t)n * 32, state_bytes, (size_t)((n - 1) * ld_sum + d) * 4, (size_t)n * 4, (size_t)ST_WORDS * 8};
-        const void *o[] = {out, seen, nn, status_out, workspace};
+        const void *const o[] = {out, seen, nn, status_out, workspace};
         const size_t o_bytes[] = {(size_t)((n - 1) * ld_out + d) * 4, (size_t)n, (size_t)n * 8, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 5; ++a) {
-            for (int i = 0; i < 5; ++i)
-                GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "gp_lift_stream_finish: an output overlaps an input");
-            for (int q = a + 1; q < 5; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "gp_lift_stream_finish: two outputs overlap");
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LsState st(sv, n);
     LsFinishWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("gp_lift_stream_finish: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
-    unsigned long long *so = reinterpret_cast<unsigned long long *>(status_out);
-    const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);
-    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
-    ls_status_kernel<<<1, 64, 0, s>>>(status, status_out);
-    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(st.keys, st.rows, st.off, n, k.keys, k.rows, k.off, so);
+    LB_TRY(ls_checked_tables(st, n, k.tables, status, LS_CARRY, status_out, s));
     ls_divide_kernel<<<(unsigned)((n * 64 + 255) / 256), 256, 0, s>>>(sums, ld_sum, count, n, d, out, ld_out, seen, nn);
     GP_CHECK_LAUNCH();
     // the fill of gp_lift_batched, over the checked copies of the tables
-    lb_fill_flags_kernel<<<nb1, 256, 0, s>>>(k.keys, k.rows, seen, n, k.ref, k.qry);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.ref, k.rs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(k.tmp, io, k.qry, k.qs, (int32_t)0, (size_t)(n + 1), rocprim::plus<int32_t>(), s));
-    lb_fill_compact_kernel<<<nb, 256, 0, s>>>(points, k.rows, k.ref, k.qry, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, so);
-    if (fill) lb_fill_kernel<<<nb, 256, 0, s>>>(points, k.keys, k.rows, k.off, k.rs, k.qs, n, k.rxyz, k.rrow, k.qpos, nn, so);
-    GP_CHECK_LAUNCH();
-    return GP_OK;
+    return lb_fill(points, n, k.tables.keys, k.tables.rows, k.tables.off, k.fill, k.tmp, k.tmp_bytes, seen, fill, nn,
+                   reinterpret_cast<unsigned long long *>(status_out), s);
 }

@@ -6,10 +6,10 @@
 // with the arithmetic of render_depth_kernel (voxelize.hip: gp_render_depth_f64, one scene and one view per call); the decision is
 // render_point of gp_project.h, the one definition both kernels run.  Entries never mix: a view renders the rows of its own entry only.
 //
-// Structure: (1) the entry tables -- gp_render_depth_batched sorts the rows stably by entry with the kernels of gp_lift_entries.h
+// Structure: (1) the entry tables -- gp_render_depth_batched sorts the rows stably by entry with lb_row_table of gp_lift_entries.h
 // (lb_row_keys_kernel, the rocPRIM radix sort on 17-bit keys, lb_offsets_kernel), the same notion of "an entry's rows" as the lifts;
 // gp_render_depth_batched_state takes them from a stream's state (gp_lift_stream_begin / gp_lift_masks_stream_begin) through
-// ls_tables_kernel, every value forced into its range, and sorts nothing; (2) the whole [V, H, W] buffer filled with 999999 by 16-byte
+// ls_checked_tables of gp_lift_stream_state.h, every value forced into its range, and sorts nothing; (2) the whole [V, H, W] buffer filled with 999999 by 16-byte
 // stores (a scalar head and tail where the buffer starts or ends off a 16-byte boundary); (3) the z-buffer: blockIdx.y = view, a view's
 // blocks stride the sorted rows of its entry (lb_counts_kernel's launch shape), one 64-bit unsigned atomicMin on the fp64 bit pattern
 // per rendered point.  Positive doubles order like their bit patterns and a minimum does not depend on the order of its operands, so
@@ -29,29 +29,13 @@ constexpr double RD_FAR = 999999.0;                              // fusion_util.
 constexpr unsigned RD_VIEW_BLOCKS = 64;                          // blocks of 256 threads per view: lb_counts_kernel's launch shape
 constexpr int64_t RD_FILL_BLOCKS = 16384;
 
-struct RdWork {                                                  // gp_render_depth_batched: the entry tables and the sort's scratch
-    uint32_t *k0, *k1;
-    int32_t *r0, *entry_rows, *entry_off;
+struct RdWork {                                                  // gp_render_depth_batched: the entry table and the sort's scratch
+    LbTable rows;
     char *tmp;
     size_t tmp_bytes;
-    RdWork(GpCarver &cv, int64_t n) {
+    RdWork(GpCarver &cv, int64_t n) : rows(lb_table(cv, n)) {
         tmp_bytes = lb_sort_bytes(n);
-        k0 = cv.take<uint32_t>(n);
-        k1 = cv.take<uint32_t>(n);
-        r0 = cv.take<int32_t>(n);
-        entry_rows = cv.take<int32_t>(n);
-        entry_off = cv.take<int32_t>(LB_TABLE);
         tmp = cv.take<char>(tmp_bytes);
-    }
-};
-
-struct RdStateWork {                                             // gp_render_depth_batched_state: the checked copies of the state's tables
-    uint32_t *keys;
-    int32_t *rows, *off;
-    RdStateWork(GpCarver &cv, int64_t n) {
-        keys = cv.take<uint32_t>(n);
-        rows = cv.take<int32_t>(n);
-        off = cv.take<int32_t>(LB_TABLE);
     }
 };
 
@@ -100,10 +84,10 @@ int rd_check(const char *who, const double *points, int64_t n, const int64_t *vi
              int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, const double *depth, const int64_t *status,
              const void *workspace) {
     GP_CHECK_ARG(points && view_entry && w2c && intrinsics && depth && status && workspace, "%s: null argument", who);
-    GP_CHECK_ARG(ls_n_ok(n), "%s: n=%lld outside 1..2^31-1", who, (long long)n);
-    GP_CHECK_ARG(nviews >= 1 && nviews <= 65535, "%s: %d views outside 1..65535", who, nviews);
-    GP_CHECK_ARG(height >= 1 && width >= 1, "%s: image %d x %d", who, height, width);
-    GP_CHECK_ARG(cut_bound >= 0, "%s: cut_bound=%d must not be negative", who, cut_bound);
+    LB_TRY(lb_check_n(who, n));
+    LB_TRY(lb_check_nviews(who, nviews));
+    LB_TRY(lb_check_image(who, height, width));
+    LB_TRY(lb_check_cut(who, cut_bound));
     GP_CHECK_ARG((reinterpret_cast<uintptr_t>(depth) & 7) == 0, "%s: depth is not 8-byte aligned", who);
     return GP_OK;
 }
@@ -124,7 +108,7 @@ int rd_render(const double *points, int64_t n, const int32_t *entry_rows, const 
 }  // namespace
 
 extern "C" size_t gp_render_depth_batched_workspace_bytes(int64_t n, int32_t nviews) {
-    if (!ls_n_ok(n) || nviews < 1 || nviews > 65535) return 0;
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews)) return 0;
     GpCarver cv(nullptr, 0);
     RdWork k(cv, n);
     return cv.off;
@@ -134,40 +118,28 @@ extern "C" int gp_render_depth_batched(const double *points, int64_t n, const in
                                        int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, double *depth, int64_t *status,
                                        void *workspace, size_t workspace_bytes, void *stream_) {
     const char *who = "gp_render_depth_batched";
-    const int rc = rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace);
-    if (rc != GP_OK) return rc;
+    LB_TRY(rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace));
     {
-        // every output against every input and every other output, over their whole extents
-        const void *in[] = {points, view_entry, w2c, intrinsics};
+        const void *const in[] = {points, view_entry, w2c, intrinsics};
         const size_t in_bytes[] = {(size_t)n * 32, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32};
-        const void *o[] = {depth, status, workspace};
+        const void *const o[] = {depth, status, workspace};
         const size_t o_bytes[] = {(size_t)nviews * height * width * 8, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 3; ++a) {
-            for (int i = 0; i < 4; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver cv(workspace, workspace_bytes);
     RdWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
     unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
-    lb_row_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(points, n, k.k0, k.r0, st);
-    GP_CHECK_LAUNCH();
-    size_t io = k.tmp_bytes;
-    GP_CHECK_HIP(rocprim::radix_sort_pairs(k.tmp, io, k.k0, k.k1, k.r0, k.entry_rows, (size_t)n, 0, LB_KEY_BITS, s));          // (stable)
-    lb_offsets_kernel<<<(LB_TABLE + 255) / 256, 256, 0, s>>>(k.k1, n, k.entry_off);
-    return rd_render(points, n, k.entry_rows, k.entry_off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, st, s);
+    LB_TRY(lb_row_table(points, n, k.rows, k.tmp, k.tmp_bytes, st, s));
+    return rd_render(points, n, k.rows.idx, k.rows.off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, st, s);
 }
 
 extern "C" size_t gp_render_depth_batched_state_workspace_bytes(int64_t n, int32_t nviews) {
-    if (!ls_n_ok(n) || nviews < 1 || nviews > 65535) return 0;
+    if (!lb_n_ok(n) || !lb_nviews_ok(nviews)) return 0;
     GpCarver cv(nullptr, 0);
-    RdStateWork k(cv, n);
+    LsState k(cv, n);
     return cv.off;
 }
 
@@ -176,32 +148,23 @@ extern "C" int gp_render_depth_batched_state(const double *points, int64_t n, co
                                              int32_t cut_bound, double *depth, int64_t *status, void *workspace, size_t workspace_bytes,
                                              void *stream_) {
     const char *who = "gp_render_depth_batched_state";
-    const int rc = rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace);
-    if (rc != GP_OK) return rc;
+    LB_TRY(rd_check(who, points, n, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, status, workspace));
     GP_CHECK_ARG(state, "%s: null argument", who);
-    GP_CHECK_ARG(state_bytes >= ls_state_bytes(n), "%s: state too small (%zu < %zu)", who, state_bytes, ls_state_bytes(n));
+    LB_TRY(lb_check_state(who, state_bytes, ls_state_bytes(n)));
     {
-        const void *in[] = {points, state, view_entry, w2c, intrinsics};
+        const void *const in[] = {points, state, view_entry, w2c, intrinsics};
         const size_t in_bytes[] = {(size_t)n * 32, state_bytes, (size_t)nviews * 8, (size_t)nviews * 128, (size_t)nviews * 32};
-        const void *o[] = {depth, status, workspace};
+        const void *const o[] = {depth, status, workspace};
         const size_t o_bytes[] = {(size_t)nviews * height * width * 8, (size_t)ST_WORDS * 8, workspace_bytes};
-        for (int a = 0; a < 3; ++a) {
-            for (int i = 0; i < 5; ++i) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], in[i], in_bytes[i]), "%s: an output overlaps an input", who);
-            for (int q = a + 1; q < 3; ++q) GP_CHECK_ARG(!lb_overlap(o[a], o_bytes[a], o[q], o_bytes[q]), "%s: two outputs overlap", who);
-        }
+        LB_TRY(lb_no_overlap(who, in, in_bytes, o, o_bytes));
     }
     GpCarver sv(const_cast<void *>(state), state_bytes), cv(workspace, workspace_bytes);
     const LsState tb(sv, n);
-    RdStateWork k(cv, n);
-    if (!cv.ok()) {
-        gp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return GP_ENOMEM;
-    }
+    const LsState k(cv, n);                                      // the checked copies of the state's tables
+    LB_TRY(lb_check_workspace(who, cv, workspace_bytes));
     hipStream_t s = gp_stream(stream_);
-    unsigned long long *st = reinterpret_cast<unsigned long long *>(status);
     GP_CHECK_HIP(hipMemsetAsync(status, 0, ST_WORDS * sizeof(int64_t), s));
-    const int64_t most = n > LB_TABLE ? n : LB_TABLE;
-    ls_tables_kernel<<<(unsigned)((most + 255) / 256), 256, 0, s>>>(tb.keys, tb.rows, tb.off, n, k.keys, k.rows, k.off, st);
-    GP_CHECK_LAUNCH();
-    return rd_render(points, n, k.rows, k.off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth, st, s);
+    LB_TRY(ls_checked_tables(tb, n, k, nullptr, 0, status, s));  // (no running words: the state's owner reports them)
+    return rd_render(points, n, k.rows, k.off, view_entry, w2c, intrinsics, nviews, height, width, cut_bound, depth,
+                     reinterpret_cast<unsigned long long *>(status), s);
 }
