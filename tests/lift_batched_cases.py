@@ -364,6 +364,145 @@ BILINEAR = tuple(n for n in CASES if "bilinear" in n)
 _CASES = {}
 
 
+# ------------------------------------------------------------------------------------------ large cases: all rows and no bytes
+# The shared kernels of csrc/gp_lift_entries.h, gp_lift_stream_state.h and lift_masks_batched.hip change behaviour at a size: a second
+# fill block (256 queries), a second LDS trip of the fill (1024 references), a second trip of the count loops and of the ordered walk
+# (16 384 rows of one entry), rows beyond the offset table's 65 538 words.  These cases reach every one of them on images of 16 x 12
+# and three channels.  They are reachable through case() and reference() and are NOT in CASES: the parametrisations over CASES run
+# "singles" partitions, per-scene sequences and restatement() -- a minute and more at 17 000 rows -- on every member.
+FILL_BLOCK, FILL_TILE, COUNT_TRIP, WALK_PARTS, ENTRY_TABLE = 256, 1024, 64 * 256, 64, MAX_ENTRIES + 2
+PLANTED_FX = 4.0
+
+
+def planted(name, seed, plan, views, D=3, **kw):
+    """plan = [(entry, n_seen, n_unseen), ...], views = {entry: views}.  No depth maps, identity cameras of focal 4 on 16 x 12 (as
+    case_fill: a row is seen when p_z > 0 and it projects inside).  A seen row is (a z, b z, z) with z in 0.5 .. 3, |a| <= 1.5 and
+    |b| <= 1: u = 4 a + 8 in 2 .. 14 and v = 4 b + 6 in 2 .. 10, clear of the image's edge (no cut) by two pixels.  An unseen row is the
+    same with z in -3 .. -0.5: p_z < 0, never visible.  So every entry has exactly n_seen seen and n_unseen unseen rows whatever the
+    number of its views -- or none seen if it has no view.  Rows shuffled across the entries, views interleaved, as generic does."""
+    rng = np.random.default_rng(seed)
+    W, H = 16, 12
+    rows = []
+    for b, n_seen, n_unseen in plan:
+        n = n_seen + n_unseen
+        z = rng.uniform(0.5, 3.0, n) * np.where(np.arange(n) < n_seen, 1.0, -1.0)
+        a, t = rng.uniform(-1.5, 1.5, n), rng.uniform(-1.0, 1.0, n)
+        rows.append(np.column_stack([np.full(n, b, f64), a * z, t * z, z]))
+    pts = np.vstack(rows)
+    pts = pts[rng.permutation(len(pts))]
+    ve = np.concatenate([np.full(n, b, np.int64) for b, n in views.items()])
+    ve = ve[rng.permutation(len(ve))]
+    M, K = _identity_views(len(ve), PLANTED_FX, W, H)
+    maps = rng.uniform(-1, 1, (len(ve), D, H, W)).astype(f32)
+    return Case(name, pts, maps, ve, M, K, None, plan={b: (s, u) for b, s, u in plan}, **kw)
+
+
+# (entry, references, queries).  Entry 2: a view and nothing before it; 3: fully seen; 6: a view and no rows; 11: rows and no view.
+FILL_BLOCKS_PLAN = ((0, 61, 239), (1, 8, 32), (2, 0, 40), (3, 50, 0), (4, 9, 21), (5, 2500, 1500), (7, 1, 700), (9, 1100, 1),
+                    (65535, 30, 30), (11, 0, 5))
+FILL_BLOCKS_VIEWS = {0: 2, 1: 1, 2: 1, 3: 1, 4: 1, 5: 2, 6: 1, 7: 1, 9: 1, 65535: 1}
+
+
+def case_fill_blocks():
+    """The scene-level fill over eleven blocks of 256 queries, the last one partial.  In the entry-sorted order the queries are 239 of
+    entry 0, 32 of entry 1, 40 of entry 2 (which has no reference), 21 of entry 4, 1500 of entry 5 ...: the second block holds queries
+    of entries 1, 2, 4 and 5 and streams the references of entry 3, which has none of its queries; entry 5's 2500 references take three
+    LDS trips.  tests/test_lift_batched_cases_host.py asserts all of it from the reference."""
+    return planted("fill_blocks", 31, FILL_BLOCKS_PLAN, FILL_BLOCKS_VIEWS)
+
+
+TIE_LINE, TIE_STEP, TIE_GONE = 2400, 2.0 ** -9, (301, 1203, 1801, 2049, 2255)
+
+
+def case_fill_tie_trips():
+    """On the exact arithmetic of case_fill (dyadic coordinates, focal 2, identity cameras, no depths).  Entry 3 holds a line of
+    references at z = 1, y = 0, x_k = (k - 1200) 2^-9 for k = 0 .. 2399 without the five odd k of TIE_GONE: u = 2 x + 8 in 3.3 .. 12.7,
+    all seen.  The rows list the even k first and then the odd ones, so spatial neighbours lie about 1200 references apart: in
+    different LDS trips of 1024.  A query sits at z = -1 (unseen) exactly midway between x_k and x_k+1: d^2 = 4 + 2^-20 to both, exactly,
+    and the lower row -- the even k, an earlier trip -- must win although the equal distance turns up a trip or two later.  The queries
+    at the x of TIE_GONE lie midway between k - 1 and k + 1, consecutive references of one trip.  Entry 0, 37 rows that are all seen, comes
+    first in the entry order: the block's range starts at reference 37, not 0.  The queries come first in the row order.
+    notes: ties = [(query row, lower row, higher row)], same_trip = the ties at TIE_GONE."""
+    W, H = 16, 12
+    x_of = lambda k: (k - 1200) * TIE_STEP                                       # noqa: E731
+    ks = [k for k in range(0, TIE_LINE, 2)] + [k for k in range(1, TIE_LINE, 2) if k not in TIE_GONE]
+    cross = [k for k in range(7, TIE_LINE - 1, 61) if k not in TIE_GONE and k + 1 not in TIE_GONE]     # both parities of k
+    queries = [(3.0, x_of(k) + TIE_STEP / 2, 0.0, -1.0) for k in cross] + [(3.0, x_of(k), 0.0, -1.0) for k in TIE_GONE]
+    line = [(3.0, x_of(k), 0.0, 1.0) for k in ks]
+    other = [(0.0, (j - 18) / 8.0, 0.25, 2.0) for j in range(37)]
+    first = len(queries)
+    row_of = {k: first + i for i, k in enumerate(ks)}
+    ties = [(q, min(row_of[k], row_of[k + 1]), max(row_of[k], row_of[k + 1])) for q, k in enumerate(cross)]
+    same = [(len(cross) + q, row_of[k - 1], row_of[k + 1]) for q, k in enumerate(TIE_GONE)]
+    ve = np.array([3, 0, 3])
+    M, K = _identity_views(len(ve), 2.0, W, H)
+    rng = np.random.default_rng(33)
+    maps = rng.uniform(-1, 1, (len(ve), 3, H, W)).astype(f32)
+    return Case("fill_tie_trips", np.array(queries + line + other, f64), maps, ve, M, K, None, ties=ties + same, same_trip=same)
+
+
+# the entry-1 views of walk_trips see 2117, 2149 and 2155 rows (tests/test_lift_batched_cases_host.py asserts the split); those among
+# the entry's first 16 384 sorted rows alone are about 90 fewer, below the bound for every view
+WALK_MAX_VISIBLE = 2130
+
+
+def case_walk_trips():
+    """An entry of 16384 + 700 rows under depth maps: the count kernels' stride loop (64 blocks of 256 rows per view) takes a second
+    trip, the ordered walk of the mask lift has per = ceil(17084 / 64) = 267 > 256 rows per part -- a second trip in every part -- and
+    the fill takes 60 blocks over the 2117 references that are left, three LDS trips.  max_visible = 2130 keeps the entry-1 view that
+    sees 2117 rows and drops the two that see 2149 and 2155; each of them sees 2071 among the first 16 384 sorted rows, so the drop is
+    decided by what the second trip counts."""
+    return generic("walk_trips", 32, {0: 200, 1: COUNT_TRIP + 700, 2: 1}, {0: 2, 1: 3, 2: 1}, 3, max_visible=WALK_MAX_VISIBLE)
+
+
+def case_rows_past_table():
+    """n = 65538 + 300 rows: more than the 65 538 words of the offset table, so the checked copy of a stream's tables has threads that
+    copy keys and rows only.  Entry 1, 65 538 rows, has no view: nothing of it is seen or filled, its reference costs nothing, and its
+    rows are 257 fill blocks of queries without a reference.  Entries 0 and 2, 150 rows and two and three views each, lie on both sides
+    of it in the sorted order; 240 of their rows are spread over the rows below 65 538 and 60 over those from 65 538 on."""
+    n_bulk, n_small = ENTRY_TABLE, 150
+    g = generic("rows_past_table", 34, {0: n_small, 1: n_bulk, 2: n_small}, {0: 2, 2: 3}, 3, shuffle=False)
+    rng = np.random.default_rng(35)
+    N = g.N
+    at = np.sort(np.concatenate([rng.choice(ENTRY_TABLE, 240, replace=False), ENTRY_TABLE + rng.choice(N - ENTRY_TABLE, 60, replace=False)]))
+    small = np.concatenate([np.arange(n_small), n_small + n_bulk + np.arange(n_small)])[rng.permutation(2 * n_small)]
+    pts = np.empty_like(g.points)
+    bulk_at = np.ones(N, bool)
+    bulk_at[at] = False
+    pts[at], pts[bulk_at] = g.points[small], g.points[n_small:n_small + n_bulk]
+    return Case("rows_past_table", pts, g.maps, g.view_entry, g.w2c, g.intr, g.depth)
+
+
+_LARGE_BUILDERS = {"fill_blocks": case_fill_blocks, "fill_tie_trips": case_fill_tie_trips, "walk_trips": case_walk_trips,
+                   "rows_past_table": case_rows_past_table}
+LARGE = tuple(_LARGE_BUILDERS)
+_BUILDERS.update(_LARGE_BUILDERS)                     # (after CASES: case() and reference() find them, no parametrisation does)
+
+
+def fill_blocking(c, mask):
+    """The blocking of the scene-level fill (lb_fill_kernel of csrc/gp_lift_entries.h) restated: rows in the entry-sorted stable order,
+    the references (mask) and the queries (not mask; every row of a case lies in a valid entry) compacted in that order, the queries
+    cut into blocks of 256; a block streams the references lo .. hi, the union of the non-empty runs of its queries' entries, in trips
+    of 1024 from lo.  -> (rank i64 [N]: the compacted position of a reference row, -1 for a query; blocks: a list of dicts with rows
+    (the block's query rows), entry, r0, r1 (each query's run), lo, hi (None, None when no query of the block has a reference))"""
+    entry = c.points[:, 0].astype(np.int64)
+    order = np.argsort(entry, kind="stable")
+    keys, is_ref = entry[order], np.asarray(mask, bool)[order]
+    rs = np.concatenate([[0], np.cumsum(is_ref)])
+    rank = np.full(c.N, -1, np.int64)
+    rank[order[is_ref]] = rs[:-1][is_ref]
+    qpos = np.nonzero(~is_ref)[0]
+    blocks = []
+    for i in range(0, len(qpos), FILL_BLOCK):
+        s = qpos[i:i + FILL_BLOCK]
+        b = keys[s]
+        r0, r1 = rs[np.searchsorted(keys, b, "left")], rs[np.searchsorted(keys, b, "right")]
+        has = r1 > r0
+        blocks.append(dict(rows=order[s], entry=b, r0=r0, r1=r1, lo=int(r0[has].min()) if has.any() else None,
+                           hi=int(r1[has].max()) if has.any() else None))
+    return rank, blocks
+
+
 def case(name):
     if name not in _CASES:
         _CASES[name] = _BUILDERS[name]()

@@ -361,6 +361,13 @@ _BUILDERS = {
 CASES = tuple(_BUILDERS)
 DTYPES = ("dtype_uint8", "dtype_int16", "dtype_int32", "dtype_int64")
 _CASES = {}
+# the large geometries of tests/lift_batched_cases.py (more than one fill block, LDS trip and count trip) under random label maps with a
+# tenth of the pixels ignored, so "voted" -- the fill's reference mask here -- is not "seen": reachable through case() and reference(),
+# not in CASES -- restatement() is not for them
+_LARGE_BUILDERS = {"fill_blocks": lambda: of_lift("fill_blocks", "fill_blocks", 5, 41, ignore_frac=0.1),
+                   "walk_trips": lambda: of_lift("walk_trips", "walk_trips", 7, 42, ignore_frac=0.1)}
+LARGE = tuple(_LARGE_BUILDERS)
+_BUILDERS.update(_LARGE_BUILDERS)
 
 
 def case(name):

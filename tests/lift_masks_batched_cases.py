@@ -408,6 +408,12 @@ _BUILDERS = {
 }
 CASES = tuple(_BUILDERS)
 _CASES = {}
+# the large geometries of tests/lift_batched_cases.py (more than one fill block, LDS trip, count trip and walk trip) under random VLM
+# outputs: reachable through case() and reference(), not in CASES -- restatement() and the per-scene sequences are not for them
+_LARGE_BUILDERS = {"fill_blocks": lambda: with_vlm("fill_blocks", lb.case("fill_blocks"), 41),
+                   "walk_trips": lambda: with_vlm("walk_trips", lb.case("walk_trips"), 42)}
+LARGE = tuple(_LARGE_BUILDERS)
+_BUILDERS.update(_LARGE_BUILDERS)
 
 
 def case(name):

@@ -55,11 +55,16 @@ def test_the_cases_cover_what_they_are_named_for():
     assert (H - 1) % (h - 1) and (W - 1) % (w - 1)                              # no integer ratio on either axis
     e = lb.case("entries")
     assert list(e.entries()) == [0, 2, 65535] and len(e.rows_of(0)) == 1
-    # generic cases hold seen and unseen points in one entry, and more than one lift block (4 points) and fill block (256 queries)
+    # generic cases hold seen and unseen points in one entry and more than one lift block (4 points).  The fill of every case in CASES
+    # is ONE block of at most 256 queries and one LDS trip: more blocks and trips are the LARGE cases' (the tests further down)
     for name in ("views_130", "views_0_1_63", "D65", "no_depth"):
         c, ref = lb.case(name), lb.reference(name)
         mixed = [b for b in c.entries() if ref.seen[c.rows_of(b)].any() and not ref.seen[c.rows_of(b)].all()]
         assert mixed and (ref.filled_from >= 0).any(), name
+    for name in lb.CASES:
+        rank, blocks = lb.fill_blocking(lb.case(name), lb.reference(name).seen)
+        assert len(blocks) <= 1 and all(b["lo"] is None or b["hi"] - b["lo"] <= lb.FILL_TILE for b in blocks), name
+    assert not set(lb.LARGE) & set(lb.CASES)
     assert lb.reference("views_130").count.max() > 64                           # a point seen by more views than one ballot holds
     assert lb.reference("views_64_65").count.max() >= 2
 
@@ -135,6 +140,147 @@ def test_fill_conditions():
     assert ref.seen[c.rows_of(2)].all() and not ref.seen[c.rows_of(4)].any() and len(c.views_of(4)) == 1
     assert len(c.views_of(5)) == 0 and not ref.features[c.rows_of(4)].any() and not ref.features[c.rows_of(5)].any()
     assert (ref.filled_from[c.rows_of(4)] == -1).all()
+
+
+# ------------------------------------------------------------------------------------------ the large cases hold what they are named for
+def _trip(b, r):
+    """the LDS trip of block b in which the reference of compacted position r is streamed"""
+    return (r - b["lo"]) // lb.FILL_TILE
+
+
+def _reference_structure(c, ref):
+    """what test_reference_equals_the_whole_batch_restatement asserts beside the restatement (which takes minutes at these sizes)"""
+    assert np.array_equal(ref.seen, ref.count > 0)
+    idle = ~ref.seen & (ref.filled_from < 0)
+    assert not ref.features[idle].any()
+    took = np.nonzero(ref.filled_from >= 0)[0]
+    assert np.array_equal(ref.features[took], ref.features[ref.filled_from[took]])
+    assert (c.points[took, 0] == c.points[ref.filled_from[took], 0]).all() and ref.seen[ref.filled_from[took]].all()
+
+
+def test_fill_blocks_spans_blocks_entries_and_trips():
+    c, ref = lb.case("fill_blocks"), lb.reference("fill_blocks")
+    _reference_structure(c, ref)
+    assert c.depth is None and (c.H, c.W, c.D) == (12, 16, 3)
+    assert (np.diff(c.view_entry) < 0).any() and (np.diff(c.view_entry) > 0).any() and (np.diff(c.points[:, 0]) < 0).any()
+    # the plan, exactly: seen and unseen rows per entry
+    assert sorted(c.entries()) == sorted(b for b, _, _ in lb.FILL_BLOCKS_PLAN) and 6 not in c.entries() and len(c.views_of(6)) == 1
+    for b, n_seen, n_unseen in lb.FILL_BLOCKS_PLAN:
+        rows = c.rows_of(b)
+        want = n_seen if len(c.views_of(b)) else 0
+        assert len(rows) == n_seen + n_unseen and int(ref.seen[rows].sum()) == want, b
+        assert int((ref.filled_from[rows] >= 0).sum()) == (n_unseen if want else 0), b
+    assert len(c.views_of(2)) == 1 and ref.view_count[c.views_of(2)[0]] == 0 and len(c.views_of(11)) == 0
+    assert ref.seen[c.rows_of(3)].all() and ref.count[c.rows_of(0)].max() == 2
+    rank, blocks = lb.fill_blocking(c, ref.seen)
+    # more than one block, a partial last block
+    assert len(blocks) == 11 and all(len(b["rows"]) == lb.FILL_BLOCK for b in blocks[:-1]) and 0 < len(blocks[-1]["rows"]) < lb.FILL_BLOCK
+    # one block spans at least three entries; its range contains the run of an entry that has none of its queries; it holds queries
+    # of an entry without references, and they are not filled
+    run_of = {int(b): (int(rank[c.rows_of(b)][ref.seen[c.rows_of(b)]].min()), int(rank[c.rows_of(b)][ref.seen[c.rows_of(b)]].max()) + 1)
+              for b in c.entries() if ref.seen[c.rows_of(b)].any()}
+    wide = [b for b in blocks if len(np.unique(b["entry"])) >= 3]
+    assert wide
+    b = wide[0]
+    assert sorted(np.unique(b["entry"])) == [1, 2, 4, 5]
+    foreign = [e for e, (s, t) in run_of.items() if e not in b["entry"] and b["lo"] <= s and t <= b["hi"]]
+    assert foreign == [3]
+    bare = b["rows"][b["r1"] == b["r0"]]
+    assert len(bare) == 40 and (c.points[bare, 0] == 2).all() and (ref.filled_from[bare] == -1).all()
+    # an entry's run starts and ends strictly inside one trip of that block: entries 3 and 4 (the latter with queries in the block)
+    for e in (3, 4):
+        s, t = run_of[e]
+        assert _trip(b, s) == _trip(b, t - 1) and (s - b["lo"]) % lb.FILL_TILE > 0 and (t - b["lo"]) % lb.FILL_TILE > 0 and t < b["hi"]
+    # ... and entry 5's starts inside the first trip of the block and ends inside its third
+    assert b["hi"] - b["lo"] > 2 * lb.FILL_TILE and _trip(b, run_of[5][0]) == 0 and (run_of[5][0] - b["lo"]) % lb.FILL_TILE > 0
+    assert _trip(b, run_of[5][1] - 1) == 2
+    # blocks with a range of more than two trips, in which the chosen references lie in every trip
+    deep = [b for b in blocks if b["lo"] is not None and b["hi"] - b["lo"] > 2 * lb.FILL_TILE]
+    assert len(deep) >= 6
+    for b in deep:
+        chosen = ref.filled_from[b["rows"]]
+        trips = set(_trip(b, rank[chosen[chosen >= 0]]).tolist())
+        assert trips == set(range(-(-(b["hi"] - b["lo"]) // lb.FILL_TILE))), trips
+    # a later block of two trips in which a run (entry 9) starts inside the first trip and ends inside the second, before hi
+    late = [b for b in blocks if 9 in b["entry"]]
+    assert len(late) == 1 and lb.FILL_TILE < late[0]["hi"] - late[0]["lo"] <= 2 * lb.FILL_TILE
+    s, t = run_of[9]
+    assert _trip(late[0], s) == 0 and s > late[0]["lo"] and _trip(late[0], t - 1) == 1 and t < late[0]["hi"]
+    assert sorted(np.unique(late[0]["entry"])) == [7, 9, 11, 65535] and c.entries().max() == 65535
+
+
+def test_fill_tie_trips_ties_across_trips():
+    c, ref = lb.case("fill_tie_trips"), lb.reference("fill_tie_trips")
+    _reference_structure(c, ref)
+    xyz = c.points[:, 1:].astype(f32).astype(f64)
+    assert np.array_equal(xyz, c.points[:, 1:])                                  # dyadic: fp32 holds every coordinate
+    d2 = lambda a, b: float((((xyz[a] - xyz[b]) ** 2)[0] + ((xyz[a] - xyz[b]) ** 2)[1]) + ((xyz[a] - xyz[b]) ** 2)[2])   # noqa: E731
+    rank, blocks = lb.fill_blocking(c, ref.seen)
+    assert len(blocks) == 1 and blocks[0]["lo"] == 37 and blocks[0]["hi"] - blocks[0]["lo"] >= 1200
+    assert int(ref.seen[c.rows_of(3)].sum()) == lb.TIE_LINE - len(lb.TIE_GONE) and ref.seen[c.rows_of(0)].all()
+    b = blocks[0]
+    same = set(c.notes["same_trip"])
+    pairs = set()
+    assert len(c.notes["ties"]) >= 40 and len(same) == len(lb.TIE_GONE)
+    for q, low, high in c.notes["ties"]:
+        assert not ref.seen[q] and ref.seen[low] and ref.seen[high] and low < high and rank[low] < rank[high]
+        assert d2(q, low) == d2(q, high)                                         # an exact tie in fp64 on the fp32-rounded xyz
+        others = np.setdiff1d(np.nonzero(ref.seen & (c.points[:, 0] == 3))[0], [low, high])
+        assert (((xyz[others] - xyz[q]) ** 2).sum(1) > d2(q, low)).all()          # ... and nobody is nearer or as near
+        assert ref.filled_from[q] == low, q
+        if (q, low, high) in same:
+            assert _trip(b, rank[low]) == _trip(b, rank[high]) and rank[high] == rank[low] + 1
+        else:
+            assert rank[high] - rank[low] > lb.FILL_TILE and _trip(b, rank[low]) < _trip(b, rank[high])
+            pairs.add((int(_trip(b, rank[low])), int(_trip(b, rank[high]))))
+            # in space the lower row may lie on either side of the query
+    assert pairs == {(0, 1), (0, 2), (1, 2)}
+    side = {bool(xyz[low, 0] < xyz[q, 0]) for q, low, high in c.notes["ties"] if (q, low, high) not in same}
+    assert side == {True, False}
+
+
+def test_walk_trips_takes_second_trips():
+    c, ref = lb.case("walk_trips"), lb.reference("walk_trips")
+    _reference_structure(c, ref)
+    rows = c.rows_of(1)
+    assert len(rows) > lb.COUNT_TRIP and c.depth is not None
+    per = -(-len(rows) // lb.WALK_PARTS)
+    assert per > 256 and per * (lb.WALK_PARTS - 1) < len(rows) < per * lb.WALK_PARTS          # 64 parts, a short last one
+    vs = c.views_of(1)
+    assert len(vs) == 3
+    first = {}
+    for v in vs:
+        pos = np.searchsorted(rows, ref.lists[int(v)][0])                        # the positions among the entry's sorted rows
+        assert len(pos) == ref.view_count[v] and (pos >= lb.COUNT_TRIP).any()    # visible rows in the count loops' second trip
+        assert (pos % per >= 256).any() and (pos % per < 256).any()              # ... and in the second trip of a part of the walk
+        assert len(np.unique(pos // per)) == lb.WALK_PARTS                       # every part has visible rows
+        first[int(v)] = int((pos < lb.COUNT_TRIP).sum())
+    kept, dropped = [v for v in vs if ref.view_keep[v]], [v for v in vs if not ref.view_keep[v]]
+    assert kept and dropped and c.min_visible == 0 and c.max_visible == lb.WALK_MAX_VISIBLE
+    assert sorted(ref.view_count[vs].tolist()) == [2117, 2149, 2155]
+    for v in dropped:                                                            # dropped by what the second trip counts
+        assert first[int(v)] <= c.max_visible < ref.view_count[v]
+    for v in kept:
+        assert 0 < ref.view_count[v] <= c.max_visible
+    rank, blocks = lb.fill_blocking(c, ref.seen)
+    assert len(blocks) > 50 and max(b["hi"] - b["lo"] for b in blocks if b["lo"] is not None) > 2 * lb.FILL_TILE
+
+
+def test_rows_past_table_lies_on_both_sides_of_the_table_length():
+    c, ref = lb.case("rows_past_table"), lb.reference("rows_past_table")
+    _reference_structure(c, ref)
+    assert c.N == lb.ENTRY_TABLE + 300 and lb.ENTRY_TABLE == 65538
+    assert len(c.views_of(1)) == 0 and len(c.rows_of(1)) == lb.ENTRY_TABLE
+    assert not ref.seen[c.rows_of(1)].any() and (ref.filled_from[c.rows_of(1)] == -1).all() and not ref.features[c.rows_of(1)].any()
+    order = np.argsort(c.points[:, 0], kind="stable")
+    for b in (0, 2):
+        rows = c.rows_of(b)
+        assert len(c.views_of(b)) >= 2 and (rows < lb.ENTRY_TABLE).any() and (rows >= lb.ENTRY_TABLE).any(), b
+        assert ref.seen[rows].any() and (ref.filled_from[rows] >= 0).any(), b
+    # in the sorted order entry 2 lies wholly beyond the table's length: positions the checked copy's table threads do not reach
+    assert (np.nonzero(c.points[order, 0] == 2)[0] >= lb.ENTRY_TABLE).all() and (np.nonzero(c.points[order, 0] == 0)[0] < 256).all()
+    rank, blocks = lb.fill_blocking(c, ref.seen)
+    assert len(blocks) > 256 and sum(b["lo"] is None for b in blocks) > 250
 
 
 # ------------------------------------------------------------------------------------------ sparse.lift's refusals without a GPU

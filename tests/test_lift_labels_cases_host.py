@@ -52,6 +52,30 @@ def test_the_cases_cover_what_they_name():
     assert ll.reference("render").seen.sum() < ll.reference("render").seen.size
 
 
+@pytest.mark.parametrize("name", ll.LARGE)
+def test_the_large_cases_fill_from_voted_which_is_not_seen(name):
+    """The fill of the label vote takes "voted" as its reference mask, the other lifts "seen": on the large geometries the two differ in
+    an entry of more than 256 queries, so the blocks, runs and trips of the fill are not those of tests/lift_batched_cases.py"""
+    import lift_batched_cases as lb
+    assert name not in ll.CASES
+    c, ref, dense = ll.case(name), ll.reference(name), lb.reference(name)
+    assert np.array_equal(c.points, lb.case(name).points) and c.C <= 8 and np.isin(c.labels, c.ignore).mean() > 0.05
+    assert np.array_equal(ref.seen, dense.seen) and np.array_equal(ref.view_count, dense.view_count) and ref.out_of_range == 0
+    voted = ref.voted > 0
+    assert not (voted & ~ref.seen).any()
+    differ = [int(b) for b in c.entries() if (ref.seen & ~voted)[c.rows_of(b)].any() and int((~voted)[c.rows_of(b)].sum()) > 256
+              and voted[c.rows_of(b)].any()]
+    assert differ, "no entry of more than 256 queries in which voted differs from seen"
+    rank, blocks = lb.fill_blocking(c, voted)
+    rank_seen, _ = lb.fill_blocking(c, ref.seen)
+    assert len(blocks) > 1 and max(b["hi"] - b["lo"] for b in blocks if b["lo"] is not None) > lb.FILL_TILE
+    assert not np.array_equal(rank, rank_seen) and not np.array_equal(ref.filled_from, dense.filled_from)
+    assert np.array_equal(ref.voted, ref.votes.sum(1)) and np.all(ref.voted <= ref.count)
+    assert not ref.votes[ref.filled_from >= 0].any() and np.all(ref.labels[~voted & (ref.filled_from < 0)] == c.unlabeled)
+    took = ref.filled_from >= 0
+    assert np.array_equal(ref.labels[took], ref.labels_unfilled[ref.filled_from[took]]) and voted[ref.filled_from[took]].all()
+
+
 def test_vote_ties_half_pixels_and_the_all_ignored_point():
     c, ref = ll.case("ties"), ll.reference("ties")
     row = {n: i for i, n in enumerate(c.notes["row_names"])}

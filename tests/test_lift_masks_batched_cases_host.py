@@ -55,6 +55,23 @@ def test_the_reference_flags_few_near_ties(name):
     assert int(ref.near.sum()) <= near_cap(c)
 
 
+@pytest.mark.parametrize("name", lm.LARGE)
+def test_the_large_cases_flag_few_near_ties_and_share_the_dense_geometry(name):
+    """the large geometries of tests/lift_batched_cases.py (no restatement: it takes minutes there): the same cap on the flags, and the
+    masks, counts and the scene-level fill's choice are the dense reference's -- both fills follow "seen" """
+    import lift_batched_cases as lb
+    assert name not in lm.CASES
+    c, ref, dense = lm.case(name), lm.reference(name), lb.reference(name)
+    print(f"{name}: {int(ref.near.sum())} of {c.N} rows flagged")
+    assert int(ref.near.sum()) <= near_cap(c)
+    assert np.array_equal(ref.seen, dense.seen) and np.array_equal(ref.count, dense.count) and np.array_equal(ref.view_count, dense.view_count)
+    assert np.array_equal(ref.view_keep, dense.view_keep) and np.array_equal(ref.filled_from, dense.filled_from)
+    for v, (rows, x, y, seg, src) in ref.views.items():
+        assert np.array_equal(rows, dense.lists[v][0]) and np.array_equal(x, dense.lists[v][1]) and np.array_equal(y, dense.lists[v][2]), v
+    took = ref.filled_from >= 0
+    assert np.array_equal(ref.features[took], ref.features[ref.filled_from[took]]) and not ref.features[~ref.seen & ~took].any()
+
+
 def test_the_cases_cover_what_they_are_named_for():
     per_entry = lambda c: sorted(len(c.views_of(b)) for b in c.entries())       # noqa: E731
     assert per_entry(lm.case("views_0_1_63")) == [0, 1, 63] and per_entry(lm.case("views_64_65")) == [64, 65]
