@@ -246,6 +246,10 @@ SIGNATURES = {
     "gp_fuse_write": (c_int32, [_P, c_int32, c_int64, _P, c_int64, c_int32, _P, c_size_t, c_int64, _P, c_int32, c_int64, _P, _P, _P]),
     "gp_fuse_dense_workspace_bytes": (c_size_t, [c_int64]),
     "gp_fuse_dense": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gp_render_rows_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "gp_render_rows": (c_int32, [_P, c_int64, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_int32, _P, _P, _P, _P,
+                                 _P, _P, c_size_t, _P]),
+    "gp_render_gather": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int32, c_int64, _P]),
 }
 
 _lib = None

@@ -183,18 +183,7 @@ __global__ void __launch_bounds__(256) fu_offsets_kernel(const int32_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ copy and convert
-template <typename TO, typename TI>
-__device__ __forceinline__ TO fu_cvt(TI x) { return (TO)x; }     // fp32 -> fp16: v_cvt_f16_f32, nearest even, inf on overflow, subnormals kept
-
-template <int VEC, typename T>
-__device__ __forceinline__ void fu_store(T *__restrict__ p, const T (&x)[VEC]) {
-    __builtin_memcpy(__builtin_assume_aligned(p, VEC * sizeof(T)), x, VEC * sizeof(T));
-}
-template <int VEC, typename T>
-__device__ __forceinline__ void fu_load(const T *__restrict__ p, T (&x)[VEC]) {
-    __builtin_memcpy(x, __builtin_assume_aligned(p, VEC * sizeof(T)), VEC * sizeof(T));
-}
-
+// (the conversion gp_cvt and the wide accesses gp_load_vec / gp_store_vec: gp_map_elem.h)
 // One wave per sorted position s.  Lane k < files holds the file's flag and its row inside the file; the source row is loaded once,
 // converted once and stored to every flagged file.  A row outside [0, n) or a destination outside [0, total_rows) -- a state that
 // gp_fuse_plan did not write -- is skipped, never accessed.
@@ -224,14 +213,14 @@ __global__ void __launch_bounds__(256) fu_copy_kernel(const TI *__restrict__ fea
         TO y[VEC];
         if (c < d) {
             TI x[VEC];
-            fu_load<VEC>(src + c, x);
+            gp_load_vec<VEC>(src + c, x);
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) y[i] = fu_cvt<TO>(x[i]);
+            for (int i = 0; i < VEC; ++i) y[i] = gp_cvt<TO>(x[i]);
         }
         for (uint32_t rest = files; rest; rest &= rest - 1) {
             const int k = __ffs(rest) - 1;
             const int64_t dst = base[k] + __shfl(pos, k, 64);
-            if (c < d) fu_store<VEC>(feat + dst * d + c, y);
+            if (c < d) gp_store_vec<VEC>(feat + dst * d + c, y);
         }
     }
 }
@@ -251,14 +240,14 @@ __global__ void __launch_bounds__(256) fu_dense_kernel(const TI *__restrict__ fe
         float y[VEC];
         if (in) {
             TI x[VEC];
-            fu_load<VEC>(src + c, x);
+            gp_load_vec<VEC>(src + c, x);
 #pragma unroll
             for (int i = 0; i < VEC; ++i) y[i] = (float)x[i];
         } else {
 #pragma unroll
             for (int i = 0; i < VEC; ++i) y[i] = 0.f;
         }
-        fu_store<VEC>(dst + c, y);
+        gp_store_vec<VEC>(dst + c, y);
     }
 }
 

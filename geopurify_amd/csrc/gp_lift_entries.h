@@ -1,5 +1,5 @@
 // Shared by every lift over BATCHED point clouds (lift_batched.hip, lift_stream.hip, lift_labels.hip -- whose fill passes the mask
-// "voted" where the others pass "seen" --, lift_masks_batched.hip, lift_masks_stream.hip, render_depth_batched.hip, fuse.hip).
+// "voted" where the others pass "seen" --, lift_masks_batched.hip, lift_masks_stream.hip, render_depth_batched.hip, render_rows.hip, fuse.hip).
 // Device code: the entry tables (rows and views sorted stably by entry, offsets by binary search), the per-view counts with the
 // view-drop rule, and the per-entry scene-level fill (references and queries compacted in the entry-sorted order).  Host code, at the
 // end of the file: the carve struct and the launch sequence of each of these (LbTable with lb_row_table / lb_view_table,

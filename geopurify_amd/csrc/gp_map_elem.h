@@ -25,6 +25,30 @@ __device__ __forceinline__ void gp_load_f32(const T *__restrict__ p, float (&x)[
     for (int i = 0; i < VEC; ++i) x[i] = gp_to_f32(raw[i]);
 }
 
+// The conversions of the kernels that write rows in another element type (fuse.hip, render_rows.hip), each element converted once, to
+// the bits of torch's .to(dtype).  fp32 -> fp16: v_cvt_f16_f32, nearest even, inf on overflow, subnormals kept.
+template <typename TO, typename TI>
+__device__ __forceinline__ TO gp_cvt(TI x) { return (TO)x; }
+// fp32 -> bf16: nearest even on the bit pattern, every NaN the one quiet NaN 0x7FC0 (the integer rounding alone would turn some NaNs
+// into zero or infinity)
+template <>
+__device__ __forceinline__ gp_bf16 gp_cvt<gp_bf16, float>(float x) {
+    const uint32_t u = __float_as_uint(x);
+    gp_bf16 y;
+    y.bits = x != x ? (uint16_t)0x7FC0 : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    return y;
+}
+
+// VEC consecutive elements by ONE access of VEC * sizeof(T) bytes; p is aligned to that many bytes
+template <int VEC, typename T>
+__device__ __forceinline__ void gp_store_vec(T *__restrict__ p, const T (&x)[VEC]) {
+    __builtin_memcpy(__builtin_assume_aligned(p, VEC * sizeof(T)), x, VEC * sizeof(T));
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void gp_load_vec(const T *__restrict__ p, T (&x)[VEC]) {
+    __builtin_memcpy(x, __builtin_assume_aligned(p, VEC * sizeof(T)), VEC * sizeof(T));
+}
+
 inline bool gp_elem_ok(int32_t elem) { return elem == GP_ELEM_F32 || elem == GP_ELEM_F16 || elem == GP_ELEM_BF16; }
 inline size_t gp_elem_size(int32_t elem) { return elem == GP_ELEM_F32 ? 4 : 2; }
 

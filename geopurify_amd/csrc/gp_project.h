@@ -1,5 +1,5 @@
 // Device functions shared by the per-scene kernels (voxelize.hip, lift.hip) and the batched lift (lift_batched.hip): the point ->
-// pixel mapping with its visibility decision, the z-buffer's decision (voxelize.hip, render_depth_batched.hip) and the bilinear tap
+// pixel mapping with its visibility decision, the z-buffer's decision (voxelize.hip, gp_render_depth.h) and the bilinear tap
 // of the LSeg resize.  One definition, so both paths take the same decision and the same bits.
 #pragma once
 #include "gp_common.h"

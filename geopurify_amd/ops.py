@@ -1920,6 +1920,94 @@ def render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, de
     return depth, status
 
 
+# ------------------------------------------------------------------------------------------ lifted clouds rendered back into their views
+RENDER_ROWS_DEPTH = {"none": 0, "maps": 1, "render": 2}      # gp_render_rows' depth_mode
+RENDER_ROWS_MAX_RADIUS = 4
+
+
+def render_rows_workspace_bytes(n, num_views, image_hw, depth_mode):
+    """gp_render_rows_workspace_bytes (no GPU needed): depth_mode "none", "maps" or "render" (the rendered maps live in the workspace)"""
+    H, W = (int(v) for v in image_hw)
+    return int(_lib.load().gp_render_rows_workspace_bytes(int(n), int(num_views), H, W, RENDER_ROWS_DEPTH[depth_mode]))
+
+
+class RenderRows:
+    """What gp_render_rows writes: rows i32 [V,H,W] (-1: no owner), depth f64 [V,H,W] (the owner's p_z, 999999 without one), view_count
+    i64 [V], pixel_count i64 [V], status i64 [8] = (bad batch rows, bad view entries, non-finite rows, top batch, 0, 0, 0, 0)."""
+
+    def __init__(self, rows, depth, view_count, pixel_count, status):
+        self.rows, self.depth, self.view_count, self.pixel_count, self.status = rows, depth, view_count, pixel_count, status
+
+
+def render_rows(points, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=None, vis_thres=0.25, radius=0, buffers=None, workspace=None):
+    """gp_render_rows, no sync: per view and pixel the row of the front-most candidate of the view's entry (visualization.py:34-48 with
+    the nearest point instead of the last; the mapping of fusion_util.py:99-147).  points f64 [n,4]; view_entry i64 [V]; w2c f64
+    [V,4,4]; intrinsics f64 [V,4]; image_hw = (H, W); depth: None (p_z > 0), f64 [V,H,W], or "render" (gp_render_depth_batched's maps,
+    made in the workspace); 0 <= radius <= 4.  -> RenderRows(rows i32 [V,H,W] (-1: no owner), depth f64 [V,H,W] (the owner's p_z,
+    999999 without one), view_count i64 [V], pixel_count i64 [V], status i64 [8] = (bad batch rows, bad view entries, non-finite rows,
+    top batch, 0, 0, 0, 0)).  buffers: optional dict of caller-owned rows / depth / view_count / pixel_count / status; workspace: uint8
+    of at least gp_render_rows_workspace_bytes(n, V, H, W, mode)."""
+    lib = _lib.load()
+    who = "render_rows"
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    n, dev = points.shape[0], points.device
+    nv, H, W, zmin = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, (buffers or {}).get("depth"), dev)
+    buffers = dict(buffers or {}, depth=zmin)
+    if isinstance(depth, str):
+        if depth != "render":
+            raise ValueError(f"{who}: depth={depth!r}: expected None, f64 [{nv}, {H}, {W}] or 'render'")
+        mode, maps = "render", None
+    elif depth is None:
+        mode, maps = "none", None
+    else:
+        mode, maps = "maps", _chk(depth, torch.float64, "depth")
+        if maps.shape != (nv, H, W):
+            raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(maps.shape)}")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= RENDER_ROWS_MAX_RADIUS:
+        raise ValueError(f"{who}: radius={radius!r} must be an integer in 0..{RENDER_ROWS_MAX_RADIUS}")
+    got = _outputs(who, {"rows": (torch.int32, (nv, H, W)), "depth": (torch.float64, (nv, H, W)), "view_count": (torch.int64, (nv,)),
+                         "pixel_count": (torch.int64, (nv,)), "status": (torch.int64, (8,))}, buffers, dev)
+    need = lib.gp_render_rows_workspace_bytes(n, nv, H, W, RENDER_ROWS_DEPTH[mode])
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_render_rows(_ptr(points), n, _ptr(view_entry), _ptr(w2c), _ptr(intrinsics), nv, H, W, int(cut_bound), RENDER_ROWS_DEPTH[mode],
+                             _ptr(maps), float(vis_thres), radius, _ptr(got["rows"]), _ptr(got["depth"]), _ptr(got["view_count"]),
+                             _ptr(got["pixel_count"]), _ptr(got["status"]), _ptr(ws), ws.numel(), _stream()), "gp_render_rows")
+    return RenderRows(got["rows"], got["depth"], got["view_count"], got["pixel_count"], got["status"])
+
+
+def render_gather(rows, src, index=None, dtype=torch.float32, out=None):
+    """gp_render_gather, no sync: out[p] = src[index[rows[p]]] (src[rows[p]] without index) converted once to dtype, a zero row where
+    rows[p] < 0 (and where an index leaves its array).  rows i32 of any shape, contiguous (npix elements); src fp32 [R, D] with unit
+    column stride and any row stride >= D (read in place, no copy); index i64 [n] or None; dtype fp32, fp16 or bf16.  -> out
+    [*rows.shape, D], or the caller's out [npix, D] of that dtype with unit column stride and any row stride >= D."""
+    lib = _lib.load()
+    who = "render_gather"
+    _chk(rows, torch.int32, "rows")
+    if dtype not in ELEM_TAG:
+        raise ValueError(f"{who}: dtype={dtype} must be torch.float32, torch.float16 or torch.bfloat16")
+    if src.dtype != torch.float32 or not src.is_cuda or src.dim() != 2 or min(src.shape) < 1 or src.stride(1) != 1 or src.stride(0) < src.shape[1]:
+        raise ValueError(f"{who}: src must be CUDA fp32 [R >= 1, D >= 1] with unit column stride and a row stride >= D, got "
+                         f"{src.dtype} {list(src.shape)} strides {src.stride() if src.dim() == 2 else None}")
+    npix, (R, D) = rows.numel(), src.shape
+    if npix < 1:
+        raise ValueError(f"{who}: rows is empty")
+    if index is not None and _chk(index, torch.int64, "index").dim() != 1:
+        raise ValueError(f"{who}: expected index [n], got {list(index.shape)}")
+    if out is None:
+        out = torch.empty((npix, D), dtype=dtype, device=src.device)
+        shaped = out.view(*rows.shape, D)
+    else:
+        if out.dtype != dtype or not out.is_cuda or out.shape != (npix, D) or out.stride(1) != 1 or out.stride(0) < D:
+            raise ValueError(f"{who}: out must be CUDA {dtype} [{npix}, {D}] with unit column stride and a row stride >= {D}, got "
+                             f"{out.dtype} {list(out.shape)}")
+        shaped = out
+    check(lib.gp_render_gather(_ptr(rows), npix, _ptr(index), 0 if index is None else index.shape[0], _ptr(src), R, D, src.stride(0),
+                               _ptr(out), ELEM_TAG[dtype], out.stride(0), _stream()), "gp_render_gather")
+    return shaped
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

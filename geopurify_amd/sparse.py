@@ -50,6 +50,15 @@ then train and evaluate from files many times without the VLM)
     chunks.save(out_dir, scene_names)                           # {scene}_{k}.pt, what FusedFeatureLoader loads; chunks.file(b, k): one dict
     feats, mask = load_fused(points, files).dense()             # files back in: fp32 [N,D] (zero rows outside the file), ready for quantize
 
+The chain's end in image space runs the other way, from points back to their views (the reference's visualize_2d_semantic,
+models/utils/visualization.py:15-59, paints 3D predictions into a view; scoring against the loader's label_2ds and pseudo-label or
+purified feature maps for a 2D model need the same): per view and pixel the front-most visible point of the view's entry
+
+    r = render_rows(points, view_entry, world_to_camera, intrinsics, (H, W), depth="render")   # .rows i32 [V,H,W], -1: no owner
+    pred_maps = r.labels(seg.pred, index=q.inverse_mapping)     # per-voxel predictions painted per view, 255 where nothing lands
+    feat_maps = r.features(y.F, index=q.inverse_mapping, dtype=torch.float16, views=slice(0, 8))   # [8,H,W,D], channels last
+    counts = segment_views(r, seg.pred, label_2ds, view_entry, C, index=q.inverse_mapping)        # (I, O, T) per entry, in image space
+
 and the objective the student is trained with (models/affinity_module.py:1099-1136, :1192-1233 for several scenes at once):
 
     pairs = sample_pairs(x.C, teacher)                          # per entry: anchors, their positive, 48 global + 15 local negatives
@@ -95,6 +104,9 @@ drop rule) in one call of ops.lift_labels_batched, one read-back; LiftLabelsStre
 fuse has no counterpart in the reference either (it ships the reader and the writer's settings, config/fusion_scannet.yaml:34-35): ops.fuse_plan
 (entry tables, an exact radix select of each (file, entry)'s threshold key, flags and scans per file), one read-back, ops.fuse_write
 (every row loaded once, converted once, stored to each file that holds it); FusedChunks.dense is ops.fuse_dense.
+render_rows is ops.render_rows (the entry tables, with "render" the z-buffer of render_depth, then two order-free passes of integer
+atomic minima: the bit pattern of p_z, then the row), one read-back; Rendered.features is ops.render_gather, Rendered.labels torch
+indexing on the small maps, segment_views a compaction in torch around ops.iou_hist_batched.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -351,6 +363,201 @@ def _render_chunk(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, w
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
     d, _ = ops.render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=depth[:V * H * W].view(V, H, W), workspace=workspace)
     return d, depth, workspace
+
+
+# ------------------------------------------------------------------------------------------ the chain's end in image space
+RENDER_FAR = 999999.0                                       # Rendered.depth where a pixel has no owner (render_depth's value)
+
+
+class Rendered:
+    """What render_rows returns: rows i32 [V,H,W] (the owner's row of points, -1 where nothing covers the pixel), depth fp64 [V,H,W]
+    (the owner's p_z, 999999 where rows == -1), view_count i64 [V] (candidates per view: lift's view_count on the same geometry and
+    options), pixel_count i64 [V] (pixels with an owner), num_entries (1 + the highest valid batch index), image_shape = (H, W),
+    num_points (N: what an index must be long)."""
+
+    def __init__(self, rows, depth, view_count, pixel_count, num_entries, image_shape, num_points):
+        self.rows, self.depth, self.view_count, self.pixel_count = rows, depth, view_count, pixel_count
+        self.num_entries, self.image_shape, self.num_points = num_entries, image_shape, num_points
+
+    def _index(self, who, index, device):
+        if index is None:
+            return None
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.shape != (self.num_points,):
+            raise ValueError(f"{who}: index must be an int64 tensor [{self.num_points}] (point -> row, e.g. a quantiser's inverse_mapping), got "
+                             f"{(list(index.shape), index.dtype) if torch.is_tensor(index) else type(index).__name__}")
+        if index.device != device:
+            raise ValueError(f"{who}: index is on {index.device}, the rendered rows on {device}")
+        return index.detach().contiguous()
+
+    def labels(self, point_labels, *, fill=255, index=None):
+        """Per-point (or, through index, per-row) integer labels painted into the views: -> [V,H,W] of point_labels' dtype, the value
+        point_labels[index[rows]] (point_labels[rows] without index) at owned pixels and fill where rows == -1.  index: i64 [N], point
+        -> row of point_labels (a quantiser's inverse_mapping, so per-voxel predictions render directly).  Torch indexing: the maps are
+        small."""
+        who = "Rendered.labels"
+        if not _is_int_tensor(point_labels) or point_labels.dim() != 1 or point_labels.shape[0] < 1:
+            raise ValueError(f"{who}: point_labels must be an integer tensor [R >= 1], got "
+                             f"{(list(point_labels.shape), point_labels.dtype) if torch.is_tensor(point_labels) else type(point_labels).__name__}")
+        if isinstance(fill, bool) or not isinstance(fill, int):
+            raise ValueError(f"{who}: fill={fill!r} must be an integer")
+        index = self._index(who, index, self.rows.device)
+        if index is None and point_labels.shape[0] != self.num_points:
+            raise ValueError(f"{who}: {point_labels.shape[0]} labels for {self.num_points} points (pass index for labels per row)")
+        if point_labels.device != self.rows.device:
+            raise ValueError(f"{who}: point_labels is on {point_labels.device}, the rendered rows on {self.rows.device}")
+        owned = self.rows >= 0
+        at = self.rows.clamp(min=0).to(torch.int64)
+        if index is not None:
+            at = index[at]
+        return torch.where(owned, point_labels.detach()[at], torch.full((), fill, dtype=point_labels.dtype, device=owned.device))
+
+    def features(self, rows_features, *, index=None, dtype=torch.float32, views=None):
+        """Per-point (or, through index, per-row) features painted into the views: -> [V',H,W,D], channels last, in fp32, fp16 or bf16.
+        A pixel holds the row rows_features[index[rows]] (rows_features[rows] without index) of its owner, every element converted once
+        with the rounding of torch's .to(dtype) (fp32 -> fp16 / bf16: to nearest even, overflow to inf, half subnormals kept; the
+        conversion fuse states); pixels without an owner are zero rows.  rows_features: fp32 [R,D] on the GPU with unit column stride
+        and any row stride >= D -- y.F straight from purify -- read in place: no per-point [N,D] copy is made.  views: a slice or an
+        integer index tensor selecting the views to materialise (the full map is V * H * W * D elements).  Inside: ops.render_gather
+        (one wave per pixel, or several pixels per wave for narrow rows; 16-byte loads where D's pitch and the base allow)."""
+        who = "Rendered.features"
+        if dtype not in ops.ELEM_TAG:
+            raise ValueError(f"{who}: dtype={dtype} must be torch.float32, torch.float16 or torch.bfloat16")
+        Fr = rows_features
+        if not torch.is_tensor(Fr) or Fr.dim() != 2 or min(Fr.shape) < 1 or Fr.dtype != torch.float32:
+            raise ValueError(f"{who}: rows_features must be fp32 [R, D] with R, D >= 1, got "
+                             f"{(list(Fr.shape), Fr.dtype) if torch.is_tensor(Fr) else type(Fr).__name__}")
+        index = self._index(who, index, self.rows.device)
+        if index is None and Fr.shape[0] != self.num_points:
+            raise ValueError(f"{who}: {Fr.shape[0]} feature rows for {self.num_points} points (pass index for features per row)")
+        if not (views is None or isinstance(views, slice) or (_is_int_tensor(views) and views.dim() == 1)):
+            raise ValueError(f"{who}: views must be None, a slice or a 1-D integer index tensor, got {type(views).__name__}")
+        if not Fr.is_cuda or not self.rows.is_cuda or Fr.device != self.rows.device:
+            raise ValueError(f"{who}: rows_features and the rendered rows must be CUDA tensors on one device (got {Fr.device} / "
+                             f"{self.rows.device}); there is no CPU path")
+        rows = self.rows if views is None else self.rows[views]
+        H, W = self.image_shape
+        D = Fr.shape[1]
+        with torch.cuda.device(Fr.device), torch.no_grad():
+            if rows.shape[0] == 0:
+                return torch.zeros((0, H, W, D), dtype=dtype, device=Fr.device)
+            src = Fr.detach()
+            if src.stride(1) != 1 or src.stride(0) < D:
+                src = src.contiguous()
+            return ops.render_gather(rows.contiguous(), src, index, dtype)
+
+
+def render_rows(points, view_entry, world_to_camera, intrinsics, image_shape, *, depth=RENDER, cut_bound=0, vis_thres=0.25, radius=0):
+    """The chain's end in image space: per view and pixel, the row of the front-most visible point of the view's entry -- what the
+    reference's visualize_2d_semantic (models/utils/visualization.py:15-59) paints a view with, except that there the last point in
+    row order that maps to a pixel wins and here the nearest does.  For all views of all entries in one call, entries never mixing.
+    points, view_entry, world_to_camera and intrinsics exactly as render_depth and lift take them (points fp64 or fp32 [N,4], upcast
+    to fp64 first; V views); image_shape = (H, W).  depth: None (p_z > 0 alone, no occlusion), fp64 [V,H,W] (sensor depth), or
+    "render" (the maps render_depth makes from the entry's own points with the same cut_bound).  radius: an integer in 0..4.
+      Candidates.  A point p of view v's entry is a candidate of v when (a) it projects inside [cut_bound, W - cut_bound) x
+        [cut_bound, H - cut_bound) (pixels rounded half to even) and |depth - p_z| <= vis_thres * depth there (without depths: p_z > 0)
+        -- lift's rule 1, so the candidates of a view are exactly the pairs lift counts in view_count -- and (b) p_z > 0.  For depth
+        maps > 0 and 0 <= vis_thres < 1 (b) is implied; it is tested regardless, because the minimum below orders doubles by their bit
+        pattern and that ordering holds only for positive values.
+      Footprint.  A candidate covers the pixels of the square of side 2 * radius + 1 centred on its own pixel (vi, ui), clipped to
+        [cut, H - cut) x [cut, W - cut).  radius = 0 is the reference's one-pixel projection.
+      Owner.  A pixel's owner is the covering candidate with the smallest p_z (fp64, the value the lifts compute); among equal p_z
+        the lowest row of points wins.  Entries never mix.  (A candidate farther than 999999 owns nothing.)
+    -> Rendered: rows i32 [V,H,W] (the owner's row, -1 where nothing covers the pixel), depth fp64 [V,H,W] (the owner's p_z, 999999
+    where rows == -1), view_count i64 [V] (candidates per view; equals lift's view_count on the same geometry and options),
+    pixel_count i64 [V] (pixels with an owner), num_entries (1 + the highest valid batch index, from the status words), image_shape.
+    A view whose entry has no points is all -1 / 999999.  Exact and reproducible: the owner is found by two order-free passes of
+    integer atomic minima (the bit pattern of p_z, then the row where the pixel holds the candidate's own p_z), so two calls give the
+    same bits, in any row order.  No stream class: views are independent, so a caller renders chunk by chunk and concatenates.  No
+    gradients, no blending: everything is a selection.
+    Inside: ops.render_rows (the entry tables, with "render" the z-buffer of render_depth in its workspace, two fills, two passes, a
+    finalise kernel).  ValueError before any kernel: render_depth's refusals for the shared fields, a depth string other than
+    "render", a depth of the wrong shape or dtype, a radius outside 0..4, CPU tensors (there is no CPU path); from the ONE status
+    read-back, with render_depth's messages and precedence: non-finite rows, rows whose batch index is no integer in 0..65535, views
+    whose entry is outside 0..65535."""
+    who = "render_rows"
+    P, E, M, K = points, view_entry, world_to_camera, intrinsics
+    _check_points(who, P)
+    if not _is_int_tensor(E) or E.dim() != 1 or E.shape[0] < 1:
+        raise ValueError(f"{who}: view_entry must be an integer tensor [V] with V >= 1, got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    V = E.shape[0]
+    if V > 65535:
+        raise ValueError(f"{who}: {V} views, at most 65535")
+    _check_poses(who, "", V, E, M, K)
+    shape = tuple(image_shape) if isinstance(image_shape, (tuple, list)) else ()
+    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+        raise ValueError(f"{who}: image_shape must be (H, W), two positive integers, got {image_shape!r}")
+    H, W = shape
+    _check_depth(who, depth, V, H, W)
+    _check_visibility_options(who, cut_bound, vis_thres, 0, None)
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= ops.RENDER_ROWS_MAX_RADIUS:
+        raise ValueError(f"{who}: radius={radius!r} must be an integer in 0..{ops.RENDER_ROWS_MAX_RADIUS}")
+    tensors = [P, E, M, K] + ([depth] if torch.is_tensor(depth) else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
+        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    with torch.cuda.device(P.device), torch.no_grad():
+        r = ops.render_rows(P.detach().to(torch.float64).contiguous(), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(),
+                            K.detach().contiguous(), shape, cut_bound, depth=depth.detach().contiguous() if torch.is_tensor(depth) else depth,
+                            vis_thres=float(vis_thres), radius=radius)
+        bad_batch, bad_view, nonfinite, top = ops.readback(r.status)[:4]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    return Rendered(r.rows, r.depth, r.view_count, r.pixel_count, top + 1, shape, P.shape[0])
+
+
+def segment_views(rendered, pred, label_maps, view_entry, num_classes, *, ignore_labels=(255,), index=None):
+    """3D predictions scored against 2D ground truth in image space: the (intersection, output, target) counts of segment, taken over
+    the owned pixels of rendered (a Rendered) whose 2D label is not ignored, separated by the view's entry.  pred: integer [N] per
+    point, or [R] per row with index i64 [N] (point -> row, a quantiser's inverse_mapping); label_maps: uint8, int16, int32 or int64
+    [V,H,W], as lift_labels takes them; view_entry: integer [V], the one render_rows was given; num_classes in 1..4096; at most 4
+    ignore labels.  A pixel with prediction p and label t counts in [entry, 1, p] when 0 <= p < C, in [entry, 2, t] when 0 <= t < C,
+    and in [entry, 0, p] when both hold and p == t.  -> counts i64 [num_entries, 3, C].  Inside: the owned pixels compacted in torch,
+    then ops.iou_hist_batched (integer atomics: exact in any order)."""
+    who = "segment_views"
+    if not isinstance(rendered, Rendered):
+        raise ValueError(f"{who}: rendered must be a Rendered, got {type(rendered).__name__}")
+    V, (H, W), dev = rendered.rows.shape[0], rendered.image_shape, rendered.rows.device
+    if not _is_int_tensor(pred) or pred.dim() != 1 or pred.shape[0] < 1:
+        raise ValueError(f"{who}: pred must be an integer tensor [R >= 1], got {(list(pred.shape), pred.dtype) if torch.is_tensor(pred) else type(pred).__name__}")
+    if not torch.is_tensor(label_maps) or label_maps.dtype not in ops.LABEL_TAG or label_maps.shape != (V, H, W):
+        raise ValueError(f"{who}: label_maps must be uint8, int16, int32 or int64 [{V}, {H}, {W}], got "
+                         f"{(list(label_maps.shape), label_maps.dtype) if torch.is_tensor(label_maps) else type(label_maps).__name__}")
+    if not _is_int_tensor(view_entry) or view_entry.shape != (V,):
+        raise ValueError(f"{who}: view_entry must be an integer tensor [{V}], got "
+                         f"{(list(view_entry.shape), view_entry.dtype) if torch.is_tensor(view_entry) else type(view_entry).__name__}")
+    if not _is_count(num_classes, 1) or num_classes > 4096:
+        raise ValueError(f"{who}: num_classes={num_classes!r} must be an integer in 1..4096")
+    ignore = [int(v) for v in ignore_labels]
+    if len(ignore) > 4:
+        raise ValueError(f"{who}: at most 4 ignore labels, got {ignore}")
+    index = rendered._index(who, index, dev)
+    if index is None and pred.shape[0] != rendered.num_points:
+        raise ValueError(f"{who}: {pred.shape[0]} predictions for {rendered.num_points} points (pass index for predictions per row)")
+    B = rendered.num_entries
+    if B * 3 * num_classes > 2 ** 27:
+        raise ValueError(f"{who}: {B} entries x 3 x {num_classes} classes exceed 2^27 counters")
+    tensors = [rendered.rows, pred, label_maps, view_entry]
+    if not all(t.is_cuda for t in tensors) or any(t.device != dev for t in tensors):
+        raise ValueError(f"{who}: the rendered rows, pred, label_maps and view_entry must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    with torch.cuda.device(dev), torch.no_grad():
+        counts = torch.zeros((B, 3, num_classes), dtype=torch.int64, device=dev)
+        owned = (rendered.rows >= 0).reshape(-1)
+        at = rendered.rows.reshape(-1)[owned].to(torch.int64)                # pixel -> point
+        if at.shape[0] == 0:
+            return counts
+        if index is not None:
+            at = index[at]                                                   # point -> row
+        coords = torch.zeros((at.shape[0], 4), dtype=torch.int32, device=dev)
+        coords[:, 0] = view_entry.detach().to(torch.int32).view(V, 1).expand(V, H * W).reshape(-1)[owned]
+        ops.iou_hist_batched(pred.detach().to(torch.int64)[at].contiguous(), coords, label_maps.detach().reshape(-1)[owned].to(torch.int64).contiguous(),
+                             B, num_classes, ignore, counts)
+    return counts
 
 
 def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):

@@ -1253,6 +1253,44 @@ int gp_fuse_dense(const double *points, int64_t n, const uint8_t *mask_full, con
                   int64_t feat_rows, int64_t d, float *out, int64_t *status, void *workspace, size_t workspace_bytes,
                   void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Lifted BATCHED point clouds rendered back into their views: per view and pixel the row of the       */
+/* front-most visible point of the view's entry (what models/utils/visualization.py:34-48 paints a    */
+/* view with, where the last point in row order wins: here the nearest), decided with the mapping of   */
+/* models/utils/fusion_util.py:99-147, and the gather that turns that index map into feature maps.     */
+/* Points, entries, views, poses and cut_bound are worded as in gp_render_depth_batched.               */
+/* depth_mode 0: no depth maps (a point is visible where it projects inside the cut bound with         */
+/* p_z > 0), depth NULL; 1: depth f64 [nviews,height,width], the depth argument of gp_lift_batched;    */
+/* 2: the maps gp_render_depth_batched makes from these points, rendered into the workspace, depth     */
+/* NULL.  A point of view v's entry is a candidate of v when gp_lift_batched would count it in         */
+/* view_count[v] (|depth - p_z| <= vis_thres * depth at its pixel, or p_z > 0 without maps) and        */
+/* p_z > 0.  It covers the square of side 2 * radius + 1 (0 <= radius <= 4) centred on its pixel,      */
+/* clipped to [cut_bound, height - cut_bound) x [cut_bound, width - cut_bound).  A pixel's owner is    */
+/* the covering candidate with the smallest p_z (fp64), among equal p_z the lowest row.                */
+/*   rows i32 [nviews,height,width]: the owner's row, -1 where nothing covers the pixel;               */
+/*   zmin f64 [nviews,height,width] (8-byte aligned): the owner's p_z, 999999 where rows is -1;        */
+/*   view_count i64 [nviews]: candidates per view (gp_lift_batched's view_count on the same            */
+/*     geometry); pixel_count i64 [nviews]: pixels with an owner;                                      */
+/*   status i64 [8]: [0]..[3] as gp_render_depth_batched.  Rows counted in [0] are never rendered,     */
+/*     the images of a view counted in [1] stay -1 / 999999.                                           */
+/* Two order-free passes (a 64-bit unsigned atomic minimum on the bit pattern of p_z, then a 32-bit    */
+/* atomic minimum of the row where the pixel holds the candidate's own p_z): integer minima and sums   */
+/* only, so two calls give the same bits in any row order.                                             */
+/* gp_render_gather: out [npix, ld_out >= d] of element type elem_out (GP_ELEM_F32 / _F16 / _BF16):    */
+/* out[p] = src[index ? index[rows[p]] : rows[p]] converted once (fp16 and bf16: nearest even, every    */
+/* bf16 NaN 0x7FC0), a zero row where rows[p] < 0 -- or where rows[p] >= n_index or the source row is   */
+/* outside 0..nrows-1, which are never accessed.  rows i32 [npix]; index i64 [n_index] or NULL with    */
+/* n_index 0; src fp32 [nrows, ld_src >= d].  Rows whose bases and pitches are multiples of 4 elements */
+/* move 16 bytes per load.  1 <= n < 2^31, 1 <= nviews <= 65535; npix, nrows, d >= 1.  No output may   */
+/* overlap an input or another output (GP_EINVAL).                                                     */
+size_t gp_render_rows_workspace_bytes(int64_t n, int32_t nviews, int32_t height, int32_t width, int32_t depth_mode);
+int gp_render_rows(const double *points, int64_t n, const int64_t *view_entry, const double *w2c, const double *intrinsics,
+                   int32_t nviews, int32_t height, int32_t width, int32_t cut_bound, int32_t depth_mode, const double *depth,
+                   double vis_thres, int32_t radius, int32_t *rows, double *zmin, int64_t *view_count, int64_t *pixel_count,
+                   int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int gp_render_gather(const int32_t *rows, int64_t npix, const int64_t *index, int64_t n_index, const float *src,
+                     int64_t nrows, int64_t d, int64_t ld_src, void *out, int32_t elem_out, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
