@@ -1504,6 +1504,25 @@ def _chk_elem(t, name):
     return ELEM_TAG[t.dtype]
 
 
+def _chk_points(who, points):
+    """points f64 [n >= 1, 4], contiguous on the GPU -> (n, their device)"""
+    _chk(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    return points.shape[0], points.device
+
+
+def _chk_views(who, nv, view_entry, w2c, intrinsics, depth=None, image_hw=None):
+    """the arrays of nv views as every batched lift, vote and render takes them: view_entry i64 [nv], w2c f64 [nv,4,4], intrinsics f64
+    [nv,4] and, where the caller has one, depth f64 [nv,H,W] with image_hw = (H, W); all contiguous on the GPU"""
+    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
+    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
+        raise ValueError(f"{who}: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
+                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, int(image_hw[0]), int(image_hw[1])):
+        raise ValueError(f"{who}: expected depth [{nv}, {image_hw[0]}, {image_hw[1]}], got {list(depth.shape)}")
+
+
 def lift_batched_col_chunk():
     """channels one pass of gp_lift_batched's lift kernel holds in registers (asked of the library)"""
     return int(_lib.load().gp_lift_batched_col_chunk())
@@ -1542,31 +1561,20 @@ def lift_batched(points, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, im
     caller-owned outputs by attribute name (out: fp32 rows of any pitch); workspace: uint8 of at least
     gp_lift_batched_workspace_bytes(n, V)."""
     lib = _lib.load()
-    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry")
+    who = "lift_batched"
+    _chk(points, torch.float64, "points")
     elem = _chk_elem(maps_pm, "maps_pm")
-    _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     (h, w), (H, W) = map_hw, image_hw
     n, dev = points.shape[0], points.device
     if points.dim() != 2 or points.shape[1] != 4 or maps_pm.dim() != 3 or maps_pm.shape[1] != h * w:
-        raise ValueError(f"lift_batched: expected points [n, 4] and maps_pm [V, {h * w}, D], got {list(points.shape)}, {list(maps_pm.shape)}")
+        raise ValueError(f"{who}: expected points [n, 4] and maps_pm [V, {h * w}, D], got {list(points.shape)}, {list(maps_pm.shape)}")
     nv, _, d = maps_pm.shape
-    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
-        raise ValueError(f"lift_batched: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
-                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
-    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
-        raise ValueError(f"lift_batched: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    _chk_views(who, nv, view_entry, w2c, intrinsics, depth, image_hw)
     want = {"seen": (torch.uint8, (n,)), "count": (torch.int32, (n,)), "view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,)),
             "status": (torch.int64, (8,))}
     if fill:
         want["nn"] = (torch.int64, (n,))
-    got = {}
-    for name, (dtype, shape) in want.items():
-        t = (buffers or {}).get(name)
-        if t is None:
-            t = torch.empty(shape, dtype=dtype, device=dev)
-        elif _chk(t, dtype, name).shape != shape:
-            raise ValueError(f"lift_batched: expected {name} {list(shape)}, got {list(t.shape)}")
-        got[name] = t
+    got = _outputs(who, want, buffers, dev)
     out = (buffers or {}).get("out")
     out = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else _rows(out, "out", n, d)
     need = lib.gp_lift_batched_workspace_bytes(n, nv)
@@ -1594,10 +1602,9 @@ def lift_stream_begin(points, d, buffers=None, workspace=None):
     dict of caller-owned state / sums / count / status (state: uint8 of at least gp_lift_stream_state_bytes(n); sums: fp32 rows of any
     pitch); workspace: uint8 of at least gp_lift_stream_begin_workspace_bytes(n)."""
     lib = _lib.load()
-    _chk(points, torch.float64, "points")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1 or int(d) < 1:
-        raise ValueError(f"lift_stream_begin: expected points [n >= 1, 4] and d >= 1, got {list(points.shape)}, d={d}")
-    n, dev, d = points.shape[0], points.device, int(d)
+    (n, dev), d = _chk_points("lift_stream_begin", points), int(d)
+    if d < 1:
+        raise ValueError(f"lift_stream_begin: expected d >= 1, got d={d}")
     got = _outputs("lift_stream_begin", {"count": (torch.int32, (n,)), "status": (torch.int64, (8,))}, buffers, dev)
     state = (buffers or {}).get("state")
     state = _ws(lib.gp_lift_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")
@@ -1625,17 +1632,12 @@ def lift_stream_add(st, maps_pm, map_hw, view_entry, w2c, intrinsics, depth, ima
     lib = _lib.load()
     who = "lift_stream_add"
     elem = _chk_elem(maps_pm, "maps_pm")
-    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     (h, w), (H, W) = map_hw, image_hw
     n, d, dev = st.points.shape[0], st.sums.shape[1], st.points.device
     if maps_pm.dim() != 3 or maps_pm.shape[1] != h * w or maps_pm.shape[2] != d:
         raise ValueError(f"{who}: expected maps_pm [V, {h * w}, {d}], got {list(maps_pm.shape)}")
     nv = maps_pm.shape[0]
-    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
-        raise ValueError(f"{who}: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
-                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
-    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
-        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    _chk_views(who, nv, view_entry, w2c, intrinsics, depth, image_hw)
     got = _outputs(who, {"view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,))}, buffers, dev)
     ws = _ws(lib.gp_lift_stream_add_workspace_bytes(nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
     check(lib.gp_lift_stream_add_t(_ptr(st.points), n, _ptr(st.state), st.state.numel(), _ptr(maps_pm), elem, d, int(h), int(w), _ptr(view_entry),
@@ -1698,15 +1700,10 @@ def _ignore_ids(who, ignore_ids):
 def _label_views(who, labels2d, view_entry, w2c, intrinsics, depth):
     """the views' arrays of a label vote, checked -> (elem, V, H, W)"""
     elem = _chk_labels(labels2d, "labels2d")
-    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     if labels2d.dim() != 3 or min(labels2d.shape) < 1:
         raise ValueError(f"{who}: expected labels2d [V, H, W], got {list(labels2d.shape)}")
     nv, H, W = labels2d.shape
-    if view_entry.shape != (nv,) or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
-        raise ValueError(f"{who}: expected view_entry [{nv}], w2c [{nv}, 4, 4], intrinsics [{nv}, 4], got {list(view_entry.shape)}, "
-                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
-    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
-        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    _chk_views(who, nv, view_entry, w2c, intrinsics, depth, (H, W))
     return elem, nv, H, W
 
 
@@ -1731,10 +1728,7 @@ def lift_labels_batched(points, labels2d, num_classes, view_entry, w2c, intrinsi
     outputs by attribute name (votes: int32 rows of any pitch); workspace: uint8 of at least gp_lift_labels_batched_workspace_bytes(n, V)."""
     lib = _lib.load()
     who = "lift_labels_batched"
-    _chk(points, torch.float64, "points")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
-        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
-    n, dev, C = points.shape[0], points.device, int(num_classes)
+    (n, dev), C = _chk_points(who, points), int(num_classes)
     elem, nv, H, W = _label_views(who, labels2d, view_entry, w2c, intrinsics, depth)
     if not 1 <= C <= LIFT_LABELS_MAX_CLASSES:
         raise ValueError(f"{who}: num_classes={num_classes} outside 1..{LIFT_LABELS_MAX_CLASSES}")
@@ -1792,12 +1786,9 @@ def lift_labels_stream_begin(points, num_classes, buffers=None, workspace=None):
     gp_lift_labels_stream_begin_workspace_bytes(n)."""
     lib = _lib.load()
     who = "lift_labels_stream_begin"
-    _chk(points, torch.float64, "points")
-    C = int(num_classes)
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1 or not 1 <= C <= LIFT_LABELS_MAX_CLASSES:
-        raise ValueError(f"{who}: expected points [n >= 1, 4] and num_classes in 1..{LIFT_LABELS_MAX_CLASSES}, got {list(points.shape)}, "
-                         f"num_classes={num_classes}")
-    n, dev = points.shape[0], points.device
+    (n, dev), C = _chk_points(who, points), int(num_classes)
+    if not 1 <= C <= LIFT_LABELS_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes={num_classes} outside 1..{LIFT_LABELS_MAX_CLASSES}")
     got = _outputs(who, {"count": (torch.int32, (n,)), "status": (torch.int64, (8,))}, buffers, dev)
     state = (buffers or {}).get("state")
     state = _ws(lib.gp_lift_labels_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")
@@ -1858,18 +1849,15 @@ def lift_labels_stream_finish(st, unlabeled=255, fill=True, buffers=None, worksp
 # ------------------------------------------------------------------------------------------ rendered depth over batched point clouds
 def _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev):
     """the views' arrays of a rendered-depth call, checked -> (V, H, W, depth f64 [V,H,W])"""
-    _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c"), _chk(intrinsics, torch.float64, "intrinsics")
     H, W = (int(v) for v in image_hw)
-    if view_entry.dim() != 1 or view_entry.shape[0] < 1 or w2c.shape != (view_entry.shape[0], 4, 4) or intrinsics.shape != (view_entry.shape[0], 4):
-        raise ValueError(f"{who}: expected view_entry [V >= 1], w2c [V, 4, 4], intrinsics [V, 4], got {list(view_entry.shape)}, "
-                         f"{list(w2c.shape)}, {list(intrinsics.shape)}")
+    if view_entry.dim() != 1 or view_entry.shape[0] < 1:
+        raise ValueError(f"{who}: expected view_entry [V >= 1], got {list(view_entry.shape)}")
     nv = view_entry.shape[0]
     if H < 1 or W < 1 or int(cut_bound) < 0:
         raise ValueError(f"{who}: expected image_hw = (H, W) >= 1 and cut_bound >= 0, got {tuple(image_hw)}, {cut_bound}")
+    _chk_views(who, nv, view_entry, w2c, intrinsics, depth, (H, W))
     if depth is None:
         depth = torch.empty((nv, H, W), dtype=torch.float64, device=dev)
-    elif _chk(depth, torch.float64, "depth").shape != (nv, H, W):
-        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
     return nv, H, W, depth
 
 
@@ -1884,10 +1872,7 @@ def render_depth_batched(points, view_entry, w2c, intrinsics, image_hw, cut_boun
     optional caller-owned outputs; workspace: uint8 of at least gp_render_depth_batched_workspace_bytes(n, V)."""
     lib = _lib.load()
     who = "render_depth_batched"
-    _chk(points, torch.float64, "points")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
-        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
-    n, dev = points.shape[0], points.device
+    n, dev = _chk_points(who, points)
     nv, H, W, depth = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev)
     status = _outputs(who, {"status": (torch.int64, (8,))}, {"status": status}, dev)["status"]
     ws = _ws(lib.gp_render_depth_batched_workspace_bytes(n, nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
@@ -1907,10 +1892,8 @@ def render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, de
     least gp_render_depth_batched_state_workspace_bytes(n, V)."""
     lib = _lib.load()
     who = "render_depth_stream"
-    points, state = _chk(st.points, torch.float64, "points"), _chk(st.state, torch.uint8, "state")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
-        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
-    n, dev = points.shape[0], points.device
+    points, state = st.points, _chk(st.state, torch.uint8, "state")
+    n, dev = _chk_points(who, points)
     nv, H, W, depth = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, dev)
     status = _outputs(who, {"status": (torch.int64, (8,))}, {"status": status}, dev)["status"]
     ws = _ws(lib.gp_render_depth_batched_state_workspace_bytes(n, nv), dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
@@ -1949,10 +1932,7 @@ def render_rows(points, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=
     of at least gp_render_rows_workspace_bytes(n, V, H, W, mode)."""
     lib = _lib.load()
     who = "render_rows"
-    _chk(points, torch.float64, "points")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
-        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
-    n, dev = points.shape[0], points.device
+    n, dev = _chk_points(who, points)
     nv, H, W, zmin = _render_views(who, view_entry, w2c, intrinsics, image_hw, cut_bound, (buffers or {}).get("depth"), dev)
     buffers = dict(buffers or {}, depth=zmin)
     if isinstance(depth, str):
@@ -2044,15 +2024,12 @@ def lift_masks_batched_lists(points, view_entry, w2c, intrinsics, depth, image_h
     total); workspace: uint8 of at least gp_lift_masks_batched_lists_workspace_bytes(n, V)."""
     lib = _lib.load()
     who = "lift_masks_batched_lists"
-    _chk(points, torch.float64, "points"), _chk(view_entry, torch.int64, "view_entry"), _chk(w2c, torch.float64, "w2c")
-    _chk(intrinsics, torch.float64, "intrinsics")
+    _chk(points, torch.float64, "points")
     H, W = image_hw
     n, nv, dev = points.shape[0], view_entry.shape[0], points.device
-    if points.dim() != 2 or points.shape[1] != 4 or view_entry.dim() != 1 or w2c.shape != (nv, 4, 4) or intrinsics.shape != (nv, 4):
-        raise ValueError(f"{who}: expected points [n, 4], view_entry [V], w2c [V, 4, 4], intrinsics [V, 4], got {list(points.shape)}, "
-                         f"{list(view_entry.shape)}, {list(w2c.shape)}, {list(intrinsics.shape)}")
-    if depth is not None and _chk(depth, torch.float64, "depth").shape != (nv, H, W):
-        raise ValueError(f"{who}: expected depth [{nv}, {H}, {W}], got {list(depth.shape)}")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError(f"{who}: expected points [n, 4], got {list(points.shape)}")
+    _chk_views(who, nv, view_entry, w2c, intrinsics, depth, image_hw)
     got = _outputs(who, {"view_off": (torch.int64, (nv + 1,)), "view_count": (torch.int64, (nv,)), "view_keep": (torch.uint8, (nv,)),
                          "status": (torch.int64, (8,))}, buffers, dev)
     need = lib.gp_lift_masks_batched_lists_workspace_bytes(n, nv)
@@ -2159,10 +2136,7 @@ def lift_masks_stream_begin(points, buffers=None, workspace=None):
     """gp_lift_masks_stream_begin, no sync: points f64 [n,4] -> LiftMasksStreamState.  buffers: optional dict of caller-owned state (uint8
     of at least gp_lift_masks_stream_state_bytes(n)) / status; workspace: uint8 of at least gp_lift_masks_stream_begin_workspace_bytes(n)."""
     lib = _lib.load()
-    _chk(points, torch.float64, "points")
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
-        raise ValueError(f"lift_masks_stream_begin: expected points [n >= 1, 4], got {list(points.shape)}")
-    n, dev = points.shape[0], points.device
+    n, dev = _chk_points("lift_masks_stream_begin", points)
     got = _outputs("lift_masks_stream_begin", {"status": (torch.int64, (8,))}, buffers, dev)
     state = (buffers or {}).get("state")
     state = _ws(lib.gp_lift_masks_stream_state_bytes(n), dev) if state is None else _chk(state, torch.uint8, "state")

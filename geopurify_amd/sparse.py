@@ -263,6 +263,92 @@ def _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visibl
         raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
 
 
+def _check_view_count(who, V):
+    if V > 65535:
+        raise ValueError(f"{who}: {V} views, at most 65535")
+
+
+def _image_shape(who, name, given, shape, tail=""):
+    """shape, the caller's reading of the image_shape it was `given`, as (H, W); tail: what the caller's message says about the pair"""
+    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
+        raise ValueError(f"{who}: {name}image_shape must be (H, W), two positive integers{tail}, got {given!r}")
+    return shape
+
+
+def _check_one_device(who, subject, tensors):
+    """the last check of every member: all on the GPU of the first (the points)"""
+    if not all(t.is_cuda for t in tensors) or any(t.device != tensors[0].device for t in tensors):
+        raise ValueError(f"{who}: {subject} must be CUDA tensors on one device (got "
+                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+
+
+def _check_render_views(who, P, E, M, K, image_shape):
+    """what render_depth and render_rows check first: the points, the bare view_entry / world_to_camera / intrinsics and image_shape
+    -> (V, (H, W))"""
+    _check_points(who, P)
+    if not _is_int_tensor(E) or E.dim() != 1 or E.shape[0] < 1:
+        raise ValueError(f"{who}: view_entry must be an integer tensor [V] with V >= 1, got "
+                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
+    V = E.shape[0]
+    _check_view_count(who, V)
+    _check_poses(who, "", V, E, M, K)
+    return V, _image_shape(who, "", image_shape, tuple(image_shape) if isinstance(image_shape, (tuple, list)) else ())
+
+
+# what every member hands to its ops call: written once
+def _points64(P):
+    return P.detach().to(torch.float64).contiguous()
+
+
+def _view_args(E, M, K, Dp=None, render=None):
+    """-> (view_entry i64, world_to_camera, intrinsics, depth), contiguous and detached.  depth: the tensor, None, or for the string
+    "render" what render(view_entry, world_to_camera, intrinsics) makes (without render the string stays: ops.render_rows takes it)"""
+    ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
+    if isinstance(Dp, str) and render is not None:
+        Dp = render(ve, w2c, intr)
+    return ve, w2c, intr, Dp.detach().contiguous() if torch.is_tensor(Dp) else Dp
+
+
+def _render_all(pts, image_hw, cut_bound):
+    """depth="render" in a one-call lift, as _view_args takes it: the z-buffer of every view, V * H * W * 8 bytes"""
+    return lambda view_entry, w2c, intrinsics: ops.render_depth_batched(pts, view_entry, w2c, intrinsics, image_hw, cut_bound)[0]
+
+
+def _clamped(max_visible):
+    return 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1)
+
+
+def _fill_rows(out, width, nn, D=None):
+    """the scene-level fill: the row of its nearest seen point for every row nn names, its own elsewhere (nn None: no fill), cut back
+    to D columns where the rows were padded to `width`"""
+    feats = out if nn is None else ops.gather_rows(out, width, torch.where(nn >= 0, nn, torch.arange(out.shape[0], device=out.device)))
+    return feats if D is None or D == width else feats[:, :D].contiguous()
+
+
+_LISTS_TORN = "the visible lists do not hold together ({} entries, {} views): the inputs changed during the call"
+_STREAM_TORN = ("what the stream keeps does not hold together ({} values of the state, the offsets or the records, {} view positions): it was "
+                "overwritten, or the inputs changed during an add")
+
+
+def _raise_status(who, status, *, num_classes=None, state=False, torn=None):
+    """The errors in the words of a member's status read-back (what ops.readback returned), lift's three first, then what the member
+    adds: num_classes -- a label vote's samples out of range (word 7); state -- a stream's entry tables out of range (word 6); torn --
+    the sentence of a mask lift whose lists (_LISTS_TORN) or kept arrays (_STREAM_TORN) do not hold together (words 6 and 7)."""
+    bad_batch, bad_view, nonfinite = status[:3]
+    if nonfinite:
+        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
+    if bad_batch:
+        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
+    if bad_view:
+        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+    if num_classes is not None and status[7]:
+        raise ValueError(f"{who}: {status[7]} sampled labels are neither in 0..{num_classes - 1} nor in ignore_labels")
+    if state and status[6]:
+        raise RuntimeError(f"{who}: {status[6]} values of the stream's entry tables are out of range: the state was overwritten")
+    if torn is not None and (status[6] or status[7]):
+        raise RuntimeError(f"{who}: {torn.format(status[6], status[7])}")
+
+
 def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible):
     """lift's argument checks, in lift's order; views None: those of the points and the options alone (LiftStream's construction).
     -> (V, D, h, w, H, W), or None without views"""
@@ -279,13 +365,9 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
         if not Fm.dtype.is_floating_point:
             raise ValueError(f"{who}: views.features must be floating point, got {Fm.dtype}")
         V, D, h, w = Fm.shape
-        if V > 65535:
-            raise ValueError(f"{who}: {V} views, at most 65535")
+        _check_view_count(who, V)
         _check_poses(who, "views.", V, E, M, K)
-        shape = (h, w) if views.image_shape is None else tuple(views.image_shape)
-        if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-            raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers, got {views.image_shape!r}")
-        H, W = shape
+        H, W = _image_shape(who, "views.", views.image_shape, (h, w) if views.image_shape is None else tuple(views.image_shape))
         _check_depth(who, Dp, V, H, W)
         if mode == "nearest" and (h, w) != (H, W):
             raise ValueError(f"{who}: mode 'nearest' samples the maps' own pixels: maps of {h} x {w} with image_shape {H} x {W} (use 'bilinear')")
@@ -293,10 +375,8 @@ def _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max
     if views is not None and Fm.requires_grad:
         raise ValueError(f"{who}: views.features require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
                          "no_grad); detach them")
-    tensors = [P] + ([Fm, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    _check_one_device(who, "points and the views' tensors",
+                      [P] + ([Fm, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else []))
     return (V, D, h, w, H, W) if views is not None else None
 
 
@@ -322,47 +402,15 @@ def render_depth(points, view_entry, world_to_camera, intrinsics, image_shape, *
     integer in 0..65535, views whose entry is outside 0..65535."""
     who = "render_depth"
     P, E, M, K = points, view_entry, world_to_camera, intrinsics
-    _check_points(who, P)
-    if not _is_int_tensor(E) or E.dim() != 1 or E.shape[0] < 1:
-        raise ValueError(f"{who}: view_entry must be an integer tensor [V] with V >= 1, got "
-                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-    V = E.shape[0]
-    if V > 65535:
-        raise ValueError(f"{who}: {V} views, at most 65535")
-    _check_poses(who, "", V, E, M, K)
-    shape = tuple(image_shape) if isinstance(image_shape, (tuple, list)) else ()
-    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-        raise ValueError(f"{who}: image_shape must be (H, W), two positive integers, got {image_shape!r}")
+    V, shape = _check_render_views(who, P, E, M, K, image_shape)
     if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
         raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
-    tensors = [P, E, M, K]
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    _check_one_device(who, "points and the views' tensors", [P, E, M, K])
     with torch.cuda.device(P.device), torch.no_grad():
-        depth, status = ops.render_depth_batched(P.detach().to(torch.float64).contiguous(), E.detach().to(torch.int64).contiguous(),
-                                                 M.detach().contiguous(), K.detach().contiguous(), shape, cut_bound)
-        bad_batch, bad_view, nonfinite = ops.readback(status)[:3]
-    if nonfinite:
-        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-    if bad_batch:
-        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-    if bad_view:
-        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+        depth, status = ops.render_depth_batched(_points64(P), *_view_args(E, M, K)[:3], shape, cut_bound)
+        status = ops.readback(status)
+    _raise_status(who, status)
     return depth
-
-
-def _render_chunk(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth, workspace):
-    """depth="render" in a stream: the z-buffers of a chunk's views from the stream's entry tables (nothing is sorted, nothing read
-    back), into scratch that grows to the largest chunk seen.  -> (fp64 [V,H,W], the depth scratch, the workspace)"""
-    V, (H, W), n, dev = view_entry.shape[0], image_hw, st.points.shape[0], st.points.device
-    if depth is None or depth.numel() < V * H * W:
-        depth = torch.empty(V * H * W, dtype=torch.float64, device=dev)
-    need = ops.render_depth_stream_workspace_bytes(n, V)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    d, _ = ops.render_depth_stream(st, view_entry, w2c, intrinsics, image_hw, cut_bound, depth=depth[:V * H * W].view(V, H, W), workspace=workspace)
-    return d, depth, workspace
 
 
 # ------------------------------------------------------------------------------------------ the chain's end in image space
@@ -476,38 +524,20 @@ def render_rows(points, view_entry, world_to_camera, intrinsics, image_shape, *,
     whose entry is outside 0..65535."""
     who = "render_rows"
     P, E, M, K = points, view_entry, world_to_camera, intrinsics
-    _check_points(who, P)
-    if not _is_int_tensor(E) or E.dim() != 1 or E.shape[0] < 1:
-        raise ValueError(f"{who}: view_entry must be an integer tensor [V] with V >= 1, got "
-                         f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-    V = E.shape[0]
-    if V > 65535:
-        raise ValueError(f"{who}: {V} views, at most 65535")
-    _check_poses(who, "", V, E, M, K)
-    shape = tuple(image_shape) if isinstance(image_shape, (tuple, list)) else ()
-    if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-        raise ValueError(f"{who}: image_shape must be (H, W), two positive integers, got {image_shape!r}")
+    V, shape = _check_render_views(who, P, E, M, K, image_shape)
     H, W = shape
     _check_depth(who, depth, V, H, W)
     _check_visibility_options(who, cut_bound, vis_thres, 0, None)
     if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= ops.RENDER_ROWS_MAX_RADIUS:
         raise ValueError(f"{who}: radius={radius!r} must be an integer in 0..{ops.RENDER_ROWS_MAX_RADIUS}")
-    tensors = [P, E, M, K] + ([depth] if torch.is_tensor(depth) else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    _check_one_device(who, "points and the views' tensors", [P, E, M, K] + ([depth] if torch.is_tensor(depth) else []))
     with torch.cuda.device(P.device), torch.no_grad():
-        r = ops.render_rows(P.detach().to(torch.float64).contiguous(), E.detach().to(torch.int64).contiguous(), M.detach().contiguous(),
-                            K.detach().contiguous(), shape, cut_bound, depth=depth.detach().contiguous() if torch.is_tensor(depth) else depth,
-                            vis_thres=float(vis_thres), radius=radius)
-        bad_batch, bad_view, nonfinite, top = ops.readback(r.status)[:4]
-    if nonfinite:
-        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-    if bad_batch:
-        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-    if bad_view:
-        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
-    return Rendered(r.rows, r.depth, r.view_count, r.pixel_count, top + 1, shape, P.shape[0])
+        pts = _points64(P)
+        ve, w2c, intr, depth = _view_args(E, M, K, depth)
+        r = ops.render_rows(pts, ve, w2c, intr, shape, cut_bound, depth=depth, vis_thres=float(vis_thres), radius=radius)
+        status = ops.readback(r.status)
+    _raise_status(who, status)
+    return Rendered(r.rows, r.depth, r.view_count, r.pixel_count, status[3] + 1, shape, P.shape[0])
 
 
 def segment_views(rendered, pred, label_maps, view_entry, num_classes, *, ignore_labels=(255,), index=None):
@@ -593,35 +623,80 @@ def lift(points, views, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visi
     who = "lift"
     V, D, h, w, H, W = _check_lift(who, points, views, mode, cut_bound, vis_thres, min_visible, max_visible)
     P, Fm, E, M, K, Dp = points, views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
-    n = P.shape[0]
-    dev = P.device
-    with torch.cuda.device(dev), torch.no_grad():
-        pts = P.detach().to(torch.float64).contiguous()
+    with torch.cuda.device(P.device), torch.no_grad():
+        pts = _points64(P)
         maps = _lift_maps(Fm)                                                # (fp32, fp16 and bf16 as they are: no fp32 copy of half maps)
         if maps.is_contiguous(memory_format=torch.channels_last):
             maps_pm = maps.permute(0, 2, 3, 1).reshape(V, h * w, D)          # (a view: channels_last is pixel-major already)
         else:
             maps_pm = ops.lift_batched_transpose(maps.contiguous())          # (of the maps' own dtype)
-        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
-            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
-        r = ops.lift_batched(pts, maps_pm, (h, w), ve, w2c, intr,
-                             None if Dp is None else Dp.detach().contiguous(), (H, W), mode == "bilinear", cut_bound, float(vis_thres),
-                             min_visible, 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1), fill=bool(fill))
-        feats = r.out
-        if fill:
-            feats = ops.gather_rows(r.out, D, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
-        bad_batch, bad_view, nonfinite = ops.readback(r.status)[:3]
-    if nonfinite:
-        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-    if bad_batch:
-        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-    if bad_view:
-        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
+        ve, w2c, intr, Dp = _view_args(E, M, K, Dp, _render_all(pts, (H, W), cut_bound))
+        r = ops.lift_batched(pts, maps_pm, (h, w), ve, w2c, intr, Dp, (H, W), mode == "bilinear", cut_bound, float(vis_thres),
+                             min_visible, _clamped(max_visible), fill=bool(fill))
+        feats = _fill_rows(r.out, D, r.nn)
+        status = ops.readback(r.status)
+    _raise_status(who, status)
     return Lifted(feats, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
 
 
-class LiftStream:
+class _LiftStream:
+    """What LiftStream, LiftLabelsStream and LiftMasksStream share: the points, the device and the visibility options; what a chunk
+    must have in common with the first (a subclass names the fields in _CHUNK and hands the tuple to _check_chunk); the running view
+    total and its limit; the refusal of a finish before any add; grow-only scratch by name; the depth="render" maps of a chunk; and
+    the per-chunk view_count / view_keep in arrival order, for the streams that keep them as lists.  A subclass keeps its own checks,
+    its ops.*_stream_* calls and its state, and assigns nothing of the stream before the last refusal of an add: _added is the commit."""
+    _CHUNK = ()                                                 # how the messages call the fields of the first-chunk tuple
+
+    def __init__(self, points, cut_bound, vis_thres, min_visible, max_visible):
+        self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = cut_bound, vis_thres, min_visible, max_visible
+        self.num_views = 0
+        self._points, self._device = points, points.device
+        self._first = None                                      # the first chunk's tuple
+        self._view_count, self._view_keep = [], []
+        self._ws = {}                                           # scratch by name
+
+    def _check_chunk(self, who, this, V):
+        if self._first is not None:
+            for name, a, b in zip(self._CHUNK, this, self._first):
+                if a != b:
+                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
+        if self.num_views + V > 65535:
+            raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
+
+    def _check_started(self, who):
+        if self._first is None:
+            raise ValueError(f"{who}: no views were added")
+
+    def _workspace(self, name, need, dtype=torch.uint8, floor=256):
+        """scratch of at least `need` elements, reallocated only when a call needs more than every call before it"""
+        ws = self._ws.get(name)
+        if ws is None or ws.numel() < need:
+            self._ws[name] = None                               # (freed before the larger one is taken)
+            ws = self._ws[name] = torch.empty(max(int(need), floor), dtype=dtype, device=self._device)
+        return ws
+
+    def _render_chunk(self, image_hw):
+        """depth="render" in a stream, as _view_args takes it: the z-buffers of a chunk's views from the stream's entry tables (nothing
+        is sorted, nothing read back), into scratch that grows to the largest chunk seen -> fp64 [V,H,W]"""
+        def render(view_entry, w2c, intrinsics):
+            V, (H, W) = view_entry.shape[0], image_hw
+            depth = self._workspace("depth", V * H * W, torch.float64, floor=0)[:V * H * W].view(V, H, W)
+            workspace = self._workspace("render", ops.render_depth_stream_workspace_bytes(self._points.shape[0], V))
+            return ops.render_depth_stream(self._st, view_entry, w2c, intrinsics, image_hw, self.cut_bound, depth=depth, workspace=workspace)[0]
+        return render
+
+    def _added(self, this, V, view_count=None, view_keep=None):
+        self._first = this
+        self.num_views += V
+        if view_count is not None:
+            self._view_count.append(view_count)
+            self._view_keep.append(view_keep)
+
+    def _views_so_far(self):
+        return torch.cat(self._view_count), torch.cat(self._view_keep).bool()
+
+
+class LiftStream(_LiftStream):
     """lift with the views arriving in chunks -- the reference's own loop (models/affinity_module.py:365-449: the VLM runs on
     max_batch_size views at a time, every chunk is added into sum_features / counter and freed, one division and one fill at the end),
     for several scenes at once.  Only one chunk's maps need to exist at a time:
@@ -662,36 +737,31 @@ class LiftStream:
     views belong to no entry and change nobody else's result.  (RuntimeError from the same read-back: the entry tables hold values
     outside their range, i.e. somebody wrote into the stream's state; the kernels force them into range before use.)"""
 
+    _CHUNK = ("(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')")
+
     def __init__(self, points, feature_dim, *, mode="nearest", cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None):
         who = "LiftStream"
         _check_lift(who, points, None, mode, cut_bound, vis_thres, min_visible, max_visible)
         if not _is_count(feature_dim, 1) or feature_dim >= 2 ** 31:
             raise ValueError(f"{who}: feature_dim={feature_dim!r} must be a positive integer")
-        self.mode, self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = mode, cut_bound, vis_thres, min_visible, max_visible
-        self.feature_dim, self.num_views = int(feature_dim), 0
-        self._points, self._device = points, points.device
-        self._first = None                                      # ((h, w), (H, W), depth present) of the first chunk
-        self._view_count, self._view_keep = [], []
-        self._scratch = self._ws_add = self._ws_finish = self._depth = self._ws_render = None
+        super().__init__(points, cut_bound, vis_thres, min_visible, max_visible)
+        self.mode, self.feature_dim = mode, int(feature_dim)
         with torch.cuda.device(self._device), torch.no_grad():
-            self._st = ops.lift_stream_begin(points.detach().to(torch.float64).contiguous(), self.feature_dim)
+            self._st = ops.lift_stream_begin(_points64(points), self.feature_dim)
 
-    def _options(self):
-        return self.mode, self.cut_bound, self.vis_thres, self.min_visible, self.max_visible
+    @property
+    def _scratch(self):
+        """the NCHW transpose scratch, as fp32 words"""
+        return self._ws.get("transpose")
 
     def add(self, views):
         """One chunk of views (a Views) onto the sums.  No host synchronisation."""
         who = "LiftStream.add"
-        V, D, h, w, H, W = _check_lift(who, self._points, views, *self._options())
+        V, D, h, w, H, W = _check_lift(who, self._points, views, self.mode, self.cut_bound, self.vis_thres, self.min_visible, self.max_visible)
         if D != self.feature_dim:
             raise ValueError(f"{who}: the chunk's maps have {D} channels, the stream was built with feature_dim={self.feature_dim}")
         this = ((h, w), (H, W), _depth_kind(views.depth))
-        if self._first is not None:
-            for name, a, b in zip(("(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')"), this, self._first):
-                if a != b:
-                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
-        if self.num_views + V > 65535:
-            raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
+        self._check_chunk(who, this, V)
         Fm, E, M, K, Dp = views.features, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         with torch.cuda.device(self._device), torch.no_grad():
             maps = _lift_maps(Fm)                                            # (fp32, fp16 and bf16 as they are; the sums are fp32)
@@ -700,51 +770,26 @@ class LiftStream:
             else:
                 nbytes = maps.numel() * maps.element_size()                 # (the scratch is sized in bytes: chunks of any dtype share it)
                 words = -(-nbytes // 4)                                      # (kept as fp32 words: an fp32 chunk's element count)
-                if self._scratch is None or self._scratch.numel() < words:
-                    self._scratch = None                                    # (freed before the larger one is taken)
-                    self._scratch = torch.empty(words, dtype=torch.float32, device=self._device)
-                maps_pm = ops.lift_batched_transpose(maps.contiguous(),
-                                                     out=self._scratch.view(torch.uint8)[:nbytes].view(maps.dtype).view(V, h * w, D))
-            need = ops.lift_stream_add_workspace_bytes(V)
-            if self._ws_add is None or self._ws_add.numel() < need:
-                self._ws_add = None
-                self._ws_add = torch.empty(need, dtype=torch.uint8, device=self._device)
-            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
-                Dp, self._depth, self._ws_render = _render_chunk(self._st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
-            vc, vk = ops.lift_stream_add(self._st, maps_pm, (h, w), ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(), (H, W),
-                                         self.mode == "bilinear", self.cut_bound, float(self.vis_thres), self.min_visible,
-                                         2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1), workspace=self._ws_add)
-        self._first = this
-        self.num_views += V
-        self._view_count.append(vc)
-        self._view_keep.append(vk)
+                scratch = self._workspace("transpose", words, torch.float32, floor=0)
+                maps_pm = ops.lift_batched_transpose(maps.contiguous(), out=scratch.view(torch.uint8)[:nbytes].view(maps.dtype).view(V, h * w, D))
+            workspace = self._workspace("add", ops.lift_stream_add_workspace_bytes(V))
+            ve, w2c, intr, Dp = _view_args(E, M, K, Dp, self._render_chunk((H, W)))
+            vc, vk = ops.lift_stream_add(self._st, maps_pm, (h, w), ve, w2c, intr, Dp, (H, W), self.mode == "bilinear", self.cut_bound,
+                                         float(self.vis_thres), self.min_visible, _clamped(self.max_visible), workspace=workspace)
+        self._added(this, V, vc, vk)
 
     def finish(self, fill=True):
         """-> Lifted over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
         who = "LiftStream.finish"
-        if self._first is None:
-            raise ValueError(f"{who}: no views were added")
-        n, D, dev = self._points.shape[0], self.feature_dim, self._device
-        with torch.cuda.device(dev), torch.no_grad():
-            if self._ws_finish is None:
-                self._ws_finish = torch.empty(ops.lift_stream_finish_workspace_bytes(n), dtype=torch.uint8, device=dev)
-            r = ops.lift_stream_finish(self._st, fill=bool(fill), workspace=self._ws_finish)
-            feats = r.out
-            if fill:
-                feats = ops.gather_rows(r.out, D, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
+        self._check_started(who)
+        with torch.cuda.device(self._device), torch.no_grad():
+            r = ops.lift_stream_finish(self._st, fill=bool(fill),
+                                       workspace=self._workspace("finish", ops.lift_stream_finish_workspace_bytes(self._points.shape[0])))
+            feats = _fill_rows(r.out, self.feature_dim, r.nn)
             count = self._st.count.clone()
-            view_count, view_keep = torch.cat(self._view_count), torch.cat(self._view_keep).bool()
+            view_count, view_keep = self._views_so_far()
             status = ops.readback(r.status)
-        bad_batch, bad_view, nonfinite, bad_state = status[0], status[1], status[2], status[6]
-        if nonfinite:
-            raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-        if bad_batch:
-            raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-        if bad_view:
-            raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
-        if bad_state:
-            raise RuntimeError(f"{who}: {bad_state} values of the stream's entry tables are out of range: the state was overwritten")
+        _raise_status(who, status, state=True)
         return Lifted(feats, r.seen.bool(), count, view_count, view_keep)
 
 
@@ -787,8 +832,7 @@ def _check_lift_labels(who, points, views, num_classes, ignore_labels, unlabeled
         if L.dtype not in LABEL_DTYPES:
             raise ValueError(f"{who}: views.labels must be uint8, int16, int32 or int64 (bool and floating label maps are refused), got {L.dtype}")
         V, H, W = L.shape
-        if V > 65535:
-            raise ValueError(f"{who}: {V} views, at most 65535")
+        _check_view_count(who, V)
         _check_poses(who, "views.", V, E, M, K)
         _check_depth(who, Dp, V, H, W)
     _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visible)
@@ -799,26 +843,9 @@ def _check_lift_labels(who, points, views, num_classes, ignore_labels, unlabeled
         raise ValueError(f"{who}: ignore_labels={ignore_labels!r} must be a tuple of at most {ops.LIFT_LABELS_MAX_IGNORE} integers")
     if not isinstance(unlabeled, int) or isinstance(unlabeled, bool) or not -2 ** 63 <= unlabeled < 2 ** 63 or 0 <= unlabeled < num_classes:
         raise ValueError(f"{who}: unlabeled={unlabeled!r} must be an integer outside 0..{num_classes - 1}, the classes")
-    tensors = [P] + ([L, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    _check_one_device(who, "points and the views' tensors",
+                      [P] + ([L, E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else []))
     return (V, H, W) if views is not None else None
-
-
-def _raise_label_status(who, status, num_classes):
-    """the status errors of a label vote, lift's three first"""
-    bad_batch, bad_view, nonfinite, bad_state, bad_label = status[0], status[1], status[2], status[6], status[7]
-    if nonfinite:
-        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-    if bad_batch:
-        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-    if bad_view:
-        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
-    if bad_label:
-        raise ValueError(f"{who}: {bad_label} sampled labels are neither in 0..{num_classes - 1} nor in ignore_labels")
-    if bad_state:
-        raise RuntimeError(f"{who}: {bad_state} values of the stream's entry tables are out of range: the state was overwritten")
 
 
 def lift_labels(points, views, num_classes, *, ignore_labels=(255,), unlabeled=255, cut_bound=0, vis_thres=0.25, min_visible=0,
@@ -851,19 +878,16 @@ def lift_labels(points, views, num_classes, *, ignore_labels=(255,), unlabeled=2
     V, H, W = _check_lift_labels(who, points, views, num_classes, ignore_labels, unlabeled, cut_bound, vis_thres, min_visible, max_visible)
     P, L, E, M, K, Dp = points, views.labels, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
     with torch.cuda.device(P.device), torch.no_grad():
-        pts = P.detach().to(torch.float64).contiguous()
-        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
-            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
-        r = ops.lift_labels_batched(pts, L.detach().contiguous(), num_classes, ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(),
-                                    cut_bound, float(vis_thres), min_visible, 2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1),
-                                    ignore_ids=tuple(ignore_labels), unlabeled=unlabeled, fill=bool(fill))
+        pts = _points64(P)
+        ve, w2c, intr, Dp = _view_args(E, M, K, Dp, _render_all(pts, (H, W), cut_bound))
+        r = ops.lift_labels_batched(pts, L.detach().contiguous(), num_classes, ve, w2c, intr, Dp, cut_bound, float(vis_thres), min_visible,
+                                    _clamped(max_visible), ignore_ids=tuple(ignore_labels), unlabeled=unlabeled, fill=bool(fill))
         status = ops.readback(r.status)
-    _raise_label_status(who, status, num_classes)
+    _raise_status(who, status, num_classes=num_classes, state=True)
     return LiftedLabels(r.labels, r.votes, r.voted, r.seen.bool(), r.count, r.view_count, r.view_keep.bool())
 
 
-class LiftLabelsStream:
+class LiftLabelsStream(_LiftStream):
     """lift_labels with the views arriving in chunks, for several scenes at once.  Only one chunk's label maps need to exist at a time:
 
         stream = LiftLabelsStream(points, num_classes=C)
@@ -890,19 +914,16 @@ class LiftLabelsStream:
     finish.  (RuntimeError from the same read-back: the entry tables hold values outside their range, i.e. somebody wrote into the
     stream's state.)"""
 
+    _CHUNK = ("(H, W)", "the presence of depth (none, tensor or 'render')")
+
     def __init__(self, points, num_classes, *, ignore_labels=(255,), unlabeled=255, cut_bound=0, vis_thres=0.25, min_visible=0,
                  max_visible=None):
         who = "LiftLabelsStream"
         _check_lift_labels(who, points, None, num_classes, ignore_labels, unlabeled, cut_bound, vis_thres, min_visible, max_visible)
+        super().__init__(points, cut_bound, vis_thres, min_visible, max_visible)
         self.num_classes, self.ignore_labels, self.unlabeled = int(num_classes), tuple(ignore_labels), unlabeled
-        self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = cut_bound, vis_thres, min_visible, max_visible
-        self.num_views = 0
-        self._points, self._device = points, points.device
-        self._first = None                                      # ((H, W), depth kind) of the first chunk
-        self._view_count, self._view_keep = [], []
-        self._ws_add = self._ws_finish = self._depth = self._ws_render = None
         with torch.cuda.device(self._device), torch.no_grad():
-            self._st = ops.lift_labels_stream_begin(points.detach().to(torch.float64).contiguous(), self.num_classes)
+            self._st = ops.lift_labels_stream_begin(_points64(points), self.num_classes)
 
     def add(self, views):
         """One chunk of views (a LabelViews) onto the votes.  No host synchronisation."""
@@ -910,44 +931,26 @@ class LiftLabelsStream:
         V, H, W = _check_lift_labels(who, self._points, views, self.num_classes, self.ignore_labels, self.unlabeled, self.cut_bound,
                                      self.vis_thres, self.min_visible, self.max_visible)
         this = ((H, W), _depth_kind(views.depth))
-        if self._first is not None:
-            for name, a, b in zip(("(H, W)", "the presence of depth (none, tensor or 'render')"), this, self._first):
-                if a != b:
-                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
-        if self.num_views + V > 65535:
-            raise ValueError(f"{who}: {V} more views after {self.num_views}, at most 65535 in all")
+        self._check_chunk(who, this, V)
         L, E, M, K, Dp = views.labels, views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         with torch.cuda.device(self._device), torch.no_grad():
-            need = ops.lift_labels_stream_add_workspace_bytes(V)
-            if self._ws_add is None or self._ws_add.numel() < need:
-                self._ws_add = None
-                self._ws_add = torch.empty(need, dtype=torch.uint8, device=self._device)
-            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
-                Dp, self._depth, self._ws_render = _render_chunk(self._st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
-            vc, vk = ops.lift_labels_stream_add(self._st, L.detach().contiguous(), ve, w2c, intr, None if Dp is None else Dp.detach().contiguous(),
-                                                self.cut_bound, float(self.vis_thres), self.min_visible,
-                                                2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1),
-                                                ignore_ids=self.ignore_labels, workspace=self._ws_add)
-        self._first = this
-        self.num_views += V
-        self._view_count.append(vc)
-        self._view_keep.append(vk)
+            workspace = self._workspace("add", ops.lift_labels_stream_add_workspace_bytes(V))
+            ve, w2c, intr, Dp = _view_args(E, M, K, Dp, self._render_chunk((H, W)))
+            vc, vk = ops.lift_labels_stream_add(self._st, L.detach().contiguous(), ve, w2c, intr, Dp, self.cut_bound, float(self.vis_thres),
+                                                self.min_visible, _clamped(self.max_visible), ignore_ids=self.ignore_labels, workspace=workspace)
+        self._added(this, V, vc, vk)
 
     def finish(self, fill=True):
         """-> LiftedLabels over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
         who = "LiftLabelsStream.finish"
-        if self._first is None:
-            raise ValueError(f"{who}: no views were added")
-        n, dev = self._points.shape[0], self._device
-        with torch.cuda.device(dev), torch.no_grad():
-            if self._ws_finish is None:
-                self._ws_finish = torch.empty(ops.lift_labels_stream_finish_workspace_bytes(n), dtype=torch.uint8, device=dev)
-            r = ops.lift_labels_stream_finish(self._st, unlabeled=self.unlabeled, fill=bool(fill), workspace=self._ws_finish)
+        self._check_started(who)
+        with torch.cuda.device(self._device), torch.no_grad():
+            r = ops.lift_labels_stream_finish(self._st, unlabeled=self.unlabeled, fill=bool(fill),
+                                              workspace=self._workspace("finish", ops.lift_labels_stream_finish_workspace_bytes(self._points.shape[0])))
             votes, count = self._st.votes.clone(), self._st.count.clone()
-            view_count, view_keep = torch.cat(self._view_count), torch.cat(self._view_keep).bool()
+            view_count, view_keep = self._views_so_far()
             status = ops.readback(r.status)
-        _raise_label_status(who, status, self.num_classes)
+        _raise_status(who, status, num_classes=self.num_classes, state=True)
         return LiftedLabels(r.labels, votes, r.voted, r.seen.bool(), count, view_count, view_keep)
 
 
@@ -1000,13 +1003,7 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
     if views is not None and not isinstance(views, MaskViews):
         raise ValueError(f"{who}: views must be a MaskViews, got {type(views).__name__}")
     P = points
-    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
-        raise ValueError(f"{who}: points must be [N, 4] (batch, x, y, z), got {_shape_of(P)}")
-    if P.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{who}: points must be fp64 or fp32, got {P.dtype}")
-    n = P.shape[0]
-    if n == 0 or n >= 2 ** 31:
-        raise ValueError(f"{who}: {n} points outside 1..2^31-1")
+    _check_points(who, P)
     if views is not None:
         Pm, Pl, Em = views.pred_masks, views.pred_logits, views.mask_embed
         E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
@@ -1014,8 +1011,7 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
             raise ValueError(f"{who}: views.pred_masks must be fp32, fp16 or bf16 [V, Q, h, w] with V, Q, h, w >= 1, got "
                              f"{(list(Pm.shape), Pm.dtype) if torch.is_tensor(Pm) else type(Pm).__name__}")
         V, Q, h, w = Pm.shape
-        if V > 65535:
-            raise ValueError(f"{who}: {V} views, at most 65535")
+        _check_view_count(who, V)
         if Q > MAX_QUERIES:
             raise ValueError(f"{who}: {Q} queries per view, at most {MAX_QUERIES} (a view's scores are sorted in LDS)")
     if not torch.is_tensor(text_embed) or text_embed.dim() != 2 or min(text_embed.shape) < 1 or not text_embed.dtype.is_floating_point:
@@ -1029,29 +1025,14 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
         if not torch.is_tensor(Em) or Em.shape != (V, Q, D) or not Em.dtype.is_floating_point:
             raise ValueError(f"{who}: views.mask_embed must be floating point [{V}, {Q}, {D}], got "
                              f"{(list(Em.shape), Em.dtype) if torch.is_tensor(Em) else type(Em).__name__}")
-        if not _is_int_tensor(E) or E.shape != (V,):
-            raise ValueError(f"{who}: views.view_entry must be an integer tensor [{V}], got "
-                             f"{(list(E.shape), E.dtype) if torch.is_tensor(E) else type(E).__name__}")
-        if not torch.is_tensor(M) or M.shape != (V, 4, 4) or M.dtype != torch.float64:
-            raise ValueError(f"{who}: views.world_to_camera must be fp64 [{V}, 4, 4], got {(list(M.shape), M.dtype) if torch.is_tensor(M) else type(M).__name__}")
-        if not torch.is_tensor(K) or K.shape != (V, 4) or K.dtype != torch.float64:
-            raise ValueError(f"{who}: views.intrinsics must be fp64 [{V}, 4] (fx, fy, cx, cy), got "
-                             f"{(list(K.shape), K.dtype) if torch.is_tensor(K) else type(K).__name__}")
-        shape = () if views.image_shape is None else tuple(views.image_shape)
-        if len(shape) != 2 or not all(_is_count(v, 1) and v < 2 ** 31 for v in shape):
-            raise ValueError(f"{who}: views.image_shape must be (H, W), two positive integers (the size the masks are resized to), got "
-                             f"{views.image_shape!r}")
-        H, W = shape
+        _check_poses(who, "views.", V, E, M, K)
+        H, W = _image_shape(who, "views.", views.image_shape, () if views.image_shape is None else tuple(views.image_shape),
+                            " (the size the masks are resized to)")
         if h > H or w > W:
             raise ValueError(f"{who}: masks of {h} x {w} are larger than image_shape {H} x {W}: the bicubic-antialias resize is evaluated for "
                              "up-sampling only")
         _check_depth(who, Dp, V, H, W)
-    if not _is_count(cut_bound, 0) or cut_bound >= 2 ** 31:
-        raise ValueError(f"{who}: cut_bound={cut_bound!r} must be an integer >= 0")
-    if isinstance(vis_thres, bool) or not isinstance(vis_thres, (int, float)) or vis_thres != vis_thres:
-        raise ValueError(f"{who}: vis_thres={vis_thres!r} must be a number")
-    if not _is_count(min_visible, 0) or not (max_visible is None or _is_count(max_visible, 0)):
-        raise ValueError(f"{who}: min_visible={min_visible!r} / max_visible={max_visible!r} must be integers >= 0 (max_visible may be None)")
+    _check_visibility_options(who, cut_bound, vis_thres, min_visible, max_visible)
     if isinstance(logit_scale, bool) or not isinstance(logit_scale, (int, float)) or logit_scale != logit_scale:
         raise ValueError(f"{who}: logit_scale={logit_scale!r} must be a number")
     named = ([("views.pred_masks", Pm), ("views.pred_logits", Pl), ("views.mask_embed", Em)] if views is not None else []) + [("text_embed", text_embed)]
@@ -1059,11 +1040,50 @@ def _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vi
         if t.requires_grad:
             raise ValueError(f"{who}: {name} require grad, but the lift takes no gradients (the VLM is frozen, the reference lifts under "
                              "no_grad); detach them")
-    tensors = [P] + ([Pm, Pl, Em] if views is not None else []) + [text_embed] + ([E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else [])
-    if not all(t.is_cuda for t in tensors) or any(t.device != P.device for t in tensors):
-        raise ValueError(f"{who}: points, text_embed and the views' tensors must be CUDA tensors on one device (got "
-                         f"{' / '.join(str(t.device) for t in tensors)}); there is no CPU path")
+    _check_one_device(who, "points, text_embed and the views' tensors", [P] + ([Pm, Pl, Em] if views is not None else []) + [text_embed]
+                      + ([E, M, K] + ([Dp] if torch.is_tensor(Dp) else []) if views is not None else []))
     return (V, Q, h, w, H, W, C, D) if views is not None else (C, D)
+
+
+# what lift_masks and LiftMasksStream.add prepare for their kernels, and what both return when no kept view sees a point
+def _unit_text(text_embed):
+    return torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
+
+
+def _padded_text(text_norm):
+    """the fusion kernel moves rows as float4: tables and rows padded to a multiple of 4 columns (zeros add nothing to a norm or a dot
+    product, and a lane's terms stay the lane's)"""
+    C, D = text_norm.shape
+    text4 = torch.zeros((C, _pad_to(D, 4)), dtype=torch.float32, device=text_norm.device)
+    text4[:, :D] = text_norm
+    return text4
+
+
+def _mask_tables(Pl, Em, text_norm, logit_scale, text4=None, f_seg=None, l_seg=None):
+    """-> scores fp32 [V,Q] (lift_masks' rule 2) and the segment tables f_seg fp32 [V,Q,d4] / l_seg fp32 [V,Q,C] of the views (rule 5,
+    ops.segment_tables over the rows padded to d4 columns).  text4: text_norm padded already (a stream's, made once); f_seg / l_seg:
+    the caller's own rows to write (a stream's slices of what it keeps) -- without them fresh ones."""
+    (V, Q, D), C, dev = Em.shape, text_norm.shape[0], Em.device
+    scores = torch.softmax(Pl.detach().float(), dim=-1)[..., :-1].max(-1).values.contiguous()
+    d4 = _pad_to(D, 4)
+    emb = torch.zeros((V * Q, d4), dtype=torch.float32, device=dev)
+    emb[:, :D] = Em.detach().float().reshape(V * Q, D)
+    if text4 is None:
+        text4 = _padded_text(text_norm)
+    if f_seg is None:
+        f_seg = torch.empty((V, Q, d4), dtype=torch.float32, device=dev)
+        l_seg = torch.empty((V, Q, C), dtype=torch.float32, device=dev)
+    f_rows, l_rows = f_seg.view(V * Q, d4), l_seg.view(V * Q, C)
+    for r0 in range(0, V * Q, _TABLE_ROWS):
+        r1 = min(r0 + _TABLE_ROWS, V * Q)
+        ops.segment_tables(emb[r0:r1], text4, float(logit_scale), f_rows[r0:r1], l_rows[r0:r1])
+    return scores, f_seg, l_seg
+
+
+def _nothing_visible(n, D, dev):
+    """features, seen and count of a mask lift in which no kept view sees a point"""
+    return (torch.zeros((n, D), dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.bool, device=dev),
+            torch.zeros(n, dtype=torch.int32, device=dev))
 
 
 def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None, fill=True):
@@ -1104,53 +1124,25 @@ def lift_masks(points, views, text_embed, logit_scale, *, cut_bound=0, vis_thres
     V, Q, h, w, H, W, C, D = _check_lift_masks(who, points, views, text_embed, logit_scale, cut_bound, vis_thres, min_visible, max_visible)
     P, Pm, Pl, Em = points, views.pred_masks, views.pred_logits, views.mask_embed
     E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
-    n = P.shape[0]
-    dev = P.device
+    n, dev = P.shape[0], P.device
     with torch.cuda.device(dev), torch.no_grad():
-        pts = P.detach().to(torch.float64).contiguous()
-        ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-        if isinstance(Dp, str):                                              # "render": the z-buffer of every view, V * H * W * 8 bytes
-            Dp = ops.render_depth_batched(pts, ve, w2c, intr, (H, W), cut_bound)[0]
-        lists = ops.lift_masks_batched_lists(pts, ve, w2c, intr,
-                                             None if Dp is None else Dp.detach().contiguous(), (H, W), cut_bound, float(vis_thres), min_visible,
-                                             2 ** 63 - 1 if max_visible is None else min(max_visible, 2 ** 63 - 1))    # (the first read-back)
-        text_norm = torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
+        pts = _points64(P)
+        ve, w2c, intr, Dp = _view_args(E, M, K, Dp, _render_all(pts, (H, W), cut_bound))
+        lists = ops.lift_masks_batched_lists(pts, ve, w2c, intr, Dp, (H, W), cut_bound, float(vis_thres), min_visible,
+                                             _clamped(max_visible))              # (the first read-back)
+        text_norm = _unit_text(text_embed)
         status = lists.status
         if lists.total == 0:
-            feats = torch.zeros((n, D), dtype=torch.float32, device=dev)
-            seen, count = torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+            feats, seen, count = _nothing_visible(n, D, dev)
         else:
-            scores = torch.softmax(Pl.detach().float(), dim=-1)[..., :-1].max(-1).values.contiguous()
-            # the fusion kernel moves rows as float4: tables and rows padded to a multiple of 4 columns (zeros add nothing to a norm or a
-            # dot product, and a lane's terms stay the lane's)
-            d4 = _pad_to(D, 4)
-            emb = torch.zeros((V * Q, d4), dtype=torch.float32, device=dev)
-            emb[:, :D] = Em.detach().float().reshape(V * Q, D)
-            text4 = torch.zeros((C, d4), dtype=torch.float32, device=dev)
-            text4[:, :D] = text_norm
-            f_seg = torch.empty((V, Q, d4), dtype=torch.float32, device=dev)
-            l_seg = torch.empty((V, Q, C), dtype=torch.float32, device=dev)
-            for r0 in range(0, V * Q, _TABLE_ROWS):
-                r1 = min(r0 + _TABLE_ROWS, V * Q)
-                ops.segment_tables(emb[r0:r1], text4, float(logit_scale), f_seg.view(V * Q, d4)[r0:r1], l_seg.view(V * Q, C)[r0:r1])
+            scores, f_seg, l_seg = _mask_tables(Pl, Em, text_norm, logit_scale)
             r = ops.lift_masks_batched(pts, ve, Pm.detach().contiguous(), scores, _tap_tables(h, w, H, W, dev), (H, W),
                                        (lists.pt, lists.x, lists.y, lists.view), lists.view_off, lists.view_keep, lists.total,
                                        max(1, -(-lists.max_views // 64)), f_seg, l_seg, fill=bool(fill))
-            feats = r.out
-            if fill:
-                feats = ops.gather_rows(r.out, d4, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
-            feats = feats[:, :D].contiguous() if d4 != D else feats
+            feats = _fill_rows(r.out, f_seg.shape[2], r.nn, D)
             seen, count, status = r.seen.bool(), r.count, r.status
-        st = ops.readback(status)                                                # (the second read-back)
-    bad_batch, bad_view, nonfinite = st[:3]
-    if nonfinite:
-        raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-    if bad_batch:
-        raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-    if bad_view:
-        raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
-    if lists.total and (st[6] or st[7]):
-        raise RuntimeError(f"{who}: the visible lists do not hold together ({st[6]} entries, {st[7]} views): the inputs changed during the call")
+        status = ops.readback(status)                                            # (the second read-back)
+    _raise_status(who, status, torn=_LISTS_TORN if lists.total else None)
     return LiftedMasks(feats, seen, count, lists.view_count, lists.view_keep.bool(), text_norm, logit_scale)
 
 
@@ -1171,7 +1163,7 @@ def _grown(t, used, need, shape_tail, dtype, device, most=None):
     return new
 
 
-class LiftMasksStream:
+class LiftMasksStream(_LiftStream):
     """lift_masks with the views arriving in chunks -- the reference's own loop (models/affinity_module.py:495-640: the X-Decoder runs on
     one view, the view's masks become per-point segments, only the small per-point record survives in point_info and the masks are
     freed; the fusion :647-686 alone looks across views), for several scenes at once.  Only one chunk's masks need to exist at a time:
@@ -1223,32 +1215,23 @@ class LiftMasksStream:
     do not hold together, i.e. somebody wrote into what the stream keeps; the kernels force them into range or leave them out first.
     No gradients, as for lift_masks."""
 
+    _CHUNK = ("Q", "(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')")
+
     def __init__(self, points, text_embed, logit_scale, *, cut_bound=0, vis_thres=0.25, min_visible=0, max_visible=None):
         who = "LiftMasksStream"
         C, D = _check_lift_masks(who, points, None, text_embed, logit_scale, cut_bound, vis_thres, min_visible, max_visible)
-        self.cut_bound, self.vis_thres, self.min_visible, self.max_visible = cut_bound, vis_thres, min_visible, max_visible
+        super().__init__(points, cut_bound, vis_thres, min_visible, max_visible)
         self.logit_scale, self.num_classes, self.feature_dim = logit_scale, C, D
-        self.num_views = self.num_records = self.most_views = 0
-        self._points, self._text, self._device = points, text_embed, points.device
-        self._first = None                                      # (Q, (h, w), (H, W), depth present) of the first chunk
+        self.num_records = self.most_views = 0
+        self._text = text_embed
+        # the per-view fields are doubling buffers here (_grown), not the base's per-chunk lists
         self._view_entry = self._view_count = self._view_keep = self._view_pos = self._rec_off = None
         self._f_seg = self._l_seg = self._rec_row = self._rec_seg = None
-        self._ws = {}                                           # add's and finish's workspaces by name
-        self._depth = self._ws_render = None                    # depth="render": a chunk's rendered depth and its workspace
-        dev = self._device
-        with torch.cuda.device(dev), torch.no_grad():
-            self._st = ops.lift_masks_stream_begin(points.detach().to(torch.float64).contiguous())
-            self.text_features = torch.nn.functional.normalize(text_embed.detach().float(), dim=-1).contiguous()
+        with torch.cuda.device(self._device), torch.no_grad():
+            self._st = ops.lift_masks_stream_begin(_points64(points))
+            self.text_features = _unit_text(text_embed)
             self._d4 = _pad_to(D, 4)
-            self._text4 = torch.zeros((C, self._d4), dtype=torch.float32, device=dev)
-            self._text4[:, :D] = self.text_features
-
-    def _workspace(self, name, need):
-        ws = self._ws.get(name)
-        if ws is None or ws.numel() < need:
-            self._ws[name] = None                               # (freed before the larger one is taken)
-            ws = self._ws[name] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=self._device)
-        return ws
+            self._text4 = _padded_text(self.text_features)
 
     def add(self, views):
         """One chunk of views (a MaskViews).  One host synchronisation (the read-back of the chunk's sizes)."""
@@ -1258,20 +1241,13 @@ class LiftMasksStream:
         V, Q, h, w, H, W, C, D = _check_lift_masks(who, self._points, views, self._text, self.logit_scale, self.cut_bound, self.vis_thres,
                                                    self.min_visible, self.max_visible)
         this = (Q, (h, w), (H, W), _depth_kind(views.depth))
-        if self._first is not None:
-            for name, a, b in zip(("Q", "(h, w)", "image_shape", "the presence of depth (none, tensor or 'render')"), this, self._first):
-                if a != b:
-                    raise ValueError(f"{who}: {name} of a chunk must be the first chunk's: {a} after {b}")
+        self._check_chunk(who, this, V)
         V0, R0 = self.num_views, self.num_records
-        if V0 + V > 65535:
-            raise ValueError(f"{who}: {V} more views after {V0}, at most 65535 in all")
         Pm, Pl, Em = views.pred_masks, views.pred_logits, views.mask_embed
         E, M, K, Dp = views.view_entry, views.world_to_camera, views.intrinsics, views.depth
         n, dev, st, d4 = self._points.shape[0], self._device, self._st, self._d4
         with torch.cuda.device(dev), torch.no_grad():
-            ve, w2c, intr = E.detach().to(torch.int64).contiguous(), M.detach().contiguous(), K.detach().contiguous()
-            if isinstance(Dp, str):                                          # "render": the chunk's z-buffers, from the stream's entry tables
-                Dp, self._depth, self._ws_render = _render_chunk(st, ve, w2c, intr, (H, W), self.cut_bound, self._depth, self._ws_render)
+            ve, w2c, intr, Dp = _view_args(E, M, K, Dp, self._render_chunk((H, W)))
             found, bufs = {}, {}
 
             def sizes(got):
@@ -1290,11 +1266,9 @@ class LiftMasksStream:
                     bufs["view"] = ent[24 * pitch:24 * pitch + 4 * total].view(torch.int32)
                 return found["total"], most
 
-            lists = ops.lift_masks_batched_lists(st.points, ve, w2c, intr,
-                                                 None if Dp is None else Dp.detach().contiguous(), (H, W), self.cut_bound, float(self.vis_thres),
-                                                 self.min_visible, 2 ** 63 - 1 if self.max_visible is None else min(self.max_visible, 2 ** 63 - 1),
-                                                 buffers=bufs, workspace=self._workspace("lists", ops.lift_masks_batched_lists_workspace_bytes(n, V)),
-                                                 sizes=sizes)
+            lists = ops.lift_masks_batched_lists(st.points, ve, w2c, intr, Dp, (H, W), self.cut_bound, float(self.vis_thres), self.min_visible,
+                                                 _clamped(self.max_visible), buffers=bufs,
+                                                 workspace=self._workspace("lists", ops.lift_masks_batched_lists_workspace_bytes(n, V)), sizes=sizes)
             total, kept = found["total"], found["kept"]
             # nothing of the stream has changed so far; from here on nothing is refused
             used = V0 + 1 if V0 else 0
@@ -1310,55 +1284,34 @@ class LiftMasksStream:
             if total:
                 self._rec_row = _grown(self._rec_row, R0, R0 + kept, (), torch.int32, dev, most=MAX_RECORDS)
                 self._rec_seg = _grown(self._rec_seg, R0, R0 + kept, (), torch.int32, dev, most=MAX_RECORDS)
-                pm = Pm.detach().contiguous()
-                scores = torch.softmax(Pl.detach().float(), dim=-1)[..., :-1].max(-1).values.contiguous()
-                taps = _tap_tables(h, w, H, W, dev)
-                emb = torch.zeros((V * Q, d4), dtype=torch.float32, device=dev)
-                emb[:, :D] = Em.detach().float().reshape(V * Q, D)
-                f_seg, l_seg = self._f_seg[V0:V0 + V].view(V * Q, d4), self._l_seg[V0:V0 + V].view(V * Q, C)
-                for r0 in range(0, V * Q, _TABLE_ROWS):
-                    r1 = min(r0 + _TABLE_ROWS, V * Q)
-                    ops.segment_tables(emb[r0:r1], self._text4, float(self.logit_scale), f_seg[r0:r1], l_seg[r0:r1])
+                pm, taps = Pm.detach().contiguous(), _tap_tables(h, w, H, W, dev)
+                scores = _mask_tables(Pl, Em, self.text_features, self.logit_scale, self._text4, self._f_seg[V0:V0 + V], self._l_seg[V0:V0 + V])[0]
             need = ops.lift_masks_stream_add_workspace_bytes(n, V, Q if total else 1, (h, w) if total else (1, 1), (H, W), total, dtype=Pm.dtype)
             ops.lift_masks_stream_add(st, ve, pm, scores, taps, (H, W), (lists.pt, lists.x, lists.y, lists.view), lists.view_off, lists.view_keep,
                                       total, self._rec_row, self._rec_seg, R0, self._rec_off[V0:V0 + V + 1], self._view_pos[V0:V0 + V],
                                       workspace=self._workspace("add", need))
-        self._first = this
-        self.num_views, self.num_records, self.most_views = V0 + V, R0 + kept, max(self.most_views, found["most"])
+        self._added(this, V)
+        self.num_records, self.most_views = R0 + kept, max(self.most_views, found["most"])
 
     def finish(self, fill=True):
         """-> LiftedMasks over the views added so far; the stream goes on.  One host synchronisation (the status read-back)."""
         who = "LiftMasksStream.finish"
-        if self._first is None:
-            raise ValueError(f"{who}: no views were added")
+        self._check_started(who)
         n, D, d4, dev, V, R = self._points.shape[0], self.feature_dim, self._d4, self._device, self.num_views, self.num_records
         with torch.cuda.device(dev), torch.no_grad():
             if R == 0:
-                feats = torch.zeros((n, D), dtype=torch.float32, device=dev)
-                seen, count = torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+                feats, seen, count = _nothing_visible(n, D, dev)
                 status = self._st.status
             else:
                 words = max(1, -(-self.most_views // 64))
                 r = ops.lift_masks_stream_finish(self._st, self._view_entry[:V], self._view_pos[:V], self._view_keep[:V], self._rec_off[:V + 1],
                                                  self._rec_row, self._rec_seg, R, words, self._f_seg, self._l_seg, fill=bool(fill),
                                                  workspace=self._workspace("finish", ops.lift_masks_stream_finish_workspace_bytes(n, V, R, words)))
-                feats = r.out
-                if fill:
-                    feats = ops.gather_rows(r.out, d4, torch.where(r.nn >= 0, r.nn, torch.arange(n, device=dev)))
-                feats = feats[:, :D].contiguous() if d4 != D else feats
+                feats = _fill_rows(r.out, d4, r.nn, D)
                 seen, count, status = r.seen.bool(), r.count, r.status
             view_count, view_keep = self._view_count[:V].clone(), self._view_keep[:V].bool()
-            st = ops.readback(status)
-        bad_batch, bad_view, nonfinite = st[:3]
-        if nonfinite:
-            raise ValueError(f"{who}: {nonfinite} rows of points are not finite")
-        if bad_batch:
-            raise ValueError(f"{who}: {bad_batch} rows have a batch index that is no integer in 0..65535")
-        if bad_view:
-            raise ValueError(f"{who}: {bad_view} views have a view_entry outside 0..65535")
-        if st[6] or st[7]:
-            raise RuntimeError(f"{who}: what the stream keeps does not hold together ({st[6]} values of the state, the offsets or the records, "
-                               f"{st[7]} view positions): it was overwritten, or the inputs changed during an add")
+            status = ops.readback(status)
+        _raise_status(who, status, torn=_STREAM_TORN)
         return LiftedMasks(feats, seen, count, view_count, view_keep, self.text_features, self.logit_scale)
 
 
