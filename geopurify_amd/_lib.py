@@ -250,6 +250,9 @@ SIGNATURES = {
     "gp_render_rows": (c_int32, [_P, c_int64, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_int32, _P, _P, _P, _P,
                                  _P, _P, c_size_t, _P]),
     "gp_render_gather": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int32, c_int64, _P]),
+    "gp_mesh_normals_batched_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "gp_mesh_normals_batched": (c_int32, [_P, c_int32, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gp_knn_normals": (c_int32, [_P, c_int32, c_int64, c_int64, _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

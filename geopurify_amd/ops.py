@@ -1988,6 +1988,90 @@ def render_gather(rows, src, index=None, dtype=torch.float32, out=None):
     return shaped
 
 
+# ------------------------------------------------------------------------------------------ geometry channels: normals
+KNN_NORMALS_MIN_K = 3
+
+
+def mesh_normals_workspace_bytes(n, num_faces, dtype=torch.float64):
+    """gp_mesh_normals_batched_workspace_bytes (no GPU needed)"""
+    return int(_lib.load().gp_mesh_normals_batched_workspace_bytes(int(n), int(num_faces), 1 if dtype == torch.float64 else 0))
+
+
+def mesh_normals_batched(points, faces, buffers=None, workspace=None):
+    """gp_mesh_normals_batched, no sync: the reference's vertex_normal (models/utils/mapping_util.py:9-29) for the meshes of several
+    entries at once, bit for bit, in the dtype of the points.  points f32 or f64 [n,4] = batch, x, y, z; faces i64 [F,3] of rows of
+    points, any order.  -> (normals [n,3] of the points' dtype, status i64 [8] = (bad batch rows, 0, non-finite rows, top batch, 0, 0,
+    faces with an index outside 0..n-1, faces whose rows are not of one entry)).  buffers: optional dict of caller-owned normals /
+    status; workspace: uint8 of at least mesh_normals_workspace_bytes(n, F, dtype)."""
+    lib = _lib.load()
+    who = "mesh_normals_batched"
+    if points.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{who}: points must be torch.float32 or torch.float64, got {points.dtype}")
+    _chk(points, points.dtype, "points"), _chk(faces, torch.int64, "faces")
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] < 1:
+        raise ValueError(f"{who}: expected points [n >= 1, 4], got {list(points.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"{who}: expected faces [F >= 1, 3], got {list(faces.shape)}")
+    n, nf, dev, fp64 = points.shape[0], faces.shape[0], points.device, 1 if points.dtype == torch.float64 else 0
+    got = _outputs(who, {"normals": (points.dtype, (n, 3)), "status": (torch.int64, (8,))}, buffers, dev)
+    need = lib.gp_mesh_normals_batched_workspace_bytes(n, nf, fp64)
+    if need == 0:
+        raise ValueError(f"{who}: {n} points / {nf} faces outside what the library takes")
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_mesh_normals_batched(_ptr(points), fp64, n, _ptr(faces), nf, _ptr(got["normals"]), _ptr(got["status"]), _ptr(ws), ws.numel(),
+                                      _stream()), "gp_mesh_normals_batched")
+    return got["normals"], got["status"]
+
+
+def knn_normals(positions, neighbors, toward=None, toward_rows=None, buffers=None):
+    """gp_knn_normals, no sync: for every row the direction of least spread of the row and its k listed rows -- the unit eigenvector of
+    the smallest eigenvalue l0 of C = sum (p - m)(p - m)^T, all in fp64 in list order -- and variation = l0 / (l0 + l1 + l2); what
+    stands in for the mesh normals of models/utils/mapping_util.py:19-29 where a cloud has no faces.  positions f32 or f64 [n, >= 3]
+    with unit column stride and any row stride (columns 0..2 are read in place: a column slice of a wider tensor is no copy);
+    neighbors i32 or i64 [n,k], 3 <= k <= 127.  Sign: with toward (floating [m,3]) and toward_rows (integer [n]) the vector of row i is
+    flipped where <n, toward[toward_rows[i]] - p_i> < 0 (left at exactly 0); without them its component of largest magnitude is made
+    positive, the lowest axis among equal magnitudes.  -> (normals f32 [n,3], variation f32 [n]).  A row with a list index outside
+    0..n-1 or a toward_rows outside 0..m-1 is returned as zeros (nothing is dereferenced) and counted in status i64 [2] = (rows with
+    a bad list index, rows with a bad toward row), which a caller reads from buffers["status"].  buffers: optional dict of
+    caller-owned normals / variation / status."""
+    lib = _lib.load()
+    who = "knn_normals"
+    P, Nb = positions, neighbors
+    if not torch.is_tensor(P) or P.dtype not in (torch.float32, torch.float64) or not P.is_cuda or P.dim() != 2 or P.shape[0] < 1 or P.shape[1] < 3 \
+            or P.stride(1) != 1 or P.stride(0) < 3:
+        raise ValueError(f"{who}: positions must be CUDA fp32 or fp64 [n >= 1, >= 3] with unit column stride and a row stride >= 3, got "
+                         f"{(P.dtype, list(P.shape), P.stride()) if torch.is_tensor(P) else type(P).__name__}")
+    n, dev = P.shape[0], P.device
+    if n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} rows outside 1..2^31-1")
+    if not torch.is_tensor(Nb) or Nb.dtype not in (torch.int32, torch.int64) or Nb.dim() != 2 or Nb.shape[0] != n:
+        raise ValueError(f"{who}: neighbors must be i32 or i64 [{n}, k], got {(Nb.dtype, list(Nb.shape)) if torch.is_tensor(Nb) else type(Nb).__name__}")
+    _chk(Nb, Nb.dtype, f"{who}: neighbors")
+    k = Nb.shape[1]
+    if not KNN_NORMALS_MIN_K <= k <= _lib.GP_KNN_MAX_K:
+        raise ValueError(f"{who}: k={k} outside {KNN_NORMALS_MIN_K}..{_lib.GP_KNN_MAX_K}")
+    if (toward is None) != (toward_rows is None):
+        raise ValueError(f"{who}: toward and toward_rows go together")
+    m = 0
+    if toward is not None:
+        if not torch.is_tensor(toward) or not toward.dtype.is_floating_point or toward.dim() != 2 or toward.shape[1] != 3 or toward.shape[0] < 1:
+            raise ValueError(f"{who}: toward must be floating point [m >= 1, 3], got "
+                             f"{(toward.dtype, list(toward.shape)) if torch.is_tensor(toward) else type(toward).__name__}")
+        if not torch.is_tensor(toward_rows) or toward_rows.dtype.is_floating_point or toward_rows.dtype == torch.bool or toward_rows.shape != (n,):
+            raise ValueError(f"{who}: toward_rows must be an integer tensor [{n}], got "
+                             f"{(toward_rows.dtype, list(toward_rows.shape)) if torch.is_tensor(toward_rows) else type(toward_rows).__name__}")
+        toward = toward.detach().to(torch.float64).contiguous()
+        toward_rows = toward_rows.detach().to(torch.int64).contiguous()
+        m = toward.shape[0]
+    if any(t.device != dev for t in (Nb, toward, toward_rows) if t is not None):
+        raise ValueError(f"{who}: positions, neighbors, toward and toward_rows must be on one device")
+    got = _outputs(who, {"normals": (torch.float32, (n, 3)), "variation": (torch.float32, (n,)), "status": (torch.int64, (2,))}, buffers, dev)
+    check(lib.gp_knn_normals(_ptr(P), 1 if P.dtype == torch.float64 else 0, P.stride(0), n, _ptr(Nb), 1 if Nb.dtype == torch.int64 else 0, k,
+                             _ptr(toward), m, _ptr(toward_rows), _ptr(got["normals"]), _ptr(got["variation"]), _ptr(got["status"]), _stream()),
+          "gp_knn_normals")
+    return got["normals"], got["variation"]
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

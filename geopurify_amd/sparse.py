@@ -43,6 +43,17 @@ label_2ds): the majority vote per point, its histogram, and the labels that segm
     voted = lift_labels(points, LabelViews(label_maps, view_entry, world_to_camera, intrinsics, depth), num_classes=C)
     # -> .labels i64 [N] (255 where nothing voted), .votes i32 [N,C]; LiftLabelsStream(points, C).add(...) / .finish() in chunks
 
+The student reads feature_dim + 6 input columns: the lifted features, then the geometry columns -- vertex colours in [0,1] and vertex
+normals (dataset/data_loader_ablation.py:162-163).  Colours come with every dataset (or from lift on the RGB images as 3-channel
+maps); the normals come from the scans' meshes the reference's way (models/utils/mapping_util.py:9-29, bit for bit), or, for a cloud
+without faces, from the neighbourhoods of its voxels:
+
+    normals = mesh_normals(points, faces)                       # faces: rows of points; all entries in one call
+    normals = estimate_normals(points, quantization_size=voxel, k=16, toward=camera_centres).normals   # no faces: poses and a cloud
+    q = quantize(points, torch.cat([lifted.features, colors, normals.float()], 1), mode="average", quantization_size=voxel)
+    x = SparseTensor(features=q.features, coordinates=q.coordinates)      # x.F = cat([lifted.features, colors, normals], 1), averaged
+    y = purify(student, x, feature_dim=D)
+
 The chain also has an end and a fourth start on disk: the fused-feature files that dataset/feature_loader.py:113-192 reads (lift once,
 then train and evaluate from files many times without the VLM)
 
@@ -107,6 +118,9 @@ fuse has no counterpart in the reference either (it ships the reader and the wri
 render_rows is ops.render_rows (the entry tables, with "render" the z-buffer of render_depth, then two order-free passes of integer
 atomic minima: the bit pattern of p_z, then the row), one read-back; Rendered.features is ops.render_gather, Rendered.labels torch
 indexing on the small maps, segment_views a compaction in torch around ops.iou_hist_batched.
+mesh_normals is ops.mesh_normals_batched (one lane per face, a stable radix sort of (vertex, face) pairs, one lane per vertex), one
+read-back; estimate_normals is quantize, knn and ops.knn_normals (fp64 covariance and a Jacobi eigen-solve in registers, the lists
+staged through LDS), then torch indexing by the inverse mapping.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -1688,6 +1702,122 @@ def knn(coordinates, k):
     with torch.cuda.device(coordinates.device):
         # sorted rows -> input rows, then the lists into the input's row order
         return perm.long()[nbr.long()].index_select(0, rank.long())
+
+
+# ------------------------------------------------------------------------------------------ the geometry columns: normals
+def mesh_normals(points, faces):
+    """The vertex normals the reference's loader hands the student (dataset/data_loader_ablation.py:162-163), computed the
+    reference's way from the scans' meshes (models/utils/dataset_utils.py:198-199 -> vertex_normal, models/utils/mapping_util.py:9-29)
+    -- for the meshes of all entries in one call, entries never mixing, bit for bit.  points fp64 or fp32 [N,4] = batch, x, y, z
+    exactly as lift takes them; faces integer [F,3] of ROW NUMBERS INTO points, in any order, the faces of different entries
+    interleaved at will.  -> normals [N,3] of the points' dtype: for every entry what vertex_normal returns on that entry alone with
+    local indices.
+      Arithmetic.  All in the dtype of points, every operation rounded once: vec = cross(p1 - p0, p2 - p0) with each product rounded
+        before the difference; length = sqrt((vec0^2 + vec1^2) + vec2^2) + 1e-8; the face contributes (vec / length) * (length * 0.5)
+        to each of its vertices, once to a vertex it names twice; a vertex sums its faces in ascending face index from 0; normal = sum
+        / (sqrt((s0^2 + s1^2) + s2^2) + 1e-8).  A vertex of no face gets a zero row, a zero-area face contributes zeros.
+      Order.  A vertex's faces come from a stable sort of (vertex, face) pairs, never from atomics on floats: two calls give the same
+        bits, and permuting the face rows changes a vertex's bits only where it changes the order of that vertex's own faces.
+    No gradients.  Inside: ops.mesh_normals_batched (a row check, one lane per face, the library's radix sort, one lane per vertex),
+    one read-back.  ValueError before any kernel: lift's refusals for points, faces that are no integer [F,3] with F >= 1, CPU tensors
+    or two devices; from the ONE status read-back: non-finite rows, rows whose batch index is no integer in 0..65535, faces with an
+    index outside 0..N-1, faces whose three rows belong to different entries."""
+    who = "mesh_normals"
+    P, Fc = points, faces
+    _check_points(who, P)
+    if not _is_int_tensor(Fc) or Fc.dim() != 2 or Fc.shape[1] != 3:
+        raise ValueError(f"{who}: faces must be an integer tensor [F, 3] of rows of points, got "
+                         f"{(list(Fc.shape), Fc.dtype) if torch.is_tensor(Fc) else type(Fc).__name__}")
+    if Fc.shape[0] == 0:
+        raise ValueError(f"{who}: no faces (F = 0): a cloud without a mesh takes estimate_normals")
+    if Fc.shape[0] * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: {Fc.shape[0]} faces, at most {(2 ** 31 - 1) // 3}")
+    _check_one_device(who, "points and faces", [P, Fc])
+    with torch.cuda.device(P.device), torch.no_grad():
+        normals, st = ops.mesh_normals_batched(P.detach().contiguous(), Fc.detach().to(torch.int64).contiguous())
+        status = ops.readback(st)
+    _raise_status(who, status)
+    if status[6]:
+        raise ValueError(f"{who}: {status[6]} faces have an index outside 0..{P.shape[0] - 1}")
+    if status[7]:
+        raise ValueError(f"{who}: {status[7]} faces name rows of different batch entries")
+    return normals
+
+
+class Normals:
+    """normals fp32 [N,3] and variation fp32 [N] per point (its voxel's), voxel_normals fp32 [nv,3] and voxel_variation fp32 [nv] per
+    voxel in the row order of quantized.coordinates, positions fp32 [nv,3] (the voxel centroids the covariance was taken over),
+    quantized (the Quantized of the points: quantized.inverse_mapping leads from a point to its voxel)."""
+
+    def __init__(self, normals, variation, voxel_normals, voxel_variation, positions, quantized):
+        self.normals, self.variation, self.voxel_normals, self.voxel_variation = normals, variation, voxel_normals, voxel_variation
+        self.positions, self.quantized = positions, quantized
+
+
+def estimate_normals(points, *, quantization_size, k=16, toward=None, quantized=None):
+    """Normals for a cloud that comes without faces (poses plus a reconstructed cloud, the depth="render" case): per voxel the
+    direction of least spread of the voxel's centroid and its k nearest voxels' inside the entry, handed back to every point of the
+    voxel -- the stand-in for mesh_normals in the student's geometry columns.  points as lift takes them (fp64 or fp32 [N,4]);
+    quantization_size as quantize takes it; 3 <= k <= 127.  toward orients the normals: None (the component of largest magnitude is
+    made positive, the lowest axis among equal magnitudes), floating [B,3] (one viewpoint per entry, indexed by the batch column; B
+    must exceed the highest batch index), or floating [N,3] (one target per point; a voxel takes that of its lowest point).  A
+    per-point target is, for example, the centre of the camera nearest to each point, which a caller has in two lines of torch:
+        centres = torch.linalg.inv(world_to_camera)[:, :3, 3]                 # [V,3]
+        toward = centres[torch.cdist(points[:, 1:], centres).argmin(1)]       # (per entry where the entries' views differ)
+    A vector is flipped where <n, target - centroid> < 0.  (toward of N rows is read per point, of any other length per entry.)
+      1. q = quantize(points, xyz as fp32 features, mode="average", quantization_size=...); a caller who quantised the same points at the
+         same size already passes quantized=q (with or without features) and saves that call's read-backs.
+      2. The voxel centroids are the three averaged columns (with quantized=q, whatever features q holds, xyz is averaged over q's
+         voxels by the same kernel in the same order, without a read-back: the same bits).
+      3. The lists are knn(q.coordinates, k): exact, inside each entry, so overlapping entries never see each other.
+      4. ops.knn_normals on the centroids, fp64 inside.
+      5. normals = voxel_normals[q.inverse_mapping].
+    -> Normals.  No gradients.  ValueError: lift's refusals for points, k outside 3..127, a toward that is no floating [B,3] / [N,3], a
+    quantized of another length; quantize's refusals; knn's, unchanged (an entry of k or fewer voxels, an axis extent of 32768 or more);
+    a [B,3] toward with B not above the highest batch index.  Read-backs: quantize's (none with quantized=), knn's one, and one of
+    two status words after the kernel."""
+    who = "estimate_normals"
+    P = points
+    _check_points(who, P)
+    if isinstance(k, bool) or not isinstance(k, int) or not ops.KNN_NORMALS_MIN_K <= k <= GP_KNN_MAX_K:
+        raise ValueError(f"{who}: k={k!r} outside {ops.KNN_NORMALS_MIN_K}..{GP_KNN_MAX_K}")
+    N = P.shape[0]
+    if toward is not None and (not torch.is_tensor(toward) or not toward.dtype.is_floating_point or toward.dim() != 2 or toward.shape[1] != 3
+                               or toward.shape[0] < 1):
+        raise ValueError(f"{who}: toward must be None, floating [B, 3] (a viewpoint per entry) or floating [{N}, 3] (a target per point), got "
+                         f"{(list(toward.shape), toward.dtype) if torch.is_tensor(toward) else type(toward).__name__}")
+    if quantized is not None and (not isinstance(quantized, Quantized) or quantized.inverse_mapping.shape[0] != N):
+        raise ValueError(f"{who}: quantized must be the Quantized of these {N} points, got "
+                         f"{quantized.inverse_mapping.shape[0] if isinstance(quantized, Quantized) else type(quantized).__name__}"
+                         f"{' rows' if isinstance(quantized, Quantized) else ''}")
+    _check_one_device(who, "points, toward and quantized",
+                      [P] + ([toward] if toward is not None else []) + ([quantized.coordinates] if quantized is not None else []))
+    with torch.cuda.device(P.device), torch.no_grad():
+        xyz = P.detach()[:, 1:].to(torch.float32)
+        q = quantized
+        if q is None:
+            q = quantize(P.detach(), xyz, mode="average", quantization_size=quantization_size)
+            centroids = q.features
+        else:
+            # the CSR form of q (a voxel's points in ascending row, as quantize reduced them) from what a Quantized keeps
+            nv = q.coordinates.shape[0]
+            order = torch.argsort(q.inverse_mapping, stable=True)
+            seg_start = torch.cat([torch.zeros(1, dtype=torch.int64, device=P.device), torch.cumsum(q.counts.to(torch.int64), 0).clamp(max=N)])
+            centroids = torch.empty((nv, 3), dtype=torch.float32, device=P.device)
+            ops.scatter_mean_csr(_rows_f32(xyz), 3, order, seg_start, nv, centroids)
+        nbr = knn(q.coordinates, k)
+        rows = None
+        if toward is not None:
+            rows = q.unique_index if toward.shape[0] == N else q.coordinates[:, 0]
+        status = torch.empty(2, dtype=torch.int64, device=P.device)
+        vn, vv = ops.knn_normals(centroids.detach(), nbr, toward, rows, buffers={"status": status})
+        bad_list, bad_toward = ops.readback(status)
+        if bad_toward:
+            raise ValueError(f"{who}: toward holds {toward.shape[0]} viewpoints, but {bad_toward} voxels are in entries beyond them")
+        if bad_list:
+            raise RuntimeError(f"{who}: {bad_list} neighbour lists name rows outside the voxels: the inputs changed during the call")
+        inv = q.inverse_mapping
+        return Normals(vn[inv], vv[inv], vn, vv, centroids, q)
 
 
 _MODE_OF_FAMILY = {"cs": "mfma_cs", "chain": "mfma_chain", "mfma": "mfma", "mfma_persist": "mfma_persist", "tiles": "tiles", "ell": "ell"}

@@ -1291,6 +1291,45 @@ int gp_render_rows(const double *points, int64_t n, const int64_t *view_entry, c
 int gp_render_gather(const int32_t *rows, int64_t npix, const int64_t *index, int64_t n_index, const float *src,
                      int64_t nrows, int64_t d, int64_t ld_src, void *out, int32_t elem_out, int64_t ld_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The geometry channels of BATCHED point clouds: vertex normals from meshes, and from neighbour lists */
+/* where a cloud has no faces (the student's six geometry columns are colours and vertex normals,      */
+/* dataset/data_loader_ablation.py:162-163; the reference takes the normals from the scan's mesh,      */
+/* models/utils/dataset_utils.py:198-199 -> vertex_normal, models/utils/mapping_util.py:9-29).         */
+/* gp_mesh_normals_batched: mapping_util.py:9-29 for the meshes of several entries at once, bit for    */
+/*   bit.  points [n,4] = batch, x, y, z and normals [n,3], both fp32 (fp64 = 0) or both fp64 (1);     */
+/*   faces i64 [nfaces,3] of rows of points, in any order, the faces of different entries interleaved  */
+/*   at will.  All arithmetic in the points' type, each operation rounded once: vec = cross(p1 - p0,   */
+/*   p2 - p0) with each product rounded before the difference (:10-12); length = sqrt((vec0^2 + vec1^2)*/
+/*   + vec2^2) + 1e-8 (:13); the contribution (vec / length) * (length * 0.5) (:14-15, :21); a vertex  */
+/*   sums the contributions of its faces in ascending face index from 0, a face that names it twice    */
+/*   counted once (:23-25, numpy's buffered +=); normal = sum / (sqrt((s0^2 + s1^2) + s2^2) + 1e-8)    */
+/*   (:27-28), so a vertex of no face gets a zero row.  The order comes from a stable sort of (vertex, */
+/*   face) pairs, never from float atomics: two calls give the same bits.  A face with an index        */
+/*   outside 0..n-1 (never dereferenced) or whose three rows are not in one valid entry contributes    */
+/*   nothing.  status i64 [8]: [0] rows whose batch index is no integer in 0..65535, [2] rows with a   */
+/*   non-finite value, [3] top batch index, [6] faces with an index outside 0..n-1, [7] faces whose    */
+/*   rows are not of one entry.  1 <= n < 2^31, 1 <= nfaces <= (2^31 - 1) / 3.                         */
+/* gp_knn_normals: for row i, in fp64, over the set i followed by its k listed rows in list order:     */
+/*   m = (sum p) / (k + 1), C = sum (p - m)(p - m)^T, l0 <= l1 <= l2 the eigenvalues of C (cyclic      */
+/*   Jacobi); normals[i] = the unit eigenvector of l0 -- what stands in for mapping_util.py:19-29      */
+/*   where there are no faces --, variation[i] = l0 / (l0 + l1 + l2) (0 where the sum is 0), both      */
+/*   rounded to fp32 last.  Every row gets a finite unit vector, also where l0 = l1 or the set is      */
+/*   collinear (the direction is then unspecified).  Sign: with toward f64 [m,3] and toward_rows i64   */
+/*   [n] the vector is flipped where <n, toward[toward_rows[i]] - p_i> < 0; with toward NULL (m = 0,   */
+/*   toward_rows NULL) its component of largest magnitude is made positive, the lowest axis among      */
+/*   equal magnitudes.  positions [n, ld_positions >= 3] fp32 (fp64 = 0) or fp64 (1), columns 0..2     */
+/*   read in place; neighbors [n,k] i32 (index64 = 0) or i64 (1), 3 <= k <= 127; normals f32 [n,3],    */
+/*   variation f32 [n]; status i64 [2]: [0] rows with a list index outside 0..n-1, [1] rows with a     */
+/*   toward_rows outside 0..m-1 -- such rows are returned as zeros and the index is never              */
+/*   dereferenced.  No workspace.  No output may overlap an input or another output (GP_EINVAL).      */
+size_t gp_mesh_normals_batched_workspace_bytes(int64_t n, int64_t nfaces, int32_t fp64);
+int gp_mesh_normals_batched(const void *points, int32_t fp64, int64_t n, const int64_t *faces, int64_t nfaces, void *normals,
+                            int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int gp_knn_normals(const void *positions, int32_t fp64, int64_t ld_positions, int64_t n, const void *neighbors, int32_t index64,
+                   int32_t k, const double *toward, int64_t m, const int64_t *toward_rows, float *normals, float *variation,
+                   int64_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
