@@ -8,10 +8,9 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_grid.h"
+#include "gp_scan_bytes.h"
 
 namespace {
-
-constexpr uint64_t kMorton48 = (1ull << 48) - 1;
 
 __global__ void init_kernel(int32_t *__restrict__ mm, int32_t *__restrict__ status) {
     if (threadIdx.x < 3) mm[threadIdx.x] = INT32_MAX;
@@ -170,12 +169,6 @@ __global__ void segment_labels_kernel(const int64_t *__restrict__ labels, int64_
     if (gp_lane() == 0) out[v] = differ ? ignore_label : first;
 }
 
-size_t scan_bytes(int64_t n) {
-    size_t tmp = 0;
-    (void)rocprim::exclusive_scan(nullptr, tmp, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return tmp;
-}
-
 size_t sort_bytes(int64_t nv) {
     size_t tmp = 0;
     (void)rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr,
@@ -240,7 +233,7 @@ struct QuantizeWs {
     uint64_t *k0, *k1;
     char *scan_tmp, *sort_tmp;
     size_t scan_tmp_bytes, sort_tmp_bytes;
-    QuantizeWs(GpCarver &cv, int64_t n) : scan_tmp_bytes(scan_bytes(n)), sort_tmp_bytes(sort_bytes(n)) {
+    QuantizeWs(GpCarver &cv, int64_t n) : scan_tmp_bytes(gp_scan_bytes<int32_t>(n)), sort_tmp_bytes(sort_bytes(n)) {
         mm = cv.take<int32_t>(8);
         k0 = cv.take<uint64_t>(n);
         k1 = cv.take<uint64_t>(n);

@@ -298,7 +298,7 @@ struct FuPlanWork {
           rank(cv.take<uint32_t>((size_t)num_files * cap)), hist(cv.take<uint32_t>((size_t)num_files * cap * 256)), r0(cv.take<int32_t>(n)),
           flag(cv.take<int32_t>(n + 1)), sel(cv.take<int32_t>(LB_MAX_ENTRIES + 1)), sel_idx(cv.take<int32_t>(LB_MAX_ENTRIES + 1)),
           sel_list(cv.take<int32_t>(cap)) {
-        tmp_bytes = std::max({lb_sort_bytes(n), lb_scan_bytes(n + 1), lb_scan_bytes(LB_MAX_ENTRIES + 1)});
+        tmp_bytes = std::max({lb_sort_bytes(n), gp_scan_bytes<int32_t>(n + 1), gp_scan_bytes<int32_t>(LB_MAX_ENTRIES + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -311,7 +311,7 @@ struct FuDenseWork {
     FuDenseWork(GpCarver &cv, int64_t n)
         : k0(cv.take<uint32_t>(n)), k1(cv.take<uint32_t>(n)), r0(cv.take<int32_t>(n)), entry_rows(cv.take<int32_t>(n)),
           flag(cv.take<int32_t>(n + 1)), scan(cv.take<int32_t>(n + 1)) {
-        tmp_bytes = std::max(lb_sort_bytes(n), lb_scan_bytes(n + 1));
+        tmp_bytes = std::max(lb_sort_bytes(n), gp_scan_bytes<int32_t>(n + 1));
         tmp = cv.take<char>(tmp_bytes);
     }
 };

@@ -14,6 +14,7 @@
 
 #include "gp_common.h"
 #include "gp_gfx950.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -63,12 +64,6 @@ fd_copy_kernel(const unsigned char *__restrict__ feat, int64_t row_bytes, const 
     for (int64_t i = lane; i < np; i += 64) d[i] = r < 0 ? z : s[i];
 }
 
-size_t fd_scan_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
-
 struct FdWork {
     int32_t *ones, *rank, *keep, *pos, *row;
     char *tmp;
@@ -81,7 +76,7 @@ size_t fd_carve(void *ws, size_t bytes, int64_t n, int64_t nv, FdWork &k) {
     k.keep = cv.take<int32_t>(nv + 1);
     k.pos = cv.take<int32_t>(nv + 1);
     k.row = cv.take<int32_t>(nv + 1);
-    const size_t a = fd_scan_tmp(n + 1), b = fd_scan_tmp(nv + 1);
+    const size_t a = gp_scan_bytes<int32_t>(n + 1), b = gp_scan_bytes<int32_t>(nv + 1);
     k.tmp_bytes = a > b ? a : b;
     k.tmp = cv.take<char>(k.tmp_bytes);
     return cv.off;

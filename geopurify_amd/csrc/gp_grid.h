@@ -54,6 +54,36 @@ __device__ __forceinline__ uint32_t gp_local9(int x, int y, int z) {
     return (uint32_t)gp_morton3(x & 7, y & 7, z & 7);
 }
 
+// ---- batched keys (gp_coords_order_batched): batch << 48 | gp_morton3(xyz - min), 16 bits per axis.  An 8^3 cell is key >> 9 =
+// batch << 39 | morton(cell coordinates), 13 bits per axis.
+constexpr uint64_t kMorton48 = (1ull << 48) - 1;
+constexpr int kMaxCellCoord = 65535 >> 3;
+
+// lower bound of q in a[0, n): the first index whose element is not below q (n when there is none)
+__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t *__restrict__ a, int64_t n, uint64_t q) {
+    int64_t lo = 0;
+    while (n > 0) {
+        const int64_t half = n >> 1;
+        if (a[lo + half] < q) { lo += half + 1; n -= half + 1; }
+        else n = half;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void decode_xyz(uint64_t key, int &x, int &y, int &z) {
+    const uint64_t m = key & kMorton48;
+    x = (int)gp_compact3(m);
+    y = (int)gp_compact3(m >> 1);
+    z = (int)gp_compact3(m >> 2);
+}
+
+// the rows of key's batch entry in the sorted a[0, n): [first key with these batch bits, first key of a higher batch index)
+__device__ __forceinline__ void entry_range_u64(const uint64_t *__restrict__ a, int64_t n, uint64_t key, int64_t &e0, int64_t &e1) {
+    const uint64_t batch = key >> 48;
+    e0 = lower_bound_u64(a, n, batch << 48);
+    e1 = batch == 65535 ? n : lower_bound_u64(a, n, (batch + 1) << 48);
+}
+
 struct GpGridView {
     const GpGridHeader *h;
     const int32_t *cell_index;

@@ -13,6 +13,7 @@
 #include "gp_common.h"
 #include "gp_map_elem.h"
 #include "gp_project.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -219,12 +220,6 @@ size_t lb_sort_bytes(int64_t n) {
     return t;
 }
 
-size_t lb_scan_bytes(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
-
 // ================================================================================================ host side
 // ------------------------------------------------------------------------------------------------ argument checks
 // Every output against every input and every later output, over their whole extents: for each output first all inputs, then the later
@@ -392,7 +387,7 @@ struct LbFill {                                                  // what the fil
 
 // keys / rows / off: the entry tables (the sort's, or the checked copies of a stream's state); mask: the rows that are references
 // ("seen", or "voted"); status words ST_SEEN and ST_QUERIES; fill == 0 stops before the search, nn is then not written.
-// tmp holds lb_scan_bytes(n + 1).
+// tmp holds gp_scan_bytes<int32_t>(n + 1).
 inline int lb_fill(const double *points, int64_t n, const uint32_t *keys, const int32_t *rows, const int32_t *off, const LbFill &f, char *tmp,
                    size_t tmp_bytes, const uint8_t *mask, int32_t fill, int64_t *nn, unsigned long long *st, hipStream_t s) {
     const unsigned nb = (unsigned)((n + 255) / 256), nb1 = (unsigned)((n + 1 + 255) / 256);

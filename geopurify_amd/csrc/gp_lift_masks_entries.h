@@ -12,12 +12,6 @@ namespace {
 
 enum { ST_LOST = 5, ST_TOTAL = 6, ST_MAX_VIEWS = 7, ST_BAD_ENTRY = 6, ST_BAD_WORDS = 7 };
 
-size_t lmb_scan64_bytes(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
-}
-
 // ------------------------------------------------------------------------------------------------ (2) the entries, checked
 // view_local[v] = the position of view v among the views of its entry (ascending view index: the sort is stable); -1 for a view
 // whose entry is outside 0..65535
@@ -234,7 +228,7 @@ struct LmbEntries {
 // seg[e] = the segment that entry e shows after the in-view fill, -1 for none.  The entries are checked and copied first -- an entry
 // that is not what the lists promise is counted in the status and replaced by one that decides nothing --, then the kernels of
 // gp_lift_masks.h run on the copies.  view_local: the position of every view inside its entry, -1 for none (lmb_view_local_kernel, or
-// a stream's view_pos).  tmp holds lb_scan_bytes(total + 1).
+// a stream's view_pos).  tmp holds gp_scan_bytes<int32_t>(total + 1).
 inline int lmb_chunk_segments(const double *points, int64_t n, const int64_t *view_entry, const int32_t *view_local, int32_t nviews,
                               const void *pred_masks, int32_t elem, int32_t q, int32_t h, int32_t w, const float *scores, const int32_t *tap_x0,
                               const float *tap_wx, const int32_t *tap_y0, const float *tap_wy, int32_t out_h, int32_t out_w,
@@ -277,7 +271,7 @@ struct LmbLists {                                                // the point ->
 
 // From the checked entries (or records) and their segments: every point's (view, segment) list in ascending position of the view
 // inside its entry, count, the consensus top-3 fusion (the kernel of the per-scene path: out, seen), and the scene-level fill inside
-// every entry over the tables keys / rows / off (nn).  tmp holds lb_scan_bytes(n + 1) and lmb_scan64_bytes(n + 1).
+// every entry over the tables keys / rows / off (nn).  tmp holds gp_scan_bytes<int32_t>(n + 1) and gp_scan_bytes<int64_t>(n + 1).
 inline int lmb_fuse_fill(const double *points, int64_t n, const int64_t *c_pt, const int32_t *c_view, const uint8_t *c_live,
                          const int32_t *view_local, const int32_t *seg, int64_t total, int32_t words, const LmbLists &l, const uint32_t *keys,
                          const int32_t *rows, const int32_t *off, const LbFill &f, char *tmp, size_t tmp_bytes, const float *f_seg,

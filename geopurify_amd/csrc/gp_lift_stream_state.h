@@ -163,7 +163,7 @@ struct LsFinishWork {
     char *tmp;
     size_t tmp_bytes;
     LsFinishWork(GpCarver &cv, int64_t n, size_t tmp_need = 0) : tables(cv, n), fill(cv, n) {
-        tmp_bytes = std::max(lb_scan_bytes(n + 1), tmp_need);
+        tmp_bytes = std::max(gp_scan_bytes<int32_t>(n + 1), tmp_need);
         tmp = cv.take<char>(tmp_bytes);
     }
 };

@@ -9,18 +9,13 @@
 // Queries whose (K+1)-th neighbour is not provably inside the block (or with too many ties) are
 // appended to a retry list for the next, larger ring; the last resort is an exhaustive scan with a
 // bisection on the (d^2, id) key, so the result is exact for every input.
-#include "gp_grid.h"
+//
+// The candidate table, the threshold / emit / tie / rank steps, the guarded retry list and the exhaustive scan are gp_knn_select.h's,
+// shared with knn_batched.hip and nn1_batched.hip; what is this file's own is the grid's cell functor, the coordinate loads and the
+// read-once (KEEP) form of the first ring.
+#include "gp_knn_select.h"
 
 namespace {
-
-constexpr int KNN_MAXSEL = 128;   // K+1 <= 128
-constexpr int KNN_MAXTIE = 256;    // ties at the threshold distance kept in LDS (more: the query retries on the next ring / exhaustively)
-
-template <int R>
-struct KnnCfg {
-    static constexpr int B = (8 * R + 1) * (8 * R + 1);
-    static constexpr int HB = (B + 63) / 64 * 64;
-};
 
 // KEEP candidates per lane stay in registers between pass 1 and pass 2 (first ring only): blocks of up to 64 KEEP candidates are read
 // ONCE -- pass 2 emits from what pass 1 kept, no second cell search and no second coordinate load.  A kept candidate is one word:
@@ -40,11 +35,11 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
     __shared__ int s_tieid[WAVES][KNN_MAXTIE];
     __shared__ int s_tierow[WAVES][KNN_MAXTIE];
     __shared__ int s_cnt[WAVES][2];
-    __shared__ int s_cstart[WAVES][(2 * R + 1) * (2 * R + 1) * (2 * R + 1)], s_coff[WAVES][(2 * R + 1) * (2 * R + 1) * (2 * R + 1) + 1];
+    __shared__ int s_cstart[WAVES][KnnCfg<R>::NC], s_coff[WAVES][KnnCfg<R>::NC + 1];
 
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int64_t widx = (int64_t)blockIdx.x * WAVES + wv;
-    int64_t total = qlist ? (int64_t)*qcount : nv;
+    int64_t total = qlist ? min((int64_t)*qcount, nv) : nv;
     if (widx >= total) return;
     const int qi = __builtin_amdgcn_readfirstlane(qlist ? qlist[widx] : (int)widx);
     GpGridView g(grid);
@@ -53,39 +48,13 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
     int *hist = s_hist[wv];
     for (int b = lane; b < HB; b += 64) hist[b] = 0;
     if (lane < 2) s_cnt[wv][lane] = 0;
-    // ---- candidate table: the (2R+1)^3 cells' (first row, rows before) in LDS, fetched with all lanes at once -- one round
-    // of dependent loads (cell index -> record) instead of one per cell -- and a flat candidate numbering 0 .. total-1
-    constexpr int SIDE = 2 * R + 1, NC = SIDE * SIDE * SIDE;
+    // ---- candidate table from the grid's records (a cell outside the grid or without a record holds nothing)
     int *cstart = s_cstart[wv], *coff = s_coff[wv];
-    int total_c = 0;
-    for (int c0 = 0; c0 < NC; c0 += 64) {
-        const int c = c0 + lane;
-        int start = 0, cnt = 0;
-        if (c < NC) {
-            const int dx = c % SIDE - R, dy = (c / SIDE) % SIDE - R, dz = c / (SIDE * SIDE) - R;
-            const int slot = g.cell_slot(cx0 + dx, cy0 + dy, cz0 + dz);
-            if (slot >= 0) { start = g.recs[slot].start; cnt = g.recs[slot].count; }
-        }
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (c < NC) { cstart[c] = start; coff[c] = total_c + incl - cnt; }
-        total_c += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) coff[NC] = total_c;
-    gp_wave_sync();
-    // candidate j -> row: the cell whose range holds j (binary search over the NC + 1 offsets in LDS)
-    auto row_of = [&](int j) {
-        int lo = 0, hi = NC - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (coff[mid] <= j) lo = mid; else hi = mid - 1;
-        }
-        return cstart[lo] + (j - coff[lo]);
-    };
+    const int total_c = knn_ring_candidates<R>(cx0, cy0, cz0, [g](int cx, int cy, int cz, int &start, int &cnt) {
+        const int slot = g.cell_slot(cx, cy, cz);
+        if (slot >= 0) { start = g.recs[slot].start; cnt = g.recs[slot].count; }
+    }, cstart, coff, lane);
+    auto row_of = [&](int j) { return knn_row_of<R>(cstart, coff, j); };
 
     // ---- pass 1: histogram of d^2 over the candidates (two per lane and round: both coordinate loads in flight together)
     static_assert(!KEEP || KnnCfg<R>::B <= 127, "a kept candidate holds d^2 in 7 bits");
@@ -125,59 +94,16 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
     gp_wave_sync();
 
     // ---- threshold: smallest T with cum(<=T) >= K+1
-    constexpr int CH = HB / 64;
-    int loc = 0;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) loc += hist[lane * CH + c];
-    int incl = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    int tot = __shfl(incl, 63, 64);
     const int need = k + 1;
-    bool fail = tot < need;
     int T = 0, c_lt = 0;
-    if (!fail) {
-        int excl = incl - loc;
-        unsigned long long m = __ballot(incl >= need);
-        int owner = __ffsll((long long)m) - 1;
-        int myT = 0, mylt = 0;
-        if (lane == owner) {
-            int run = excl;
-            for (int c = 0; c < CH; ++c) {
-                int h = hist[lane * CH + c];
-                if (run + h >= need) { myT = lane * CH + c; mylt = run; break; }
-                run += h;
-            }
-        }
-        T = __shfl(myT, owner, 64);
-        c_lt = __shfl(mylt, owner, 64);
-        if (hist[T] > KNN_MAXTIE) fail = true;
-    }
-    if (fail) {
-        if (lane == 0) {
-            int p = atomicAdd(fail_count, 1);
-            fail_list[p] = qi;
-        }
+    if (!knn_threshold<R>(hist, need, lane, T, c_lt)) {
+        knn_fail_append(fail_list, fail_count, nv, qi, lane);
         return;
     }
 
     // ---- pass 2: emit winners below T, collect ties at T
-    auto emit = [&](int64_t r, int d2) {
-        if (d2 < T) {
-            int id = ids ? ids[r] : (int)r;
-            int p = atomicAdd(&s_cnt[wv][0], 1);
-            s_selkey[wv][p] = ((unsigned long long)(unsigned)d2 << 32) | (unsigned)id;
-            s_selrow[wv][p] = (int)r;
-        } else if (d2 == T) {
-            int id = ids ? ids[r] : (int)r;
-            int p = atomicAdd(&s_cnt[wv][1], 1);
-            s_tieid[wv][p] = id;
-            s_tierow[wv][p] = (int)r;
-        }
-    };
+    const KnnSel sel{s_selkey, s_selrow, s_tieid, s_tierow, s_cnt, wv};
+    auto emit = [&](int64_t r, int d2) { knn_emit(sel, ids, r, d2, T); };
     if constexpr (KEEP) {
         if (kept) {
 #pragma unroll
@@ -193,27 +119,8 @@ knn_ring_kernel(const void *grid, const int32_t *__restrict__ coords, const int3
             emit(r, ex * ex + ey * ey + ez * ez);
         }
     }
-    gp_wave_sync();
-    const int m_tie = s_cnt[wv][1];
-    const int take = need - c_lt;                  // ties to keep: the `take` smallest ids
-    for (int t = lane; t < m_tie; t += 64) {
-        int id = s_tieid[wv][t];
-        int rank = 0;
-        for (int u = 0; u < m_tie; ++u) rank += (s_tieid[wv][u] < id);
-        if (rank < take) {
-            s_selkey[wv][c_lt + rank] = ((unsigned long long)(unsigned)T << 32) | (unsigned)id;
-            s_selrow[wv][c_lt + rank] = s_tierow[wv][t];
-        }
-    }
-    gp_wave_sync();
-
-    // ---- pass 3: rank sort of the K+1 winners, drop rank 0 (self)
-    for (int t = lane; t < need; t += 64) {
-        unsigned long long key = s_selkey[wv][t];
-        int rank = 0;
-        for (int u = 0; u < need; ++u) rank += (s_selkey[wv][u] < key);
-        if (rank > 0) nbr[(int64_t)qi * k + rank - 1] = s_selrow[wv][t];
-    }
+    // ---- ties by lowest id, then pass 3: rank sort of the K+1 winners, drop rank 0 (self)
+    knn_select_finish(sel, T, c_lt, need, lane, nbr + (int64_t)qi * k);
 }
 
 // Measured and left out (round 6; `knn_cell_kernel`, not in the tree): the first ring as one WORKGROUP PER 8^3 CELL -- the 27-cell block staged
@@ -230,47 +137,17 @@ knn_exhaustive_kernel(const int32_t *__restrict__ coords, const int32_t *__restr
     __shared__ unsigned long long s_selkey[KNN_MAXSEL];
     __shared__ int s_selrow[KNN_MAXSEL];
     __shared__ int s_n;
-    const int total = *qcount;
+    const int total = (int)min((int64_t)*qcount, nv);
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
         const int qi = qlist[w];
         const int qx = coords[(int64_t)qi * 3], qy = coords[(int64_t)qi * 3 + 1], qz = coords[(int64_t)qi * 3 + 2];
-        const int need = k + 1;
         auto keyof = [&](int64_t r) {
             long long ex = coords[r * 3] - qx, ey = coords[r * 3 + 1] - qy, ez = coords[r * 3 + 2] - qz;
             unsigned long long d2 = (unsigned long long)(ex * ex + ey * ey + ez * ez);
             unsigned id = (unsigned)(ids ? ids[r] : (int)r);
             return (d2 << 32) | id;      // extents are < 2^15 (gp_grid_build), so d2 < 2^32
         };
-        // smallest key value t such that count(key <= t) >= need, by bisection over 64 bits
-        unsigned long long lo = 0, hi = ~0ull;
-        while (lo < hi) {
-            unsigned long long mid = lo + ((hi - lo) >> 1);
-            int c = 0;
-            for (int64_t r = threadIdx.x; r < nv; r += 256) c += (keyof(r) <= mid);
-            c = gp_wave_sum_i(c);
-            __syncthreads();
-            if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
-            __syncthreads();
-            int tot = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-            if (tot >= need) hi = mid; else lo = mid + 1;
-        }
-        if (threadIdx.x == 0) s_n = 0;
-        __syncthreads();
-        for (int64_t r = threadIdx.x; r < nv; r += 256) {
-            unsigned long long key = keyof(r);
-            if (key <= lo) {
-                int p = atomicAdd(&s_n, 1);
-                if (p < KNN_MAXSEL) { s_selkey[p] = key; s_selrow[p] = (int)r; }
-            }
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < need; t += 256) {
-            unsigned long long key = s_selkey[t];
-            int rank = 0;
-            for (int u = 0; u < need; ++u) rank += (s_selkey[u] < key);
-            if (rank > 0) nbr[(int64_t)qi * k + rank - 1] = s_selrow[t];
-        }
-        __syncthreads();
+        knn_exhaustive_select(0, nv, k + 1, keyof, s_red, s_selkey, s_selrow, &s_n, nbr + (int64_t)qi * k);
     }
 }
 

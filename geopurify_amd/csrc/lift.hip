@@ -5,6 +5,7 @@
 
 #include "gp_common.h"
 #include "gp_project.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -405,16 +406,6 @@ extern "C" int gp_lift_masks_view(const float *pred_masks, int32_t q, int32_t h,
 }
 
 // ---- all views of a scene at once (entries from gp_views_visible_lists)
-static size_t lv_scan32_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
-static size_t lv_scan64_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
-}
 struct LvWork {
     LvSegWork seg;                                       // the segment decision and the in-view fill (gp_lift_masks.h); 130: 128 views + 2
     unsigned long long *vmask;
@@ -425,7 +416,7 @@ struct LvWork {
         : seg(cv, nsrc, q, h, w, total, fill_cap, sizeof(float), 130) {
         vmask = cv.take<unsigned long long>(n * 2);
         cnt = cv.take<int64_t>(n + 1);
-        size_t a = lv_scan32_tmp(total + 1), b = lv_scan64_tmp(n + 1);
+        size_t a = gp_scan_bytes<int32_t>(total + 1), b = gp_scan_bytes<int64_t>(n + 1);
         tmp_bytes = a > b ? a : b;
         tmp = cv.take<char>(tmp_bytes);
     }
@@ -500,9 +491,7 @@ extern "C" int gp_pv_count(const int64_t *pt, int64_t n_v, int64_t *cnt, void *s
 }
 
 extern "C" size_t gp_scan_workspace_bytes(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return gp_align_up(t, 256);
+    return gp_align_up(gp_scan_bytes<int64_t>(n), 256);
 }
 
 extern "C" int gp_exclusive_scan_i64(const int64_t *in, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes,

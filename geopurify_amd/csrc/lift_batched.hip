@@ -149,7 +149,7 @@ struct LbWork {
     char *tmp;
     size_t tmp_bytes;
     LbWork(GpCarver &cv, int64_t n, int32_t nviews) : t(cv, n, nviews), f(cv, n) {
-        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1)});
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), gp_scan_bytes<int32_t>(n + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };

@@ -189,7 +189,7 @@ struct LlWork {
     char *tmp;
     size_t tmp_bytes;
     LlWork(GpCarver &cv, int64_t n, int32_t nviews) : t(cv, n, nviews), f(cv, n) {
-        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1)});
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), gp_scan_bytes<int32_t>(n + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -200,7 +200,7 @@ struct LlFinishWork {                                            // the checked 
     char *tmp;
     size_t tmp_bytes;
     LlFinishWork(GpCarver &cv, int64_t n) : tables(cv, n), f(cv, n) {
-        tmp_bytes = lb_scan_bytes(n + 1);
+        tmp_bytes = gp_scan_bytes<int32_t>(n + 1);
         tmp = cv.take<char>(tmp_bytes);
     }
 };

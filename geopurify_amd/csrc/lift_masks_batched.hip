@@ -129,7 +129,7 @@ struct LmlWork {
         const int64_t nb = (n + 255) / 256;
         parts = (int)(nb < LML_PARTS ? nb : LML_PARTS);
         const size_t slots = (size_t)nviews * parts + 1;
-        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lmb_scan64_bytes((int64_t)slots)});
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), gp_scan_bytes<int64_t>((int64_t)slots)});
         blkcnt = cv.take<int64_t>(slots);
         scan = cv.take<int64_t>(slots);
         tmp = cv.take<char>(tmp_bytes);
@@ -149,7 +149,7 @@ struct LmbWork {
             int64_t fill_cap, size_t esize)
         : t(cv, n, nviews), f(cv, n), view_local(cv.take<int32_t>(nviews)), e(cv, n, nviews, out_h, out_w, total),
           k(cv, nviews, q, h, w, total, fill_cap, esize, (size_t)nviews + 1), l(cv, n, total, words) {
-        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), lb_scan_bytes(n + 1), lb_scan_bytes(total + 1), lmb_scan64_bytes(n + 1)});
+        tmp_bytes = std::max({lb_sort_bytes(n), lb_sort_bytes(nviews), gp_scan_bytes<int32_t>(n + 1), gp_scan_bytes<int32_t>(total + 1), gp_scan_bytes<int64_t>(n + 1)});
         tmp = cv.take<char>(tmp_bytes);
     }
 };

@@ -77,7 +77,7 @@ struct LmsAddWork {
             k = LvSegWork(cv, nviews, q, h, w, total, fill_cap, esize, (size_t)nviews + 1);
             seg = cv.take<int32_t>(total);
         }
-        tmp_bytes = std::max(lb_sort_bytes(nviews), lb_scan_bytes(total + 1));
+        tmp_bytes = std::max(lb_sort_bytes(nviews), gp_scan_bytes<int32_t>(total + 1));
         tmp = cv.take<char>(tmp_bytes);
     }
 };
@@ -90,7 +90,7 @@ struct LmsFinishWork {
     uint8_t *c_live, *c_keep;
     LmbLists l;                                                  // the point -> (view, segment) lists
     LmsFinishWork(GpCarver &cv, int64_t n, int32_t nviews, int64_t total, int32_t words)
-        : base(cv, n, lmb_scan64_bytes(n + 1)), view_local(cv.take<int32_t>(nviews)), c_view(cv.take<int32_t>(total)),
+        : base(cv, n, gp_scan_bytes<int64_t>(n + 1)), view_local(cv.take<int32_t>(nviews)), c_view(cv.take<int32_t>(total)),
           c_seg(cv.take<int32_t>(total)), voff(cv.take<int64_t>((size_t)nviews + 1)), c_pt(cv.take<int64_t>(total)),
           c_live(cv.take<uint8_t>(total)), c_keep(cv.take<uint8_t>(nviews)), l(cv, n, total, words) {}
 };

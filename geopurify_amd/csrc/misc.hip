@@ -3,6 +3,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -342,12 +343,6 @@ __global__ void vis_compact_kernel(const int64_t *__restrict__ mapping, const in
     if (i == n - 1) *count = sc[i] + (v ? 1 : 0);
 }
 
-size_t scan32_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
-
 int nn1_splits(int64_t n_ref, int64_t n_q) {
     int64_t qblocks = (n_q + 255) / 256;
     int s = (int)(2048 / (qblocks > 0 ? qblocks : 1));
@@ -670,7 +665,7 @@ extern "C" size_t gp_nn1_masked_workspace_bytes(int64_t n) {
     GpCarver cv(nullptr, 0);
     cv.take<int32_t>(n); cv.take<int32_t>(n); cv.take<int32_t>(n); cv.take<int32_t>(n);
     cv.take<float>(3 * n); cv.take<int64_t>(n); cv.take<int64_t>(n); cv.take<int32_t>(64);
-    cv.take<char>(scan32_tmp(n > (int64_t)NGMAX * NGMAX * NGMAX + 1 ? n : (int64_t)NGMAX * NGMAX * NGMAX + 1));
+    cv.take<char>(gp_scan_bytes<int32_t>(n > (int64_t)NGMAX * NGMAX * NGMAX + 1 ? n : (int64_t)NGMAX * NGMAX * NGMAX + 1));
     // grid path
     cv.take<float>(8); cv.take<int32_t>(n); cv.take<int32_t>((size_t)NGMAX * NGMAX * NGMAX + 1); cv.take<int32_t>((size_t)NGMAX * NGMAX * NGMAX + 1);
     cv.take<int32_t>((size_t)NGMAX * NGMAX * NGMAX + 1); cv.take<float>(3 * n); cv.take<int64_t>(n);
@@ -691,7 +686,7 @@ extern "C" int gp_nn1_masked_f64(const float *xyz, int64_t n, const uint8_t *ref
     int NG = g_gp_knobs[6] > 0 ? g_gp_knobs[6] : 128;
     if (NG > NGMAX) NG = NGMAX;
     const int64_t ncell = (int64_t)NG * NG * NG;
-    size_t tb = scan32_tmp(n > ncell_max + 1 ? n : ncell_max + 1);
+    size_t tb = gp_scan_bytes<int32_t>(n > ncell_max + 1 ? n : ncell_max + 1);
     char *tmp = cv.take<char>(tb);
     float *bb = cv.take<float>(8);
     int32_t *rcell = cv.take<int32_t>(n);
@@ -753,7 +748,7 @@ extern "C" int gp_nn1_masked_f64(const float *xyz, int64_t n, const uint8_t *ref
 extern "C" size_t gp_visible_lists_workspace_bytes(int64_t n) {
     if (n <= 0) return 0;
     GpCarver cv(nullptr, 0);
-    cv.take<int32_t>(n); cv.take<int32_t>(n); cv.take<char>(scan32_tmp(n));
+    cv.take<int32_t>(n); cv.take<int32_t>(n); cv.take<char>(gp_scan_bytes<int32_t>(n));
     return cv.off;
 }
 
@@ -762,7 +757,7 @@ extern "C" int gp_visible_lists(const int64_t *mapping, int64_t n, int64_t *pt, 
     GP_CHECK_ARG(mapping && pt && x && y && count_dev && workspace && n > 0, "gp_visible_lists: null/empty argument");
     GpCarver cv(workspace, workspace_bytes);
     int32_t *f = cv.take<int32_t>(n), *sc = cv.take<int32_t>(n);
-    size_t tb = scan32_tmp(n);
+    size_t tb = gp_scan_bytes<int32_t>(n);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_visible_lists: workspace too small"); return GP_ENOMEM; }
     hipStream_t st = gp_stream(stream_);

@@ -2,12 +2,13 @@
 //
 // The input is what gp_knn_batched takes -- the sorted keys of gp_coords_order_batched (batch << 48 | morton(xyz - min)) and the rows'
 // ids -- plus two masks in sorted-row order.  Coordinates are decoded from the keys.  The REFERENCE rows are compacted first (flags +
-// rocPRIM scan; the compacted keys stay sorted), and the 8^3 cell table of knn_batched.hip (cell = key >> 9, batch bits included; head
+// rocPRIM scan; the compacted keys stay sorted), and the 8^3 cell table of gp_key_cells.h (cell = key >> 9, batch bits included; head
 // flags + scan) is built over the reference keys only, so a cell holds nothing but candidates and a cell of another entry never
 // compares equal.
 //
-// One wave per query.  Ring R takes the references of the (2R+1)^3 cells around the query's cell (binary search of the cell keys, all
-// lanes at once) and reduces (d^2 << 32 | id) to its minimum over the wave.  The answer is final only when its d^2 is STRICTLY below
+// One wave per query.  Ring R takes the references of the (2R+1)^3 cells around the query's cell (gp_knn_select.h's candidate table, the
+// walk of the kNN kernels, over a binary search of the cell keys) and reduces (d^2 << 32 | id) to its minimum over the wave -- this
+// file's own reduction, with its own bound.  The answer is final only when its d^2 is STRICTLY below
 // (8R+1)^2: a reference outside the block differs from the query by 8R+1 or more on some axis (the query sits at offset 0..7 of its
 // cell, the block ends 8R cells' edges away), so its d^2 is at least (8R+1)^2 -- it cannot beat a smaller d^2, but at equality it can
 // hold the lower id.  Ladder: ring 1 for every query, ring 3 for what is left, then a scan of the entry's own reference rows -- the run
@@ -17,36 +18,15 @@
 // Bounds: every compacted index comes from the cell table (runs inside 0 .. nref-1) or from a lower bound inside 0 .. nref, nref <= nv
 // by construction of the scan; every sorted row stored in nn is rrow[] of such an index.  Integer arithmetic only; integer atomics only
 // (counters and the work lists, whose order does not reach the result).  Nothing waits on memory written by another workgroup.
-#include <rocprim/device/device_scan.hpp>
-
-#include "gp_grid.h"
+#include "gp_key_cells.h"
+#include "gp_knn_select.h"
 
 namespace {
 
-constexpr uint64_t kMorton48 = (1ull << 48) - 1;
-constexpr int kMaxCellCoord = 65535 >> 3;
 constexpr unsigned long long kNoKey = ~0ull;
 
 // workspace words (i32): [0] ring-1 failures, [1] ring-3 failures (or all queries with axes != 7), [2] reference rows, [3] cells
 enum { W_FAIL1 = 0, W_FAIL3 = 1, W_NREF = 2, W_NCELLS = 3 };
-
-// (lower_bound_u64 and decode_xyz: knn_batched.hip's, copied -- that file stays as it is)
-__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t *__restrict__ a, int64_t n, uint64_t q) {
-    int64_t lo = 0;
-    while (n > 0) {
-        const int64_t half = n >> 1;
-        if (a[lo + half] < q) { lo += half + 1; n -= half + 1; }
-        else n = half;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ void decode_xyz(uint64_t key, int &x, int &y, int &z) {
-    const uint64_t m = key & kMorton48;
-    x = (int)gp_compact3(m);
-    y = (int)gp_compact3(m >> 1);
-    z = (int)gp_compact3(m >> 2);
-}
 
 // minimum of (key, row) over the wave by key; every lane returns the winner (kNoKey: no lane held a candidate)
 __device__ __forceinline__ void wave_min_key(unsigned long long &key, int &row) {
@@ -97,29 +77,6 @@ __global__ void nb_compact_kernel(const uint64_t *__restrict__ keys, const int32
     if (i == nv - 1) words[W_NREF] = (int32_t)(j + (flag[i] ? 1 : 0));
 }
 
-// head[j] = 1 where the compacted row j < nref opens a cell; 0 for j >= nref, so the scan runs over nv elements whatever nref is
-__global__ void nb_cell_heads_kernel(const uint64_t *__restrict__ rkeys, const int32_t *__restrict__ words, int64_t nv, int32_t *__restrict__ head) {
-    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (j >= nv) return;
-    const int64_t nref = min((int64_t)words[W_NREF], nv);
-    head[j] = (j < nref && (j == 0 || (rkeys[j] >> 9) != (rkeys[j - 1] >> 9))) ? 1 : 0;
-}
-
-__global__ void nb_cell_table_kernel(const uint64_t *__restrict__ rkeys, const int32_t *__restrict__ head, const int32_t *__restrict__ cells_before,
-                                     int64_t nv, uint64_t *__restrict__ cell_key, int32_t *__restrict__ cell_start, int32_t *__restrict__ words) {
-    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t nref = min((int64_t)words[W_NREF], nv);
-    if (j >= nref) return;
-    const int64_t c = cells_before[j];
-    if ((uint64_t)c >= (uint64_t)nv) return;                  // (cannot happen: at most j heads before row j)
-    if (head[j]) { cell_key[c] = rkeys[j] >> 9; cell_start[c] = (int32_t)j; }
-    if (j == nref - 1) {
-        const int64_t nc = c + (head[j] ? 1 : 0);             // 1 .. nref
-        cell_start[nc] = (int32_t)nref;
-        words[W_NCELLS] = (int32_t)nc;
-    }
-}
-
 // axes != 7: every query goes to the entry scan
 __global__ void nb_collect_kernel(const uint8_t *__restrict__ query_mask, int64_t nv, int32_t *__restrict__ list, int32_t *__restrict__ count) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -136,9 +93,8 @@ nn1_batched_ring_kernel(const uint64_t *__restrict__ keys, const int32_t *__rest
                         const int32_t *__restrict__ cell_start, const int32_t *__restrict__ words, int32_t *__restrict__ nn,
                         const int32_t *__restrict__ qlist, const int32_t *__restrict__ qcount, int32_t *__restrict__ fail_list,
                         int32_t *__restrict__ fail_count) {
-    constexpr int SIDE = 2 * R + 1, NC = SIDE * SIDE * SIDE;
-    constexpr unsigned long long BOUND = (unsigned long long)(8 * R + 1) * (8 * R + 1);
-    __shared__ int s_cstart[WAVES][NC], s_coff[WAVES][NC + 1];
+    constexpr unsigned long long BOUND = KnnCfg<R>::B;
+    __shared__ int s_cstart[WAVES][KnnCfg<R>::NC], s_coff[WAVES][KnnCfg<R>::NC + 1];
 
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t widx = (int64_t)blockIdx.x * WAVES + wv;
@@ -150,48 +106,18 @@ nn1_batched_ring_kernel(const uint64_t *__restrict__ keys, const int32_t *__rest
     const uint64_t qkey = keys[qi];
     int qx, qy, qz;
     decode_xyz(qkey, qx, qy, qz);
-    const int cx0 = qx >> 3, cy0 = qy >> 3, cz0 = qz >> 3;
-    const uint64_t cell_batch = (qkey >> 48) << 39;                  // key >> 9 = batch << 39 | morton(cell coordinates), 13 bits per axis
     const int64_t nref = min((int64_t)words[W_NREF], nv);
-    const int64_t nc = min((int64_t)words[W_NCELLS], nref);
-    // candidate table, as knn_batched_ring_kernel: the block's cells' (first compacted row, candidates before) in LDS.  A cell outside
-    // 0..8191 on an axis has no key: skipped, never wrapped.
+    // the block's cells' (first compacted row, candidates before) in LDS
     int *cstart = s_cstart[wv], *coff = s_coff[wv];
-    int total_c = 0;
-    for (int c0 = 0; c0 < NC; c0 += 64) {
-        const int c = c0 + lane;
-        int start = 0, cnt = 0;
-        if (c < NC) {
-            const int cx = cx0 + c % SIDE - R, cy = cy0 + (c / SIDE) % SIDE - R, cz = cz0 + c / (SIDE * SIDE) - R;
-            if ((unsigned)cx <= (unsigned)kMaxCellCoord && (unsigned)cy <= (unsigned)kMaxCellCoord && (unsigned)cz <= (unsigned)kMaxCellCoord) {
-                const uint64_t q = cell_batch | gp_morton3((uint32_t)cx, (uint32_t)cy, (uint32_t)cz);
-                const int64_t at = lower_bound_u64(cell_key, nc, q);
-                if (at < nc && cell_key[at] == q) { start = cell_start[at]; cnt = cell_start[at + 1] - start; }
-            }
-        }
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (c < NC) { cstart[c] = start; coff[c] = total_c + incl - cnt; }
-        total_c += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) coff[NC] = total_c;
-    gp_wave_sync();
+    const KnnKeyCells cells{cell_key, cell_start, min((int64_t)words[W_NCELLS], nref), (qkey >> 48) << 39};
+    const int total_c = knn_ring_candidates<R>(qx >> 3, qy >> 3, qz >> 3, cells, cstart, coff, lane);
 
     unsigned long long best = kNoKey;
     int best_row = 0x7fffffff;
     for (int j0 = 0; j0 < total_c; j0 += 64) {
         const int j = j0 + lane;
         if (j < total_c) {
-            int lo = 0, hi = NC - 1;                                 // the cell whose range holds candidate j
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (coff[mid] <= j) lo = mid; else hi = mid - 1;
-            }
-            const int64_t r = cstart[lo] + (j - coff[lo]);           // compacted row, inside its cell's run
+            const int64_t r = knn_row_of<R>(cstart, coff, j);       // compacted row, inside its cell's run
             int x, y, z;
             decode_xyz(rkeys[r], x, y, z);
             // (rows of the block's cells: every coordinate difference is below 8 (R + 1))
@@ -204,9 +130,8 @@ nn1_batched_ring_kernel(const uint64_t *__restrict__ keys, const int32_t *__rest
     wave_min_key(best, best_row);
     if (best != kNoKey && (best >> 32) < BOUND) {
         if (lane == 0) nn[qi] = best_row;
-    } else if (lane == 0) {
-        const int p = atomicAdd(fail_count, 1);
-        if (p < nv) fail_list[p] = qi;
+    } else {
+        knn_fail_append(fail_list, fail_count, nv, qi, lane);
     }
 }
 
@@ -227,10 +152,8 @@ nn1_batched_scan_kernel(const uint64_t *__restrict__ keys, const int32_t *__rest
         const uint64_t qkey = keys[qi];
         int qx, qy, qz;
         decode_xyz(qkey, qx, qy, qz);
-        // the entry's references: [first compacted key with these batch bits, first of a higher batch index)
-        const uint64_t batch = qkey >> 48;
-        const int64_t e0 = lower_bound_u64(rkeys, nref, batch << 48);
-        const int64_t e1 = batch == 65535 ? nref : lower_bound_u64(rkeys, nref, (batch + 1) << 48);
+        int64_t e0, e1;                                              // the entry's references among the compacted keys
+        entry_range_u64(rkeys, nref, qkey, e0, e1);
         if (e1 <= e0) {
             if (threadIdx.x == 0) atomicAdd(&status[2], 1);          // nn[qi] keeps its -1
             continue;
@@ -262,29 +185,13 @@ nn1_batched_scan_kernel(const uint64_t *__restrict__ keys, const int32_t *__rest
     }
 }
 
-size_t scan_bytes(int64_t n) {
-    size_t tmp = 0;
-    (void)rocprim::exclusive_scan(nullptr, tmp, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return tmp;
-}
-
 struct Nn1BatchedWs {
-    int32_t *words, *list_a, *list_b, *flag, *before, *rrow, *cell_start;
-    uint64_t *rkeys, *cell_key;
-    char *scan_tmp;
-    size_t scan_tmp_bytes;
-    Nn1BatchedWs(GpCarver &cv, int64_t nv) : scan_tmp_bytes(scan_bytes(nv)) {
-        words = cv.take<int32_t>(64);
-        list_a = cv.take<int32_t>(nv);
-        list_b = cv.take<int32_t>(nv);
-        flag = cv.take<int32_t>(nv);                                 // reference flags, then the cell heads
-        before = cv.take<int32_t>(nv);                               // their exclusive scans
-        rrow = cv.take<int32_t>(nv);
-        cell_start = cv.take<int32_t>(nv + 1);
-        rkeys = cv.take<uint64_t>(nv);
-        cell_key = cv.take<uint64_t>(nv);
-        scan_tmp = cv.take<char>(scan_tmp_bytes);
-    }
+    int32_t *words, *list_a, *list_b, *rrow;
+    uint64_t *rkeys;
+    KeyCellWs cells;                                                 // (its head / before / scan_tmp serve the reference flags first)
+    Nn1BatchedWs(GpCarver &cv, int64_t nv)
+        : words(cv.take<int32_t>(64)), list_a(cv.take<int32_t>(nv)), list_b(cv.take<int32_t>(nv)), rrow(cv.take<int32_t>(nv)),
+          rkeys(cv.take<uint64_t>(nv)), cells(cv, nv) {}
 };
 
 // ------------------------------------------------------------------------------------------------ per-entry IoU histograms
@@ -353,26 +260,23 @@ extern "C" int gp_nn1_batched(const uint64_t *keys_sorted, const int32_t *ids, c
     hipStream_t s = gp_stream(stream_);
     const int blocks = (int)((nv + 255) / 256);
     nb_init_kernel<<<1, 64, 0, s>>>(ws.words, status);
-    nb_flags_kernel<<<blocks, 256, 0, s>>>(keys_sorted, ref_mask, query_mask, nv, ws.flag, nn, status);
+    nb_flags_kernel<<<blocks, 256, 0, s>>>(keys_sorted, ref_mask, query_mask, nv, ws.cells.head, nn, status);
     GP_CHECK_LAUNCH();
-    size_t tmp_io = ws.scan_tmp_bytes;
-    GP_CHECK_HIP(rocprim::exclusive_scan(ws.scan_tmp, tmp_io, ws.flag, ws.before, (int32_t)0, (size_t)nv, rocprim::plus<int32_t>(), s));
-    nb_compact_kernel<<<blocks, 256, 0, s>>>(keys_sorted, ws.flag, ws.before, nv, ws.rkeys, ws.rrow, ws.words);
+    size_t tmp_io = ws.cells.scan_tmp_bytes;
+    GP_CHECK_HIP(rocprim::exclusive_scan(ws.cells.scan_tmp, tmp_io, ws.cells.head, ws.cells.before, (int32_t)0, (size_t)nv,
+                                         rocprim::plus<int32_t>(), s));
+    nb_compact_kernel<<<blocks, 256, 0, s>>>(keys_sorted, ws.cells.head, ws.cells.before, nv, ws.rkeys, ws.rrow, ws.words);
     const int scan_blocks = (int)min((int64_t)2048, nv);
     if (axes == 7) {
-        nb_cell_heads_kernel<<<blocks, 256, 0, s>>>(ws.rkeys, ws.words, nv, ws.flag);
-        GP_CHECK_LAUNCH();
-        tmp_io = ws.scan_tmp_bytes;
-        GP_CHECK_HIP(rocprim::exclusive_scan(ws.scan_tmp, tmp_io, ws.flag, ws.before, (int32_t)0, (size_t)nv, rocprim::plus<int32_t>(), s));
-        nb_cell_table_kernel<<<blocks, 256, 0, s>>>(ws.rkeys, ws.flag, ws.before, nv, ws.cell_key, ws.cell_start, ws.words);
+        if (int rc = key_cell_table<true>(ws.rkeys, ws.words + W_NREF, nv, ws.cells, ws.words + W_NCELLS, nullptr, s)) return rc;
         constexpr int W1 = 4, W3 = 4;
         // ring 1: every row, the waves of rows that are no query leave at once
-        nn1_batched_ring_kernel<1, W1><<<(int)((nv + W1 - 1) / W1), W1 * 64, 0, s>>>(keys_sorted, ids, query_mask, nv, ws.rkeys, ws.rrow, ws.cell_key,
-                                                                                  ws.cell_start, ws.words, nn, nullptr, nullptr, ws.list_a,
+        nn1_batched_ring_kernel<1, W1><<<(int)((nv + W1 - 1) / W1), W1 * 64, 0, s>>>(keys_sorted, ids, query_mask, nv, ws.rkeys, ws.rrow, ws.cells.cell_key,
+                                                                                  ws.cells.cell_start, ws.words, nn, nullptr, nullptr, ws.list_a,
                                                                                   ws.words + W_FAIL1);
         // ring 3: what ring 1 left (grid sized for the worst case; surplus waves exit immediately)
-        nn1_batched_ring_kernel<3, W3><<<(int)((nv + W3 - 1) / W3), W3 * 64, 0, s>>>(keys_sorted, ids, query_mask, nv, ws.rkeys, ws.rrow, ws.cell_key,
-                                                                                  ws.cell_start, ws.words, nn, ws.list_a, ws.words + W_FAIL1,
+        nn1_batched_ring_kernel<3, W3><<<(int)((nv + W3 - 1) / W3), W3 * 64, 0, s>>>(keys_sorted, ids, query_mask, nv, ws.rkeys, ws.rrow, ws.cells.cell_key,
+                                                                                  ws.cells.cell_start, ws.words, nn, ws.list_a, ws.words + W_FAIL1,
                                                                                   ws.list_b, ws.words + W_FAIL3);
     } else {
         nb_collect_kernel<<<blocks, 256, 0, s>>>(query_mask, nv, ws.list_b, ws.words + W_FAIL3);

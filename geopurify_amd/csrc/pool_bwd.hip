@@ -4,6 +4,7 @@
 // slot i * k + j for the transposed lists), so the gradients are bitwise reproducible.  One wave per destination row (and 256-column
 // slab), 16 B per lane, wave-uniform indices and weights -- the shape of pool_ell_kernel.
 #include "gp_common.h"
+#include "gp_scan_bytes.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -22,12 +23,6 @@ __global__ void tr_keys_count_kernel(const int32_t *__restrict__ nbr, int64_t to
     keys[p] = ok ? (uint32_t)m : (uint32_t)nv;
     slots[p] = (int32_t)p;
     if (ok) atomicAdd(cnt + m, 1ull);
-}
-
-size_t tr_scan_bytes(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
 }
 
 int tr_key_bits(int64_t nv) {                                    // keys are 0 .. nv
@@ -250,7 +245,7 @@ extern "C" size_t gp_pool_transpose_workspace_bytes(int64_t nv, int32_t k) {
     cv.take<uint32_t>(total);
     cv.take<uint32_t>(total);
     cv.take<int32_t>(total);
-    cv.take<char>(tr_scan_bytes(nv + 1));
+    cv.take<char>(gp_scan_bytes<int64_t>(nv + 1));
     cv.take<char>(tr_sort_bytes(total, tr_key_bits(nv)));
     return cv.off;
 }
@@ -265,7 +260,7 @@ extern "C" int gp_pool_transpose_build(const int32_t *nbr, int64_t nv, int32_t k
     hipStream_t s = gp_stream(stream_);
     const int64_t total = nv * k;
     const int bits = tr_key_bits(nv);
-    const size_t scan_tmp = tr_scan_bytes(nv + 1), sort_tmp = tr_sort_bytes(total, bits);
+    const size_t scan_tmp = gp_scan_bytes<int64_t>(nv + 1), sort_tmp = tr_sort_bytes(total, bits);
     GpCarver cv(workspace, workspace_bytes);
     int64_t *cnt = cv.take<int64_t>(nv + 1);
     uint32_t *k0 = cv.take<uint32_t>(total);

@@ -18,6 +18,7 @@
 
 #include "gp_common.h"
 #include "gp_gfx950.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -852,12 +853,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) pool_mfma_tuning_ker
 #undef PQ_PARAMS
 #undef PQ_FWD
 
-size_t pm_scan_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
-}
-
 int pm_np2(int64_t n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 template <int NW, int NC, int MT, int CGN>
@@ -947,7 +942,7 @@ extern "C" size_t gp_pool_mfma_workspace_bytes(int64_t nv, int32_t block_rows) {
     int64_t nb = (nv + block_rows - 1) / block_rows;
     GpCarver cv(nullptr, 0);
     cv.take<int64_t>(nb + 1);
-    cv.take<char>(pm_scan_tmp(nb + 1));
+    cv.take<char>(gp_scan_bytes<int64_t>(nb + 1));
     return cv.off;
 }
 
@@ -961,7 +956,7 @@ extern "C" int gp_pool_mfma_count(const int32_t *nbr, int64_t nv, int32_t k, int
     int64_t nb = (nv + block_rows - 1) / block_rows;
     GpCarver cv(workspace, workspace_bytes);
     int64_t *cnt = cv.take<int64_t>(nb + 1);
-    size_t tb = pm_scan_tmp(nb + 1);
+    size_t tb = gp_scan_bytes<int64_t>(nb + 1);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_pool_mfma_count: workspace too small"); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);

@@ -22,6 +22,7 @@
 
 #include "gp_common.h"
 #include "gp_gfx950.h"
+#include "gp_scan_bytes.h"
 
 
 namespace {
@@ -989,11 +990,6 @@ cs_deps_sym_kernel(const int64_t *__restrict__ bu_off, const int32_t *__restrict
     }
 }
 
-size_t cs_scan_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
-}
 int cs_np2(int64_t n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 }  // namespace
@@ -1009,7 +1005,7 @@ extern "C" size_t gp_pool_cs_workspace_bytes(int64_t nv, int32_t rows_per_block)
     int64_t nb = (nv + rows_per_block - 1) / rows_per_block;
     GpCarver cv(nullptr, 0);
     cv.take<int64_t>(nb + 1);
-    cv.take<char>(cs_scan_tmp(nb + 1));
+    cv.take<char>(gp_scan_bytes<int64_t>(nb + 1));
     return cv.off;
 }
 
@@ -1023,7 +1019,7 @@ extern "C" int gp_pool_cs_count(const int32_t *nbr, int64_t nv, int32_t k, int32
     int64_t nb = (nv + rows_per_block - 1) / rows_per_block;
     GpCarver cv(workspace, workspace_bytes);
     int64_t *cnt = cv.take<int64_t>(nb + 1);
-    size_t tb = cs_scan_tmp(nb + 1);
+    size_t tb = gp_scan_bytes<int64_t>(nb + 1);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_pool_cs_count: workspace too small"); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);

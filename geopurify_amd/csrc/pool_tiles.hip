@@ -15,6 +15,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gp_common.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -290,12 +291,6 @@ pool_tiles64_kernel(const float *__restrict__ x, int64_t ld_x, const int64_t *__
     }
 }
 
-size_t scan64_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
-}
-
 }  // namespace
 
 #define g_pool_nf4 g_gp_knobs[1]
@@ -306,7 +301,7 @@ extern "C" size_t gp_pool_tiles_workspace_bytes(int64_t nv, int32_t r) {
     int64_t nt = (nv + r - 1) / r;
     GpCarver cv(nullptr, 0);
     cv.take<int64_t>(nt + 1);
-    cv.take<char>(scan64_tmp(nt + 1));
+    cv.take<char>(gp_scan_bytes<int64_t>(nt + 1));
     return cv.off;
 }
 
@@ -319,7 +314,7 @@ extern "C" int gp_pool_tiles_count(const int32_t *nbr, int64_t nv, int32_t k, in
     int64_t nt = (nv + r - 1) / r;
     GpCarver cv(workspace, workspace_bytes);
     int64_t *cnt = cv.take<int64_t>(nt + 1);
-    size_t tb = scan64_tmp(nt + 1);
+    size_t tb = gp_scan_bytes<int64_t>(nt + 1);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_pool_tiles_count: workspace too small"); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);

@@ -8,6 +8,7 @@
 // into the loss and the per-entry means.  No float atomics anywhere: every sum runs in an order that depends on the data alone, so
 // two calls give the same bits.
 #include "gp_common.h"
+#include "gp_scan_bytes.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -140,12 +141,6 @@ __global__ void __launch_bounds__(1024) sl_entry_weights_kernel(const unsigned l
         entry_w[b] = c == 0 ? 0.f : (float)(reduction ? 1.0 / (E * (double)c) : 1.0 / V);
     }
     if (threadIdx.x == 0) status[3] = tot[0];
-}
-
-size_t sl_scan_bytes(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), 0);
-    return t;
 }
 
 int sl_key_bits(int64_t top) {                                   // keys are 0 .. top
@@ -334,7 +329,7 @@ extern "C" size_t gp_segment_loss_items_workspace_bytes(int64_t n, int64_t p) {
     cv.take<uint32_t>(p);
     cv.take<uint32_t>(p);
     cv.take<int32_t>(p);
-    cv.take<char>(sl_scan_bytes(n + 1));
+    cv.take<char>(gp_scan_bytes<int64_t>(n + 1));
     cv.take<char>(sl_sort_bytes(p, sl_key_bits(n)));
     return cv.off;
 }
@@ -377,7 +372,7 @@ extern "C" int gp_segment_loss_items(const int32_t *coords, const uint8_t *zero,
     size_t scan_tmp = 0, sort_tmp = 0;
     const int bits = sl_key_bits(n);
     if (index) {
-        scan_tmp = sl_scan_bytes(n + 1);
+        scan_tmp = gp_scan_bytes<int64_t>(n + 1);
         sort_tmp = sl_sort_bytes(p, bits);
         GpCarver cv(workspace, workspace_bytes);
         cnt = cv.take<int64_t>(n + 1);

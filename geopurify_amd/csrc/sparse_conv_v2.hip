@@ -26,6 +26,7 @@
 
 #include "gp_common.h"
 #include "gp_gfx950.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -1342,12 +1343,6 @@ weight_split_blocked_kernel(const float *__restrict__ w, int kv, int cin, int co
     }
 }
 
-size_t scan_tmp32(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
-
 }  // namespace
 
 #define g_conv_ablate g_gp_knobs[3]
@@ -1358,7 +1353,7 @@ extern "C" size_t gp_conv_pairs_workspace_bytes(int64_t nv, int32_t kv) {
     GpCarver cv(nullptr, 0);
     cv.take<int32_t>((size_t)kv * nv);
     cv.take<int32_t>((size_t)kv * nv);
-    cv.take<char>(scan_tmp32((int64_t)kv * nv));
+    cv.take<char>(gp_scan_bytes<int32_t>((int64_t)kv * nv));
     return cv.off;
 }
 
@@ -1371,7 +1366,7 @@ extern "C" int gp_conv_pairs_build(const int32_t *nbr_map, int64_t nv, int32_t k
     int64_t total = (int64_t)kv * nv;
     GpCarver cv(workspace, workspace_bytes);
     int32_t *f = cv.take<int32_t>(total), *sc = cv.take<int32_t>(total);
-    size_t tb = scan_tmp32(total);
+    size_t tb = gp_scan_bytes<int32_t>(total);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_conv_pairs_build: workspace too small (%zu < %zu)", workspace_bytes, cv.off); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);

@@ -7,6 +7,7 @@
 
 #include "gp_common.h"
 #include "gp_project.h"
+#include "gp_scan_bytes.h"
 
 namespace {
 
@@ -266,15 +267,10 @@ extern "C" int gp_project_points_f64(const double *coords, int64_t n, const doub
     return GP_OK;
 }
 
-static size_t views_scan_tmp(int64_t n) {
-    size_t t = 0;
-    (void)rocprim::exclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), 0);
-    return t;
-}
 extern "C" size_t gp_views_visible_lists_workspace_bytes(int64_t n, int32_t nviews) {
     if (n <= 0 || nviews <= 0) return 0;
     GpCarver cv(nullptr, 0);
-    cv.take<int32_t>(n * nviews); cv.take<int32_t>(n * nviews); cv.take<char>(views_scan_tmp(n * nviews));
+    cv.take<int32_t>(n * nviews); cv.take<int32_t>(n * nviews); cv.take<char>(gp_scan_bytes<int32_t>(n * nviews));
     return cv.off;
 }
 extern "C" int gp_views_visible_lists(const double *coords, int64_t n, const double *params, const double *depth, int32_t nviews,
@@ -287,7 +283,7 @@ extern "C" int gp_views_visible_lists(const double *coords, int64_t n, const dou
     GP_CHECK_ARG(n * (int64_t)nviews < (int64_t)INT32_MAX, "gp_views_visible_lists: n * views must stay below 2^31");
     GpCarver cv(workspace, workspace_bytes);
     int32_t *flags = cv.take<int32_t>(n * nviews), *sc = cv.take<int32_t>(n * nviews);
-    size_t tb = views_scan_tmp(n * nviews);
+    size_t tb = gp_scan_bytes<int32_t>(n * nviews);
     char *tmp = cv.take<char>(tb);
     if (!cv.ok()) { gp_set_error("gp_views_visible_lists: workspace too small"); return GP_ENOMEM; }
     hipStream_t s = gp_stream(stream_);
