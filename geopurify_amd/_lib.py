@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("GP_LIB") or os.path.join(_HERE, "libgeopurify_hip.so"
 
 _P = c_void_p  # every device pointer travels as void*
 GP_KNN_MAX_K = 127  # include/geopurify_hip.h: K+1 <= 128
+GP_KNN_QUERY_MAX_K = 32  # include/geopurify_hip.h: gp_knn_query keeps a list in the lanes of one wave
 GP_ELEM_F32, GP_ELEM_F16, GP_ELEM_BF16 = 0, 1, 2  # include/geopurify_hip.h: the element-type tags of the batched lifts' *_t entry points
 GP_LABEL_U8, GP_LABEL_I16, GP_LABEL_I32, GP_LABEL_I64 = 0, 1, 2, 3  # include/geopurify_hip.h: the element-type tags of the label maps
 
@@ -253,6 +254,11 @@ SIGNATURES = {
     "gp_mesh_normals_batched_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "gp_mesh_normals_batched": (c_int32, [_P, c_int32, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "gp_knn_normals": (c_int32, [_P, c_int32, c_int64, c_int64, _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gp_knn_query_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gp_knn_query": (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_knn_interpolate": (c_int32, [_P, c_int32, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, c_int64, c_int32, c_double,
+                                     _P, _P, _P]),
+    "gp_knn_interpolate_labels": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P]),
 }
 
 _lib = None

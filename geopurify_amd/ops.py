@@ -2072,6 +2072,94 @@ def knn_normals(positions, neighbors, toward=None, toward_rows=None, buffers=Non
     return got["normals"], got["variation"]
 
 
+# ------------------------------------------------------------------------------------------ results carried to another cloud
+KNN_QUERY_STATUS_WORDS = 16
+KNN_INTERPOLATE_MODES = {"inverse_distance": 0, "nearest": 1}     # gp_knn_interpolate's mode
+
+
+def knn_query_workspace_bytes(n, m):
+    """gp_knn_query_workspace_bytes (no GPU needed): a function of the two row counts alone"""
+    return int(_lib.load().gp_knn_query_workspace_bytes(int(n), int(m)))
+
+
+def knn_query(points, queries, k, buffers=None, workspace=None):
+    """gp_knn_query, no sync: for every row of queries the k nearest rows of points inside the query's own batch entry, exactly (the
+    role of the KDTree queries of models/affinity_module.py:445-447, 693-697, for k neighbours, a second cloud and all entries at
+    once).  points f64 [n,4] and queries f64 [m,4] = batch, x, y, z; 1 <= k <= 32.  xyz rounded to fp32 first, d^2 = (dx*dx + dy*dy) +
+    dz*dz in fp64, a list ascending in (d^2, row).  -> (indices i64 [m,k] of rows of points, dist2 f64 [m,k], status i64 [16]); slots
+    past the entry's count hold -1 / +inf.  status: [0] / [2] rows of points with a batch index that is no integer in 0..65535 / with
+    a value that is not finite, [3] the points' top batch index, [8] / [10] the same two counts for the queries, [9] queries whose
+    entry has no points, [11] queries that took the entry scan, [12..15] queries that stopped after shell 0..3 of the grid walk.
+    buffers: optional dict of caller-owned indices / dist2 / status; workspace: uint8 of at least knn_query_workspace_bytes(n, m)."""
+    lib = _lib.load()
+    who = "knn_query"
+    n, dev = _chk_points(who, points)
+    _chk(queries, torch.float64, "queries")
+    if queries.dim() != 2 or queries.shape[1] != 4 or queries.shape[0] < 1:
+        raise ValueError(f"{who}: expected queries [m >= 1, 4], got {list(queries.shape)}")
+    m = queries.shape[0]
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: k={k!r} outside 1..{_lib.GP_KNN_QUERY_MAX_K}")
+    if queries.device != dev:
+        raise ValueError(f"{who}: points and queries must be on one device")
+    got = _outputs(who, {"indices": (torch.int64, (m, k)), "dist2": (torch.float64, (m, k)), "status": (torch.int64, (KNN_QUERY_STATUS_WORDS,))},
+                   buffers, dev)
+    need = lib.gp_knn_query_workspace_bytes(n, m)
+    if need == 0:
+        raise ValueError(f"{who}: {n} points / {m} queries outside what the library takes (1..2^31-1 each)")
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_knn_query(_ptr(points), n, _ptr(queries), m, k, _ptr(got["indices"]), _ptr(got["dist2"]), _ptr(got["status"]), _ptr(ws),
+                           ws.numel(), _stream()), "gp_knn_query")
+    return got["indices"], got["dist2"], got["status"]
+
+
+def knn_interpolate(values, indices, dist2, index=None, mode="inverse_distance", eps=1e-8, unlabeled=255, buffers=None):
+    """gp_knn_interpolate / gp_knn_interpolate_labels, no sync: rows of values carried through the lists of knn_query.  indices i64
+    [m,k], dist2 f64 [m,k]; index i64 [n] (point -> row of values) or None (the lists name rows of values).
+    Floating values [R,D] (fp32, fp16 or bf16, unit column stride, any row stride >= D, read in place) -> out f32 [m,D]: mode
+    "inverse_distance": w_j = 1 / (d^2_j + eps) in fp64 over the slots that are not -1, normalised in fp64 and rounded to fp32 (slots
+    with d^2_j + eps == 0 share the weight alone), out = sum_j w_j v_j in fp32 in list order; mode "nearest": slot 0.  A row without
+    a valid slot is zero.  values i64 [R] -> out i64 [m]: values at slot 0 whatever the mode, `unlabeled` where there is none.
+    A list entry outside -1..n-1 or an index value outside 0..R-1 is never dereferenced: the row is zero / unlabeled and counted in
+    status i64 [2] = (rows with such a list entry, rows with such an index value), which a caller reads from buffers["status"].
+    -> out.  buffers: optional dict of caller-owned out / status."""
+    lib = _lib.load()
+    who = "knn_interpolate"
+    _chk(indices, torch.int64, "indices"), _chk(dist2, torch.float64, "dist2")
+    if indices.dim() != 2 or indices.shape[0] < 1 or not 1 <= indices.shape[1] <= _lib.GP_KNN_QUERY_MAX_K or dist2.shape != indices.shape:
+        raise ValueError(f"{who}: expected indices and dist2 [m >= 1, 1 <= k <= {_lib.GP_KNN_QUERY_MAX_K}], got {list(indices.shape)} and "
+                         f"{list(dist2.shape)}")
+    m, k = indices.shape
+    dev = indices.device
+    if mode not in KNN_INTERPOLATE_MODES:
+        raise ValueError(f"{who}: mode={mode!r} must be one of {tuple(KNN_INTERPOLATE_MODES)}")
+    labels = values.dtype == torch.int64
+    if labels:
+        if _chk(values, torch.int64, "values").dim() != 1 or values.shape[0] < 1:
+            raise ValueError(f"{who}: expected integer values [R >= 1], got {list(values.shape)}")
+    elif values.dtype not in ELEM_TAG or not values.is_cuda or values.dim() != 2 or min(values.shape) < 1 or values.stride(1) != 1 \
+            or values.stride(0) < values.shape[1]:
+        raise ValueError(f"{who}: values must be CUDA fp32, fp16 or bf16 [R >= 1, D >= 1] with unit column stride and a row stride >= D (or "
+                         f"int64 [R]), got {values.dtype} {list(values.shape)} strides {values.stride()}")
+    R = values.shape[0]
+    if index is not None and (_chk(index, torch.int64, "index").dim() != 1 or index.shape[0] < 1):
+        raise ValueError(f"{who}: expected index [n >= 1], got {list(index.shape)}")
+    if any(t.device != dev for t in (values, dist2, index) if t is not None):
+        raise ValueError(f"{who}: values, indices, dist2 and index must be on one device")
+    n_index, npoints = (0, R) if index is None else (index.shape[0], index.shape[0])
+    if labels:
+        got = _outputs(who, {"out": (torch.int64, (m,)), "status": (torch.int64, (2,))}, buffers, dev)
+        check(lib.gp_knn_interpolate_labels(_ptr(values), R, _ptr(index), n_index, _ptr(indices), m, k, npoints, int(unlabeled), _ptr(got["out"]),
+                                            _ptr(got["status"]), _stream()), "gp_knn_interpolate_labels")
+        return got["out"]
+    D = values.shape[1]
+    got = _outputs(who, {"out": (torch.float32, (m, D)), "status": (torch.int64, (2,))}, buffers, dev)
+    check(lib.gp_knn_interpolate(_ptr(values), ELEM_TAG[values.dtype], R, D, values.stride(0), _ptr(index), n_index, _ptr(indices), _ptr(dist2),
+                                 m, k, npoints, KNN_INTERPOLATE_MODES[mode], float(eps), _ptr(got["out"]), _ptr(got["status"]), _stream()),
+          "gp_knn_interpolate")
+    return got["out"]
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

@@ -16,6 +16,13 @@ features out:
     per_point = y.F[q.inverse_mapping]
     seg = segment(y, text, scale, labels=point_labels, inverse_mapping=q.inverse_mapping)   # labels per point, (I, O, T) counts per scene
 
+and, where the cloud that is scored (a benchmark's vertices) is not the cloud that was lifted (a subsample, another reconstruction),
+the results carried over: the k nearest working points of every vertex inside its entry, exactly, and rows interpolated through them
+
+    nb = knn_query(points, benchmark_vertices, 3)
+    feat = interpolate(y.F, nb, index=q.inverse_mapping)            # purified features on the benchmark's vertices
+    pred = interpolate(seg.pred, nb, index=q.inverse_mapping)       # nearest working point's voxel prediction
+
 or, with the VLM producing its maps a batch of views at a time (the reference's own loop, :365-449), the same start without ever
 holding more than one batch of maps:
 
@@ -121,6 +128,9 @@ indexing on the small maps, segment_views a compaction in torch around ops.iou_h
 mesh_normals is ops.mesh_normals_batched (one lane per face, a stable radix sort of (vertex, face) pairs, one lane per vertex), one
 read-back; estimate_normals is quantize, knn and ops.knn_normals (fp64 covariance and a Jacobi eigen-solve in registers, the lists
 staged through LDS), then torch indexing by the inverse mapping.
+knn_query is ops.knn_query (the points' entry table, per entry a bounding box and a uniform grid, a wave per query walking the grid's
+shells in the (d^2, row) order of lift's fill, an entry scan for the queries the walk leaves), one read-back; interpolate is
+ops.knn_interpolate (a wave per query row, weights in fp64, sums in fp32 in list order), no read-back.
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -134,7 +144,7 @@ ops.segment_loss_rows, ops.segment_loss_reduce and ops.l2norm_rows_backward.
 import torch
 
 from . import ops
-from ._lib import GP_KNN_MAX_K
+from ._lib import GP_KNN_MAX_K, GP_KNN_QUERY_MAX_K
 
 MODES = ("average", "subsample")
 COLLISIONS = ("differ", "count", "first")
@@ -1702,6 +1712,127 @@ def knn(coordinates, k):
     with torch.cuda.device(coordinates.device):
         # sorted rows -> input rows, then the lists into the input's row order
         return perm.long()[nbr.long()].index_select(0, rank.long())
+
+
+# ------------------------------------------------------------------------------------------ results carried to another cloud
+INTERPOLATE_MODES = tuple(ops.KNN_INTERPOLATE_MODES)        # "inverse_distance", "nearest"
+INTERPOLATE_DTYPES = tuple(ops.ELEM_TAG)                    # fp32, fp16, bf16
+
+
+class Neighbors:
+    """What knn_query returns and interpolate reads: indices i64 [M,k] (rows of the points, -1 in the slots past the entry's count),
+    distances2 f64 [M,k] (the exact fp64 d^2 of the rule, +inf in those slots), num_points (N of the points the rows refer to; None
+    for lists made by hand: interpolate then takes the length of index, or of values, as the range)."""
+
+    def __init__(self, indices, distances2, num_points=None):
+        self.indices, self.distances2, self.num_points = indices, distances2, num_points
+
+
+def _check_cloud(who, name, letter, P):
+    """_check_points' checks and words for a cloud called `name`"""
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError(f"{who}: {name} must be [{letter}, 4] (batch, x, y, z), got {_shape_of(P)}")
+    if P.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: {name} must be fp64 or fp32, got {P.dtype}")
+    n = P.shape[0]
+    if n == 0 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} {name} outside 1..2^31-1")
+
+
+def knn_query(points, queries, k):
+    """The k nearest points of one cloud for every point of another, inside each batch entry, exactly: the way from a working cloud to
+    the vertices a benchmark scores on, or from an annotated mesh to the working cloud (the reference's preprocessors keep the two
+    apart; its KDTree queries, models/affinity_module.py:445-447, 693-697, are the k = 1, one-scene case).  points [N,4] and queries
+    [M,4]: fp64 or fp32, columns batch, x, y, z, on one GPU, any row order; entries may overlap in space and interleave in rows;
+    duplicate rows are allowed.  k: an int in 1..32.  -> Neighbors(indices i64 [M,k], distances2 f64 [M,k]).
+      The rule, the library's for float clouds (lift's scene-level fill): xyz is rounded to fp32 first; d^2 = (dx*dx + dy*dy) + dz*dz
+        in fp64, each operation rounded once; row j lists the points of query j's own entry in ascending (d^2, row).  indices are
+        input rows of points, distances2 those exact fp64 values.  A query never matches across entries.  A point that coincides
+        with a query is an ordinary neighbour at distance 0: nothing is dropped, unlike knn.
+      Short entries.  A query whose entry holds fewer than k points, none included, has -1 and +inf in the slots past the entry's
+        count: data, not an error.
+    No gradients.  Inside: ops.knn_query (the points' entry table, per entry a bounding box and a uniform grid of at most as many cells
+    as it has points, a wave per query walking the grid's shells, the queries it leaves scanning their entry), then ONE status
+    read-back, the call's only host synchronisation.  ValueError before any kernel: k that is a bool, no int or outside 1..32; points
+    or queries that are no fp64 / fp32 [*, 4] tensor with 1..2^31-1 rows; CPU tensors or two devices; from the read-back: rows of
+    points, or of queries, with a value that is not finite or with a batch index that is no integer in 0..65535."""
+    who = "knn_query"
+    P, Q = points, queries
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: k={k!r} outside 1..{GP_KNN_QUERY_MAX_K}")
+    _check_cloud(who, "points", "N", P)
+    _check_cloud(who, "queries", "M", Q)
+    _check_one_device(who, "points and queries", [P, Q])
+    with torch.cuda.device(P.device), torch.no_grad():
+        indices, dist2, st = ops.knn_query(_points64(P), _points64(Q), k)
+        status = ops.readback(st)
+    for name, base in (("points", 0), ("queries", 8)):
+        if status[base + 2]:
+            raise ValueError(f"{who}: {status[base + 2]} rows of {name} are not finite")
+        if status[base]:
+            raise ValueError(f"{who}: {status[base]} rows of {name} have a batch index that is no integer in 0..65535")
+    return Neighbors(indices, dist2, P.shape[0])
+
+
+def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, unlabeled=255, status=None):
+    """Rows carried through the lists of knn_query: purified features or predictions of the working cloud delivered on another
+    cloud's points.  nb: the Neighbors of knn_query(points, queries, k).
+      values floating [R,D] (fp32, fp16 or bf16; any row stride, unit column stride; read in place) -> fp32 [M,D], contiguous.
+        mode "inverse_distance": w_j = 1 / (d^2_j + eps) in fp64 over the valid slots, normalised in fp64 and rounded to fp32; out =
+        sum_j w_j v_j accumulated in fp32 in list order.  With eps = 0 a row with zero-distance neighbours takes the mean of exactly
+        those.  mode "nearest": slot 0.  A query with no valid slot gives a zero row.  A half input gives the bits of the same call on
+        its fp32 upcast.
+      values integer [R] (labels, predictions) -> int64 [M]: the value at slot 0 whatever the mode, `unlabeled` where there is none.
+      index: an optional integer [N], point -> row of values, as in Rendered.features: pass q.inverse_mapping to read per-voxel rows
+        through per-point lists.  Without it R == N.
+    A list entry outside -1..N-1 or an index value outside 0..R-1 is never dereferenced: the row comes back zero / `unlabeled` and is
+    counted.  The counts stay on the device and nothing is read back: pass status, an int64 [2] tensor on the values' device, to
+    receive (rows with such a list entry, rows with such an index value).
+    No autograd: values.requires_grad is ignored and the result is detached (gradients through the lists are not implemented).
+    Inside: ops.knn_interpolate (a wave per query row: the list read once, the weights in fp64 by k lanes, the rows gathered by the
+    widest loads the row stride allows), no host synchronisation.  ValueError: an nb that is no Neighbors; values that are neither
+    floating [R,D] of the three dtypes with unit column stride nor integer [R]; an index that is no integer [N]; R (or the index's
+    length) other than the N of nb; a mode outside INTERPOLATE_MODES; eps no finite number >= 0; unlabeled no int; CPU tensors or two
+    devices."""
+    who = "interpolate"
+    V = values
+    if not isinstance(nb, Neighbors):
+        raise ValueError(f"{who}: nb must be the Neighbors of knn_query, got {type(nb).__name__}")
+    I, D2 = nb.indices, nb.distances2
+    if not torch.is_tensor(I) or not torch.is_tensor(D2) or I.dtype != torch.int64 or D2.dtype != torch.float64 or I.dim() != 2 \
+            or D2.shape != I.shape or I.shape[0] < 1 or not 1 <= I.shape[1] <= GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: nb must hold indices i64 [M, k] and distances2 f64 [M, k] with M >= 1 and k in 1..{GP_KNN_QUERY_MAX_K}, got "
+                         f"{_shape_of(I)} and {_shape_of(D2)}")
+    labels = _is_int_tensor(V)
+    if labels:
+        if V.dim() != 1 or V.shape[0] < 1:
+            raise ValueError(f"{who}: integer values must be [R] with R >= 1, got {list(V.shape)}")
+    elif not torch.is_tensor(V) or V.dtype not in INTERPOLATE_DTYPES or V.dim() != 2 or min(V.shape) < 1:
+        raise ValueError(f"{who}: values must be fp32, fp16 or bf16 [R, D] with R, D >= 1, or an integer tensor [R], got "
+                         f"{(list(V.shape), V.dtype) if torch.is_tensor(V) else type(V).__name__}")
+    elif V.stride(1) != 1 or V.stride(0) < V.shape[1]:
+        raise ValueError(f"{who}: values must have unit column stride and a row stride >= D, got strides {V.stride()}")
+    if index is not None and (not _is_int_tensor(index) or index.dim() != 1 or index.shape[0] < 1):
+        raise ValueError(f"{who}: index must be an integer tensor [N] (point -> row of values), got "
+                         f"{(list(index.shape), index.dtype) if torch.is_tensor(index) else type(index).__name__}")
+    span, what = (V.shape[0], "values") if index is None else (index.shape[0], "index")
+    if nb.num_points is not None and span != nb.num_points:
+        raise ValueError(f"{who}: {what} holds {span} rows, the lists name rows of {nb.num_points} points"
+                         f"{' (pass index, point -> row of values)' if index is None else ''}")
+    if mode not in INTERPOLATE_MODES:
+        raise ValueError(f"{who}: mode={mode!r} must be one of {INTERPOLATE_MODES}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
+        raise ValueError(f"{who}: eps={eps!r} must be a finite number >= 0")
+    if isinstance(unlabeled, bool) or not isinstance(unlabeled, int) or not -2 ** 63 <= unlabeled < 2 ** 63:
+        raise ValueError(f"{who}: unlabeled={unlabeled!r} must be an int")
+    if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int64 or status.shape != (2,) or not status.is_contiguous()):
+        raise ValueError(f"{who}: status must be a contiguous int64 [2] tensor, got {_shape_of(status)}")
+    _check_one_device(who, "values, nb, index and status", [V, I, D2] + [t for t in (index, status) if t is not None])
+    with torch.cuda.device(V.device), torch.no_grad():
+        vals = V.detach().to(torch.int64).contiguous() if labels else V.detach()
+        idx = None if index is None else index.detach().to(torch.int64).contiguous()
+        return ops.knn_interpolate(vals, I.detach().contiguous(), D2.detach().contiguous(), idx, mode, float(eps), unlabeled,
+                                   buffers=None if status is None else {"status": status})
 
 
 # ------------------------------------------------------------------------------------------ the geometry columns: normals

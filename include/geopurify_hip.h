@@ -1330,6 +1330,48 @@ int gp_knn_normals(const void *positions, int32_t fp64, int64_t ld_positions, in
                    int32_t k, const double *toward, int64_t m, const int64_t *toward_rows, float *normals, float *variation,
                    int64_t *status, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Results carried from one BATCHED cloud to another: the k nearest points of cloud A for every point  */
+/* of cloud B, per batch entry, exactly, and rows interpolated through such lists.  The role of the    */
+/* reference's KDTree queries (models/affinity_module.py:445-447, 693-697: the nearest seen point of   */
+/* every unseen one), generalised to k neighbours, to a second cloud and to several entries at once.   */
+/* gp_knn_query: points f64 [n,4] and queries f64 [m,4] = batch, x, y, z in any row order, duplicates  */
+/*   allowed.  xyz rounded to fp32 first; d^2 = (dx*dx + dy*dy) + dz*dz in fp64, each operation        */
+/*   rounded once; row j of a query lists the points of the query's own entry in ascending (d^2, row): */
+/*   indices i64 [m,k] (rows of points), dist2 f64 [m,k] (those d^2).  A coinciding point is an        */
+/*   ordinary neighbour at distance 0.  Slots past the entry's count hold -1 / +inf.  Per entry a      */
+/*   uniform grid of ng^3 <= max(count, 1) cubic cells over its fp32 bounding box; one wave per query  */
+/*   walks the shells of Chebyshev radius 0..3 around the query's (clamped) cell and stops after shell */
+/*   r once it holds k points with d^2_k <= (r h (1 - 1e-9))^2, or the shells cover the grid; the      */
+/*   queries left over scan their whole entry, one workgroup each.  1 <= k <= GP_KNN_QUERY_MAX_K.      */
+/*   status i64 [16]: [0] rows of points whose batch index is no integer in 0..65535, [2] rows of      */
+/*   points with a value that is not finite (in fp64, or xyz in fp32), [3] top batch index of the      */
+/*   points; [8], [10]: the same two counts for the queries (such a query gets -1 / +inf);             */
+/*   [9] queries whose entry has no points; [11] queries that took the entry scan; [12 + r] queries    */
+/*   that stopped after shell r = 0..3.  1 <= n, m < 2^31.  No read-back inside.                        */
+/* gp_knn_interpolate: out f32 [m,d], contiguous.  values [nrows, ld_values >= d] of element type elem */
+/*   (GP_ELEM_F32 / _F16 / _BF16), read in place; index i64 [n_index] (point -> row of values) or NULL */
+/*   with n_index 0; npoints = the range of the list entries (n_index with an index, nrows without).   */
+/*   mode 0 (inverse distance): over the slots with indices != -1, w_j = 1 / (d^2_j + eps) in fp64,    */
+/*   normalised in fp64, rounded to fp32; where some d^2_j + eps is 0, those slots share the weight    */
+/*   equally and the others get 0.  mode 1 (nearest): slot 0 with weight 1.  out = sum_j w_j v_j in    */
+/*   fp32 in list order, each product and each sum rounded once.  A row without a valid slot is zero.  */
+/*   A list entry outside -1..npoints-1 or an index value outside 0..nrows-1 (of the slots the mode    */
+/*   reads) is never dereferenced: the row is zero and counted in status i64 [2]: [0] rows with such a */
+/*   list entry, [1] rows with such an index value.                                                     */
+/* gp_knn_interpolate_labels: out i64 [m] = values[index ? index[indices[q,0]] : indices[q,0]], or     */
+/*   `unlabeled` where slot 0 is -1 or out of range (counted as above).  values i64 [nrows].           */
+/* No output may overlap an input or another output (GP_EINVAL).                                       */
+#define GP_KNN_QUERY_MAX_K 32
+size_t gp_knn_query_workspace_bytes(int64_t n, int64_t m);
+int gp_knn_query(const double *points, int64_t n, const double *queries, int64_t m, int32_t k, int64_t *indices, double *dist2,
+                 int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int gp_knn_interpolate(const void *values, int32_t elem, int64_t nrows, int64_t d, int64_t ld_values, const int64_t *index,
+                       int64_t n_index, const int64_t *indices, const double *dist2, int64_t m, int32_t k, int64_t npoints,
+                       int32_t mode, double eps, float *out, int64_t *status, void *stream);
+int gp_knn_interpolate_labels(const int64_t *values, int64_t nrows, const int64_t *index, int64_t n_index, const int64_t *indices,
+                              int64_t m, int32_t k, int64_t npoints, int64_t unlabeled, int64_t *out, int64_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
