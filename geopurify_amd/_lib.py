@@ -259,6 +259,10 @@ SIGNATURES = {
     "gp_knn_interpolate": (c_int32, [_P, c_int32, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, c_int64, c_int32, c_double,
                                      _P, _P, _P]),
     "gp_knn_interpolate_labels": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P]),
+    "gp_knn_interpolate_weights": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, c_int64, c_int64, c_int32, c_double, _P, _P]),
+    "gp_knn_interpolate_transpose_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
+    "gp_knn_interpolate_transpose": (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gp_knn_interpolate_backward": (c_int32, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_int64, _P, c_int32, _P]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@
 // every unseen point is at least r * h away, so the walk stops once d^2_k <= (r h (1 - 1e-9))^2 or the shells cover the grid.  The queries
 // left over are listed and scan their whole entry, one workgroup each, the four waves' lists merged through LDS.  The lists do not
 // depend on the order candidates arrive in: the k smallest of a total order.  No kernel waits on another workgroup.
+#include "gp_knn_interp.h"
 #include "gp_lift_entries.h"
 
 namespace {
@@ -432,18 +433,13 @@ __global__ void __launch_bounds__(256) kq_scan_kernel(const double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ interpolation
-enum { KI_INVERSE_DISTANCE = 0, KI_NEAREST = 1, KI_WORDS = 2 };
+enum { KI_WORDS = 2 };
 constexpr int KI_BLOCKS = 1 << 16;
 
-__device__ __forceinline__ double kq_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One wave per query row.  Lanes 0 .. slots-1 read the list once, check it and make the weights in fp64; the rows and the fp32 weights
-// go through the wave's LDS slice, and every lane then runs the slots in list order over its columns: VEC columns per load where the
-// base and the pitch allow it, the columns past the last whole group one by one; wide_store: rows of out are 16-byte aligned.
+// One wave per query row.  Lanes 0 .. slots-1 read the list once, check it and make the weights in fp64 (ki_list_weights of
+// gp_knn_interp.h, the backward's definition too); the rows and the fp32 weights go through the wave's LDS slice, and every lane then
+// runs the slots in list order over its columns: VEC columns per load where the base and the pitch allow it, the columns past the
+// last whole group one by one; wide_store: rows of out are 16-byte aligned.
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256) ki_kernel(const T *__restrict__ values, int64_t nrows, int64_t d, int64_t ld,
                                                  const int64_t *__restrict__ index, const int64_t *__restrict__ indices,
@@ -455,36 +451,13 @@ __global__ void __launch_bounds__(256) ki_kernel(const T *__restrict__ values, i
     const int slots = mode == KI_NEAREST ? 1 : k;                    // <= KQ_MAX_K
     unsigned c_list = 0, c_index = 0;
     for (int64_t q = (int64_t)blockIdx.x * 4 + w; q < m; q += (int64_t)gridDim.x * 4) {
-        int64_t row = -1;
-        double d2 = 0.0;
-        bool bad_list = false, bad_index = false;
-        if (lane < slots) {
-            const int64_t id = indices[q * k + lane];
-            if (id != -1) {
-                if ((uint64_t)id >= (uint64_t)npoints) bad_list = true;
-                else {
-                    row = index ? index[id] : id;
-                    if ((uint64_t)row >= (uint64_t)nrows) { bad_index = true; row = -1; }
-                }
-                d2 = dist2[q * k + lane];
-            }
-        }
-        const bool any_list = __ballot(bad_list) != 0, any_index = __ballot(bad_index) != 0;
+        float wt;
+        bool any_list, any_index;
+        const int64_t row = ki_list_weights(indices, dist2, index, q, k, slots, npoints, nrows, mode, eps, wt, any_list, any_index);
         c_list += any_list ? 1 : 0;
         c_index += any_index ? 1 : 0;
-        double wt = 0.0;
-        if (mode == KI_NEAREST) wt = row >= 0 ? 1.0 : 0.0;
-        else {
-            const double t = d2 + eps;
-            const bool zero = row >= 0 && t == 0.0;
-            const bool any_zero = __ballot(zero) != 0;
-            const double w0 = row >= 0 ? (any_zero ? (zero ? 1.0 : 0.0) : 1.0 / t) : 0.0;
-            const double sum = kq_wave_sum_d(w0);
-            wt = sum > 0.0 ? w0 / sum : 0.0;
-        }
-        if (any_list || any_index) row = -1;                             // a zero row
         gp_wave_sync();                                                  // (the previous row's reads are done)
-        if (lane < slots) { s_row[w][lane] = row; s_w[w][lane] = (float)wt; }
+        if (lane < slots) { s_row[w][lane] = row; s_w[w][lane] = wt; }
         gp_wave_sync();
         float *o = out + q * d;
         const int64_t whole = VEC > 1 ? d / VEC * VEC : 0;

@@ -2160,6 +2160,103 @@ def knn_interpolate(values, indices, dist2, index=None, mode="inverse_distance",
     return got["out"]
 
 
+KNN_INTERPOLATE_MAX_SLOTS = 2 ** 31 - 1                           # flat slots j * k + s of the backward are i32
+
+
+def _chk_knn_lists(who, indices, index, nrows, mode, dist2=None):
+    """the lists of the interpolation's backward: indices i64 [m,k] (dist2 f64 alike, where given), index i64 [n] or None, nrows the
+    rows of values -> (m, k, n_index, npoints, their device)"""
+    _chk(indices, torch.int64, "indices")
+    if indices.dim() != 2 or indices.shape[0] < 1 or not 1 <= indices.shape[1] <= _lib.GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: expected indices [m >= 1, 1 <= k <= {_lib.GP_KNN_QUERY_MAX_K}], got {list(indices.shape)}")
+    m, k = indices.shape
+    if dist2 is not None and _chk(dist2, torch.float64, "dist2").shape != indices.shape:
+        raise ValueError(f"{who}: expected dist2 {list(indices.shape)}, got {list(dist2.shape)}")
+    if m * k > KNN_INTERPOLATE_MAX_SLOTS:
+        raise ValueError(f"{who}: m * k = {m * k} flat slots, more than 2^31-1")
+    if isinstance(nrows, bool) or not isinstance(nrows, int) or not 1 <= nrows < 2 ** 31:
+        raise ValueError(f"{who}: nrows={nrows!r} outside 1..2^31-1")
+    if mode not in KNN_INTERPOLATE_MODES:
+        raise ValueError(f"{who}: mode={mode!r} must be one of {tuple(KNN_INTERPOLATE_MODES)}")
+    if index is not None and (_chk(index, torch.int64, "index").dim() != 1 or index.shape[0] < 1):
+        raise ValueError(f"{who}: expected index [n >= 1], got {list(index.shape)}")
+    if any(t.device != indices.device for t in (dist2, index) if t is not None):
+        raise ValueError(f"{who}: indices, dist2 and index must be on one device")
+    n_index, npoints = (0, nrows) if index is None else (index.shape[0], index.shape[0])
+    return m, k, n_index, npoints, indices.device
+
+
+def knn_interpolate_weights(indices, dist2, index=None, nrows=None, mode="inverse_distance", eps=1e-8, buffers=None):
+    """gp_knn_interpolate_weights, no sync: the fp32 weights knn_interpolate applies, by the same device code, as weights f32 [m,k]; 0
+    where the slot is no reference (a -1 entry, a slot the mode does not read, a query row with a list entry outside -1..n-1 or an
+    index value outside 0..nrows-1).  nrows: the rows of values (R).  buffers: optional dict with a caller-owned weights."""
+    lib = _lib.load()
+    who = "knn_interpolate_weights"
+    m, k, n_index, npoints, dev = _chk_knn_lists(who, indices, index, nrows, mode, dist2)
+    got = _outputs(who, {"weights": (torch.float32, (m, k))}, buffers, dev)
+    check(lib.gp_knn_interpolate_weights(_ptr(indices), _ptr(dist2), _ptr(index), n_index, m, k, npoints, nrows, KNN_INTERPOLATE_MODES[mode],
+                                         float(eps), _ptr(got["weights"]), _stream()), "gp_knn_interpolate_weights")
+    return got["weights"]
+
+
+def knn_interpolate_transpose_workspace_bytes(m, k, nrows):
+    """gp_knn_interpolate_transpose_workspace_bytes (no GPU needed); 0: sizes the library does not take"""
+    return int(_lib.load().gp_knn_interpolate_transpose_workspace_bytes(int(m), int(k), int(nrows)))
+
+
+def knn_interpolate_transpose(indices, weights, index=None, nrows=None, mode="inverse_distance", buffers=None, workspace=None):
+    """gp_knn_interpolate_transpose, no sync: the lists of knn_interpolate inverted, for its backward.  weights: what
+    knn_interpolate_weights returned for the same lists, index, mode and eps.  -> (offsets i64 [nrows+1], slots i32 [m*k], sorted_weights
+    f32 [m*k]): the references of row r of values are the flat slots f = j * k + s at slots[offsets[r] : offsets[r+1]], ascending, their
+    weights beside them; offsets[nrows] counts the references, the slots past it are the flat slots that are none.  buffers: optional
+    dict of caller-owned offsets / slots / sorted_weights; workspace: uint8 of at least knn_interpolate_transpose_workspace_bytes(m,
+    k, nrows)."""
+    lib = _lib.load()
+    who = "knn_interpolate_transpose"
+    m, k, n_index, npoints, dev = _chk_knn_lists(who, indices, index, nrows, mode)
+    if _chk(weights, torch.float32, "weights").shape != (m, k) or weights.device != dev:
+        raise ValueError(f"{who}: expected weights [{m}, {k}] on the lists' device, got {list(weights.shape)}")
+    got = _outputs(who, {"offsets": (torch.int64, (nrows + 1,)), "slots": (torch.int32, (m * k,)), "sorted_weights": (torch.float32, (m * k,))},
+                   buffers, dev)
+    need = lib.gp_knn_interpolate_transpose_workspace_bytes(m, k, nrows)
+    ws = _ws(need, dev) if workspace is None else _chk(workspace, torch.uint8, "workspace")
+    check(lib.gp_knn_interpolate_transpose(_ptr(indices), _ptr(index), n_index, m, k, npoints, nrows, KNN_INTERPOLATE_MODES[mode], _ptr(weights),
+                                           _ptr(got["offsets"]), _ptr(got["slots"]), _ptr(got["sorted_weights"]), _ptr(ws), ws.numel(),
+                                           _stream()), "gp_knn_interpolate_transpose")
+    return got["offsets"], got["slots"], got["sorted_weights"]
+
+
+def knn_interpolate_backward(g, offsets, slots, sorted_weights, k, dtype=torch.float32, buffers=None):
+    """gp_knn_interpolate_backward, no sync: d_values [R,D] of `dtype` (fp32, fp16 or bf16; contiguous) from g = d_out f32 [m,D] (unit
+    column stride, any row stride >= D, read in place) through the lists of knn_interpolate_transpose: per element acc = acc + w * g[j]
+    in fp32 over the row's references in ascending flat slot, from +0, rounded to dtype once; zeros for a row without references.
+    No atomics: two calls give the same bits.  buffers: optional dict with a caller-owned out."""
+    lib = _lib.load()
+    who = "knn_interpolate_backward"
+    if not torch.is_tensor(g) or g.dtype != torch.float32 or not g.is_cuda or g.dim() != 2 or min(g.shape) < 1 or g.stride(1) != 1 \
+            or g.stride(0) < g.shape[1]:
+        raise ValueError(f"{who}: g must be CUDA fp32 [m >= 1, D >= 1] with unit column stride and a row stride >= D, got "
+                         f"{(g.dtype, list(g.shape), g.stride()) if torch.is_tensor(g) else type(g).__name__}")
+    m, D = g.shape
+    if dtype not in ELEM_TAG:
+        raise ValueError(f"{who}: dtype must be one of {tuple(ELEM_TAG)}, got {dtype}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: k={k!r} outside 1..{_lib.GP_KNN_QUERY_MAX_K}")
+    if m * k > KNN_INTERPOLATE_MAX_SLOTS:
+        raise ValueError(f"{who}: m * k = {m * k} flat slots, more than 2^31-1")
+    _chk(offsets, torch.int64, "offsets"), _chk(slots, torch.int32, "slots"), _chk(sorted_weights, torch.float32, "sorted_weights")
+    if offsets.dim() != 1 or offsets.shape[0] < 2 or slots.shape != (m * k,) or sorted_weights.shape != (m * k,):
+        raise ValueError(f"{who}: expected offsets [R + 1], slots and sorted_weights [{m * k}], got {list(offsets.shape)}, {list(slots.shape)} "
+                         f"and {list(sorted_weights.shape)}")
+    R, dev = offsets.shape[0] - 1, g.device
+    if any(t.device != dev for t in (offsets, slots, sorted_weights)):
+        raise ValueError(f"{who}: g, offsets, slots and sorted_weights must be on one device")
+    got = _outputs(who, {"out": (dtype, (R, D))}, buffers, dev)
+    check(lib.gp_knn_interpolate_backward(_ptr(g), g.stride(0), m, D, _ptr(offsets), _ptr(slots), _ptr(sorted_weights), k, R, _ptr(got["out"]),
+                                          ELEM_TAG[dtype], _stream()), "gp_knn_interpolate_backward")
+    return got["out"]
+
+
 # ------------------------------------------------------------------------------------------ the mask lift over batched point clouds
 def _outputs(who, want, buffers, dev):
     """the named outputs: the caller's (checked) or fresh ones"""

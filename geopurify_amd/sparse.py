@@ -23,6 +23,11 @@ the results carried over: the k nearest working points of every vertex inside it
     feat = interpolate(y.F, nb, index=q.inverse_mapping)            # purified features on the benchmark's vertices
     pred = interpolate(seg.pred, nb, index=q.inverse_mapping)       # nearest working point's voxel prediction
 
+and, to train on the cloud that is scored, the same call with gradients to the rows it reads (exact and reproducible: no atomics):
+
+    t = nb.transpose(q.inverse_mapping, y.F.shape[0])               # the lists inverted, once for a training run
+    feat = interpolate(purify(student, x, differentiable=True).F, nb, index=q.inverse_mapping, differentiable=True, transpose=t)
+
 or, with the VLM producing its maps a batch of views at a time (the reference's own loop, :365-449), the same start without ever
 holding more than one batch of maps:
 
@@ -130,7 +135,10 @@ read-back; estimate_normals is quantize, knn and ops.knn_normals (fp64 covarianc
 staged through LDS), then torch indexing by the inverse mapping.
 knn_query is ops.knn_query (the points' entry table, per entry a bounding box and a uniform grid, a wave per query walking the grid's
 shells in the (d^2, row) order of lift's fill, an entry scan for the queries the walk leaves), one read-back; interpolate is
-ops.knn_interpolate (a wave per query row, weights in fp64, sums in fp32 in list order), no read-back.
+ops.knn_interpolate (a wave per query row, weights in fp64, sums in fp32 in list order), no read-back; with differentiable=True its
+backward is ops.knn_interpolate_weights (the forward's weights again, by the forward's device code), ops.knn_interpolate_transpose (a
+stable radix sort of (row of values, flat slot) pairs; Neighbors.transpose builds it once for a run) and ops.knn_interpolate_backward (a
+wave per row of values adding its references in ascending flat slot: no float atomics, the same bits every time).
 The indices come from ops.quantize_batched (the key and order of ops.coords_order_batched: batch << 48 | morton(xyz - min)); the
 features are reduced by the kernels the pipeline already has, ops.scatter_mean_csr ("average") and ops.gather_rows ("subsample").
 The neighbour lists come from ops.knn_batched over the same sorted keys; affinity and pooling are ops.affinity_softmax and the
@@ -1727,6 +1735,88 @@ class Neighbors:
     def __init__(self, indices, distances2, num_points=None):
         self.indices, self.distances2, self.num_points = indices, distances2, num_points
 
+    def transpose(self, index=None, num_rows=None, *, mode="inverse_distance", eps=1e-8):
+        """The lists inverted for interpolate(..., differentiable=True): per row of values its references in ascending flat slot, with
+        the forward's weights.  index, mode, eps: as the interpolate calls that will use it; num_rows: R of their values (with an
+        index it must be given; without one it defaults to num_points).  The lists are constant over a training run: build this
+        once and pass transpose= to every step.  -> NeighborsTranspose.  No host synchronisation."""
+        who = "Neighbors.transpose"
+        I, D2 = _check_lists(who, self)
+        if index is not None and (not _is_int_tensor(index) or index.dim() != 1 or index.shape[0] < 1):
+            raise ValueError(f"{who}: index must be an integer tensor [N] (point -> row of values), got "
+                             f"{(list(index.shape), index.dtype) if torch.is_tensor(index) else type(index).__name__}")
+        if num_rows is None and index is None:
+            num_rows = self.num_points
+        if isinstance(num_rows, bool) or not isinstance(num_rows, int) or not 1 <= num_rows < 2 ** 31:
+            raise ValueError(f"{who}: num_rows={num_rows!r} must be the row count of values, an int in 1..2^31-1"
+                             f"{' (an index does not tell it)' if index is not None else ''}")
+        span, what = (num_rows, "num_rows") if index is None else (index.shape[0], "index")
+        if self.num_points is not None and span != self.num_points:
+            raise ValueError(f"{who}: {what} {'is' if index is None else 'holds'} {span} rows, the lists name rows of {self.num_points} points")
+        _check_mode_eps(who, mode, eps)
+        _check_slots(who, I)
+        _check_one_device(who, "nb and index", [I, D2] + ([] if index is None else [index]))
+        with torch.cuda.device(I.device), torch.no_grad():
+            idx = None if index is None else index.detach().to(torch.int64).contiguous()
+            return _transpose(I.detach().contiguous(), D2.detach().contiguous(), idx, num_rows, mode, float(eps))
+
+
+class NeighborsTranspose:
+    """What Neighbors.transpose returns and interpolate(differentiable=True) applies in its backward: offsets i64 [R+1], slots i32
+    [M*k] (the references of row r of values are the flat slots j * k + s at slots[offsets[r] : offsets[r+1]], ascending; offsets[R]
+    counts them), weights f32 [M*k] (the forward's fp32 weights in that order), and what it was built for: M, k, R, mode, eps."""
+
+    def __init__(self, offsets, slots, weights, M, k, R, mode, eps):
+        self.offsets, self.slots, self.weights = offsets, slots, weights
+        self.M, self.k, self.R, self.mode, self.eps = M, k, R, mode, eps
+
+
+def _transpose(I, D2, idx, R, mode, eps):
+    w = ops.knn_interpolate_weights(I, D2, idx, R, mode, eps)
+    offsets, slots, weights = ops.knn_interpolate_transpose(I, w, idx, R, mode)
+    return NeighborsTranspose(offsets, slots, weights, I.shape[0], I.shape[1], R, mode, eps)
+
+
+class _Interpolate(torch.autograd.Function):
+    """out = ops.knn_interpolate(values, ...); d values[r] = sum over the references f = j * k + s of r, in ascending f, of w32[f] *
+    d out[j] (ops.knn_interpolate_backward over a NeighborsTranspose: fp32, one rounding to the dtype of values)"""
+
+    @staticmethod
+    def forward(ctx, values, I, D2, idx, mode, eps, status, transpose):
+        ctx.lists, ctx.transpose, ctx.dtype, ctx.R = (I, D2, idx, mode, eps), transpose, values.dtype, values.shape[0]
+        return ops.knn_interpolate(values.detach(), I, D2, idx, mode, eps, buffers=None if status is None else {"status": status})
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        with torch.cuda.device(d_out.device):
+            g = d_out.float()
+            if g.stride(1) != 1 or g.stride(0) < g.shape[1]:
+                g = g.contiguous()
+            t = ctx.transpose if ctx.transpose is not None else _transpose(*ctx.lists[:3], ctx.R, *ctx.lists[3:])
+            return ops.knn_interpolate_backward(g, t.offsets, t.slots, t.weights, t.k, ctx.dtype), None, None, None, None, None, None, None
+
+
+def _check_lists(who, nb):
+    I, D2 = nb.indices, nb.distances2
+    if not torch.is_tensor(I) or not torch.is_tensor(D2) or I.dtype != torch.int64 or D2.dtype != torch.float64 or I.dim() != 2 \
+            or D2.shape != I.shape or I.shape[0] < 1 or not 1 <= I.shape[1] <= GP_KNN_QUERY_MAX_K:
+        raise ValueError(f"{who}: nb must hold indices i64 [M, k] and distances2 f64 [M, k] with M >= 1 and k in 1..{GP_KNN_QUERY_MAX_K}, got "
+                         f"{_shape_of(I)} and {_shape_of(D2)}")
+    return I, D2
+
+
+def _check_mode_eps(who, mode, eps):
+    if mode not in INTERPOLATE_MODES:
+        raise ValueError(f"{who}: mode={mode!r} must be one of {INTERPOLATE_MODES}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
+        raise ValueError(f"{who}: eps={eps!r} must be a finite number >= 0")
+
+
+def _check_slots(who, I):
+    if I.shape[0] * I.shape[1] > ops.KNN_INTERPOLATE_MAX_SLOTS:
+        raise ValueError(f"{who}: M * k = {I.shape[0] * I.shape[1]} flat slots, more than 2^31-1: the backward numbers them in i32")
+
 
 def _check_cloud(who, name, letter, P):
     """_check_points' checks and words for a cloud called `name`"""
@@ -1774,7 +1864,8 @@ def knn_query(points, queries, k):
     return Neighbors(indices, dist2, P.shape[0])
 
 
-def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, unlabeled=255, status=None):
+def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, unlabeled=255, status=None, differentiable=False,
+                transpose=None):
     """Rows carried through the lists of knn_query: purified features or predictions of the working cloud delivered on another
     cloud's points.  nb: the Neighbors of knn_query(points, queries, k).
       values floating [R,D] (fp32, fp16 or bf16; any row stride, unit column stride; read in place) -> fp32 [M,D], contiguous.
@@ -1788,9 +1879,24 @@ def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, un
     A list entry outside -1..N-1 or an index value outside 0..R-1 is never dereferenced: the row comes back zero / `unlabeled` and is
     counted.  The counts stay on the device and nothing is read back: pass status, an int64 [2] tensor on the values' device, to
     receive (rows with such a list entry, rows with such an index value).
-    No autograd: values.requires_grad is ignored and the result is detached (gradients through the lists are not implemented).
+    differentiable=False (the default): values.requires_grad is ignored and the result is detached.
+    differentiable=True: floating values that require grad, under enabled grad mode, get the same forward bits inside the autograd
+      graph; values that need no gradient get the plain result.  backward returns d_values [R,D], contiguous (whatever the pitch of
+      values), in the dtype of values.  The rule: a reference is a flat slot f = j*k + s whose forward weight is in effect -- slot s is
+      one the mode reads ("nearest": slot 0 only, weight 1), its list entry is valid, its row r = index[indices[j,s]] (or
+      indices[j,s]) is valid, and query row j is not excused: a query row with any list entry outside -1..N-1 or any index value
+      outside 0..R-1 is a zero row in the forward and contributes no reference.  d_values[r,c] starts at +0.f and takes, over the
+      references of r in ascending f, acc = acc + w32[f] * g[j,c] with the product rounded once and the sum rounded once in fp32
+      (the library builds with -ffp-contract=off), w32 the forward's own fp32 weight; fp16 / bf16 are rounded once at the end.  A
+      row without references gets an explicit zero row.  The result depends on nothing but the inputs: no float atomics, two calls
+      give the same bits.  No gradient to nb.distances2, to the weights or to any coordinate; no double backward.
+      transpose: a NeighborsTranspose of nb.transpose(index, R, mode=mode, eps=eps), built once for a training run; without it
+      every backward builds its own.  ValueError: integer values; M * k > 2^31-1 (flat slots are i32); a transpose whose (M, k,
+      R, mode, eps) are not the call's.
     Inside: ops.knn_interpolate (a wave per query row: the list read once, the weights in fp64 by k lanes, the rows gathered by the
-    widest loads the row stride allows), no host synchronisation.  ValueError: an nb that is no Neighbors; values that are neither
+    widest loads the row stride allows), no host synchronisation; the backward: ops.knn_interpolate_weights (the forward's device
+    code), ops.knn_interpolate_transpose (a stable radix sort of (row, flat slot) pairs), ops.knn_interpolate_backward (a wave per row
+    of values walking its list in order).  ValueError: an nb that is no Neighbors; values that are neither
     floating [R,D] of the three dtypes with unit column stride nor integer [R]; an index that is no integer [N]; R (or the index's
     length) other than the N of nb; a mode outside INTERPOLATE_MODES; eps no finite number >= 0; unlabeled no int; CPU tensors or two
     devices."""
@@ -1798,11 +1904,7 @@ def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, un
     V = values
     if not isinstance(nb, Neighbors):
         raise ValueError(f"{who}: nb must be the Neighbors of knn_query, got {type(nb).__name__}")
-    I, D2 = nb.indices, nb.distances2
-    if not torch.is_tensor(I) or not torch.is_tensor(D2) or I.dtype != torch.int64 or D2.dtype != torch.float64 or I.dim() != 2 \
-            or D2.shape != I.shape or I.shape[0] < 1 or not 1 <= I.shape[1] <= GP_KNN_QUERY_MAX_K:
-        raise ValueError(f"{who}: nb must hold indices i64 [M, k] and distances2 f64 [M, k] with M >= 1 and k in 1..{GP_KNN_QUERY_MAX_K}, got "
-                         f"{_shape_of(I)} and {_shape_of(D2)}")
+    I, D2 = _check_lists(who, nb)
     labels = _is_int_tensor(V)
     if labels:
         if V.dim() != 1 or V.shape[0] < 1:
@@ -1819,18 +1921,34 @@ def interpolate(values, nb, *, index=None, mode="inverse_distance", eps=1e-8, un
     if nb.num_points is not None and span != nb.num_points:
         raise ValueError(f"{who}: {what} holds {span} rows, the lists name rows of {nb.num_points} points"
                          f"{' (pass index, point -> row of values)' if index is None else ''}")
-    if mode not in INTERPOLATE_MODES:
-        raise ValueError(f"{who}: mode={mode!r} must be one of {INTERPOLATE_MODES}")
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
-        raise ValueError(f"{who}: eps={eps!r} must be a finite number >= 0")
+    _check_mode_eps(who, mode, eps)
     if isinstance(unlabeled, bool) or not isinstance(unlabeled, int) or not -2 ** 63 <= unlabeled < 2 ** 63:
         raise ValueError(f"{who}: unlabeled={unlabeled!r} must be an int")
     if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int64 or status.shape != (2,) or not status.is_contiguous()):
         raise ValueError(f"{who}: status must be a contiguous int64 [2] tensor, got {_shape_of(status)}")
-    _check_one_device(who, "values, nb, index and status", [V, I, D2] + [t for t in (index, status) if t is not None])
+    if not isinstance(differentiable, bool):
+        raise ValueError(f"{who}: differentiable={differentiable!r} must be a bool")
+    if transpose is not None and not differentiable:
+        raise ValueError(f"{who}: transpose goes with differentiable=True")
+    if differentiable:
+        if labels:
+            raise ValueError(f"{who}: differentiable=True takes floating values, got {V.dtype}")
+        _check_slots(who, I)
+        t = transpose
+        if t is not None:
+            if not isinstance(t, NeighborsTranspose):
+                raise ValueError(f"{who}: transpose must be the NeighborsTranspose of nb.transpose, got {type(t).__name__}")
+            mine, its = (I.shape[0], I.shape[1], V.shape[0], mode, float(eps)), (t.M, t.k, t.R, t.mode, float(t.eps))
+            if mine != its:
+                raise ValueError(f"{who}: transpose was built for (M, k, R, mode, eps) = {its}, this call has {mine}")
+    _check_one_device(who, "values, nb, index, status and transpose",
+                      [V, I, D2] + [t for t in (index, status) if t is not None] + ([] if transpose is None else [transpose.offsets]))
+    idx = None if index is None else index.detach().to(torch.int64).contiguous()
+    if differentiable and V.requires_grad and torch.is_grad_enabled():
+        with torch.cuda.device(V.device):
+            return _Interpolate.apply(V, I.detach().contiguous(), D2.detach().contiguous(), idx, mode, float(eps), status, transpose)
     with torch.cuda.device(V.device), torch.no_grad():
         vals = V.detach().to(torch.int64).contiguous() if labels else V.detach()
-        idx = None if index is None else index.detach().to(torch.int64).contiguous()
         return ops.knn_interpolate(vals, I.detach().contiguous(), D2.detach().contiguous(), idx, mode, float(eps), unlabeled,
                                    buffers=None if status is None else {"status": status})
 

@@ -1372,6 +1372,37 @@ int gp_knn_interpolate(const void *values, int32_t elem, int64_t nrows, int64_t 
 int gp_knn_interpolate_labels(const int64_t *values, int64_t nrows, const int64_t *index, int64_t n_index, const int64_t *indices,
                               int64_t m, int32_t k, int64_t npoints, int64_t unlabeled, int64_t *out, int64_t *status, void *stream);
 
+/* ---- the backward of gp_knn_interpolate (knn_interpolate_grad.hip) ---------------------------------- */
+/* d_values [nrows,d] from g = d_out f32 [m,d]: the role of the autograd the reference gets from torch  */
+/* indexing where it carries features through KDTree lists (models/affinity_module.py:445-452,         */
+/* 693-714), for k neighbours, weights and an index, exactly and reproducibly: no float atomics.        */
+/* A reference is a flat slot f = j*k + s whose forward weight is in effect: s is a slot the mode reads */
+/*   (all k; slot 0 for mode 1), its list entry is in 0..npoints-1, its row r = index[entry] (or the    */
+/*   entry) in 0..nrows-1, and no slot of query row j that the mode reads holds a list entry outside    */
+/*   -1..npoints-1 or an index value outside 0..nrows-1 (such a query row is the forward's zero row).   */
+/*   d_values[r,c] starts at +0 and takes, over the references of r in ascending f, acc = acc +         */
+/*   w32[f] * g[j,c], the product and the sum each rounded once in fp32; one rounding to the element    */
+/*   type at the end; a row without references is written as zeros.                                     */
+/* gp_knn_interpolate_weights: weights f32 [m,k] = the forward's own fp32 weight of every reference     */
+/*   (the same device code), 0 where the slot is none.  Arguments as gp_knn_interpolate.                */
+/* gp_knn_interpolate_transpose: offsets i64 [nrows+1], slots i32 [m*k], sorted_weights f32 [m*k]: the  */
+/*   references of row r are slots[offsets[r] .. offsets[r+1]) in ascending f with their weights beside  */
+/*   them; offsets[nrows] = the number of references, the slots past it are the flat slots that are     */
+/*   none (weight 0).  A stable radix sort of (row, f) pairs over the bits of 0..nrows; weights: what   */
+/*   gp_knn_interpolate_weights wrote for the same lists, index, mode and eps.  The result depends on   */
+/*   those alone: build it once for a training run.  m * k <= 2^31-1, nrows < 2^31.                     */
+/* gp_knn_interpolate_backward: out [nrows,d] of element type out_elem, contiguous; g [m, ld_g >= d].   */
+/*   One wave per row of out; offsets and slots are clamped where they are read, so a damaged transpose */
+/*   gives wrong numbers and no access outside g.  No output may overlap an input or another output.    */
+int gp_knn_interpolate_weights(const int64_t *indices, const double *dist2, const int64_t *index, int64_t n_index, int64_t m, int32_t k,
+                               int64_t npoints, int64_t nrows, int32_t mode, double eps, float *weights, void *stream);
+size_t gp_knn_interpolate_transpose_workspace_bytes(int64_t m, int32_t k, int64_t nrows);
+int gp_knn_interpolate_transpose(const int64_t *indices, const int64_t *index, int64_t n_index, int64_t m, int32_t k, int64_t npoints,
+                                 int64_t nrows, int32_t mode, const float *weights, int64_t *offsets, int32_t *slots, float *sorted_weights,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int gp_knn_interpolate_backward(const float *g, int64_t ld_g, int64_t m, int64_t d, const int64_t *offsets, const int32_t *slots,
+                                const float *sorted_weights, int32_t k, int64_t nrows, void *out, int32_t out_elem, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
